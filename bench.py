@@ -1,11 +1,14 @@
 """Headline benchmark: images/sec of a Hybrid Octic ViT-H/14 224² bf16 TRAINING step (fwd + bwd + LAMB + EMA)
 on synthetic batches, 1/2/4/8 MI355X (BASELINE.json `metric`, configs[1]: batch 64 per GPU).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  `value` is whole-job images/s (weak scaling: 64 images per GPU).
+Prints ONE JSON line on rank 0.  `value` is whole-job images/s (weak scaling: 64 images per GPU), `ms_per_step` the
+wall time of one timed step.  A plain run sets up, warms up, times `--steps` steps, writes the outputs of the last one
+(`--dump-outputs DIR`) and prints the line.  Everything else is measured with `--full` only: the per-kernel table and
+`roofline`, the forward-only figure, the step variants and the data-parallel / DINOv2 side figures, the CPU baseline.
 `roofline` is for the dominant kernel of the WHOLE step — the engine's launches and the BLAS-library GEMMs of the
 standard half alike — timed live with HIP events on the stream they are launched on during the timed steps
 (`roofline_hbm_kernel`: the dominant HBM-bound one when the dominant one is MFMA-bound); `cpu_baseline` is the CPU oracle timed on this box's
@@ -157,6 +160,47 @@ def step_variants(trainer, model, samples, targets, args, n=8):
     return out
 
 
+DUMP_SAMPLE = 1 << 21                # elements per sampled array of --dump-outputs (8 MB in f32; 4 arrays + the loss)
+
+
+@torch.no_grad()
+def dump_outputs(path, trainer, loss):
+    """What the timed path computed in its last step, as float32 .npy files: the step's loss and a fixed, seeded sample of
+    the state it hands back - master parameters, EMA weights and the optimizer's first / second moments - at the same
+    positions in each (every tensor of at most DUMP_SAMPLE / #tensors elements whole, the others at that many seeded
+    positions; tensors in `named_parameters` order).  Two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    model, opt = trainer.raw_model, trainer.optimizer
+    params = [p for _, p in model.named_parameters() if p.requires_grad]
+    per = max(1, DUMP_SAMPLE // len(params))
+    index = []
+    for i, p in enumerate(params):
+        n = p.numel()
+        if n <= per:
+            index.append(None)
+        else:
+            g = torch.Generator().manual_seed(1000 + i)
+            index.append(torch.randint(0, n, (per,), generator=g).sort().values.to(p.device))
+
+    def sample(tensors):
+        parts = [t.detach().reshape(-1) if ix is None else t.detach().reshape(-1)[ix] for t, ix in zip(tensors, index)]
+        return torch.cat([t.float() for t in parts]).cpu().numpy()
+
+    out = {"loss": loss.detach().float().reshape(1).cpu().numpy(), "params": sample(params)}
+    pos = {id(p): k for k, p in enumerate(getattr(opt, "params", []))}
+    if pos and all(id(p) in pos for p in params) and hasattr(opt, "m"):      # train.FusedLamb: flat state in its own order
+        flat = lambda buf: [buf[opt._offs[pos[id(p)]]:opt._offs[pos[id(p)]] + p.numel()] for p in params]
+        out["lamb_m"], out["lamb_v"] = sample(flat(opt.m)), sample(flat(opt.v))
+        if opt.ema is not None or opt._ema_ext is not None:
+            ema = opt.ema_state()
+            out["ema"] = sample([ema[pos[id(p)]] for p in params])
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed step written to {path}: "
+        + ", ".join(f"{k} {v.size}" for k, v in out.items()))
+
+
 def _baseline_metric():
     """BASELINE.json's metric string, verbatim (the driver matches on it)."""
     try:
@@ -231,6 +275,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch (BASELINE configs[1]: 64)")
     ap.add_argument("--model", default="hybrid_deit_huge_patch14")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32): its loss and a "
+                         "seeded sample of the parameters, EMA weights and optimizer moments it leaves (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: per-kernel table + roofline, forward-only figure, step "
+                         "variants, data-parallel and DINOv2 side figures, CPU baseline (each still subject to its --no-* flag)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-forward-only", action="store_true")
@@ -486,7 +536,8 @@ def main():
             if os.environ.get("OCTIC_BENCH_FAKE_HANG") and watchdog is not None:     # developer: exercise the watchdog
                 time.sleep(1e6)
             # torch.cuda.graph() empties the caching allocator before it captures: one more eager step here lets the
-            # eager kernel-timing steps of the timed region reuse cached blocks instead of calling hipMalloc
+            # eager kernel-timing steps of the timed region reuse cached blocks instead of calling hipMalloc (taken without
+            # --full as well: the timed steps are then the same iterations, on the same weights, in both kinds of run)
             if not args.no_kernel_timing:
                 trainer.step(samples, targets)
             torch.cuda.synchronize()
@@ -513,8 +564,10 @@ def main():
         elapsed, issued, loss = timed_region(graphed.replay if graphed is not None else trainer.step)
     if watchdog is not None:
         watchdog.cancel()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss)
     sampled = []
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         ops.KERNEL_TIMER.enable()
         sampled = [0, 1]
         for _ in sampled:
@@ -530,7 +583,7 @@ def main():
     # reference runs torch.amp.autocast (fp16) + torch.compile; here bf16 autocast (the engine's compute dtype) and the
     # HIP kernels.  Reported under "extra", outside the timed train region.
     fwd_only = None
-    if rank == 0 and not args.no_forward_only:
+    if rank == 0 and args.full and not args.no_forward_only:
         model.eval()
         times = []
         with torch.no_grad():
@@ -697,16 +750,16 @@ def main():
                                               "the timed region itself is `steps` full iterations with no event records, no host read"}
         if fwd_only is not None:
             line["extra"] = {"forward_only": fwd_only}
-        if world == 1 and not ddp and graphed is not None and not args.no_step_variants:
+        if args.full and world == 1 and not ddp and graphed is not None and not args.no_step_variants:
             try:
                 line.update(step_variants(trainer, model, samples, targets, args))
             except Exception as e:                    # side figures only: the line and its `value` are complete without them
                 line["step_variants_error"] = f"{type(e).__name__}: {e}"[:300]
-        if world == 1 and not ddp and not args.no_step_variants:
+        if args.full and world == 1 and not ddp and not args.no_step_variants:
             line.update(ddp_side_figure(args))
-        if world == 1 and not args.no_ssl_side and not args.no_step_variants:
+        if args.full and world == 1 and not args.no_ssl_side and not args.no_step_variants:
             line.update(ssl_side_figure())
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), file=real_stdout, flush=True)
     if dist.is_available() and dist.is_initialized():

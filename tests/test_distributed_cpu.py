@@ -3,6 +3,7 @@ process-group init from the torchrun environment, DDP gradient averaging, identi
 equivalence with single-process training on the concatenated batch, and the max-over-ranks timing reduction."""
 import os
 import socket
+import sys
 
 import pytest
 import torch
@@ -16,6 +17,22 @@ def _free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def _gloo_rank(rank, world, port):
+    """torchrun's environment for one spawned rank of these CPU tests, which check the gloo path: the rank sees no GPU, as on a
+    machine without one (with a GPU visible, init_distributed would pick RCCL and put rank 1 on a device a one-GPU box lacks)."""
+    torch.cuda.is_available = lambda: False
+    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                      MASTER_PORT=str(port))
+
+
+def _leave():
+    """End a spawned rank once its work is done and its result is saved: os._exit skips the interpreter's teardown, where the
+    process group's native threads met the C++ static destructors at random (an abort, SIGABRT, after a passed check)."""
+    sys.stdout.flush()
+    sys.stderr.flush()
+    os._exit(0)
 
 
 def _make_model():
@@ -34,8 +51,7 @@ def _batch(rank, world):
 
 
 def _worker(rank, world, port, out):
-    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+    _gloo_rank(rank, world, port)
     from octic_vits_amd.train import Lamb, init_distributed
     w, r, lr_ = init_distributed()
     assert (w, r) == (world, rank) and dist.get_backend() == "gloo"
@@ -59,6 +75,7 @@ def _worker(rank, world, port, out):
         torch.save(flat, out)
     dist.barrier()
     dist.destroy_process_group()
+    _leave()
 
 
 @pytest.mark.timeout(300)
@@ -109,8 +126,7 @@ def _accum_batch():
 
 
 def _accum_worker(rank, world, port, out, flat_numel=None, own=False):
-    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+    _gloo_rank(rank, world, port)
     from octic_vits_amd import train as TR
     from octic_vits_amd.train import Trainer, init_distributed
     init_distributed()
@@ -141,6 +157,7 @@ def _accum_worker(rank, world, port, out, flat_numel=None, own=False):
         torch.save(flat, out)
     dist.barrier()
     dist.destroy_process_group()
+    _leave()
 
 
 @pytest.mark.timeout(300)
@@ -182,8 +199,7 @@ def test_trainer_accumulation_under_ddp_matches_single_process(tmp_path):
 
 
 def _reducer_worker(rank, world, port, out):
-    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+    _gloo_rank(rank, world, port)
     from octic_vits_amd import train as TR
     from octic_vits_amd.train import GradReducer, Trainer, init_distributed
     init_distributed()
@@ -213,6 +229,7 @@ def _reducer_worker(rank, world, port, out):
         torch.save(flat, out)
     dist.barrier()
     dist.destroy_process_group()
+    _leave()
 
 
 @pytest.mark.timeout(300)

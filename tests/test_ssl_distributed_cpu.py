@@ -14,6 +14,7 @@ the equality runs: its nearest neighbour is searched inside the local batch in t
 sharded batch is a different loss by construction."""
 import os
 import socket
+import sys
 
 import pytest
 import torch
@@ -30,6 +31,14 @@ def _free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def _leave():
+    """End a spawned rank once its work is done and its result is saved: os._exit skips the interpreter's teardown, where the
+    process group's native threads met the C++ static destructors at random (an abort, SIGABRT, after a passed check)."""
+    sys.stdout.flush()
+    sys.stderr.flush()
+    os._exit(0)
 
 
 class _TinyBackbone(nn.Module):
@@ -145,6 +154,7 @@ def _worker(rank, world, port, centering, out):
     torch.save(res, f"{out}.{rank}")
     dist.barrier()
     dist.destroy_process_group()
+    _leave()
 
 
 @pytest.mark.timeout(600)

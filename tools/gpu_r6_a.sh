@@ -8,7 +8,7 @@ echo "tests rc=$?" >> $O/a_tests.log
 tail -5 $O/a_tests.log
 timeout 600 python bench.py --force-ddp --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only --no-ssl-side --no-step-variants > $O/a_ddp.json 2> $O/a_ddp.err
 echo "ddp bench rc=$?"; tail -3 $O/a_ddp.err; cut -c1-1500 $O/a_ddp.json
-timeout 900 python bench.py --no-cpu-baseline --no-ssl-side --no-forward-only > $O/a_base.json 2> $O/a_base.err
+timeout 900 python bench.py --full --no-cpu-baseline --no-ssl-side --no-forward-only > $O/a_base.json 2> $O/a_base.err
 echo "base bench rc=$?"; tail -3 $O/a_base.err
 python - <<'PY'
 import json

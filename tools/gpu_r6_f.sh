@@ -1,7 +1,7 @@
 #!/bin/bash
 set -u
 O=gpurun_out; mkdir -p $O
-( time python bench.py > $O/f_bench_full.json 2> $O/f_bench_full.err ) 2>&1 | tail -3
+( time python bench.py --full > $O/f_bench_full.json 2> $O/f_bench_full.err ) 2>&1 | tail -3
 python3 - <<'PY'
 import json
 d = json.loads(open('gpurun_out/f_bench_full.json').read().strip().splitlines()[-1])

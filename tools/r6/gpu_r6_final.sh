@@ -4,7 +4,7 @@ set -u
 O=gpurun_out; mkdir -p $O
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" 2>&1 | tail -2
 timeout 3000 python -m pytest tests -m gpu -q 2>&1 | tail -6 > $O/gputest_r6.txt; tail -3 $O/gputest_r6.txt
-( time python bench.py > $O/bench_r6_n1.json 2> $O/bench_r6_n1.err ) 2>&1 | tail -3
+( time python bench.py --full > $O/bench_r6_n1.json 2> $O/bench_r6_n1.err ) 2>&1 | tail -3
 python3 -c "
 import json
 d = json.loads(open('gpurun_out/bench_r6_n1.json').read().strip().splitlines()[-1])

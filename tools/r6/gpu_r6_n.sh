@@ -8,7 +8,7 @@ for i in 1 2 3; do
 timeout 900 python bench.py $S --force-ddp > $O/n_ddp$i.json 2> $O/n_ddp$i.err; echo ddp rc=$?
 done
 OCTIC_BENCH_FAKE_HANG=1 OCTIC_BENCH_WATCHDOG_S=45 timeout 900 python bench.py $S --force-ddp > $O/n_hang.json 2> $O/n_hang.err; echo hang rc=$?
-( time python bench.py --no-cpu-baseline --no-ssl-side --no-forward-only > $O/n_full.json 2> $O/n_full.err ) 2>&1 | tail -3
+( time python bench.py --full --no-cpu-baseline --no-ssl-side --no-forward-only > $O/n_full.json 2> $O/n_full.err ) 2>&1 | tail -3
 python3 - <<'PY'
 import json
 for f in ("gpurun_out/n_ddp1.json", "gpurun_out/n_ddp2.json", "gpurun_out/n_ddp3.json", "gpurun_out/n_hang.json", "gpurun_out/n_full.json"):
