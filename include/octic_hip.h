@@ -74,7 +74,8 @@ enum {
   OCTIC_ROUTE_ATTN_BWD_PAIR = 8,   /* octic_attn_bwd*: 1 = the dq + dkv kernel pair instead of the single-pass backward   */
   OCTIC_ROUTE_DENSE_IMAGE = 9,     /* octic_dense_gemm_nt_tokens: 1 = per-image panels wherever legal, 2 = never, 3 = plain only */
   OCTIC_ROUTE_DENSE_CLS2 = 10,     /* class-token rows of per-image launches as two launches (K split): 1 = never, 2 = wherever legal */
-  OCTIC_ROUTE_COUNT = 11
+  OCTIC_ROUTE_ATTN_STREAM = 11,    /* octic_attn_*: 1 = the streaming (K / V through LDS in blocks) kernels for every T too   */
+  OCTIC_ROUTE_COUNT = 12
 };
 int octic_route_override(int knob, int value);
 
@@ -241,8 +242,9 @@ int octic_attn_unpack_heads(void* const heads[3], const octic_view* y, int64_t B
  * (d8_layers.py:645-648) and the standard blocks (deit/vit.py:41-45).  Element (b,h,t,d) of q/k/v is at
  * base + b*sB + h*sH + t*sT + d (one stride set for the three, so [B,H,T,hd] and the [B,T,3,H,hd] views of a
  * fused qkv tensor both work); o likewise with oB/oH/oT.  lse ([B,H,T] f32, may be NULL) receives the
- * log2-domain log-sum-exp needed by the backward.  T <= 320, hd a multiple of 16 (<= 128); otherwise
- * OCTIC_ESHAPE (callers keep torch SDPA for such shapes).                                            */
+ * log2-domain log-sum-exp needed by the backward.  T <= 16384, hd a multiple of 16 (<= 128); otherwise
+ * OCTIC_ESHAPE (callers keep torch SDPA for such shapes).  T <= 320 keeps K and V of a head resident in LDS; longer
+ * sequences (and every T under OCTIC_ROUTE_ATTN_STREAM = 1) stream them through LDS in blocks.       */
 int octic_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int H, int T, int hd,
                    int64_t sB, int64_t sH, int64_t sT, int64_t oB, int64_t oH, int64_t oT, float scale, void* stream);
 
@@ -257,7 +259,7 @@ int octic_attn_bwd(const void* q, const void* k, const void* v, const void* o, c
 /* AttentionD8 straight on packed rows - reference octic_vits/d8_layers.py:631-656 (head split of the five-irrep
  * projection output, F.scaled_dot_product_attention, re-assembly of the irreps) WITHOUT the pack / unpack copies:
  * qkv = LinearD8 output [B, T, 3*8c] (row stride ld_qkv elements), o = packed [B, T, 8c] input of the output
- * projection.  c / H must be 10 (head_dim 80), bf16.  lse [B,H,T] as in octic_attn_fwd. */
+ * projection.  c / H must be 10 (head_dim 80) or 8 (head_dim 64), bf16, T <= 16384.  lse [B,H,T] as in octic_attn_fwd. */
 int octic_attn_fwd_packed(const void* qkv, void* o, float* lse, int64_t B, int H, int T, int c, int64_t ld_qkv,
                           int64_t ld_o, float scale, void* stream);
 /* Backward of octic_attn_fwd_packed (autograd of d8_layers.py:631-656): dqkv packed like qkv (row stride ld_g)

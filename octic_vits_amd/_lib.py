@@ -15,7 +15,7 @@ F32, BF16 = 0, 1
 ABI_VERSION = 20
 # knobs of octic_route_override (include/octic_hip.h)
 (ROUTE_DENSE_TILE, ROUTE_DENSE_SPLIT, ROUTE_WGRAD_SLABS, ROUTE_WGRAD_TILE, ROUTE_LINEAR_RING, ROUTE_RING_EVEN,
- ROUTE_ATTN_LEGACY, ROUTE_ATTN_ONLINE, ROUTE_ATTN_BWD_PAIR, ROUTE_DENSE_IMAGE, ROUTE_DENSE_CLS2) = range(11)
+ ROUTE_ATTN_LEGACY, ROUTE_ATTN_ONLINE, ROUTE_ATTN_BWD_PAIR, ROUTE_DENSE_IMAGE, ROUTE_DENSE_CLS2, ROUTE_ATTN_STREAM) = range(12)
 
 c_i64, c_int, c_float, c_void_p = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
@@ -159,11 +159,17 @@ def lib():
     return _LIB
 
 
+# the values set through route_override (the library keeps the authoritative table; this mirror lets the Python side
+# name the launches a forced route runs, e.g. KERNEL_TIMER under ROUTE_ATTN_STREAM)
+ROUTES = {}
+
+
 def route_override(knob: int, value: int) -> int:
     """Force a kernel / tiling choice for an A/B or a test (0 = automatic); returns the previous value."""
     old = lib().octic_route_override(knob, value)
     if old < 0:
         raise ValueError(f"octic_route_override: unknown knob {knob}")
+    ROUTES[knob] = value
     return old
 
 

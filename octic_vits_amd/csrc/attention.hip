@@ -1,4 +1,5 @@
-// Softmax attention core for gfx950, bf16, short sequences (T <= 512: ViT token counts 197 / 257).
+// Softmax attention core for gfx950, bf16, short sequences (T <= 320: ViT token counts 197 / 257; longer sequences go to
+// the streaming kernels of csrc/attn_stream.hip, which the entry points below route to).
 // Replaces F.scaled_dot_product_attention in AttentionD8 (reference octic_vits/d8_layers.py:645-648) and in the
 // standard blocks (deit/vit.py:41-45).  On MI355X the stock SDPA backward for head_dim 80 takes ~640 us per call
 // (64 x 16 heads x 257 tokens); the sequence is short enough for a much simpler structure than flash attention:
@@ -243,18 +244,6 @@ inline int attn_waves(int nt) { return nt == kAttnWaves + 1 ? kAttnWaves : nt; }
 
 // One pass of the forward over key tiles kt0, kt0+kstep, ... < nt for query tile `qtile`; online softmax state
 // (m, l: per lane = per query, l still split between the half-waves) and O^T accumulators are updated in place.
-// lane (r, half) holds Q[query][16 ks + 8 half .. +7] = B operand of K Q^T
-template <int KS>
-__device__ __forceinline__ void load_rows8(bf16x8 (&f)[KS], const bf16* base, int64_t st, int tile, int T, int lane,
-                                           const HeadMap m = HeadMap{0, 0}) {
-  const int r = lane & 31, half = lane >> 5;
-  const int i = tile * 32 + r;
-  const int ic = i < T ? i : T - 1;
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-    f[ks] = __builtin_bit_cast(bf16x8, hm_load16(base + (int64_t)ic * st, 2 * ks + half, m));
-}
-
 template <int KS, int DT>
 __device__ __forceinline__ void fwd_pass(const AttnArgs& a, const char* Ks, const char* Vs, int rsk, int rsv,
                                          const bf16x8 (&qf)[KS], int kt0, int kstep, int nt, int lane, float& m,
@@ -722,7 +711,7 @@ static int attn_fwd_launch(const AttnArgs& a, int64_t B, hipStream_t s) {
   size_t smem = (size_t)nt * 32 * (rsk + rsv);
   const size_t comb = ((size_t)W * 32 * (DT * 32 + kPartPad) + (2 * W + 1) * 32) * sizeof(float);
   if (nt != W && comb > smem) smem = comb;
-  if (smem > 160 * 1024) return OCTIC_ESHAPE;
+  if (smem > 160 * 1024) return attn_stream_fwd_launch(a, B, s);   // K and V of the head do not fit: stream them
   static DeviceOnce once;
   if (once.first()) {
     (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<KS, DT, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -743,44 +732,6 @@ static int attn_fwd_launch(const AttnArgs& a, int64_t B, hipStream_t s) {
 //   attn_bwd_dkv_kernel: wave owns 32 KEYS; Q and dO rows (+ lse, delta) in LDS; un-swapped scores X'[q][key]
 //                        keep the key on the lane, so dK^T and dV^T accumulate lane-locally.
 // =================================================================================================
-// per-query operands of the dq kernel for one query tile: Q and dO fragments, log-sum-exp, delta = <dO, O>
-template <int KS>
-struct DqRows {
-  bf16x8 qf[KS], dof[KS], of[KS];
-  float lse, delta;
-};
-// issue the loads only: the staging loads follow right behind, so the two memory round trips overlap ...
-template <int KS>
-__device__ __forceinline__ void load_dq_rows(DqRows<KS>& R, const AttnBwdArgs& a, int64_t in_off, int64_t o_off,
-                                             int64_t stat_off, int qtile, int lane, const HeadMaps& hm) {
-  const int T = a.T;
-  const int r = lane & 31, half = lane >> 5;
-  const int qi = qtile * 32 + r;
-  const int qc = qi < T ? qi : T - 1;
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    R.qf[ks] = __builtin_bit_cast(bf16x8, hm_load16(a.q + in_off + (int64_t)qc * a.sT, 2 * ks + half, hm.q));
-    R.dof[ks] = __builtin_bit_cast(bf16x8, hm_load16(a.dout + o_off + (int64_t)qc * a.oT, 2 * ks + half, hm.o));
-    R.of[ks] = __builtin_bit_cast(bf16x8, hm_load16(a.o + o_off + (int64_t)qc * a.oT, 2 * ks + half, hm.o));
-  }
-  R.lse = a.lse[stat_off + qc];
-}
-// ... and delta = <dO, O> once everything has landed
-template <int KS>
-__device__ __forceinline__ void finish_dq_rows(DqRows<KS>& R, const AttnBwdArgs& a, int64_t stat_off, int qtile,
-                                               int lane, bool write_delta) {
-  const int r = lane & 31, half = lane >> 5;
-  const int qi = qtile * 32 + r;
-  float delta = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) delta += (float)R.dof[ks][j] * (float)R.of[ks][j];
-  delta += __shfl_xor(delta, 32, 64);
-  R.delta = delta;
-  if (write_delta && qi < a.T && half == 0) a.delta[stat_off + qi] = delta;
-}
-
 template <int KS, int DT>
 __device__ __forceinline__ void dq_pass(const AttnBwdArgs& a, const char* Ks, const char* Vs, int rs,
                                         const DqRows<KS>& R, int kt0, int kstep, int nt, int lane,
@@ -944,24 +895,6 @@ __global__ __launch_bounds__(MAXT) void attn_bwd_dq_kernel(AttnBwdArgs a, int rs
 }
 
 // dK^T, dV^T of key tile `ktile` accumulated over query tiles qt0, qt0+qstep, ...
-// the wave's key rows: lane (r, half) holds K[key][16 ks + 8 half ..] and V[key][..] = B operands (key on the lane)
-template <int KS>
-struct KvRows {
-  bf16x8 kf[KS], vf[KS];
-};
-template <int KS>
-__device__ __forceinline__ void load_kv_rows(KvRows<KS>& R, const AttnBwdArgs& a, int64_t in_off, int ktile, int lane,
-                                             const HeadMaps& hm) {
-  const int r = lane & 31, half = lane >> 5;
-  const int ki = ktile * 32 + r;
-  const int kcl = ki < a.T ? ki : a.T - 1;
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    R.kf[ks] = __builtin_bit_cast(bf16x8, hm_load16(a.k + in_off + (int64_t)kcl * a.sT, 2 * ks + half, hm.k));
-    R.vf[ks] = __builtin_bit_cast(bf16x8, hm_load16(a.v + in_off + (int64_t)kcl * a.sT, 2 * ks + half, hm.v));
-  }
-}
-
 template <int KS, int DT>
 __device__ __forceinline__ void dkv_pass(const AttnBwdArgs& a, const char* Qs, const char* Ds, const float* lse_s,
                                          const float* del_s, int rs, const KvRows<KS>& R, int qt0, int qstep, int nt,
@@ -1116,7 +1049,7 @@ static int attn_bwd_launch(const AttnBwdArgs& a, int64_t B, int phase, hipStream
   const size_t comb = (size_t)W * 32 * (DT * 32 + kPartPad) * sizeof(float);
   if (nt != W && comb > smem_dq) smem_dq = comb;
   if (nt != W && comb > smem_kv) smem_kv = comb;
-  if (smem_kv > 160 * 1024 || smem_dq > 160 * 1024) return OCTIC_ESHAPE;
+  if (smem_kv > 160 * 1024 || smem_dq > 160 * 1024) return attn_stream_bwd_launch(a, B, phase, s);   // do not fit: stream
   static DeviceOnce once;
   if (once.first()) {
     (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<KS, DT, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1136,6 +1069,10 @@ static int attn_bwd_launch(const AttnBwdArgs& a, int64_t B, int phase, hipStream
   return launch_status();
 }
 
+// T > 320, or every T under OCTIC_ROUTE_ATTN_STREAM = 1: the streaming kernels (csrc/attn_stream.hip)
+static bool attn_stream_route(int T) { return T > 320 || route(OCTIC_ROUTE_ATTN_STREAM) == 1; }
+constexpr int kAttnMaxT = 16384;
+
 }  // namespace octic
 
 using namespace octic;
@@ -1145,7 +1082,7 @@ extern "C" {
 int octic_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int H, int T, int hd,
                    int64_t sB, int64_t sH, int64_t sT, int64_t oB, int64_t oH, int64_t oT, float scale, void* stream) {
   if (!q || !k || !v || !o) return OCTIC_ENULL;
-  if (B <= 0 || H <= 0 || T <= 0 || T > 320 || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
+  if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o)) & 15) return OCTIC_EALIGN;
   if ((sB | sH | sT | oB | oH | oT) & 7) return OCTIC_EALIGN;   // rows must stay 16-byte aligned (8 bf16)
   AttnArgs a;
@@ -1157,6 +1094,7 @@ int octic_attn_fwd(const void* q, const void* k, const void* v, void* o, float* 
   a.scale_log2 = scale * 1.4426950408889634f;
   a.cv_in = a.cv_out = a.c = 0;
   hipStream_t s = (hipStream_t)stream;
+  if (attn_stream_route(T)) return attn_stream_fwd_launch(a, B, s);
   switch (hd / 16) {
     case 1: return attn_fwd_launch<1, 1>(a, B, s);
     case 2: return attn_fwd_launch<2, 1>(a, B, s);
@@ -1175,7 +1113,7 @@ int octic_attn_bwd(const void* q, const void* k, const void* v, const void* o, c
                    int phase, void* stream) {
   if (!q || !k || !v || !o || !dout || !lse || !delta || !dq || !dk || !dv) return OCTIC_ENULL;
   if (phase < 1 || phase > 3) return OCTIC_ESHAPE;
-  if (B <= 0 || H <= 0 || T <= 0 || T > 320 || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
+  if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o) | ((uintptr_t)dout) | ((uintptr_t)dq) |
        ((uintptr_t)dk) | ((uintptr_t)dv)) & 15)
     return OCTIC_EALIGN;
@@ -1190,6 +1128,7 @@ int octic_attn_bwd(const void* q, const void* k, const void* v, const void* o, c
   a.scale_log2 = scale * 1.4426950408889634f;
   a.cv_in = a.cv_out = a.c = 0;
   hipStream_t s = (hipStream_t)stream;
+  if (attn_stream_route(T)) return attn_stream_bwd_launch(a, B, phase, s);
   switch (hd / 16) {
     case 1: return attn_bwd_launch<1, 1>(a, B, phase, s);
     case 2: return attn_bwd_launch<2, 1>(a, B, phase, s);
@@ -1210,7 +1149,7 @@ int octic_attn_bwd(const void* q, const void* k, const void* v, const void* o, c
 int octic_attn_fwd_packed(const void* qkv, void* o, float* lse, int64_t B, int H, int T, int c, int64_t ld_qkv,
                           int64_t ld_o, float scale, void* stream) {
   if (!qkv || !o) return OCTIC_ENULL;
-  if (B <= 0 || H <= 0 || T <= 0 || T > 320 || c <= 0 || (c != 10 * H && c != 8 * H)) return OCTIC_ESHAPE;
+  if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || c <= 0 || (c != 10 * H && c != 8 * H)) return OCTIC_ESHAPE;
   if (((((uintptr_t)qkv) | ((uintptr_t)o)) & 15) || ((ld_qkv | ld_o) & 7) || ld_qkv < 24 * c || ld_o < 8 * c) return OCTIC_EALIGN;
   AttnArgs a;
   a.q = a.k = a.v = (const bf16*)qkv;
@@ -1220,6 +1159,7 @@ int octic_attn_fwd_packed(const void* qkv, void* o, float* lse, int64_t B, int H
   a.H = H; a.T = T; a.hd = 8 * (c / H);
   a.scale_log2 = scale * 1.4426950408889634f;
   a.cv_in = 3 * c; a.cv_out = c; a.c = c;
+  if (attn_stream_route(T)) return attn_stream_fwd_launch(a, B, (hipStream_t)stream);
   if (a.hd == 64) return attn_fwd_launch<4, 2>(a, B, (hipStream_t)stream);
   return attn_fwd_launch<5, 3>(a, B, (hipStream_t)stream);
 }
@@ -1230,7 +1170,7 @@ int octic_attn_bwd_packed(const void* qkv, const void* o, const void* dout, cons
                           int phase, void* stream) {
   if (!qkv || !o || !dout || !lse || !delta || !dqkv) return OCTIC_ENULL;
   if (phase < 1 || phase > 3) return OCTIC_ESHAPE;
-  if (B <= 0 || H <= 0 || T <= 0 || T > 320 || c <= 0 || (c != 10 * H && c != 8 * H)) return OCTIC_ESHAPE;
+  if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || c <= 0 || (c != 10 * H && c != 8 * H)) return OCTIC_ESHAPE;
   if (((((uintptr_t)qkv) | ((uintptr_t)o) | ((uintptr_t)dout) | ((uintptr_t)dqkv)) & 15) || ((ld_qkv | ld_o | ld_g) & 7) ||
       ld_qkv < 24 * c || ld_g < 24 * c || ld_o < 8 * c)
     return OCTIC_EALIGN;
@@ -1243,6 +1183,7 @@ int octic_attn_bwd_packed(const void* qkv, const void* o, const void* dout, cons
   a.scale = scale;
   a.scale_log2 = scale * 1.4426950408889634f;
   a.cv_in = 3 * c; a.cv_out = c; a.c = c;
+  if (attn_stream_route(T)) return attn_stream_bwd_launch(a, B, phase, (hipStream_t)stream);
   if (a.hd == 64) return attn_bwd_launch<4, 2>(a, B, phase, (hipStream_t)stream);
   return attn_bwd_launch<5, 3>(a, B, phase, (hipStream_t)stream);
 }

@@ -190,11 +190,85 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[DT]) {
 }
 
 
+// ---- per-wave row fragments shared by the resident-K/V kernels (csrc/attention.hip) and the streaming ones
+// (csrc/attn_stream.hip)
+// lane (r, half) holds Q[query][16 ks + 8 half .. +7] = B operand of K Q^T
+template <int KS>
+__device__ __forceinline__ void load_rows8(bf16x8 (&f)[KS], const bf16* base, int64_t st, int tile, int T, int lane,
+                                           const HeadMap m = HeadMap{0, 0}) {
+  const int r = lane & 31, half = lane >> 5;
+  const int i = tile * 32 + r;
+  const int ic = i < T ? i : T - 1;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+    f[ks] = __builtin_bit_cast(bf16x8, hm_load16(base + (int64_t)ic * st, 2 * ks + half, m));
+}
+
+// per-query operands of the dq kernel for one query tile: Q and dO fragments, log-sum-exp, delta = <dO, O>
+template <int KS>
+struct DqRows {
+  bf16x8 qf[KS], dof[KS], of[KS];
+  float lse, delta;
+};
+// issue the loads only: the staging loads follow right behind, so the two memory round trips overlap ...
+template <int KS>
+__device__ __forceinline__ void load_dq_rows(DqRows<KS>& R, const AttnBwdArgs& a, int64_t in_off, int64_t o_off,
+                                             int64_t stat_off, int qtile, int lane, const HeadMaps& hm) {
+  const int T = a.T;
+  const int r = lane & 31, half = lane >> 5;
+  const int qi = qtile * 32 + r;
+  const int qc = qi < T ? qi : T - 1;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    R.qf[ks] = __builtin_bit_cast(bf16x8, hm_load16(a.q + in_off + (int64_t)qc * a.sT, 2 * ks + half, hm.q));
+    R.dof[ks] = __builtin_bit_cast(bf16x8, hm_load16(a.dout + o_off + (int64_t)qc * a.oT, 2 * ks + half, hm.o));
+    R.of[ks] = __builtin_bit_cast(bf16x8, hm_load16(a.o + o_off + (int64_t)qc * a.oT, 2 * ks + half, hm.o));
+  }
+  R.lse = a.lse[stat_off + qc];
+}
+// ... and delta = <dO, O> once everything has landed
+template <int KS>
+__device__ __forceinline__ void finish_dq_rows(DqRows<KS>& R, const AttnBwdArgs& a, int64_t stat_off, int qtile,
+                                               int lane, bool write_delta) {
+  const int r = lane & 31, half = lane >> 5;
+  const int qi = qtile * 32 + r;
+  float delta = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) delta += (float)R.dof[ks][j] * (float)R.of[ks][j];
+  delta += __shfl_xor(delta, 32, 64);
+  R.delta = delta;
+  if (write_delta && qi < a.T && half == 0) a.delta[stat_off + qi] = delta;
+}
+
+// the wave's key rows: lane (r, half) holds K[key][16 ks + 8 half ..] and V[key][..] = B operands (key on the lane)
+template <int KS>
+struct KvRows {
+  bf16x8 kf[KS], vf[KS];
+};
+template <int KS>
+__device__ __forceinline__ void load_kv_rows(KvRows<KS>& R, const AttnBwdArgs& a, int64_t in_off, int ktile, int lane,
+                                             const HeadMaps& hm) {
+  const int r = lane & 31, half = lane >> 5;
+  const int ki = ktile * 32 + r;
+  const int kcl = ki < a.T ? ki : a.T - 1;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    R.kf[ks] = __builtin_bit_cast(bf16x8, hm_load16(a.k + in_off + (int64_t)kcl * a.sT, 2 * ks + half, hm.k));
+    R.vf[ks] = __builtin_bit_cast(bf16x8, hm_load16(a.v + in_off + (int64_t)kcl * a.sT, 2 * ks + half, hm.v));
+  }
+}
+
+
 // csrc/attn80.hip: persistent head_dim-80 kernels (all operands by LDS-DMA, one head ahead)
 int attn80_fwd_ok(const AttnArgs& a);
 int attn80_fwd_launch(const AttnArgs& a, int64_t B, hipStream_t s);
 // csrc/attn80_bwd.hip: single-pass backward (dq, dk, dv from ONE recomputation of P) for head_dim 80, T = 257
 int attn80_bwd_ok(const AttnBwdArgs& a);
 int attn80_bwd_launch(const AttnBwdArgs& a, int64_t B, hipStream_t s);
+// csrc/attn_stream.hip: K / V (Q / dO) streamed through LDS in blocks, any T (the entry points allow T <= 16384)
+int attn_stream_fwd_launch(const AttnArgs& a, int64_t B, hipStream_t s);
+int attn_stream_bwd_launch(const AttnBwdArgs& a, int64_t B, int phase, hipStream_t s);
 
 }  // namespace octic

@@ -708,7 +708,7 @@ class AttentionD8(nn.Module):
             on = Octic(_R.AttnPackedRaggedFn.apply(qkv.packed, rag, self.num_heads, c, (8 * c // self.num_heads) ** -0.5), c)
         elif (OF.ATTN_PACKED and drop == 0. and qkv.packed.is_cuda
                 and OF.ops.attn_packed_ok(qkv.packed.shape[1], c, self.num_heads, qkv.packed.dtype)):
-            # head split, softmax core and irrep re-assembly in the attention kernels themselves (head_dim 80)
+            # head split, softmax core and irrep re-assembly in the attention kernels themselves (head_dim 80 / 64, any T)
             if torch.compiler.is_compiling():
                 from . import dispatch as _D   # noqa: F401
                 on = Octic(torch.ops.octic.attn_packed(qkv.packed, self.num_heads, c, (8 * c // self.num_heads) ** -0.5)[0], c)
@@ -716,7 +716,7 @@ class AttentionD8(nn.Module):
                 on = Octic(OF.AttnPackedFn.apply(qkv.packed, self.num_heads, c, (8 * c // self.num_heads) ** -0.5), c)
         else:
             q, k, v = OF.PackHeadsFn.apply(qkv.packed, self.num_heads, c)
-            # HIP attention core for the shapes it covers (bf16, T <= 320, no dropout); torch SDPA (== self.att) otherwise
+            # HIP attention core for the shapes it covers (bf16, T <= 16384, no dropout); torch SDPA (== self.att) otherwise
             o = OF.attention_core(q, k, v, dropout_p=drop)
             on = Octic(OF.UnpackHeadsFn.apply(o, c), c)
         if self.proj_drop.active or resid is None:

@@ -482,7 +482,7 @@ class AttnFusedQKVFn(torch.autograd.Function):
 
 def attention_core(q, k, v, dropout_p=0.0):
     """Drop-in for F.scaled_dot_product_attention(q, k, v) on [B,H,T,hd]: HIP kernels for the shapes they cover
-    (bf16, short sequences, no dropout), torch SDPA otherwise (f32 exact path, odd head sizes)."""
+    (bf16, T <= 16384, no dropout), torch SDPA otherwise (f32 exact path, fp16, head sizes that are not multiples of 16)."""
     B, H, T, hd = q.shape
     if dropout_p == 0.0 and q.is_cuda and ops.attn_supported(T, hd, q.dtype):
         return AttnFn.apply(q, k, v, hd ** -0.5)

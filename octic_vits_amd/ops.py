@@ -512,17 +512,30 @@ def attn_fwd(q, k, v, scale):
     t = KERNEL_TIMER.start()
     check(lib().octic_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, T, hd, st[0], st[1], st[2],
                                o.stride(0), o.stride(1), o.stride(2), float(scale), _stream(q)))
-    KERNEL_TIMER.stop(t, "attn_fwd_kernel", 4 * q.numel() * 2, 4.0 * B * H * T * T * hd)
+    KERNEL_TIMER.stop(t, _attn_fwd_name(T, hd), 4 * q.numel() * 2, 4.0 * B * H * T * T * hd)
     return o, lse
 
 
+ATTN_MAX_T = 16384      # octic_attn_*: longest sequence of the streaming kernels
+
+
 def attn_supported(T, hd, dtype):
-    """Shapes the HIP attention core handles (others keep torch SDPA): bf16, T <= 320, hd % 16 == 0, LDS fits."""
-    if dtype != torch.bfloat16 or T > 320 or hd % 16 or hd > 128:
-        return False
+    """Shapes the HIP attention core handles (others keep torch SDPA): bf16, 0 < T <= 16384, hd % 16 == 0, hd <= 128."""
+    return dtype == torch.bfloat16 and 0 < T <= ATTN_MAX_T and hd % 16 == 0 and 0 < hd <= 128
+
+
+def attn_streams(T, hd):
+    """True where the entry points run the streaming kernels (csrc/attn_stream.hip: K / V through LDS in blocks):
+    T > 320, a head whose K and V do not fit in LDS at once, or every shape under ROUTE_ATTN_STREAM = 1."""
+    if T > 320 or _lib.ROUTES.get(_lib.ROUTE_ATTN_STREAM, 0) == 1:
+        return True
     tp = (T + 31) // 32 * 32
     cols = max((hd + 31) // 32 * 32, hd)
-    return 2 * tp * (cols * 2 + 16) + 2 * tp * 4 <= 160 * 1024
+    return 2 * tp * (cols * 2 + 16) + 2 * tp * 4 > 160 * 1024
+
+
+def _attn_fwd_name(T, hd):
+    return "attn_fwd_stream_kernel" if attn_streams(T, hd) else "attn_fwd_kernel"
 
 
 # Single-pass attention backward (csrc/attn80_bwd.hip: P and dS computed once, 10 T^2 hd FLOP) for head_dim 80, T = 257;
@@ -532,6 +545,8 @@ ATTN_BWD_FUSED = True
 
 def _attn_bwd_phases(T, hd):
     """(phase, timer name, algorithmic bytes per element of q, flops per B H T^2 hd) of the backward launches."""
+    if attn_streams(T, hd):                               # phase 1: dq (3 products), phase 2: dk, dv (4 products)
+        return ((1, "attn_bwd_dq_stream_kernel", 6, 6.0), (2, "attn_bwd_dkv_stream_kernel", 6, 8.0))
     if ATTN_BWD_FUSED and hd == 80 and (T == 257 or 192 < T <= 256 or T <= 64):    # csrc/attn80_bwd.hip: attn80_bwd_ok
         return ((3, "attn_bwd_kernel", 8, 10.0),)         # reads q k v o dO, writes dq dk dv
     return ((1, "attn_bwd_dq_kernel", 6, 6.0), (2, "attn_bwd_dkv_kernel", 6, 8.0))
@@ -553,8 +568,8 @@ def attn_bwd(q, k, v, o, dout, lse, scale, dq, dk, dv):
 
 
 def attn_packed_ok(T, c, H, dtype):
-    """Shapes of octic_attn_{fwd,bwd}_packed: bf16, head_dim 80 (c = 10 H: ViT-H/14) or 64 (c = 8 H: ViT-L/16), T <= 320."""
-    return dtype == torch.bfloat16 and c in (10 * H, 8 * H) and 0 < T <= 320 and attn_supported(T, 8 * (c // H), dtype)
+    """Shapes of octic_attn_{fwd,bwd}_packed: bf16, head_dim 80 (c = 10 H: ViT-H/14) or 64 (c = 8 H: ViT-L/16), T <= 16384."""
+    return dtype == torch.bfloat16 and c in (10 * H, 8 * H) and attn_supported(T, 8 * (c // H), dtype)
 
 
 def attn_fwd_packed(qkv, H, c, scale, out=None):
@@ -565,7 +580,7 @@ def attn_fwd_packed(qkv, H, c, scale, out=None):
     t = KERNEL_TIMER.start()
     check(lib().octic_attn_fwd_packed(_p(qkv), _p(o), _p(lse), B, H, T, c, qkv.stride(1), o.stride(1), float(scale),
                                       _stream(qkv)))
-    KERNEL_TIMER.stop(t, "attn_fwd_kernel", 4 * B * T * 8 * c * 2, 4.0 * B * T * T * 8 * c)
+    KERNEL_TIMER.stop(t, _attn_fwd_name(T, 8 * (c // H)), 4 * B * T * 8 * c * 2, 4.0 * B * T * T * 8 * c)
     return o, lse
 
 
