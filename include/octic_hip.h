@@ -330,6 +330,22 @@ int octic_adamw_step(void* const* p, void* const* g, void* const* m, void* const
                      const int* tensor_chunk_begin, int ntensors, int nchunks, float* workspace, float lr, float beta1,
                      float beta2, float eps, float max_grad_norm, int step, float ema_decay, void* const* bf16_shadow,
                      void* stream);
+/* The same two steps with the schedule-driven hyper-parameters read from DEVICE memory (same kernels, same arithmetic):
+ * lr = [ntensors] f32, the absolute learning rate of each tensor (read once per chunk, like wd); ema_decay = ONE f32 (may
+ * be NULL when ema is NULL), the EMA weight 1 - decay is formed on the device in f32.  A hipGraph that captured the call
+ * follows whatever the host copies into those buffers between replays (timm / DINOv2 schedules, layer-wise lr decay).
+ * With every lr[i] = x and *ema_decay = d the results equal octic_lamb_step / octic_adamw_step(lr = x, ema_decay = d)
+ * bit for bit.                                                                                                           */
+int octic_lamb_step_hp(void* const* p, void* const* g, void* const* m, void* const* v, void* const* ema, const float* wd,
+                       const int* chunk_tensor, const int64_t* chunk_off, const int* chunk_len,
+                       const int* tensor_chunk_begin, int ntensors, int nchunks, float* workspace, const float* lr,
+                       float beta1, float beta2, float eps, float max_grad_norm, int step, const float* ema_decay,
+                       void* const* bf16_shadow, void* stream);
+int octic_adamw_step_hp(void* const* p, void* const* g, void* const* m, void* const* v, void* const* ema, const float* wd,
+                        const int* chunk_tensor, const int64_t* chunk_off, const int* chunk_len,
+                        const int* tensor_chunk_begin, int ntensors, int nchunks, float* workspace, const float* lr,
+                        float beta1, float beta2, float eps, float max_grad_norm, int step, const float* ema_decay,
+                        void* const* bf16_shadow, void* stream);
 
 /* ---- standard (non-equivariant) half of the hybrid: row kernels around the library GEMMs ----------------
  * The reference's standard blocks (deit/models_v2.py Layer_scale_init_Block, used for the second half of the

@@ -59,6 +59,10 @@ _PROTOS = {
                                                   c_int, c_float, c_void_p, c_void_p]),
     "octic_adamw_step": (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_float,
                                                    c_int, c_float, c_void_p, c_void_p]),
+    "octic_lamb_step_hp": (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
+                                                     c_int, c_void_p, c_void_p, c_void_p]),
+    "octic_adamw_step_hp": (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
+                                                      c_int, c_void_p, c_void_p, c_void_p]),
     "octic_dense_blocks": (c_int, [c_i64]),
     "octic_dense_layernorm_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int,
                                           c_float, c_void_p]),

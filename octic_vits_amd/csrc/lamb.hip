@@ -10,6 +10,8 @@
 //   4. ratios   : per-tensor trust ratio |p|/|u|                       (tiny, fixed-order => reproducible)
 //   5. stage2   : p -= lr*ratio*u ; ema += (1-decay)(p-ema)
 // Traffic 4+28+20 = 52 B/param vs ~100+ for the op-by-op foreach formulation.  Bound: HBM.
+// The *_hp entry points read lr (per tensor) and the EMA decay from device memory instead of launch arguments, so a
+// captured step follows a schedule the host writes between replays; the scalar entry points run the same kernels.
 #include "octic_common.hpp"
 
 namespace octic {
@@ -154,8 +156,10 @@ __global__ __launch_bounds__(256) void lamb_ratio_kernel(LambTables t, int ntens
   ratio[ti] = (t.wd[ti] != 0.f && wn > 0.f && un > 0.f) ? wn / un : 1.0f;
 }
 
-__global__ __launch_bounds__(256) void lamb_stage2_kernel(LambTables t, const float* scal, const float* ratio, float lr,
-                                                          float ema_w) {
+// lr_t (may be null): per-tensor learning rates, else the scalar lr.  decay_t (may be null): the EMA decay as one device
+// float, else ema_w = 1 - decay as the host formed it (the same f32 subtraction).
+__global__ __launch_bounds__(256) void lamb_stage2_kernel(LambTables t, const float* scal, const float* ratio,
+                                                          const float* lr_t, float lr, const float* decay_t, float ema_w) {
   const int ch = blockIdx.x;
   if (scal[2] != 0.f) return;                  // skipped step: weights, EMA and bf16 copies stay as they are
   const int ti = t.chunk_tensor[ch];
@@ -165,7 +169,8 @@ __global__ __launch_bounds__(256) void lamb_stage2_kernel(LambTables t, const fl
   float* e = t.ema ? t.ema[ti] + off : nullptr;
   bf16* sh = (t.shadow && t.shadow[ti]) ? t.shadow[ti] + off : nullptr;
   const int n = t.chunk_len[ch];
-  const float step = lr * ratio[ti];
+  const float step = (lr_t ? lr_t[ti] : lr) * ratio[ti];
+  if (e && decay_t) ema_w = 1.0f - decay_t[0];
   const bool al = ((((uintptr_t)p) | ((uintptr_t)u) | ((uintptr_t)e)) & 15) == 0 && (((uintptr_t)sh) & 7) == 0;
   const int n4 = al ? (n >> 2) : 0;
   for (int i = threadIdx.x; i < n4; i += 256) {
@@ -194,11 +199,12 @@ using namespace octic;
 
 extern "C" {
 
+// lr_t / decay_t: the device hyper-parameters of the *_hp entry points (null from the scalar ones: lr / ema_decay are used)
 static int lamb_impl(void* const* p, void* const* g, void* const* m, void* const* v, void* const* ema, const float* wd,
                      const int* chunk_tensor, const int64_t* chunk_off, const int* chunk_len,
-                     const int* tensor_chunk_begin, int ntensors, int nchunks, float* workspace, float lr, float beta1,
-                     float beta2, float eps, float max_grad_norm, int step, float ema_decay, void* const* bf16_shadow,
-                     void* stream, int adam) {
+                     const int* tensor_chunk_begin, int ntensors, int nchunks, float* workspace, const float* lr_t,
+                     float lr, float beta1, float beta2, float eps, float max_grad_norm, int step, const float* decay_t,
+                     float ema_decay, void* const* bf16_shadow, void* stream, int adam) {
   if (!p || !g || !m || !v || !wd || !chunk_tensor || !chunk_off || !chunk_len || !tensor_chunk_begin || !workspace)
     return OCTIC_ENULL;
   if (ntensors <= 0 || nchunks <= 0 || step < 0) return OCTIC_ESHAPE;
@@ -218,7 +224,7 @@ static int lamb_impl(void* const* p, void* const* g, void* const* m, void* const
   lamb_scalars_kernel<<<1, 256, 0, s>>>(g2, nchunks, max_grad_norm, beta1, beta2, step, scal);
   lamb_stage1_kernel<<<nchunks, 256, 0, s>>>(t, scal, beta1, beta2, eps, p2, u2);
   lamb_ratio_kernel<<<(ntensors + 255) / 256, 256, 0, s>>>(t, ntensors, p2, u2, ratio, adam);
-  lamb_stage2_kernel<<<nchunks, 256, 0, s>>>(t, scal, ratio, lr, ema ? 1.0f - ema_decay : 0.f);
+  lamb_stage2_kernel<<<nchunks, 256, 0, s>>>(t, scal, ratio, lr_t, lr, decay_t, ema ? 1.0f - ema_decay : 0.f);
   return launch_status();
 }
 
@@ -227,8 +233,8 @@ int octic_lamb_step(void* const* p, void* const* g, void* const* m, void* const*
                     const int* tensor_chunk_begin, int ntensors, int nchunks, float* workspace, float lr, float beta1,
                     float beta2, float eps, float max_grad_norm, int step, float ema_decay, void* const* bf16_shadow,
                     void* stream) {
-  return lamb_impl(p, g, m, v, ema, wd, chunk_tensor, chunk_off, chunk_len, tensor_chunk_begin, ntensors, nchunks, workspace, lr,
-                   beta1, beta2, eps, max_grad_norm, step, ema_decay, bf16_shadow, stream, 0);
+  return lamb_impl(p, g, m, v, ema, wd, chunk_tensor, chunk_off, chunk_len, tensor_chunk_begin, ntensors, nchunks, workspace,
+                   nullptr, lr, beta1, beta2, eps, max_grad_norm, step, nullptr, ema_decay, bf16_shadow, stream, 0);
 }
 
 int octic_adamw_step(void* const* p, void* const* g, void* const* m, void* const* v, void* const* ema, const float* wd,
@@ -236,8 +242,28 @@ int octic_adamw_step(void* const* p, void* const* g, void* const* m, void* const
                      const int* tensor_chunk_begin, int ntensors, int nchunks, float* workspace, float lr, float beta1,
                      float beta2, float eps, float max_grad_norm, int step, float ema_decay, void* const* bf16_shadow,
                      void* stream) {
-  return lamb_impl(p, g, m, v, ema, wd, chunk_tensor, chunk_off, chunk_len, tensor_chunk_begin, ntensors, nchunks, workspace, lr,
-                   beta1, beta2, eps, max_grad_norm, step, ema_decay, bf16_shadow, stream, 1);
+  return lamb_impl(p, g, m, v, ema, wd, chunk_tensor, chunk_off, chunk_len, tensor_chunk_begin, ntensors, nchunks, workspace,
+                   nullptr, lr, beta1, beta2, eps, max_grad_norm, step, nullptr, ema_decay, bf16_shadow, stream, 1);
+}
+
+int octic_lamb_step_hp(void* const* p, void* const* g, void* const* m, void* const* v, void* const* ema, const float* wd,
+                       const int* chunk_tensor, const int64_t* chunk_off, const int* chunk_len,
+                       const int* tensor_chunk_begin, int ntensors, int nchunks, float* workspace, const float* lr,
+                       float beta1, float beta2, float eps, float max_grad_norm, int step, const float* ema_decay,
+                       void* const* bf16_shadow, void* stream) {
+  if (!lr || (ema && !ema_decay)) return OCTIC_ENULL;
+  return lamb_impl(p, g, m, v, ema, wd, chunk_tensor, chunk_off, chunk_len, tensor_chunk_begin, ntensors, nchunks, workspace,
+                   lr, 0.f, beta1, beta2, eps, max_grad_norm, step, ema_decay, 0.f, bf16_shadow, stream, 0);
+}
+
+int octic_adamw_step_hp(void* const* p, void* const* g, void* const* m, void* const* v, void* const* ema, const float* wd,
+                        const int* chunk_tensor, const int64_t* chunk_off, const int* chunk_len,
+                        const int* tensor_chunk_begin, int ntensors, int nchunks, float* workspace, const float* lr,
+                        float beta1, float beta2, float eps, float max_grad_norm, int step, const float* ema_decay,
+                        void* const* bf16_shadow, void* stream) {
+  if (!lr || (ema && !ema_decay)) return OCTIC_ENULL;
+  return lamb_impl(p, g, m, v, ema, wd, chunk_tensor, chunk_off, chunk_len, tensor_chunk_begin, ntensors, nchunks, workspace,
+                   lr, 0.f, beta1, beta2, eps, max_grad_norm, step, ema_decay, 0.f, bf16_shadow, stream, 1);
 }
 
 int64_t octic_lamb_workspace_floats(int ntensors, int nchunks) { return 8 + 3 * (int64_t)nchunks + ntensors; }

@@ -535,10 +535,13 @@ class _TeacherRefresh:
 
 class SSLTrainer:
     """One iteration of dinov2/train/train.py:253-296: schedules' values are arguments; zero_grad -> forward_backward (bf16
-    autocast student, ssl_default_config.yaml:25-31) -> clip_grad_norm_(3.0) per sub-model -> AdamW -> teacher EMA."""
+    autocast student, ssl_default_config.yaml:25-31) -> clip_grad_norm_(3.0) per sub-model -> AdamW -> teacher EMA.
+
+    The recipe's schedules (``schedules.build_schedulers``) drive ``step(images, teacher_temp, momentum, lr, wd,
+    last_layer_lr)``: given values go into every optimizer group by the reference's rule (``schedules.apply_optim_scheduler``)."""
 
     def __init__(self, arch: SSLMetaArch, lr=1e-3, weight_decay=0.04, betas=(0.9, 0.999), clip_grad=3.0, autocast=True,
-                 distributed=False, local_rank=0, fused_optimizer=None, own_reducer=True):
+                 distributed=False, local_rank=0, fused_optimizer=None, own_reducer=True, optim_groups=None):
         """fused_optimizer (default: on the GPU): clip_grad_norm_ per sub-model, AdamW and the teacher's EMA as the fused
         multi-tensor HIP step (train.FusedLamb(adam=True) = octic_adamw_step: two streaming passes per sub-model that also
         leave the bf16 weight copies of the standard half and the prepared LinearD8 weights behind) instead of ~60 foreach
@@ -546,16 +549,29 @@ class SSLTrainer:
         own_reducer (distributed only, round 6): average every student gradient (backbone and heads) with train.GradReducer
         instead of a DistributedDataParallel wrapper around the backbone + a flat all-reduce for the rest - no autograd hooks,
         so the step keeps its batched finishes and paired weight gradients at N > 1; a pass that uses its modules more than once
-        (the set-by-set crop loop) reduces everything after the backward pass."""
+        (the set-by-set crop loop) reduces everything after the backward pass.
+        optim_groups: None = two groups (decay / no decay by ``SSLMetaArch._no_decay``); {"layerwise_decay": 0.9,
+        "patch_embed_lr_mult": 0.2} = the reference's groups per sub-model (get_params_groups_with_decay + fuse_params_groups,
+        ssl_meta_arch.py:385-402: layer-wise lr decay, no decay for biases / norms / layer scales, the head's last layer
+        flagged), with lr = lr * lr_multiplier and weight_decay = weight_decay * wd_multiplier until ``step`` is given
+        values."""
         self.arch, self.clip_grad, self.autocast = arch, clip_grad, autocast
         self.device_type = next(arch.parameters()).device.type
         self.lr, self.weight_decay, self.betas = lr, weight_decay, betas
+        self.optim_groups = None if optim_groups is None else dict(optim_groups)
         self.fused = (self.device_type == "cuda") if fused_optimizer is None else bool(fused_optimizer)
         self._fused_opts = None                                   # built after the first backward (which tensors get gradients)
         self._teacher_refresh = None
         self.optimizer = None
         if not self.fused:
-            self.optimizer = torch.optim.AdamW(arch.get_params_groups(weight_decay), lr=lr, betas=betas)
+            if self.optim_groups is None:
+                groups = arch.get_params_groups(weight_decay)
+                for g, wdm in zip(groups, (1.0, 0.0)):
+                    g.update(lr_multiplier=1.0, wd_multiplier=wdm, is_last_layer=False)
+            else:
+                groups = [g for k in arch.student for g in self._submodel_groups(
+                    k, [(n, p) for n, p in arch.student[k].named_parameters() if p.requires_grad])]
+            self.optimizer = torch.optim.AdamW(groups, lr=lr, betas=betas)
             from .functional import track_optimizer
             track_optimizer(arch.student, self.optimizer)         # AdamW's foreach path updates parameters in place
         self._reducer = None
@@ -587,7 +603,31 @@ class SSLTrainer:
                 gradient_as_bucket_view=True)
             arch._student_call = lambda g, l, m: tuple(self._ddp(g, l, m))
 
-    def step(self, images, teacher_temp=0.07, momentum=0.992):
+    def _submodel_groups(self, k, named):
+        """The optimizer groups of student sub-model ``k`` over its tensors ``named`` ((name, tensor) pairs; see optim_groups),
+        each with lr, weight_decay, lr_multiplier, wd_multiplier and is_last_layer."""
+        arch = self.arch
+        if self.optim_groups is None:
+            groups = [{"params": [p for n, p in named if not arch._no_decay(k + "." + n, p)], "weight_decay": self.weight_decay,
+                       "wd_multiplier": 1.0},
+                      {"params": [p for n, p in named if arch._no_decay(k + "." + n, p)], "weight_decay": 0.0,
+                       "wd_multiplier": 0.0}]
+            for g in groups:
+                g.update(lr=self.lr, lr_multiplier=1.0, is_last_layer=False)
+            return groups
+        from .schedules import fuse_params_groups, params_groups_with_decay
+        keep = {id(p) for _, p in named}
+        per = params_groups_with_decay(arch.student[k], lr_decay_rate=self.optim_groups.get("layerwise_decay", 1.0),
+                                       patch_embed_lr_mult=self.optim_groups.get("patch_embed_lr_mult", 1.0))
+        groups = fuse_params_groups([d for d in per if id(d["params"]) in keep])
+        for g in groups:
+            g["lr"] = self.lr * g["lr_multiplier"]
+            g["weight_decay"] = self.weight_decay * g["wd_multiplier"]
+        return groups
+
+    def step(self, images, teacher_temp=0.07, momentum=0.992, lr=None, wd=None, last_layer_lr=None):
+        """lr / wd / last_layer_lr (the schedules' values of this iteration, dinov2/train/train.py:266-271): applied to every
+        group of every sub-model before the optimizer step; None leaves the groups as they are."""
         self.arch.train()
         if self.optimizer is not None:
             self.optimizer.zero_grad(set_to_none=True)
@@ -614,11 +654,13 @@ class SSLTrainer:
         if self._ddp is not None and _world() > 1:                # the heads (outside the DDP wrapper) + the backbone's small tensors
             self._flat_reducer.reduce()
         if self.fused:
-            self._fused_step(momentum)
+            self._fused_step(momentum, lr, wd, last_layer_lr)
             return loss_dict
         if self.clip_grad:
             for k in self.arch.student:
                 torch.nn.utils.clip_grad_norm_(self.arch.student[k].parameters(), self.clip_grad)
+        from .schedules import apply_optim_scheduler
+        apply_optim_scheduler(self.optimizer.param_groups, lr, wd, last_layer_lr)
         self.optimizer.step()
         self.arch.update_teacher(momentum)
         return loss_dict
@@ -635,9 +677,10 @@ class SSLTrainer:
                 and getattr(bb, "_single_use_pass", False))
         return _FinishScope(ops.DEFERRED_FINISHES, safe)
 
-    def _fused_step(self, momentum):
-        """One octic_adamw_step per sub-model (dinov2/train/train.py:274-296: clip per sub-model, optimizer step, teacher EMA).
+    def _fused_step(self, momentum, lr=None, wd=None, last_layer_lr=None):
+        """One octic_adamw_step_hp per sub-model (dinov2/train/train.py:274-296: clip per sub-model, optimizer step, teacher EMA).
         Like torch.optim.AdamW, tensors that receive no gradient are left alone - the set is fixed by the first step."""
+        from .schedules import apply_optim_scheduler
         from .train import FusedLamb, library_gemm_layers, octic_weight_preps
         arch = self.arch
         if self._fused_opts is None:
@@ -648,8 +691,7 @@ class SSLTrainer:
                 live = [(n, p) for n, p in sp.items() if p.requires_grad and p.grad is not None]
                 if not live:
                     continue
-                groups = [{"params": [p for n, p in live if not arch._no_decay(k + "." + n, p)], "weight_decay": self.weight_decay},
-                          {"params": [p for n, p in live if arch._no_decay(k + "." + n, p)], "weight_decay": 0.0}]
+                groups = self._submodel_groups(k, live)
                 twin = {id(p): tp[n].data for n, p in live}
                 sub = arch.student[k]
                 self._fused_opts[k] = (FusedLamb(groups, lr=self.lr, betas=self.betas, eps=1e-8,
@@ -661,7 +703,8 @@ class SSLTrainer:
             have = sum(1 for p in arch.student[k].parameters() if p.requires_grad and p.grad is not None)
             if have != nlive:
                 raise RuntimeError(f"SSLTrainer: the set of student tensors with gradients changed ({have} vs {nlive} in '{k}')")
-            opt.lr, opt.ema_decay = self.lr, momentum
+            apply_optim_scheduler(opt.param_groups, lr, wd, last_layer_lr)
+            opt.ema_decay = momentum
             opt.step()
         from .functional import invalidate_weight_caches
         invalidate_weight_caches(arch.teacher)                    # the kernel rewrote the teacher's parameters

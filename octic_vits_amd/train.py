@@ -96,9 +96,15 @@ class Lamb(torch.optim.Optimizer):
 
 
 class FusedLamb:
-    """LAMB + EMA as ONE fused multi-tensor HIP step (octic_lamb_step, csrc/lamb.hip): same math as ``Lamb`` /
+    """LAMB + EMA as ONE fused multi-tensor HIP step (octic_lamb_step_hp, csrc/lamb.hip): same math as ``Lamb`` /
     ``ModelEma`` above, 5 launches per step instead of ~100 foreach kernels, 52 B/param of HBM traffic.
-    Gradients are consumed (overwritten) by the step."""
+    Gradients are consumed (overwritten) by the step.
+
+    ``param_groups``: one dict per constructor group with ``params``, ``lr``, ``weight_decay`` and whatever other keys the
+    caller passed (``lr_multiplier``, ``initial_lr``, ...), like ``torch.optim``'s: a scheduler writes ``group["lr"]`` /
+    ``group["weight_decay"]`` and the next step - eager or a replay of a captured one - uses the new values.  ``opt.lr = x``
+    gives every tensor x; ``ema_decay`` is read at every step.  The kernels read the per-tensor lr, wd and the EMA decay
+    from one device buffer (``hyper``) that ``push_hyper`` refreshes, stream-ordered, whenever a value changed."""
 
     CHUNK = 65536
 
@@ -107,18 +113,23 @@ class FusedLamb:
         """shadow_layers: (nn.Linear, functional.DenseWeightCache) pairs; their weights/biases get a bf16 copy
         written by the update kernel itself, handed to the cache after every step (no per-step cast launches).
         adam=True: the same fused passes without the layer-wise trust ratio = AdamW with decoupled weight decay
-        (octic_adamw_step; the DINOv2 recipe's optimizer).  ema_tensors: {id(param): tensor} - the EMA is kept IN these tensors
-        (the DINOv2 teacher's parameters) instead of a flat buffer of this object; ema_decay is then the per-step momentum."""
+        (octic_adamw_step_hp; the DINOv2 recipe's optimizer).  ema_tensors: {id(param): tensor} - the EMA is kept IN these tensors
+        (the DINOv2 teacher's parameters) instead of a flat buffer of this object; ema_decay is then the per-step momentum.
+        A group without ``lr`` takes ``lr``; one without ``weight_decay`` gets 0."""
         from . import _lib
         self._lib = _lib
         self.adam = bool(adam)
-        self.lr, self.betas, self.eps, self.max_grad_norm, self.ema_decay = lr, betas, eps, max_grad_norm, ema_decay
-        self.params, wds = [], []
+        self._lr, self.betas, self.eps, self.max_grad_norm, self.ema_decay = lr, betas, eps, max_grad_norm, ema_decay
+        self.params, self.param_groups, self._group_sizes = [], [], []
         for g in param_groups:
-            for p in g["params"]:
-                if p.requires_grad:
-                    self.params.append(p)
-                    wds.append(float(g.get("weight_decay", 0.0)))
+            ps = [p for p in g["params"] if p.requires_grad]
+            group = {k: v for k, v in g.items() if k != "params"}
+            group["params"] = ps
+            group.setdefault("lr", lr)
+            group.setdefault("weight_decay", 0.0)
+            self.param_groups.append(group)
+            self._group_sizes.append(len(ps))
+            self.params += ps
         dev = self.params[0].device
         if dev.type != "cuda":
             raise RuntimeError("FusedLamb runs on the GPU only")
@@ -151,7 +162,12 @@ class FusedLamb:
         self.chunk_off = torch.tensor(co, dtype=i64, device=dev)
         self.chunk_len = torch.tensor(cl, dtype=i32, device=dev)
         self.tensor_chunk_begin = torch.tensor(tb, dtype=i32, device=dev)
-        self.wd = torch.tensor(wds, dtype=torch.float32, device=dev)
+        # the hyper-parameters the kernels read from device memory: [ntensors] lr | [ntensors] wd | EMA decay
+        n = len(self.params)
+        key = self._hyper_key()
+        self.hyper = torch.from_numpy(self._hyper_values(key)).to(dev)
+        self.lr_t, self.wd, self.ema_decay_t = self.hyper[:n], self.hyper[n:2 * n], self.hyper[2 * n:]
+        self._hp_key, self._hp_ring, self._hp_i = key, None, 0
         base = lambda t: [t.data_ptr() + 4 * o for o in offs]
         self.p_ptrs = torch.tensor([p.data_ptr() for p in self.params], dtype=i64, device=dev)
         self.m_ptrs = torch.tensor(base(self.m), dtype=i64, device=dev)
@@ -212,6 +228,50 @@ class FusedLamb:
         self._prep_source, self._prep_batch = prep_source, None
 
     @property
+    def lr(self):
+        return self._lr
+
+    @lr.setter
+    def lr(self, value):
+        """One learning rate for every tensor (every group's ``lr`` := value)."""
+        self._lr = value
+        for g in self.param_groups:
+            g["lr"] = value
+
+    def _hyper_key(self):
+        return (tuple((float(g["lr"]), float(g["weight_decay"])) for g in self.param_groups), float(self.ema_decay or 0.0))
+
+    def _hyper_values(self, key):
+        """The contents of ``hyper`` for ``key``: groups expanded to their tensors in f64, rounded to f32 once."""
+        import numpy as np
+        groups, decay = key
+        lr = np.repeat(np.array([a for a, _ in groups], dtype=np.float64), self._group_sizes)
+        wd = np.repeat(np.array([b for _, b in groups], dtype=np.float64), self._group_sizes)
+        return np.concatenate([lr, wd, [decay]]).astype(np.float32)
+
+    def push_hyper(self):
+        """Upload the groups' lr / weight_decay and ``ema_decay`` if any changed since the last upload: one stream-ordered
+        H2D copy from a pinned slot (four in rotation; a slot is refilled only after its copy finished), so the host never
+        waits for the work in front of it.  Nothing is uploaded while the stream is capturing: a captured step reads
+        ``hyper`` when it is replayed, and ``GraphedStep.replay`` calls this in front of every replay (a graph of one's own
+        that contains ``step``: call it before each ``replay()``).  Returns True when it uploaded."""
+        key = self._hyper_key()
+        if key == self._hp_key or torch.cuda.is_current_stream_capturing():
+            return False
+        if self._hp_ring is None:
+            self._hp_ring = [[torch.empty(self.hyper.numel(), dtype=torch.float32).pin_memory(), None] for _ in range(4)]
+        slot = self._hp_ring[self._hp_i]
+        self._hp_i = (self._hp_i + 1) % len(self._hp_ring)
+        if slot[1] is not None:
+            slot[1].synchronize()
+        slot[0].copy_(torch.from_numpy(self._hyper_values(key)))
+        self.hyper.copy_(slot[0], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        self._hp_key = key
+        return True
+
+    @property
     def last_grad_norm(self):
         return self.ws[1]
 
@@ -230,13 +290,16 @@ class FusedLamb:
     def state_dict(self):
         """Everything a resumed run needs: first / second moments and EMA as flat f32 tensors (the layout is the
         parameter order of the param groups, each tensor padded to a multiple of 4 elements), the device-side
-        bias-correction step (ws[3]) and skipped-step counter (ws[6]), and the hyper-parameters."""
+        bias-correction step (ws[3]) and skipped-step counter (ws[6]), and the hyper-parameters - per group its lr,
+        weight_decay and the other keys with a number as value (a scheduler's ``initial_lr``, ``lr_multiplier``, ...)."""
+        num = lambda v: isinstance(v, (int, float))
         return {"m": self.m.detach().clone(), "v": self.v.detach().clone(),
                 "ema": None if self.ema is None else self.ema.detach().clone(),
                 "device_step": float(self.ws[3].item()), "skipped_steps": float(self.ws[6].item()),
                 "step_count": int(self.step_count), "numel": [int(p.numel()) for p in self.params],
                 "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
-                          "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay}}
+                          "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay},
+                "param_groups": [{k: v for k, v in g.items() if k != "params" and num(v)} for g in self.param_groups]}
 
     def load_state_dict(self, sd):
         if list(sd["numel"]) != [int(p.numel()) for p in self.params]:
@@ -252,7 +315,16 @@ class FusedLamb:
             self.ws[6] = float(sd["skipped_steps"])
         self.step_count = int(sd["step_count"])
         h = sd.get("hyper", {})
-        self.lr, self.eps = h.get("lr", self.lr), h.get("eps", self.eps)
+        groups = sd.get("param_groups")
+        if groups is not None and len(groups) != len(self.param_groups):
+            raise ValueError("FusedLamb.load_state_dict: the number of parameter groups differs from the checkpoint's")
+        if groups is None:
+            self.lr = h.get("lr", self.lr)             # (a checkpoint without groups: one lr for every tensor)
+        else:
+            self._lr = h.get("lr", self._lr)
+            for g, saved in zip(self.param_groups, groups):
+                g.update(saved)
+        self.eps = h.get("eps", self.eps)
         self.betas = tuple(h.get("betas", self.betas))
         self.max_grad_norm, self.ema_decay = h.get("max_grad_norm", self.max_grad_norm), h.get("ema_decay", self.ema_decay)
 
@@ -286,8 +358,9 @@ class FusedLamb:
 
     def prepare_capture(self):
         """Page-locked staging for the gradient address table of a step that is about to be captured (host
-        allocations are not allowed while a stream is capturing)."""
+        allocations are not allowed while a stream is capturing), and the current hyper-parameters on the device."""
         self._g_capture_host = torch.empty(len(self.params), dtype=torch.int64).pin_memory()
+        self.push_hyper()
 
     def zero_grad(self, set_to_none=True):
         for p in self.params:
@@ -339,19 +412,20 @@ class FusedLamb:
             slot[1] = torch.cuda.Event()
             slot[1].record()
             self._g_key = key
+        self.push_hyper()
         self.step_count += 1
         vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.m.device).cuda_stream)
-        fn = self._lib.lib().octic_adamw_step if self.adam else self._lib.lib().octic_lamb_step
+        fn = self._lib.lib().octic_adamw_step_hp if self.adam else self._lib.lib().octic_lamb_step_hp
         from . import ops as _ops
         nparam = int(self.m.numel())
         kt = _ops.KERNEL_TIMER.start()
         self._lib.check(fn(
             vp(self.p_ptrs), vp(self.g_ptrs), vp(self.m_ptrs), vp(self.v_ptrs), vp(self.e_ptrs), vp(self.wd),
             vp(self.chunk_tensor), vp(self.chunk_off), vp(self.chunk_len), vp(self.tensor_chunk_begin),
-            self.ntensors, self.nchunks, vp(self.ws), float(self.lr), float(self.betas[0]), float(self.betas[1]),
+            self.ntensors, self.nchunks, vp(self.ws), vp(self.lr_t), float(self.betas[0]), float(self.betas[1]),
             float(self.eps), float(self.max_grad_norm or 0.0), 0 if self.device_step else self.step_count,
-            float(self.ema_decay or 0.0),
+            vp(self.ema_decay_t),
             vp(self.s_ptrs), stream))
         # algorithmic bytes per parameter: gradient norm 4 + (g, m, v, p in; m, v, u out) 28 + (u, p, ema in; p, ema out) 20
         # + the bf16 copies of the standard half's weights 2 (csrc/lamb.hip)
@@ -936,7 +1010,11 @@ class Trainer:
     32 GPUs x 64, experiments/train_deit.py:7-12,66): gradients of the micro-batch mean losses are averaged, the
     all-reduce runs once, in the last micro-batch's backward (``no_sync`` before).  ``opt_eps`` is the recipe's
     ``--opt-eps`` (deit/main.py:68, default 1e-8, which timm forwards to apex FusedLAMB).  ``bf16_buckets`` halves
-    the all-reduce payload (DDP's bf16 compression hook: buckets are cast to bf16, summed, cast back)."""
+    the all-reduce payload (DDP's bf16 compression hook: buckets are cast to bf16, summed, cast back).
+
+    Schedules (the recipe's cosine with warm-up, deit/main.py ``lr_scheduler.step(epoch)``): write the new values into
+    ``trainer.optimizer.param_groups[*]["lr"]`` (and ``["weight_decay"]``, ``trainer.optimizer.ema_decay``), then call
+    ``step`` or ``GraphedStep.replay`` - both pass them to the kernels; a captured step needs no re-capture."""
 
     def __init__(self, model, lr=3e-3, weight_decay=0.02, ema_decay=0.99996, distributed=False, local_rank=0,
                  fused_optimizer=True, tuned_gemms=True, opt_eps=1e-8, accum_steps=1, bf16_buckets=False,
@@ -1283,6 +1361,8 @@ class GraphedStep:
             self.samples.copy_(samples, non_blocking=True)
         if targets is not None and targets.data_ptr() != self.targets.data_ptr():
             self.targets.copy_(targets, non_blocking=True)
+        # a schedule's new lr / weight decay / EMA decay: copied in front of the replay (the captured kernels read them)
+        t.optimizer.push_hyper()
         self.graph.replay()
         t.optimizer.step_count += 1
         t._watch.push(self.loss)
