@@ -496,11 +496,13 @@ int octic_dense_gemm_plan(int M, int N, int K, int mode, int tokens, int* out4);
  * dY, X bf16 row-major (ldy, ldx row strides in elements), N % 256 == 0, K % 256 == 0 or K % 320 == 0, at most 1024
  * output tiles, M * ld * 2 < 2^31.  The reduction over the M token rows is cut into row slabs (one workgroup per slab and
  * 256 x 256 or 256 x 320 tile, all tiles of a slab walking the same rows in lockstep); the f32 partial tiles are summed in slab order by the
- * last workgroup of a tile (bitwise reproducible).  workspace: octic_dense_wgrad_workspace_bytes(M,N,K) bytes, zeroed
+ * last workgroup of a tile (bitwise reproducible).  Shapes those tiles do not divide with N % 64 == 0 and K % 64 == 0 (the
+ * narrow DeiT-III blocks, D = 192 / 384) take 64 x 64 tiles: row slabs of f32 partial tiles summed in slab order by a
+ * second launch (also bitwise reproducible).  workspace: octic_dense_wgrad_workspace_bytes(M,N,K) bytes, zeroed
  * once at allocation.                                                                                                 */
 int64_t octic_dense_wgrad_workspace_bytes(int M, int N, int K);
 /* Tile width along K the launch will use: 256 (256 x 256 tiles, whenever K % 256 == 0) or 320 (256 x 320 tiles: K % 320 == 0
- * only).  Informational (profilers see dense_tn_kernel<4> / <5>). */
+ * only), 64 on the narrow path, 0 for a shape no path takes.  Informational (profilers see dense_tn_kernel<4> / <5>). */
 int octic_dense_wgrad_tile(int M, int N, int K);
 int octic_dense_wgrad_tn(const void* dY, const void* X, int M, int N, int K, int64_t ldy, int64_t ldx, float* dW,
                          void* workspace, void* stream);

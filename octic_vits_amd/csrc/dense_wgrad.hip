@@ -489,6 +489,80 @@ __global__ __launch_bounds__(512, 1) void dense_tn_kernel(DwArgs a) {
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------------- narrow shapes
+// dW = dY^T X where the 256-wide tiles do not divide the output: N and K multiples of 64 (the standard blocks of the narrow
+// DeiT-III models: D = 192 / 384 give qkv 576 / 1152 x D, proj D x D, fc1 4D x D, fc2 D x 4D).  64 x 64 output tile per
+// workgroup (256 threads, 4 x 4 outputs each, f32 FMA on operands staged through LDS 32 token rows at a time); the token
+// rows are cut into S slabs like the wide kernel's: S = 1 writes dW, S > 1 leaves f32 partial tiles that
+// dense_tn_narrow_finish adds in slab order (bitwise reproducible, no atomics).
+constexpr int DWN_T = 64;                     // output tile side
+constexpr int DWN_R = 32;                     // token rows per LDS stage
+
+__global__ __launch_bounds__(256) void dense_tn_narrow_kernel(const bf16* __restrict__ Y, const bf16* __restrict__ X,
+                                                              int64_t ldy, int64_t ldx, int M, int N, int K, int tiles_k,
+                                                              int S, float* __restrict__ out) {
+  __shared__ float ys[DWN_R][DWN_T];
+  __shared__ float xs[DWN_R][DWN_T];
+  const int tile = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
+  const int n0 = (tile / tiles_k) * DWN_T, k0 = (tile % tiles_k) * DWN_T;
+  const int64_t r0 = (int64_t)M * s / S, r1 = (int64_t)M * (s + 1) / S;
+  const int tx = t & 15, ty = t >> 4;         // outputs (n0 + 4 ty + i, k0 + 4 tx + j)
+  const int lr = t >> 3, lc = (t & 7) * 8;    // staging: row lr, 8 columns from lc (32 rows x 64 columns per operand)
+  float acc[4][4] = {};
+  for (int64_t rb = r0; rb < r1; rb += DWN_R) {
+    const int64_t r = rb + lr;
+    float yv[8], xv[8];
+    if (r < r1) {
+      load8<bf16>(Y + r * ldy + n0 + lc, yv);
+      load8<bf16>(X + r * ldx + k0 + lc, xv);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) yv[i] = xv[i] = 0.f;
+    }
+    __syncthreads();                          // the previous stage has been consumed
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      ys[lr][lc + i] = yv[i];
+      xs[lr][lc + i] = xv[i];
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int q = 0; q < DWN_R; ++q) {
+      const float4 a = *reinterpret_cast<const float4*>(&ys[q][4 * ty]);
+      const float4 b = *reinterpret_cast<const float4*>(&xs[q][4 * tx]);
+      const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
+    }
+  }
+  if (S == 1) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      *reinterpret_cast<float4*>(out + (int64_t)(n0 + 4 * ty + i) * K + k0 + 4 * tx) =
+          make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+  } else {                                    // partial tile [s][tile] as 64 x 64 row-major
+    float* p = out + ((int64_t)s * gridDim.x + tile) * (DWN_T * DWN_T);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      *reinterpret_cast<float4*>(p + (4 * ty + i) * DWN_T + 4 * tx) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+  }
+}
+
+__global__ __launch_bounds__(256) void dense_tn_narrow_finish(const float* __restrict__ part, int tiles, int tiles_k, int S,
+                                                              int N, int K, float* __restrict__ W) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;       // one output element of dW [N, K]
+  if (e >= (int64_t)N * K) return;
+  const int n = (int)(e / K), k = (int)(e - (int64_t)n * K);
+  const int tile = (n / DWN_T) * tiles_k + k / DWN_T;
+  const int off = (n % DWN_T) * DWN_T + k % DWN_T;
+  float v = 0.f;
+  for (int s = 0; s < S; ++s) v += part[((int64_t)s * tiles + tile) * (DWN_T * DWN_T) + off];
+  W[e] = v;
+}
+
 }  // namespace octic
 
 using namespace octic;
@@ -510,6 +584,32 @@ static int dw_launch(DwArgs& a, hipStream_t s) {
 }
 
 extern "C" {
+
+// The narrow path (dense_tn_narrow_kernel): taken where the wide tiles do not divide the shape; N, K multiples of 64.
+static bool dwn_shape(int N, int K) { return N % DWN_T == 0 && K % DWN_T == 0 && ((N % DW_T) || ((K % 256) && (K % 320))); }
+static int dwn_slabs(int tiles, int M) {
+  const int steps = (M + DWN_R - 1) / DWN_R;
+  int S = (2 * device_cus() + tiles - 1) / tiles;                 // about two workgroups per CU
+  S = S > 32 ? 32 : S;
+  S = S > steps / 4 ? steps / 4 : S;                               // at least four stages per slab
+  return S < 1 ? 1 : S;
+}
+static int64_t dwn_workspace_bytes(int M, int N, int K) {
+  const int tiles = (N / DWN_T) * (K / DWN_T);
+  return (int64_t)tiles * dwn_slabs(tiles, M) * DWN_T * DWN_T * 4 + 4096;
+}
+static int dwn_launch(const bf16* Y, const bf16* X, int64_t ldy, int64_t ldx, int M, int N, int K, float* dW, void* workspace,
+                      hipStream_t s) {
+  const int tiles_k = K / DWN_T, tiles = (N / DWN_T) * tiles_k;
+  const int S = dwn_slabs(tiles, M);
+  float* part = (float*)((char*)workspace + 4096);                 // (the wide kernel's ticket region stays untouched)
+  dense_tn_narrow_kernel<<<dim3(tiles, S), 256, 0, s>>>(Y, X, ldy, ldx, M, N, K, tiles_k, S, S == 1 ? dW : part);
+  if (S > 1) {
+    const int64_t n = (int64_t)N * K;
+    dense_tn_narrow_finish<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(part, tiles, tiles_k, S, N, K, dW);
+  }
+  return launch_status();
+}
 
 // Row slabs: the items (tiles8 x S) run in ceil(items / CUs) rounds of ceil(steps / S) reduction steps each; every item
 // also pays a fixed prologue + slab epilogue (about 8 steps' worth).  Pick the S with the shortest estimate.
@@ -560,12 +660,14 @@ static DwPlan dw_plan(int M, int N, int K) {
   return make(4);
 }
 
-int octic_dense_wgrad_tile(int M, int N, int K) {      // tile width the launch uses (256 | 320)
+int octic_dense_wgrad_tile(int M, int N, int K) {      // tile width the launch uses (256 | 320; 64 = the narrow path)
+  if (M > 0 && N > 0 && K > 0 && dwn_shape(N, K)) return DWN_T;
   if (M <= 0 || N <= 0 || K <= 0 || (N % DW_T) || ((K % 256) && (K % 320))) return 0;
   return dw_plan(M, N, K).kw * 64;
 }
 
 int64_t octic_dense_wgrad_workspace_bytes(int M, int N, int K) {
+  if (M > 0 && dwn_shape(N, K)) return dwn_workspace_bytes(M, N, K);
   // room for either width and any forced slab count: [4 KiB tickets (<= 1024 tiles) | slabs]
   const int steps = (M + DW_BR - 1) / DW_BR;
   int64_t need = 0;
@@ -582,6 +684,11 @@ int64_t octic_dense_wgrad_workspace_bytes(int M, int N, int K) {
 int octic_dense_wgrad_tn(const void* dY, const void* X, int M, int N, int K, int64_t ldy, int64_t ldx, float* dW,
                          void* workspace, void* stream) {
   if (!dY || !X || !dW || !workspace) return OCTIC_ENULL;
+  if (M > 0 && N > 0 && K > 0 && dwn_shape(N, K)) {
+    if ((ldy % 8) || (ldx % 8) || ldy < N || ldx < K) return OCTIC_ESHAPE;
+    if ((((uintptr_t)dY) | ((uintptr_t)X) | ((uintptr_t)dW)) & 15) return OCTIC_EALIGN;
+    return dwn_launch((const bf16*)dY, (const bf16*)X, ldy, ldx, M, N, K, dW, workspace, (hipStream_t)stream);
+  }
   if (M <= 0 || N <= 0 || K <= 0 || (N % DW_T) || ((K % 256) && (K % 320)) || (ldy % 8) || (ldx % 8)) return OCTIC_ESHAPE;
   if ((int64_t)M * ldy * 2 >= (1ll << 31) || (int64_t)M * ldx * 2 >= (1ll << 31)) return OCTIC_ESHAPE;   // 32-bit buffer offsets
   if ((((uintptr_t)dY) | ((uintptr_t)X) | ((uintptr_t)dW)) & 15) return OCTIC_EALIGN;

@@ -4,6 +4,7 @@ registry reachable through ``create_model`` (same call shape as ``timm.create_mo
 from .d8_layers import Layer_scale_init_BlockD8
 from .model import OcticVisionTransformer
 from .vit import Layer_scale_init_Block
+from . import vit_models as _std
 
 _LOCAL_REGISTRY = {}
 
@@ -52,3 +53,9 @@ def d8_inv_early_deit_huge_patch14(img_size=224, **kwargs):
 @register_model
 def d8_inv_early_deit_large_patch16(img_size=224, **kwargs):
     return _octic_deit(img_size, 16, 1024, 24, 16, True, kwargs)
+
+
+# the standard DeiT-III baselines of the same comparison (deit/vit.py:396-546; experiments/complexity.py:19-28)
+for _fn in _std.LS_FACTORIES:
+    register_model(_fn)
+from . import dinov2_vit  # noqa: E402,F401  (registers the standard DINOv2 vit_large / vit_huge)

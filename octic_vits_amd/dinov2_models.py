@@ -279,3 +279,7 @@ def d8_inv_early_dinov2_vit_large_patch16(patch_size=16, num_register_tokens=0, 
 @register_model
 def d8_inv_early_dinov2_vit_huge_patch16(patch_size=16, num_register_tokens=0, **kwargs):
     return _dinov2(patch_size, 1280, 32, 16, True, num_register_tokens, kwargs)
+
+
+# the standard DINOv2 baselines (dinov2/models/vision_transformer.py:342-367), registered next to the octic models
+from .dinov2_vit import DinoVisionTransformer, vit_huge, vit_large  # noqa: E402,F401

@@ -290,7 +290,11 @@ _DW_WS = {}
 
 
 def dense_wgrad_ok(M, N, K):
-    return N % 256 == 0 and (K % 256 == 0 or K % 320 == 0) and (N // 256) * (K // 256) <= 256 and M > 0
+    """Shapes csrc/dense_wgrad.hip takes: the 256 x (256 | 320) tiles where they divide N x K (at most 256 of them), else
+    the 64 x 64 narrow path for N, K multiples of 64 (the standard blocks of DeiT-III tiny / small: D = 192, 384)."""
+    wide = N % 256 == 0 and (K % 256 == 0 or K % 320 == 0)
+    narrow = N % 64 == 0 and K % 64 == 0 and not wide
+    return M > 0 and ((wide and (N // 256) * (K // 256) <= 256) or narrow)
 
 
 # Where a weight gradient is to be WRITTEN (train.Trainer under DistributedDataParallel, one micro-batch): parameter address ->
