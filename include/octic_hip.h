@@ -530,6 +530,47 @@ int octic_soft_ce_bwd(const void* s, int s_dtype, int64_t lds, const float* tpro
                       const float* g, const float* lse, const float* tsum, void* ds, int64_t ldd, int64_t rows, int K,
                       void* stream);
 
+/* ---- linear-probe evaluation of a frozen backbone (dinov2/eval/linear.py) ----------------------------------------------
+ * The grid of nn.Linear(K_h, C) classifiers of setup_linear_classifiers (linear.py:237-258) as one launch per stage over
+ * all classifiers.  Every classifier reads a column range [col0, col0 + K) of one f32 feature row
+ * F = [cls(L-n) | ... | cls(L-1) | mean patch(L-1)] (create_linear_input, linear.py:173-185) and is described by one entry of
+ * a DEVICE table; tile0 is the running sum of K / 64 over the entries before it (the table is in tile0 order).  K % 64 == 0,
+ * col0 % 4 == 0, w / mw 16-byte aligned, W is [C, K] row-major (nn.Linear's layout); the host cannot see the table, so
+ * these are the caller's to keep.  Exact f32 (f32-input MFMA), no atomics, fixed summation orders: bitwise reproducible. */
+typedef struct {
+  float* w;       /* [C, K] weight           */
+  float* b;       /* [C]    bias             */
+  float* mw;      /* [C, K] momentum of w    */
+  float* mb;      /* [C]    momentum of b    */
+  int32_t col0;   /* first feature column    */
+  int32_t K;      /* input width             */
+  int32_t lr_index; /* index into the device learning-rate buffer of octic_probe_sgd */
+  int32_t tile0;  /* sum of K / 64 over the entries before this one */
+} octic_probe_head;
+/* F[b, i D : (i+1) D] = float(cls[i][b, :]) for i < n (n <= 4; cls[i] + b cls_ld[i] is image b's class token of the i-th
+ * normed block output), F[b, n D : (n+1) D] = the mean of the P patch tokens patch[b, t, :] (strides patch_ld_b /
+ * patch_ld_t in elements) of the last one: f32 sum in token order, times 1/P, rounded to the token dtype as torch.mean
+ * rounds it.  cls and cls_ld are HOST arrays of n entries; tokens f32 or bf16; D % 64 == 0.                              */
+int octic_probe_features(const void* const* cls, const int64_t* cls_ld, int n, const void* patch, int64_t patch_ld_b,
+                         int64_t patch_ld_t, int dtype, int64_t B, int P, int D, float* F, int64_t ldf, void* stream);
+/* logits[h][B, C] = F[:, col0_h : col0_h + K_h] W_h^T + b_h for every table entry (LinearClassifier.forward,
+ * linear.py:201-203; AllClassifiers.forward, linear.py:212-213).  B and C arbitrary; logits is [nheads, B, C] contiguous.  */
+int octic_probe_forward(const octic_probe_head* heads, int nheads, const float* F, int64_t ldf, int B, int C, float* logits,
+                        void* stream);
+/* Per logit row: the cross entropy against labels[b] (int64 class indices in [0, C)), rowloss / rowrank (rank = number of
+ * logits strictly greater than the label's; both [nheads, B] scratch) and, when dlogits is not NULL, dlogits =
+ * (softmax - onehot) / B (the gradient of nn.CrossEntropyLoss(), linear.py:357).  Then per classifier, each optional:
+ * loss_mean[h] = the batch mean, loss_sum[h] += the batch sum, topk[2h] += rows with rank < 1, topk[2h+1] += rows with
+ * rank < 5 (the MEAN_ACCURACY top-1 / top-5 of evaluate_linear_classifiers, linear.py:262-312) - device accumulators.    */
+int octic_probe_ce(const float* logits, const int64_t* labels, int nheads, int B, int C, float* dlogits, float* rowloss,
+                   int* rowrank, float* loss_mean, float* loss_sum, int* topk, void* stream);
+/* Weight gradient and torch.optim.SGD(momentum, weight_decay=0) step in one pass (linear.py:361-365, 519): per 64 x 64 tile
+ * of W_h, g = dlogits_h^T F[:, col0_h + ...] summed over b = 0 .. B-1 in order, mw = momentum mw + g, w -= lr[lr_index_h] mw;
+ * the same for the bias with the column sums of dlogits_h.  Zero momentum buffers reproduce SGD's first step.  lr is a
+ * device f32 buffer.  total_ktiles = sum of K_h / 64.                                                                  */
+int octic_probe_sgd(const octic_probe_head* heads, int nheads, int total_ktiles, const float* F, int64_t ldf,
+                    const float* dlogits, int B, int C, const float* lr, float momentum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

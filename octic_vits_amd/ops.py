@@ -1118,3 +1118,48 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
         _finish(cs, cs_rows, N // 2, colsum, None, None, _stream(a), out1_ptr=colsum.data_ptr() + 2 * N)
         return c, colsum
     return c
+
+
+# ------------------------------------------------------------------------------------------ linear probe (csrc/probe.hip)
+def probe_features(pairs, F):
+    """pairs: the (patch tokens [B, P, D], class token [B, D]) tuples of get_intermediate_layers(..., return_class_token=True),
+    at most 4; F: f32 [B, >= (n+1) D].  Writes F[:, :(n+1) D] = [cls ... | mean patch of the last pair]."""
+    n = len(pairs)
+    patch, cls0 = pairs[-1][0], pairs[0][1]
+    _require_cuda(patch)
+    B, P, D = patch.shape
+    dtype = patch.dtype
+    for p, c in pairs:
+        if c.dtype != dtype or p.dtype != dtype or tuple(c.shape) != (B, D) or c.stride(1) != 1:
+            raise ValueError("probe_features: class tokens must be [B, D] rows of one dtype")
+    if patch.stride(2) != 1 or F.dtype != torch.float32 or F.stride(1) != 1 or F.shape[0] < B:
+        raise ValueError("probe_features: patch tokens / F must have contiguous channels")
+    cls = (ctypes.c_void_p * n)(*[c.data_ptr() for _, c in pairs])
+    cls_ld = (ctypes.c_int64 * n)(*[c.stride(0) for _, c in pairs])
+    t = KERNEL_TIMER.start()
+    check(lib().octic_probe_features(cls, cls_ld, n, _p(patch), patch.stride(0), patch.stride(1), dt_code(dtype), B, P, D,
+                                     _p(F), F.stride(0), _stream(patch)))
+    KERNEL_TIMER.stop(t, f"probe_features_kernel<{_DTN[dtype]}>", B * D * (P + n) * patch.element_size() + 4 * B * (n + 1) * D)
+    return F
+
+
+def probe_forward(table, nheads, F, B, C, logits, sumK):
+    t = KERNEL_TIMER.start()
+    check(lib().octic_probe_forward(_p(table), nheads, _p(F), F.stride(0), B, C, _p(logits), _stream(F)))
+    KERNEL_TIMER.stop(t, "probe_forward_kernel", 4 * (C * sumK + nheads * B * C), 2.0 * B * C * sumK)
+
+
+def probe_ce(logits, labels, nheads, B, C, dlogits, rowloss, rowrank, loss_mean=None, loss_sum=None, topk=None):
+    if labels.dtype != torch.int64 or not labels.is_contiguous() or labels.numel() != B:
+        raise ValueError("probe_ce: labels must be a contiguous int64 tensor of B class indices")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_probe_ce(_p(logits), _p(labels), nheads, B, C, _p(dlogits), _p(rowloss), _p(rowrank), _p(loss_mean),
+                               _p(loss_sum), _p(topk), _stream(logits)))
+    KERNEL_TIMER.stop(t, "probe_ce_kernel", 4 * nheads * B * C * (3 if dlogits is not None else 2))
+
+
+def probe_sgd(table, nheads, total_ktiles, F, dlogits, B, C, lr, momentum, sumK):
+    t = KERNEL_TIMER.start()
+    check(lib().octic_probe_sgd(_p(table), nheads, total_ktiles, _p(F), F.stride(0), _p(dlogits), B, C, _p(lr),
+                                float(momentum), _stream(F)))
+    KERNEL_TIMER.stop(t, "probe_sgd_kernel", 16 * C * sumK, 2.0 * B * C * sumK)
