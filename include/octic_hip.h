@@ -571,6 +571,41 @@ int octic_probe_ce(const float* logits, const int64_t* labels, int nheads, int B
 int octic_probe_sgd(const octic_probe_head* heads, int nheads, int total_ktiles, const float* F, int64_t ldf,
                     const float* dlogits, int B, int C, const float* lr, float momentum, void* stream);
 
+/* ---- linear segmentation evaluation of a frozen backbone (dinov2/eval/segmentation/eval_segmentation.py) --------------
+ * Multinomial logistic regression (LogregClassifier, :281-337) on standardised f32 patch features X [N, D] (row stride ldx
+ * elements, 16-byte aligned rows) resident in device memory; W is [C, D] row-major, contiguous.  Supported: 2 <= C <= 256,
+ * D % 64 == 0, N >= 1 (anything else: OCTIC_ESHAPE before any launch).  Exact f32 (f32-input MFMA), no floating-point
+ * atomics, fixed summation orders: bitwise reproducible.  All row and element offsets are 64-bit.
+ * octic_seg_ldd: the row stride of dlogits, 32 ceil(C / 32) floats (columns C .. ldd-1 are written as zero).
+ * octic_seg_slabs: row slabs the weight gradient cuts N into (informational).
+ * octic_seg_workspace_bytes: one workspace (256-byte aligned) serves octic_seg_value_dlogits and octic_seg_wgrad.       */
+int octic_seg_ldd(int C);
+int octic_seg_slabs(int64_t N, int D, int C);
+int64_t octic_seg_workspace_bytes(int64_t N, int D, int C);
+/* value[0] (DEVICE f64) = sum_n CE(X_n W^T + b, y_n) and dlogits [N, ldd] = softmax - onehot; y holds int32 class indices,
+ * a row whose y is outside [0, C) contributes nothing.  The logits never reach memory.                                  */
+int octic_seg_value_dlogits(const float* X, int64_t ldx, int64_t N, int D, const float* W, const float* b, int C,
+                            const int32_t* y, float* dlogits, double* value, void* workspace, void* stream);
+/* pred[n] = argmax_c (X_n W^T + b)_c, the first maximum (LogisticRegression.predict before the classes_ lookup).        */
+int octic_seg_predict(const float* X, int64_t ldx, int64_t N, int D, const float* W, const float* b, int C, int32_t* pred,
+                      void* stream);
+/* dW [C, D] = scale dlogits^T X + lambda W and db [C] = scale colsum(dlogits): N cut into row slabs over all CUs, f32 partial
+ * tiles summed in slab order (f64) by a finish launch.  X is read once, dlogits D / tile-width times.                    */
+int octic_seg_wgrad(const float* X, int64_t ldx, int64_t N, int D, const float* dlogits, int C, const float* W, double scale,
+                    double lambda, float* dW, float* db, void* workspace, void* stream);
+/* StandardScaler (segmentation/utils.py:566-573): per-column mean and population variance over the N rows accumulated in f64
+ * (mean, var: DEVICE f64 [D]), and the transform in place, x = float(float(x - mean) / scale).                          */
+int64_t octic_seg_colstats_workspace_bytes(int64_t N, int D);
+int octic_seg_colstats(const float* X, int64_t ldx, int64_t N, int D, double* mean, double* var, void* workspace, void* stream);
+int octic_seg_standardize(float* X, int64_t ldx, int64_t N, int D, const double* mean, const double* scale, void* stream);
+/* mode[r] = the most frequent of the L pixel labels labels[r, :] (integers of esize 1, 2, 4 or 8 bytes, values 0 .. 255),
+ * the smallest on a tie, as torch.mode (Classifier.fit, eval_segmentation.py:83; LogregClassifier._fit :331).           */
+int octic_seg_patch_mode(const void* labels, int esize, int64_t R, int L, int32_t* mode, void* stream);
+/* counts[t * 256 + pred[r]] += number of pixels of row r with label t, for every t with ignore[t] == 0 (ignore: DEVICE
+ * uint8 [256]; counts: DEVICE int64 [256 * 256], accumulated): the confusion matrix behind accuracy / mIoU (:50-61).     */
+int octic_seg_confusion(const void* labels, int esize, int64_t R, int L, const int32_t* pred, const uint8_t* ignore,
+                        int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

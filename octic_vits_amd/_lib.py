@@ -18,6 +18,7 @@ ABI_VERSION = 20
  ROUTE_ATTN_LEGACY, ROUTE_ATTN_ONLINE, ROUTE_ATTN_BWD_PAIR, ROUTE_DENSE_IMAGE, ROUTE_DENSE_CLS2, ROUTE_ATTN_STREAM) = range(12)
 
 c_i64, c_int, c_float, c_void_p = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+c_double = ctypes.c_double
 
 
 class OcticView(ctypes.Structure):
@@ -139,6 +140,19 @@ _PROTOS = {
     "octic_probe_ce": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
     "octic_probe_sgd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p]),
+    "octic_seg_ldd": (c_int, [c_int]),
+    "octic_seg_slabs": (c_int, [c_i64, c_int, c_int]),
+    "octic_seg_workspace_bytes": (c_i64, [c_i64, c_int, c_int]),
+    "octic_seg_value_dlogits": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
+    "octic_seg_predict": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "octic_seg_wgrad": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "octic_seg_colstats_workspace_bytes": (c_i64, [c_i64, c_int]),
+    "octic_seg_colstats": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "octic_seg_standardize": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p]),
+    "octic_seg_patch_mode": (c_int, [c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p]),
+    "octic_seg_confusion": (c_int, [c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

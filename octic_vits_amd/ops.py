@@ -1163,3 +1163,131 @@ def probe_sgd(table, nheads, total_ktiles, F, dlogits, B, C, lr, momentum, sumK)
     check(lib().octic_probe_sgd(_p(table), nheads, total_ktiles, _p(F), F.stride(0), _p(dlogits), B, C, _p(lr),
                                 float(momentum), _stream(F)))
     KERNEL_TIMER.stop(t, "probe_sgd_kernel", 16 * C * sumK, 2.0 * B * C * sumK)
+
+
+# ------------------------------------------------------------------------------------------ segmentation logreg (csrc/segeval.hip)
+def _seg_rows(X):
+    """X as f32 rows: [N, D] with contiguous channels and a 16-byte aligned row stride."""
+    _require_cuda(X)
+    if X.dim() != 2 or X.dtype != torch.float32 or X.stride(1) != 1:
+        raise ValueError("segmentation ops take an f32 [N, D] matrix with contiguous channels")
+    return X.shape[0], X.shape[1], X.stride(0)
+
+
+def seg_ldd(C):
+    """Row stride (floats) of the dlogits buffer for C classes: 32 ceil(C / 32)."""
+    ldd = lib().octic_seg_ldd(int(C))
+    check(min(ldd, 0))
+    return ldd
+
+
+def seg_workspace(N, D, C, device):
+    """The workspace of seg_value_dlogits / seg_wgrad for this shape (loss partials, slab tiles)."""
+    nbytes = lib().octic_seg_workspace_bytes(N, D, C)
+    check(min(nbytes, 0))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def seg_value_dlogits(X, W, b, y, dlogits, value, workspace):
+    """value[0] (f64) = sum_n CE(X_n W^T + b, y_n); dlogits [N, seg_ldd(C)] = softmax - onehot.  y: int32 class indices."""
+    N, D, ldx = _seg_rows(X)
+    C = W.shape[0]
+    if (W.dtype != torch.float32 or not W.is_contiguous() or W.shape[1] != D or b.dtype != torch.float32 or b.numel() != C
+            or not b.is_contiguous()):
+        raise ValueError("seg_value_dlogits: W must be a contiguous f32 [C, D], b a contiguous f32 [C]")
+    if y.dtype != torch.int32 or not y.is_contiguous() or y.numel() != N:
+        raise ValueError("seg_value_dlogits: y must be a contiguous int32 tensor of N class indices")
+    if (dlogits.dtype != torch.float32 or not dlogits.is_contiguous() or dlogits.numel() < N * max(seg_ldd(C), 0)
+            or value.dtype != torch.float64):
+        raise ValueError("seg_value_dlogits: dlogits must be a contiguous f32 [N, seg_ldd(C)], value an f64 scalar")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_seg_value_dlogits(_p(X), ldx, N, D, _p(W), _p(b), C, _p(y), _p(dlogits), _p(value), _p(workspace),
+                                        _stream(X)))
+    KERNEL_TIMER.stop(t, "seg_forward_kernel", 4 * N * (D + seg_ldd(C)), 2.0 * N * C * D)
+
+
+def seg_predict(X, W, b, pred):
+    """pred[n] (int32) = argmax_c (X_n W^T + b)_c, the first maximum."""
+    N, D, ldx = _seg_rows(X)
+    C = W.shape[0]
+    if W.dtype != torch.float32 or not W.is_contiguous() or W.shape[1] != D or b.dtype != torch.float32 or b.numel() != C:
+        raise ValueError("seg_predict: W must be a contiguous f32 [C, D], b an f32 [C]")
+    if pred.dtype != torch.int32 or not pred.is_contiguous() or pred.numel() != N:
+        raise ValueError("seg_predict: pred must be a contiguous int32 [N]")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_seg_predict(_p(X), ldx, N, D, _p(W), _p(b), C, _p(pred), _stream(X)))
+    KERNEL_TIMER.stop(t, "seg_forward_kernel<predict>", 4 * N * (D + 1), 2.0 * N * C * D)
+
+
+def seg_wgrad(X, dlogits, W, scale, lam, dW, db, workspace):
+    """dW = scale dlogits^T X + lam W, db = scale colsum(dlogits) (f32 [C, D] / [C])."""
+    N, D, ldx = _seg_rows(X)
+    C = W.shape[0]
+    if (dW.dtype != torch.float32 or not dW.is_contiguous() or tuple(dW.shape) != (C, D) or db.dtype != torch.float32
+            or db.numel() != C or not W.is_contiguous() or W.dtype != torch.float32):
+        raise ValueError("seg_wgrad: W / dW must be contiguous f32 [C, D], db an f32 [C]")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_seg_wgrad(_p(X), ldx, N, D, _p(dlogits), C, _p(W), float(scale), float(lam), _p(dW), _p(db),
+                                _p(workspace), _stream(X)))
+    KERNEL_TIMER.stop(t, "seg_wgrad_kernel", 4 * N * D, 2.0 * N * C * D)
+
+
+def seg_colstats(X):
+    """(mean, var): f64 [D] column mean and population variance of the f32 rows X [N, D]."""
+    N, D, ldx = _seg_rows(X)
+    nbytes = lib().octic_seg_colstats_workspace_bytes(N, D)
+    check(min(nbytes, 0))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=X.device)
+    mean = torch.empty(D, dtype=torch.float64, device=X.device)
+    var = torch.empty(D, dtype=torch.float64, device=X.device)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_seg_colstats(_p(X), ldx, N, D, _p(mean), _p(var), _p(ws), _stream(X)))
+    KERNEL_TIMER.stop(t, "seg_colstats_kernel", 4 * N * D)
+    return mean, var
+
+
+def seg_standardize_(X, mean, scale):
+    """In place: x = float(float(x - mean) / scale) with f64 [D] mean and scale."""
+    N, D, ldx = _seg_rows(X)
+    for v in (mean, scale):
+        if v.dtype != torch.float64 or v.numel() != D or not v.is_contiguous() or v.device != X.device:
+            raise ValueError("seg_standardize_: mean and scale must be contiguous f64 [D] on X's device")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_seg_standardize(_p(X), ldx, N, D, _p(mean), _p(scale), _stream(X)))
+    KERNEL_TIMER.stop(t, "seg_standardize_kernel", 8 * N * D)
+    return X
+
+
+_SEG_LABEL_DTYPES = (torch.uint8, torch.int16, torch.int32, torch.int64)
+
+
+def _seg_labels(labels):
+    _require_cuda(labels)
+    if labels.dim() != 2 or labels.dtype not in _SEG_LABEL_DTYPES or not labels.is_contiguous():
+        raise ValueError("segmentation labels must be a contiguous [R, L] tensor of uint8 / int16 / int32 / int64 values 0 .. 255")
+    return labels.shape[0], labels.shape[1], labels.element_size()
+
+
+def seg_patch_mode(labels):
+    """mode[r] (int32) = the most frequent value of labels[r, :], the smallest on a tie (torch.mode)."""
+    R, L, es = _seg_labels(labels)
+    mode = torch.empty(R, dtype=torch.int32, device=labels.device)
+    if R:
+        t = KERNEL_TIMER.start()
+        check(lib().octic_seg_patch_mode(_p(labels), es, R, L, _p(mode), _stream(labels)))
+        KERNEL_TIMER.stop(t, "seg_mode_kernel", R * (L * es + 4))
+    return mode
+
+
+def seg_confusion(labels, pred, ignore, counts):
+    """counts[t, pred[r]] += pixels of row r with label t, for every t with ignore[t] == 0 (uint8 [256]); counts: int64
+    [256, 256], accumulated."""
+    R, L, es = _seg_labels(labels)
+    if (pred.dtype != torch.int32 or pred.numel() != R or not pred.is_contiguous() or ignore.dtype != torch.uint8
+            or ignore.numel() != 256 or counts.dtype != torch.int64 or counts.numel() != 65536 or not counts.is_contiguous()):
+        raise ValueError("seg_confusion: pred int32 [R], ignore uint8 [256], counts int64 [256, 256]")
+    if R:
+        t = KERNEL_TIMER.start()
+        check(lib().octic_seg_confusion(_p(labels), es, R, L, _p(pred), _p(ignore), _p(counts), _stream(labels)))
+        KERNEL_TIMER.stop(t, "seg_confusion_kernel", R * (L * es + 4))
+    return counts
