@@ -606,6 +606,39 @@ int octic_seg_patch_mode(const void* labels, int esize, int64_t R, int L, int32_
 int octic_seg_confusion(const void* labels, int esize, int64_t R, int L, const int32_t* pred, const uint8_t* ignore,
                         int64_t* counts, void* stream);
 
+/* ---- Mixup / CutMix and the BCE loss of the DeiT-III recipe (timm/data/mixup.py; deit/engine.py:47-59) -----------------
+ * The host draws the per-sample parameters and uploads them as a DEVICE table of B rows; the kernels take everything about
+ * the draw from it (never from arguments), so one captured launch serves every replay.  A row whose partner is outside
+ * [0, B) or whose lam is outside [0, 1) means "not mixed".  f32 arithmetic, no atomics, fixed summation orders.          */
+typedef struct {
+  int32_t partner; /* the sample this one is mixed with (timm: B - 1 - i)                     */
+  float lam;       /* weight of the sample itself; 1 = not mixed                              */
+  int32_t cut;     /* != 0: CutMix (the box is pasted), 0: Mixup (the images are blended)     */
+  int32_t yl, yh;  /* box rows    [yl, yh)                                                    */
+  int32_t xl, xh;  /* box columns [xl, xh)                                                    */
+  int32_t pad;
+} octic_mix_row;
+/* dst[i] (f32 [B, C, H, W], out of place) = src[partner] inside sample i's box, bit for bit; elsewhere src[i] bit for bit
+ * when the row is a cut or lam == 1, else lam src[i] + (1 - lam) src[partner] (Mixup._mix_batch / _mix_elem / _mix_pair).
+ * Any W: 16-byte accesses along W when W % 4 == 0 and both pointers are 16-byte aligned, element accesses otherwise; boxes
+ * start and end at any column.  C H W < 2^31 - 4.  src and dst must not overlap (OCTIC_ESHAPE).                       */
+int octic_mix_images(const float* src, float* dst, const octic_mix_row* table, int B, int C, int H, int W, void* stream);
+/* targets [rows, num_classes] (f32, contiguous) for the batch rows row0 .. row0 + rows - 1 (mixup_target):
+ * t = lam onehot(labels[b], on, off) + (1 - lam) onehot(labels[partner], on, off) with timm's three f32 roundings, and
+ * t = (t > 0) when binarize != 0 (deit/engine.py:53-54).  labels: int64 [B] - partners are indexed in the WHOLE batch.  A
+ * label outside [0, num_classes) gives an all-`off` one-hot row and is counted nowhere else.  rows <= 65535.            */
+int octic_mix_targets(const int64_t* labels, const octic_mix_row* table, int B, int row0, int rows, int num_classes, float on,
+                      float off, int binarize, float* targets, void* stream);
+/* nn.BCEWithLogitsLoss(reduction="mean") of logits [rows, num_classes] (f32 or bf16, row stride ldl elements) against the
+ * targets octic_mix_targets would write for the same arguments, without materialising them: per element
+ * max(x, 0) - x t + log1p(exp(-|x|)) in f32, summed in f64 in a fixed order.  Each output is optional (not both NULL):
+ * loss[0] (DEVICE f32) = the mean, needs workspace (rows doubles, 8-byte aligned);
+ * dlogits (the logits' dtype, row stride ldd) = gscale[0] (sigmoid(x) - t) / (rows num_classes), gscale a DEVICE f32 (the
+ * incoming gradient; NULL = 1).                                                                                      */
+int octic_mix_bce(const void* logits, int dtype, int64_t ldl, const int64_t* labels, const octic_mix_row* table, int B, int row0,
+                  int rows, int num_classes, float on, float off, int binarize, float* loss, const float* gscale,
+                  void* dlogits, int64_t ldd, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1291,3 +1291,69 @@ def seg_confusion(labels, pred, ignore, counts):
         check(lib().octic_seg_confusion(_p(labels), es, R, L, _p(pred), _p(ignore), _p(counts), _stream(labels)))
         KERNEL_TIMER.stop(t, "seg_confusion_kernel", R * (L * es + 4))
     return counts
+
+
+# ------------------------------------------------------------------------------------------ Mixup / CutMix + BCE (csrc/mixup.hip)
+def _mix_table(table, B):
+    _require_cuda(table)
+    if table.dtype != torch.int32 or tuple(table.shape) != (B, 8) or not table.is_contiguous():
+        raise ValueError(f"mix ops: the parameter table must be a contiguous int32 [{B}, 8] tensor (MixParams.table())")
+    return table
+
+
+def _mix_labels(labels, B=None):
+    _require_cuda(labels)
+    if labels.dtype != torch.int64 or labels.dim() != 1 or not labels.is_contiguous() or (B is not None and labels.numel() != B):
+        raise ValueError("mix ops: labels must be a contiguous int64 tensor of B class indices")
+    return labels
+
+
+def mix_images(src, table, dst):
+    """dst = the batch src [B, C, H, W] (f32, contiguous) mixed as the device table says; out of place."""
+    _require_cuda(src)
+    _require_cuda(dst)
+    if src.dim() != 4 or src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("mix_images: images must be a contiguous f32 [B, C, H, W] tensor")
+    if dst.shape != src.shape or dst.dtype != torch.float32 or not dst.is_contiguous():
+        raise ValueError("mix_images: the output must be a contiguous f32 tensor of the images' shape")
+    B, C, H, W = src.shape
+    _mix_table(table, B)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_mix_images(_p(src), _p(dst), _p(table), B, C, H, W, _stream(src)))
+    KERNEL_TIMER.stop(t, "mix_images_kernel", 12 * src.numel())
+    return dst
+
+
+def mix_targets(labels, table, num_classes, on, off, binarize, targets, row0=0):
+    """targets [rows, num_classes] f32 for the batch rows row0 .. row0 + rows - 1."""
+    _require_cuda(targets)
+    B = _mix_labels(labels).numel()
+    _mix_table(table, B)
+    if targets.dtype != torch.float32 or targets.dim() != 2 or targets.shape[1] != num_classes or not targets.is_contiguous():
+        raise ValueError("mix_targets: the output must be a contiguous f32 [rows, num_classes] tensor")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_mix_targets(_p(labels), _p(table), B, int(row0), targets.shape[0], int(num_classes), float(on), float(off),
+                                  int(bool(binarize)), _p(targets), _stream(labels)))
+    KERNEL_TIMER.stop(t, "mix_targets_kernel", 4 * targets.numel())
+    return targets
+
+
+def mix_bce(logits, labels, table, on, off, binarize, row0=0, loss=None, workspace=None, gscale=None, dlogits=None):
+    """BCEWithLogitsLoss(mean) of logits [rows, num_classes] (f32 / bf16, unit column stride) against the mixed targets of the
+    batch rows row0 ..: loss (f32 scalar, with workspace = rows f64) and / or dlogits (the logits' dtype) scaled by gscale."""
+    _require_cuda(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("mix_bce: logits must be [rows, num_classes] with contiguous columns")
+    rows, nc = logits.shape
+    B = _mix_labels(labels).numel()
+    _mix_table(table, B)
+    if dlogits is not None and (dlogits.dtype != logits.dtype or dlogits.shape != logits.shape or dlogits.stride(1) != 1):
+        raise ValueError("mix_bce: dlogits must have the logits' shape and dtype")
+    if loss is not None and (loss.dtype != torch.float32 or workspace is None or workspace.dtype != torch.float64
+                             or workspace.numel() < rows):
+        raise ValueError("mix_bce: the loss is an f32 scalar and needs a workspace of rows f64")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_mix_bce(_p(logits), dt_code(logits.dtype), logits.stride(0), _p(labels), _p(table), B, int(row0), rows, nc,
+                              float(on), float(off), int(bool(binarize)), _p(loss), _p(gscale), _p(dlogits),
+                              dlogits.stride(0) if dlogits is not None else 0, _p(workspace), _stream(logits)))
+    KERNEL_TIMER.stop(t, f"mix_bce_kernel<{_DTN[logits.dtype]}>", logits.numel() * logits.element_size() * (2 if dlogits is not None else 1))

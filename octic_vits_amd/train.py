@@ -9,7 +9,11 @@ targets -> backward (gradients all-reduced over RCCL by DDP bucket hooks, overla
     the host never waits for work the GPU has not finished long ago, so it can enqueue step k+1 while step k runs
     (the reference calls loss.item() and torch.cuda.synchronize() every iteration);
   * the logged gradient norm is the one LAMB computes anyway (the reference makes a second pass,
-    engine.py:84).
+    engine.py:84);
+  * Mixup / CutMix (engine.py:47-54, timm's ``mixup_fn`` + ``targets.gt(0)``) are part of the step when the trainer is given a
+    ``mixup.Mixup``: the draw on the host, the mix and the BCE loss as HIP kernels driven by a small device table
+    (``Trainer(mixup=...)``); without one the caller passes mixed float targets as before.
+``evaluate`` is the reference's evaluation loop (engine.py:98-128) on one GPU.
 """
 import math
 import os
@@ -1019,8 +1023,15 @@ class Trainer:
     def __init__(self, model, lr=3e-3, weight_decay=0.02, ema_decay=0.99996, distributed=False, local_rank=0,
                  fused_optimizer=True, tuned_gemms=True, opt_eps=1e-8, accum_steps=1, bf16_buckets=False,
                  autocast=True, check_every=1, device_type=None, bucket_cap_mb=None, segment_graphs=0, ddp_proxy=None,
-                 own_reducer=None):
-        """segment_graphs = n > 0 (GPU only): forward and backward run as 2 n hipGraph replays (``SegmentedModel``), the
+                 own_reducer=None, mixup=None, fused_loss=True):
+        """mixup: a ``mixup.Mixup`` (GPU only) - ``step`` / ``capture`` / ``GraphedStep.replay`` then take ``(images, int64 labels
+        [B])``: every step draws the Mixup / CutMix parameters on the host, uploads them as one small device table (pinned ring,
+        no stream drain), mixes the WHOLE batch once with the HIP kernels of csrc/mixup.hip and takes the recipe's BCE loss
+        against the binarised mixed targets (deit/engine.py:47-59 with ``--bce-loss``).  fused_loss: the loss and its gradient
+        come from ``mixup.mix_bce_loss`` without materialised targets; False materialises them (``mixup.mix_targets``) for
+        ``nn.BCEWithLogitsLoss``.  Data parallel: every rank owns its ``Mixup``, seeded ``seed + rank`` as the reference seeds
+        its ranks.  None: the caller mixes, ``step`` takes float multi-hot targets as before.
+        segment_graphs = n > 0 (GPU only): forward and backward run as 2 n hipGraph replays (``SegmentedModel``), the
         loss, the gradient all-reduce hooks and the optimizer stay eager - the cheap-on-the-host step for gradient
         accumulation, where the whole-step graph of ``capture`` does not apply.
         own_reducer (distributed only): average the gradients with ``GradReducer`` instead of DistributedDataParallel - the
@@ -1029,6 +1040,9 @@ class Trainer:
         others add to them, the collectives follow the last one).  None = wherever it applies: f32 buckets, f32 master
         parameters, no segment graphs; everything else goes through DistributedDataParallel as before."""
         self.raw_model = model
+        self.mixup, self.fused_loss, self._mix_tables = mixup, bool(fused_loss), {}
+        if mixup is not None and (device_type or next(model.parameters()).device.type) != "cuda":
+            raise RuntimeError("Trainer(mixup=...): Mixup / CutMix run on the GPU only (HIP kernels, no CPU fallback)")
         self.segmented = None
         if segment_graphs:
             self.segmented = SegmentedModel(model, segment_graphs)
@@ -1150,8 +1164,45 @@ class Trainer:
         if self.autocast:
             with torch.autocast(self.device_type, dtype=torch.bfloat16):
                 outputs = self.model(samples)
-                return self.criterion(outputs.float(), targets)
-        return self.criterion(self.model(samples).float(), targets)
+                return self._loss(outputs, targets)
+        return self._loss(self.model(samples), targets)
+
+    def _loss(self, outputs, targets):
+        if isinstance(targets, _MixedTargets):          # the fused loss reads the logits in their own dtype
+            return targets.loss(outputs)
+        return self.criterion(outputs.float(), targets)
+
+    @staticmethod
+    def _mix_check(samples, labels):
+        if not torch.is_tensor(labels) or labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] != samples.shape[0]:
+            what = f"{tuple(labels.shape)} {labels.dtype}" if torch.is_tensor(labels) else type(labels).__name__
+            raise TypeError(f"Trainer(mixup=...): step takes int64 class labels [B], got {what} - the trainer mixes the "
+                            "targets itself (float multi-hot targets belong to a Trainer without mixup)")
+        if not samples.is_cuda or not labels.is_cuda:
+            raise RuntimeError("Trainer(mixup=...): Mixup / CutMix run on the GPU only (HIP kernels, no CPU fallback)")
+
+    def _mix_table(self, B, device):
+        up = self._mix_tables.get(B)
+        if up is None:
+            from .mixup import TableUploader
+            up = self._mix_tables[B] = TableUploader(B, device)
+        return up
+
+    def _mix_draw(self, samples):
+        """A fresh draw for this batch shape, on its way to the device table (stream-ordered, in front of the step)."""
+        B, _, H, W = samples.shape
+        return self._mix_table(B, samples.device).upload(self.mixup.draw(B, H, W))
+
+    def _mix_batch(self, samples, labels):
+        """The launches of the mix (also what ``capture`` records): the whole batch mixed once, out of place, and the targets
+        as ``_MixedTargets`` (fused loss) or a materialised, binarised [B, num_classes] tensor."""
+        from . import mixup as M
+        table = self._mix_table(samples.shape[0], samples.device).table
+        mixed = M.mix_images(samples, table)
+        on, off = self.mixup.on_off()
+        if self.fused_loss:
+            return mixed, _MixedTargets(labels, table, on, off)
+        return mixed, M.mix_targets(labels, table, self.mixup.num_classes, on=on, off=off, binarize=True)
 
     def _batched_finishes(self, first_of_many=False):
         """The parameter-gradient slab reductions of the backward pass as one batched launch at its end
@@ -1206,11 +1257,16 @@ class Trainer:
         if self._ddp_args is not None and self.model is self.segmented:
             raise RuntimeError("Trainer(distributed=True, segment_graphs=n): call capture_segments(micro_batch) before the "
                                "first step (the slices are captured, then wrapped in DistributedDataParallel)")
+        if self.mixup is not None:
+            self._mix_check(samples, targets)
         self.model.train()
         # engine.py:67-71 two steps late on a pinned host copy (_LossWatch): no stream drain per step
         self._steps += 1
         if self._steps % self.check_every == 0:
             self._watch.check()
+        if self.mixup is not None:
+            self._mix_draw(samples)
+            samples, targets = self._mix_batch(samples, targets)
         k = self.accum_steps
         if k > 1 and self.segmented is not None and self.segmented.graphed:
             # Graphed slices hand autograd the SAME static gradient buffers every backward: with .grad = None the first
@@ -1282,6 +1338,10 @@ class Trainer:
         from . import ops
         if ops.KERNEL_TIMER.on:
             raise RuntimeError("Trainer.capture: disable the kernel timer first")
+        if self.mixup is not None:
+            # sx / sy are the staging images and labels; the parameter table is the third static input (``_mix_table``):
+            # ``GraphedStep.replay`` refills all three in front of the replay, the mix kernels and the loss are in the graph
+            self._mix_check(samples, targets)
         sx, sy = samples.clone(), targets.clone()
         for _ in range(max(1, warmup)):
             self.step(sx, sy)
@@ -1304,6 +1364,8 @@ class Trainer:
 
     def _capture_body(self, graph, mode, sx, sy):
         with torch.cuda.graph(graph, **mode):
+            if self.mixup is not None:
+                sx, sy = self._mix_batch(sx, sy)
             if self.accum_steps > 1:
                 loss = self._accumulate(sx, sy)           # (k forward / backward passes over the chunks of the static batch)
             else:
@@ -1343,6 +1405,27 @@ class _FinishScope:
         return False
 
 
+class _MixedTargets:
+    """The mixed targets of the batch rows row0 .. row0 + rows - 1 as (labels of the WHOLE batch, parameter table) - never
+    materialised: ``loss`` is ``mixup.mix_bce_loss`` against their binarised form.  ``chunk`` cuts them like ``Tensor.chunk``
+    cuts the images (gradient accumulation mixes the whole batch once; a chunk's partners may lie in another chunk)."""
+
+    def __init__(self, labels, table, on, off, row0=0, rows=None):
+        self.labels, self.table, self.on, self.off, self.row0 = labels, table, on, off, row0
+        self.rows = labels.shape[0] - row0 if rows is None else rows
+
+    def chunk(self, k):
+        size = -(-self.rows // k)
+        return [_MixedTargets(self.labels, self.table, self.on, self.off, self.row0 + o, min(size, self.rows - o))
+                for o in range(0, self.rows, size)]
+
+    def loss(self, logits):
+        from .mixup import mix_bce_loss
+        if logits.shape[0] != self.rows:
+            raise ValueError("Trainer: the logits do not match the mixed targets' rows")
+        return mix_bce_loss(logits, self.labels, self.table, on=self.on, off=self.off, binarize=True, row0=self.row0)
+
+
 class GraphedStep:
     """A captured training iteration (see ``Trainer.capture``).  ``replay`` copies the batch into the graph's input
     buffers, launches the graph and returns the (device-resident) loss of this iteration."""
@@ -1360,7 +1443,11 @@ class GraphedStep:
         if samples is not None and samples.data_ptr() != self.samples.data_ptr():
             self.samples.copy_(samples, non_blocking=True)
         if targets is not None and targets.data_ptr() != self.targets.data_ptr():
+            if t.mixup is not None:
+                t._mix_check(self.samples, targets)
             self.targets.copy_(targets, non_blocking=True)
+        if t.mixup is not None:                         # this step's Mixup / CutMix draw: the captured kernels read the table
+            t._mix_draw(self.samples)
         # a schedule's new lr / weight decay / EMA decay: copied in front of the replay (the captured kernels read them)
         t.optimizer.push_hyper()
         self.graph.replay()
@@ -1375,6 +1462,46 @@ class _null:
 
     def __exit__(self, *a):
         return False
+
+
+@torch.no_grad()
+def evaluate(model, batches, graphed=True):
+    """deit/engine.py:98-128 on one GPU: eval mode, bf16 autocast, ``batches`` yields (images, int64 labels).  Per batch the
+    cross-entropy sum and the top-1 / top-5 counts accumulate ON THE DEVICE (``ops.probe_ce`` with one head); the host reads
+    them once at the end.  Returns {"loss": mean over the images, "acc1", "acc5": percentages} as the reference's
+    ``global_avg`` meters (weighted by batch size).  graphed: batches of the first batch's shape run through
+    ``serve.GraphedForward``, a ragged last batch eagerly."""
+    from . import ops
+    model.eval()
+    gf = None
+    loss_sum = topk = None
+    n = 0
+    for images, labels in batches:
+        ops._require_cuda(images)
+        ops._require_cuda(labels)
+        if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] != images.shape[0]:
+            raise ValueError("evaluate: labels must be int64 class indices [B]")
+        if loss_sum is None:
+            loss_sum = torch.zeros(1, dtype=torch.float32, device=images.device)
+            topk = torch.zeros(2, dtype=torch.int32, device=images.device)
+        if graphed and gf is None:
+            from .serve import GraphedForward
+            gf = GraphedForward(model, images)
+        if gf is not None and images.shape == gf.static_in.shape and images.dtype == gf.static_in.dtype:
+            logits = gf(images, copy_out=False)
+        else:
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                logits = model(images)
+        logits = logits.float().contiguous()
+        B, C = logits.shape
+        rowloss = torch.empty(B, dtype=torch.float32, device=logits.device)
+        rowrank = torch.empty(B, dtype=torch.int32, device=logits.device)
+        ops.probe_ce(logits, labels.contiguous(), 1, B, C, None, rowloss, rowrank, loss_sum=loss_sum, topk=topk)
+        n += B
+    if n == 0:
+        raise ValueError("evaluate: no batch")
+    total = torch.cat([loss_sum.double(), topk.double()]).cpu()      # the one host read
+    return {"loss": float(total[0]) / n, "acc1": 100.0 * float(total[1]) / n, "acc5": 100.0 * float(total[2]) / n}
 
 
 def init_distributed(force=False):
