@@ -522,7 +522,7 @@ dense_layernorm.register_autograd(_dln_backward, setup_context=_dln_setup)
 
 
 def _hip_gemm_ok(rows, N, K):
-    return K % 64 == 0 and K >= 128 and N % 64 == 0 and N >= 128 and rows * max(N, K) * 2 < 2 ** 31
+    return ops.dense_gemm_ok(rows, N, K)
 
 
 @_lib.custom_op("octic::dense_linear", mutates_args=())

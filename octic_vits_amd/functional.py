@@ -791,9 +791,7 @@ def dense_hip_ok(x, w, which=None):
     """bf16 autocast on the GPU, a shape csrc/dense_gemm.hip covers in BOTH directions (forward: K = in_features,
     input gradient: K = out_features; the kernel needs K % 64 == 0, K >= 128, N % 8 == 0) and routed."""
     rows = x.numel() // max(1, x.shape[-1])
-    return ((which is None or which in DENSE_HIP) and x.is_cuda and w.shape[1] % 64 == 0 and w.shape[1] >= 128
-            and w.shape[0] % 64 == 0 and w.shape[0] >= 128
-            and rows * max(w.shape) * 2 < 2 ** 31)          # 32-bit buffer offsets in the kernel (it refuses larger operands)
+    return (which is None or which in DENSE_HIP) and x.is_cuda and ops.dense_gemm_ok(rows, w.shape[0], w.shape[1])
 
 
 def _f32(t):
@@ -937,6 +935,80 @@ def _tok(shape):
     return int(shape[-2]) if len(shape) >= 3 else 0
 
 
+def _gemm_fwd(tag, x2, wb, b, cache, name, tokens):
+    """x2 wb^T + b (bf16): csrc/dense_gemm.hip with a plain epilogue (f32 bias b) where `tag` is routed to it (DENSE_HIP),
+    else the BLAS library with the cache's compute-dtype bias."""
+    if tag in DENSE_HIP:
+        return ops.dense_gemm_nt(x2, wb, 0, bias=_f32(b), name=f"dense_nt_kernel<{name}>", tokens=tokens)
+    return _linear_lib(x2, wb, None if b is None else cache.b)
+
+
+def _gemm_dgrad(g2, wt, wb, shape, dtype):
+    """Input gradient g2 W as `shape` in `dtype`: csrc/dense_gemm.hip on the transposed copy wt where the cache made one (the
+    input gradient is routed to it), else the BLAS library on wb."""
+    gx = (ops.dense_gemm_nt(g2, wt, 0, name="dense_nt_kernel<dgrad>", tokens=_tok(shape)) if wt is not None
+          else _mm_lib(g2, wb))
+    return gx.view(shape).to(dtype)
+
+
+def _resid_tail_fwd(ctx, x, tag, a2, wb, b, cache, tokens, g32, rs32, rps, nw, nb, neps, rows_to, stream):
+    """out = x + rs * gamma * br with br = a2 wb^T + b, the GEMM `tag` (proj / fc2): the tail of both branches of a standard
+    block.  neps is not None: the residual add and LayerNorm(out; nw, nb, neps) in bf16 as one row pass -> (out, yn).
+    rows_to: x are compact rows of `stream`, the result goes back into it through the row map -> stream.
+    Returns (the node's outputs, the tensors _resid_tail_bwd wants back from ctx.save_for_backward)."""
+    ctx.rows_to, ctx.x_shape = rows_to, x.shape
+    ctx.tail = (neps is not None, rps, b is not None, nw is not None, nb is not None)
+    x2 = x.view(-1, wb.shape[0])
+    if neps is None and rows_to is None and tag in DENSE_HIP and DENSE_RESID_FUSED:
+        br, out = ops.dense_gemm_nt(a2, wb, 2, bias=_f32(b), gamma=g32, rs=rs32, rps=rps, x=x2, name="dense_nt_kernel<resid>")
+        return out.view(x.shape), (br, g32, rs32)
+    br = _gemm_fwd(tag, a2, wb, b, cache, tag, tokens)
+    if neps is not None:
+        nw32, nb32 = _f32(nw), _f32(nb)
+        out, yn, stats = ops.dense_resid_layernorm_fwd(x2, br, g32, rs32, rps, nw32, nb32, neps, torch.bfloat16)
+        ctx.set_materialize_grads(False)
+        return (out.view(x.shape), yn.view(x.shape)), (br, g32, rs32, out, stats, nw32)
+    if rows_to is not None:
+        ops.scale_residual_fwd_rows_(stream, rows_to.rowmap, x2, br, g32, rs32, rps)
+        ctx.mark_dirty(stream)
+        return stream, (br, g32, rs32, rows_to.rowmap)
+    return ops.scale_residual_fwd(x2, br, g32, rs32, rps).view(x.shape), (br, g32, rs32)
+
+
+def _resid_tail_bwd(ctx, tail, gout, gyn, want_norm):
+    """Backward of _resid_tail_fwd.  tail: what it handed to save_for_backward; gyn: the cotangent of the next-norm output;
+    want_norm: the norm's parameters want gradients.  Returns (stream cotangent - None under rows_to, where it travels
+    through rows_to.link.g -, cotangent of br, d gamma, column sums of that cotangent = the bias gradient, d nw, d nb)."""
+    norm, rps, has_b, has_nw, has_nb = ctx.tail
+    br, g32, rs32, *rest = tail
+    has_gamma = g32 is not None
+    dnw = dnb = gbr = None
+    if norm:
+        out, stats, nw32 = rest
+        if gyn is not None:      # LayerNorm backward with the residual cotangent added in the same pass
+            want = has_nw and want_norm
+            dres = None if gout is None else _c(gout.float()).view(out.shape)
+            g2 = _c(gyn).view(out.shape)
+            if LN_TAIL_FUSED and ops.dense_ln_bwd_tail_ok(g2, br, out.shape[-1]):
+                gout, dnw, dnb, gbr, dgamma, colsum = ops.dense_layernorm_bwd_tail(
+                    g2, out, nw32, stats, dres, br, g32, rs32, rps, want_param_grads=want, want_gamma=has_gamma,
+                    want_colsum=has_b)
+            else:
+                gout, dnw, dnb = ops.dense_layernorm_bwd(g2, out, nw32, stats, dres, want_param_grads=want)
+            dnw, dnb = (dnw if has_nw else None), (dnb if has_nb else None)
+    elif ctx.rows_to is not None:
+        gout = _c(gout.float())
+        ctx.rows_to.link.g = gout             # the LayerNorm of this branch edits it in place and hands it on
+        gbr, dgamma, colsum = ops.scale_residual_bwd(gout, br, g32, rs32, rps, want_gamma=has_gamma, want_colsum=has_b,
+                                                     rowmap=rest[0])
+    if gbr is None:
+        gout = _c(gout.float())
+        gbr, dgamma, colsum = ops.scale_residual_bwd(gout.view(br.shape), br, g32, rs32, rps, want_gamma=has_gamma,
+                                                     want_colsum=has_b)
+    gx = None if ctx.rows_to is not None else gout.view(ctx.x_shape)
+    return gx, gbr, dgamma, colsum, dnw, dnb
+
+
 class DenseLinearNTFn(torch.autograd.Function):
     """nn.Linear (bf16 operands, f32 accumulate, f32 bias added before the one rounding to bf16): forward and input
     gradient on csrc/dense_gemm.hip.  deit/vit.py:33 (``self.qkv(x)``)."""
@@ -948,10 +1020,7 @@ class DenseLinearNTFn(torch.autograd.Function):
         xb = _c(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16))
         wb, wt = cache.get_nt(w, b, ("d" + tag) in DENSE_HIP and ctx.needs_input_grad[0])
         x2 = xb.reshape(-1, wb.shape[1])
-        if tag in DENSE_HIP:
-            y = ops.dense_gemm_nt(x2, wb, 0, bias=_f32(b), name="dense_nt_kernel<plain>", tokens=_tok(x.shape))
-        else:
-            y = _linear_lib(x2, wb, None if b is None else cache.b)
+        y = _gemm_fwd(tag, x2, wb, b, cache, "plain", _tok(x.shape))
         ctx.save_for_backward(x2, wb, wt)          # wt is None unless the input gradient is routed to the HIP kernel
         ctx.meta = (b is not None, x.dtype, x.shape, tag)
         return y.view(*x.shape[:-1], wb.shape[0])
@@ -961,10 +1030,7 @@ class DenseLinearNTFn(torch.autograd.Function):
         x2, wb, wt = ctx.saved_tensors
         has_b, x_dtype, x_shape, tag = ctx.meta
         g2 = _c(gy).reshape(-1, wb.shape[0])
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = (ops.dense_gemm_nt(g2, wt, 0, name="dense_nt_kernel<dgrad>", tokens=_tok(x_shape)) if wt is not None
-                  else _mm_lib(g2, wb)).view(x_shape).to(x_dtype)
+        gx = _gemm_dgrad(g2, wt, wb, x_shape, x_dtype) if ctx.needs_input_grad[0] else None
         gb = None
         if has_b:
             gb = (ops.dense_colsum(g2) if g2.is_cuda and g2.dtype == torch.bfloat16 and g2.shape[1] % 8 == 0
@@ -993,84 +1059,28 @@ class DenseProjResidFn(torch.autograd.Function):
         the same row pass that adds the residual (NEXT_NORM_FUSED).  rows_to (RowsTo; stream = rows_to.stream, passed as a
         tensor so that autograd sees the in-place edit): x are compact rows of the stream, the result goes back into it."""
         ctx.pair = pair
-        ctx.rows_to = rows_to
         ctx.wparam = w
         x = _c(x)
         ab = _c(a if a.dtype == torch.bfloat16 else a.to(torch.bfloat16))
         wb, wt = cache.get_nt(w, b, "dproj" in DENSE_HIP and ctx.needs_input_grad[1])
         a2 = ab.reshape(-1, wb.shape[1])
-        g32, rs32 = _f32(gamma), _f32(rs)
-        ctx.norm = neps is not None
-        ctx.x_shape = x.shape
-        if ctx.norm:
-            y = ops.dense_gemm_nt(a2, wb, 0, bias=_f32(b), name="dense_nt_kernel<proj>", tokens=_tok(a.shape))
-            nw32, nb32 = _f32(nw), _f32(nb)
-            out, yn, stats = ops.dense_resid_layernorm_fwd(x.view(-1, wb.shape[0]), y, g32, rs32, rps, nw32, nb32, neps,
-                                                           torch.bfloat16)
-            ctx.save_for_backward(a2, wb, wt, y, g32, rs32, out, stats, nw32)
-            ctx.meta = (rps, b is not None, gamma is not None, a.dtype, a.shape, nw is not None, nb is not None)
-            ctx.set_materialize_grads(False)
-            return out.view(x.shape), yn.view(x.shape)
-        if rows_to is not None:
-            y = ops.dense_gemm_nt(a2, wb, 0, bias=_f32(b), name="dense_nt_kernel<proj>", tokens=_tok(a.shape))
-            ops.scale_residual_fwd_rows_(stream, rows_to.rowmap, x.view(-1, wb.shape[0]), y, g32, rs32, rps)
-            ctx.save_for_backward(a2, wb, wt, y, g32, rs32, rows_to.rowmap)
-            ctx.meta = (rps, b is not None, gamma is not None, a.dtype, a.shape)
-            ctx.mark_dirty(stream)
-            return stream
-        if DENSE_RESID_FUSED:
-            y, out = ops.dense_gemm_nt(a2, wb, 2, bias=_f32(b), gamma=g32, rs=rs32, rps=rps, x=x.view(-1, wb.shape[0]),
-                                       name="dense_nt_kernel<resid>")
-        else:
-            y = ops.dense_gemm_nt(a2, wb, 0, bias=_f32(b), name="dense_nt_kernel<proj>", tokens=_tok(a.shape))
-            out = ops.scale_residual_fwd(x.view(-1, wb.shape[0]), y, g32, rs32, rps)
-        ctx.save_for_backward(a2, wb, wt, y, g32, rs32)
-        ctx.meta = (rps, b is not None, gamma is not None, a.dtype, a.shape)
-        return out.view(x.shape)
+        outs, tail = _resid_tail_fwd(ctx, x, "proj", a2, wb, b, cache, _tok(a.shape), _f32(gamma), _f32(rs), rps,
+                                     nw, nb, neps, rows_to, stream)
+        ctx.save_for_backward(a2, wb, wt, *tail)
+        ctx.meta = (a.dtype, a.shape)
+        return outs
 
     @staticmethod
     def backward(ctx, gout, gyn=None):
-        dnw = dnb = None
-        tail_done = False
-        if ctx.norm:
-            a2, wb, wt, y, g32, rs32, out, stats, nw32 = ctx.saved_tensors
-            rps, has_b, has_gamma, a_dtype, a_shape, has_nw, has_nb = ctx.meta
-            if gyn is not None:      # LayerNorm backward with the residual cotangent added in the same pass
-                want = has_nw and (ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
-                dres = None if gout is None else _c(gout.float()).view(out.shape)
-                g2 = _c(gyn).view(out.shape)
-                if LN_TAIL_FUSED and ops.dense_ln_bwd_tail_ok(g2, y, out.shape[-1]):
-                    gout, dnw, dnb, gy, dgamma, colsum = ops.dense_layernorm_bwd_tail(
-                        g2, out, nw32, stats, dres, y, g32, rs32, rps, want_param_grads=want, want_gamma=has_gamma,
-                        want_colsum=has_b)
-                    tail_done = True
-                else:
-                    gout, dnw, dnb = ops.dense_layernorm_bwd(g2, out, nw32, stats, dres, want_param_grads=want)
-                dnw, dnb = (dnw if has_nw else None), (dnb if has_nb else None)
-        elif ctx.rows_to is not None:
-            a2, wb, wt, y, g32, rs32, rowmap = ctx.saved_tensors
-            rps, has_b, has_gamma, a_dtype, a_shape = ctx.meta
-            gout = _c(gout.float())
-            ctx.rows_to.link.g = gout             # the LayerNorm of this branch edits it in place and hands it on
-            gy, dgamma, colsum = ops.scale_residual_bwd(gout, y, g32, rs32, rps, want_gamma=has_gamma, want_colsum=has_b,
-                                                        rowmap=rowmap)
-            tail_done = True
-        else:
-            a2, wb, wt, y, g32, rs32 = ctx.saved_tensors
-            rps, has_b, has_gamma, a_dtype, a_shape = ctx.meta
-        if not tail_done:
-            gout = _c(gout.float())
-            gy, dgamma, colsum = ops.scale_residual_bwd(gout.view(y.shape), y, g32, rs32, rps, want_gamma=has_gamma,
-                                                        want_colsum=has_b)
-        ga = None
-        if ctx.needs_input_grad[1]:
-            ga = (ops.dense_gemm_nt(gy, wt, 0, name="dense_nt_kernel<dgrad>", tokens=_tok(a_shape)) if wt is not None
-                  else _mm_lib(gy, wb)).view(a_shape).to(a_dtype)
+        a2, wb, wt, *tail = ctx.saved_tensors
+        a_dtype, a_shape = ctx.meta
+        gx, gy, dgamma, colsum, dnw, dnb = _resid_tail_bwd(ctx, tail, gout, gyn,
+                                                           ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
+        ga = _gemm_dgrad(gy, wt, wb, a_shape, a_dtype) if ctx.needs_input_grad[1] else None
         if _pair_ready(ctx.pair, gy, a2) and ops.dense_wgrad_ok(gy.shape[0], gy.shape[1], a2.shape[1]):
             dw = ctx.pair.park(gy, a2, ctx.wparam)   # written by the qkv weight gradient's launch (or at the end of the pass)
         else:
             dw = _wgrad_lib(gy, a2, ctx.wparam)
-        gx = None if ctx.rows_to is not None else gout.view(ctx.x_shape)
         return gx, ga, dw, colsum, dgamma, None, None, None, dnw, dnb, None, None, None, None
 
 
@@ -1085,7 +1095,6 @@ class DenseMlpFn(torch.autograd.Function):
     def forward(ctx, y, x, w1, b1, w2, b2, gamma, rs, rps, c1, c2, nw=None, nb=None, neps=None, rows_to=None, stream=None):
         """neps is not None: also return LayerNorm(out; nw, nb, neps) in bf16 (the NEXT block's norm1) from the row pass
         that adds the residual.  rows_to / stream: as in DenseProjResidFn."""
-        ctx.rows_to = rows_to
         ctx.wparams = (w1, w2)
         x = _c(x)
         yb = _c(y if y.dtype == torch.bfloat16 else y.to(torch.bfloat16))
@@ -1108,73 +1117,18 @@ class DenseMlpFn(torch.autograd.Function):
         else:
             h = _linear_lib(y2, w1b, None if b1 is None else c1.b)
             a = torch.nn.functional.gelu(h)
-        ctx.norm = neps is not None
-        ctx.x_shape = x.shape
-        if ctx.norm:
-            br = (ops.dense_gemm_nt(a, w2b, 0, bias=_f32(b2), name="dense_nt_kernel<fc2>", tokens=_tok(y.shape)) if "fc2" in DENSE_HIP
-                  else _linear_lib(a, w2b, None if b2 is None else c2.b))
-            nw32, nb32 = _f32(nw), _f32(nb)
-            out, yn, stats = ops.dense_resid_layernorm_fwd(x.view(-1, w2b.shape[0]), br, g32, rs32, rps, nw32, nb32, neps,
-                                                           torch.bfloat16)
-            ctx.save_for_backward(y2, h, a, br, w1b, w1t, w2b, w2t, g32, rs32, out, stats, nw32)
-            ctx.meta = (rps, b1 is not None, b2 is not None, gamma is not None, y.dtype, y.shape, nw is not None, nb is not None)
-            ctx.set_materialize_grads(False)
-            return out.view(x.shape), yn.view(x.shape)
-        if rows_to is not None:
-            br = (ops.dense_gemm_nt(a, w2b, 0, bias=_f32(b2), name="dense_nt_kernel<fc2>", tokens=_tok(y.shape)) if "fc2" in DENSE_HIP
-                  else _linear_lib(a, w2b, None if b2 is None else c2.b))
-            ops.scale_residual_fwd_rows_(stream, rows_to.rowmap, x.view(-1, w2b.shape[0]), br, g32, rs32, rps)
-            ctx.save_for_backward(y2, h, a, br, w1b, w1t, w2b, w2t, g32, rs32, rows_to.rowmap)
-            ctx.meta = (rps, b1 is not None, b2 is not None, gamma is not None, y.dtype, y.shape)
-            ctx.mark_dirty(stream)
-            return stream
-        if "fc2" in DENSE_HIP and DENSE_RESID_FUSED:
-            br, out = ops.dense_gemm_nt(a, w2b, 2, bias=_f32(b2), gamma=g32, rs=rs32, rps=rps, x=x.view(-1, w2b.shape[0]),
-                                        name="dense_nt_kernel<resid>")
-        elif "fc2" in DENSE_HIP:
-            br = ops.dense_gemm_nt(a, w2b, 0, bias=_f32(b2), name="dense_nt_kernel<fc2>", tokens=_tok(y.shape))
-            out = ops.scale_residual_fwd(x.view(-1, w2b.shape[0]), br, g32, rs32, rps)
-        else:
-            br = _linear_lib(a, w2b, None if b2 is None else c2.b)
-            out = ops.scale_residual_fwd(x.view(-1, w2b.shape[0]), br, g32, rs32, rps)
-        ctx.save_for_backward(y2, h, a, br, w1b, w1t, w2b, w2t, g32, rs32)
-        ctx.meta = (rps, b1 is not None, b2 is not None, gamma is not None, y.dtype, y.shape)
-        return out.view(x.shape)
+        outs, tail = _resid_tail_fwd(ctx, x, "fc2", a, w2b, b2, c2, _tok(y.shape), g32, rs32, rps,
+                                     nw, nb, neps, rows_to, stream)
+        ctx.save_for_backward(y2, h, a, w1b, w1t, w2b, w2t, *tail)
+        ctx.meta = (b1 is not None, y.dtype, y.shape)
+        return outs
 
     @staticmethod
     def backward(ctx, gout, gyn=None):
-        dnw = dnb = None
-        tail_done = False
-        if ctx.norm:
-            y2, h, a, br, w1b, w1t, w2b, w2t, g32, rs32, out, stats, nw32 = ctx.saved_tensors
-            rps, has_b1, has_b2, has_gamma, y_dtype, y_shape, has_nw, has_nb = ctx.meta
-            if gyn is not None:      # LayerNorm backward with the residual cotangent added in the same pass
-                want = has_nw and (ctx.needs_input_grad[11] or ctx.needs_input_grad[12])
-                dres = None if gout is None else _c(gout.float()).view(out.shape)
-                g2 = _c(gyn).view(out.shape)
-                if LN_TAIL_FUSED and ops.dense_ln_bwd_tail_ok(g2, br, out.shape[-1]):
-                    gout, dnw, dnb, gbr, dgamma, db2 = ops.dense_layernorm_bwd_tail(
-                        g2, out, nw32, stats, dres, br, g32, rs32, rps, want_param_grads=want, want_gamma=has_gamma,
-                        want_colsum=has_b2)
-                    tail_done = True
-                else:
-                    gout, dnw, dnb = ops.dense_layernorm_bwd(g2, out, nw32, stats, dres, want_param_grads=want)
-                dnw, dnb = (dnw if has_nw else None), (dnb if has_nb else None)
-        elif ctx.rows_to is not None:
-            y2, h, a, br, w1b, w1t, w2b, w2t, g32, rs32, rowmap = ctx.saved_tensors
-            rps, has_b1, has_b2, has_gamma, y_dtype, y_shape = ctx.meta
-            gout = _c(gout.float())
-            ctx.rows_to.link.g = gout
-            gbr, dgamma, db2 = ops.scale_residual_bwd(gout, br, g32, rs32, rps, want_gamma=has_gamma, want_colsum=has_b2,
-                                                      rowmap=rowmap)
-            tail_done = True
-        else:
-            y2, h, a, br, w1b, w1t, w2b, w2t, g32, rs32 = ctx.saved_tensors
-            rps, has_b1, has_b2, has_gamma, y_dtype, y_shape = ctx.meta
-        if not tail_done:
-            gout = _c(gout.float())
-            gbr, dgamma, db2 = ops.scale_residual_bwd(gout.view(br.shape), br, g32, rs32, rps, want_gamma=has_gamma,
-                                                      want_colsum=has_b2)
+        y2, h, a, w1b, w1t, w2b, w2t, *tail = ctx.saved_tensors
+        has_b1, y_dtype, y_shape = ctx.meta
+        gx, gbr, dgamma, db2, dnw, dnb = _resid_tail_bwd(ctx, tail, gout, gyn,
+                                                         ctx.needs_input_grad[11] or ctx.needs_input_grad[12])
         if w2t is not None:
             md = 5 if ctx.factor else 3
             if has_b1:                                                                  # gelu'(h) * (gbr W2), + db1
@@ -1186,11 +1140,7 @@ class DenseMlpFn(torch.autograd.Function):
             dh, db1 = ops.dense_gelu_bwd(h, _mm_lib(gbr, w2b), want_colsum=has_b1)
         gw2 = _wgrad_lib(gbr, a, ctx.wparams[1])
         gw1 = _wgrad_lib(dh, y2, ctx.wparams[0])
-        gy = None
-        if ctx.needs_input_grad[0]:
-            gy = (ops.dense_gemm_nt(dh, w1t, 0, name="dense_nt_kernel<dgrad>", tokens=_tok(y_shape)) if w1t is not None
-                  else _mm_lib(dh, w1b)).view(y_shape).to(y_dtype)
-        gx = None if ctx.rows_to is not None else gout.view(ctx.x_shape)
+        gy = _gemm_dgrad(dh, w1t, w1b, y_shape, y_dtype) if ctx.needs_input_grad[0] else None
         return gy, gx, gw1, db1, gw2, db2, dgamma, None, None, None, None, dnw, dnb, None, None, None
 
 

@@ -289,6 +289,11 @@ def layernorm_bwd_cast(g, x, stats, alpha5, dres, c, rs, rps, want_param_grads=T
 _DW_WS = {}
 
 
+def dense_gemm_ok(rows, N, K):
+    """Shapes csrc/dense_gemm.hip takes (y [rows,N] = x [rows,K] W^T; 32-bit buffer offsets: it refuses larger operands)."""
+    return K % 64 == 0 and K >= 128 and N % 64 == 0 and N >= 128 and rows * max(N, K) * 2 < 2 ** 31
+
+
 def dense_wgrad_ok(M, N, K):
     """Shapes csrc/dense_wgrad.hip takes: the 256 x (256 | 320) tiles where they divide N x K (at most 256 of them), else
     the 64 x 64 narrow path for N, K multiples of 64 (the standard blocks of DeiT-III tiny / small: D = 192, 384)."""

@@ -37,6 +37,12 @@ def _rows_per_scale(y, rs):
     return y.shape[1]
 
 
+def _tail_args(next_norm, rows_to):
+    """Trailing arguments of DenseProjResidFn / DenseMlpFn: (nw, nb, neps) of the norm to fuse, then (rows_to, its stream)."""
+    norm = (None, None, None) if next_norm is None else (next_norm.weight, next_norm.bias, next_norm.eps)
+    return norm, (rows_to, None if rows_to is None else rows_to.stream)
+
+
 class Mlp(nn.Module):
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, norm_layer=None,
                  bias=True, drop=0.):
@@ -68,19 +74,13 @@ class Mlp(nn.Module):
         nn.LayerNorm): the hand-written path also returns next_norm(result) from the residual row pass -> (x, y_next).
         rows_to (functional.RowsTo): y / xres are compact rows of a stream; the result is written back into it."""
         rps = _rows_per_scale(y, rs)
-        if rows_to is not None:
-            if not (dtype == torch.bfloat16 and self.rows_ok(y)) or next_norm is not None:
-                raise RuntimeError("Mlp.forward_fused: rows_to needs the hand-written bf16 path (check rows_ok first)")
+        hip = dtype == torch.bfloat16 and self.rows_ok(y)
+        if rows_to is not None and (not hip or next_norm is not None):
+            raise RuntimeError("Mlp.forward_fused: rows_to needs the hand-written bf16 path (check rows_ok first)")
+        if hip:
+            norm, rows = _tail_args(next_norm, rows_to)
             return _OF.DenseMlpFn.apply(y, xres, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, gamma,
-                                        rs, rps, self._c1, self._c2, None, None, None, rows_to, rows_to.stream)
-        if (dtype == torch.bfloat16 and _OF.dense_hip_ok(y, self.fc1.weight) and _OF.dense_hip_ok(y, self.fc2.weight)
-                and ({"fc1", "fc2", "dfc1", "dfc2"} & _OF.DENSE_HIP)):
-            if next_norm is not None:
-                return _OF.DenseMlpFn.apply(y, xres, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, gamma,
-                                            rs, rps, self._c1, self._c2, next_norm.weight, next_norm.bias,
-                                            next_norm.eps)
-            return _OF.DenseMlpFn.apply(y, xres, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, gamma,
-                                        rs, rps, self._c1, self._c2)
+                                        rs, rps, self._c1, self._c2, *norm, *rows)
         if next_norm is not None:
             return self.forward_fused(y, xres, gamma, rs, dtype), None
         if dtype == torch.bfloat16 and self.fc1.out_features % 8 == 0:
@@ -132,17 +132,13 @@ class Attention(nn.Module):
         else:
             a = _OF.AttnFusedQKVFn.apply(qkv.view(B, N, 3, self.num_heads, hd), hd ** -0.5)
         rps = _rows_per_scale(y, rs)
-        if rows_to is not None:
-            if not (bf and self.rows_ok(y)) or next_norm is not None:
-                raise RuntimeError("Attention.forward_fused: rows_to needs the hand-written bf16 path (check rows_ok first)")
+        hip = bf and self.rows_ok(y)
+        if rows_to is not None and (not hip or next_norm is not None):
+            raise RuntimeError("Attention.forward_fused: rows_to needs the hand-written bf16 path (check rows_ok first)")
+        if hip:
+            norm, rows = _tail_args(next_norm, rows_to)
             return _OF.DenseProjResidFn.apply(xres, a, self.proj.weight, self.proj.bias, gamma, rs, rps, self._c2,
-                                              None, None, None, self._wgpair, rows_to, rows_to.stream)
-        if bf and _OF.dense_hip_ok(y, self.proj.weight, "proj"):
-            if next_norm is not None:
-                return _OF.DenseProjResidFn.apply(xres, a, self.proj.weight, self.proj.bias, gamma, rs, rps, self._c2,
-                                                  next_norm.weight, next_norm.bias, next_norm.eps, self._wgpair)
-            return _OF.DenseProjResidFn.apply(xres, a, self.proj.weight, self.proj.bias, gamma, rs, rps, self._c2,
-                                              None, None, None, self._wgpair)
+                                              *norm, self._wgpair, *rows)
         out = _OF.LinearScaleResidualFn.apply(xres, a, self.proj.weight, self.proj.bias, gamma, rs, rps, dtype, self._c2)
         return out if next_norm is None else (out, None)
 
@@ -179,13 +175,12 @@ def _drop_path_scale(dp, x):
     return mask.view(-1)
 
 
-def _fused_block(x, norm1, attn, gamma1, dp1, norm2, mlp, gamma2, dp2, next_norm=None):
-    """bf16-autocast forward of one standard block on the engine's row kernels + GEMMs, or None when the block is not
-    in that regime (f32 run, CPU, dropout active, exotic sub-modules): the caller then runs eager.
-    With functional.NEXT_NORM_FUSED the residual add of a branch and the LayerNorm that opens the next branch are one row
-    pass: norm2 comes out of the attention branch's tail; norm1 of the NEXT block (next_norm, set by link_blocks) out of
-    the MLP's tail and travels as an attribute of the returned stream tensor (`_octic_prenorm`), which that block picks
-    up instead of running its own norm1."""
+def _engine_regime(x, norm1, attn, norm2, mlp, scales, ntok=None):
+    """[gamma1, gamma2] - the layer-scale vectors, None where a branch has none - of a standard block whose forward can run
+    on the engine: bf16 autocast on the GPU over the f32 stream [B, N, d], LayerNorms the row kernels take, fusable
+    sub-modules.  None when the block is not in that regime (f32 run, CPU, dropout active, exotic sub-modules).
+    scales: per branch the layer-scale vector itself (or None), or the block's LayerScale / nn.Identity module.
+    ntok: tokens per image where that is not x.shape[1] (the rows of several crop sets: ragged.py)."""
     if not (x.is_cuda and x.ndim == 3 and x.dtype == torch.float32 and torch.is_autocast_enabled("cuda")
             and torch.get_autocast_dtype("cuda") == torch.bfloat16):
         return None
@@ -193,13 +188,35 @@ def _fused_block(x, norm1, attn, gamma1, dp1, norm2, mlp, gamma2, dp2, next_norm
     for n in (norm1, norm2):
         if type(n) is not nn.LayerNorm or tuple(n.normalized_shape) != (d,) or d % 4 or d > 2048:
             return None
-    if not (isinstance(attn, Attention) and isinstance(mlp, Mlp) and attn.fusable(x.shape[1], torch.bfloat16)
-            and mlp.fusable()):
+    if not (isinstance(attn, Attention) and isinstance(mlp, Mlp) and mlp.fusable()
+            and attn.fusable(x.shape[1] if ntok is None else ntok, torch.bfloat16)):
+        return None
+    gammas = []
+    for ls in scales:
+        if ls is None or isinstance(ls, nn.Identity):
+            gammas.append(None)
+        elif isinstance(ls, torch.Tensor):
+            gammas.append(ls)
+        elif isinstance(ls, LayerScale) and not ls.inplace:
+            gammas.append(ls.gamma)
+        else:
+            return None
+    return gammas
+
+
+def _fused_block(x, norm1, attn, gamma1, dp1, norm2, mlp, gamma2, dp2, next_norm=None):
+    """bf16-autocast forward of one standard block on the engine's row kernels + GEMMs, or None when the block is not
+    in that regime (f32 run, CPU, dropout active, exotic sub-modules): the caller then runs eager.
+    With functional.NEXT_NORM_FUSED the residual add of a branch and the LayerNorm that opens the next branch are one row
+    pass: norm2 comes out of the attention branch's tail; norm1 of the NEXT block (next_norm, set by link_blocks) out of
+    the MLP's tail and travels as an attribute of the returned stream tensor (`_octic_prenorm`), which that block picks
+    up instead of running its own norm1."""
+    if _engine_regime(x, norm1, attn, norm2, mlp, (gamma1, gamma2)) is None:
         return None
     for dp in (dp1, dp2):
         if not isinstance(dp, (DropPath, nn.Identity)):
             return None
-    dt = torch.bfloat16
+    d, dt = x.shape[-1], torch.bfloat16
     from . import d8_layers as _L
     if torch.compiler.is_compiling():
         return _traced_block(x, norm1, attn, gamma1, dp1, norm2, mlp, gamma2, dp2)
@@ -379,24 +396,11 @@ class NestedTensorBlock(Block):
         back - instead of the eager composition (ATen LayerNorm, library GEMMs, layer-scale multiply, index_add).  The subsets
         are drawn exactly like the reference draws them (one randperm per branch, dinov2/layers/block.py:121-123), so a
         seeded run picks the same samples as the eager path.  None when the block is not in that regime."""
-        if not (x.is_cuda and x.ndim == 3 and x.dtype == torch.float32 and torch.is_autocast_enabled("cuda")
-                and torch.get_autocast_dtype("cuda") == torch.bfloat16 and not torch.compiler.is_compiling()):
+        if torch.compiler.is_compiling():
             return None
-        d = x.shape[-1]
-        for n in (self.norm1, self.norm2):
-            if type(n) is not nn.LayerNorm or tuple(n.normalized_shape) != (d,) or d % 4 or d > 2048:
-                return None
-        if not (isinstance(self.attn, Attention) and isinstance(self.mlp, Mlp)
-                and self.attn.fusable(x.shape[1], torch.bfloat16) and self.mlp.fusable()):
+        gammas = _engine_regime(x, self.norm1, self.attn, self.norm2, self.mlp, (self.ls1, self.ls2))
+        if gammas is None:
             return None
-        gammas = []
-        for ls in (self.ls1, self.ls2):
-            if isinstance(ls, nn.Identity):
-                gammas.append(None)
-            elif isinstance(ls, LayerScale) and not ls.inplace:
-                gammas.append(ls.gamma)
-            else:
-                return None
         from . import d8_layers as _L
         b = x.shape[0]
         keep = max(int(b * (1 - self.sample_drop_ratio)), 1)
@@ -419,26 +423,12 @@ class NestedTensorBlock(Block):
         per-row stochastic-depth masks.  None when the block cannot take the engine path (the caller splits the sets)."""
         from . import d8_layers as _L
         from . import ragged as _R
-        if not (x.is_cuda and x.dtype == torch.float32 and torch.is_autocast_enabled("cuda")
-                and torch.get_autocast_dtype("cuda") == torch.bfloat16 and not torch.compiler.is_compiling()):
+        if torch.compiler.is_compiling():
             return None
-        d = x.shape[-1]
-        for n in (self.norm1, self.norm2):
-            if type(n) is not nn.LayerNorm or tuple(n.normalized_shape) != (d,) or d % 4 or d > 2048:
-                return None
-        hd = d // self.attn.num_heads if isinstance(self.attn, Attention) else 0
-        if not (isinstance(self.attn, Attention) and isinstance(self.mlp, Mlp) and self.mlp.fusable()
-                and self.attn.fusable(rag.sets[0][1], torch.bfloat16) and _R.attn_sets_supported(rag, hd, torch.bfloat16)):
+        gammas = _engine_regime(x, self.norm1, self.attn, self.norm2, self.mlp, (self.ls1, self.ls2), ntok=rag.sets[0][1])
+        d, bf = x.shape[-1], torch.bfloat16
+        if gammas is None or not _R.attn_sets_supported(rag, d // self.attn.num_heads, bf):
             return None
-        gammas = []
-        for ls in (self.ls1, self.ls2):
-            if isinstance(ls, nn.Identity):
-                gammas.append(None)
-            elif isinstance(ls, LayerScale) and not ls.inplace:
-                gammas.append(ls.gamma)
-            else:
-                return None
-        bf = torch.bfloat16
         if self.training and self.sample_drop_ratio > 0.1:
             if not STREAM_OWNED[0]:
                 x = x.clone()

@@ -419,3 +419,67 @@ def test_deferred_octic_layernorm_finishes_are_bitwise_the_immediate_ones():
     assert len(res[False]) == len(res[True]) > 20
     for a, b in zip(res[False], res[True]):
         assert torch.equal(a, b)
+
+
+def _close(got, want, tol, msg):
+    got, want = got.double(), want.double()
+    scale = max(1.0, float(want.abs().max()))
+    err = float((got - want).abs().max())
+    print(f"{msg}: max err {err:.3e}, scale {scale:.3g}")
+    assert err <= tol * scale, f"{msg}: max err {err:.3e} > {tol:g} x {scale:.3g}"
+
+
+def test_resid_fused_node_path_matches_the_separate_row_pass():
+    """functional.DENSE_RESID_FUSED through the autograd nodes of a block (proj and fc2 with x + rs*gamma*y in the GEMM's
+    epilogue) against the plain epilogue + scale_residual_fwd: 150 rows (ragged row tiles), drop-path masks from the same
+    seed.  Output within 1e-5 of scale (the bound test_dense_nt_resid holds the epilogue to against the same formula), the
+    input gradient and every parameter gradient within 2e-2 of scale (bf16); the fused run launches two
+    dense_nt_kernel<resid> and no scale_residual_fwd, the other run the reverse."""
+    from octic_vits_amd import functional as OF
+    blk = _blocks("layer_scale", 256, 4, 0.3)[0].train()
+    x = gen(51, 3, 50, 256).to(DEV)
+    cot = gen(52, 3, 50, 256).to(DEV)
+    o = ops()
+    res, launches = {}, {}
+    saved = OF.NEXT_NORM_FUSED, OF.DENSE_RESID_FUSED
+    OF.NEXT_NORM_FUSED = False             # (with it on the next-norm row pass adds the residual and the flag is never read)
+    try:
+        for mode in (True, False):
+            OF.DENSE_RESID_FUSED = mode
+            blk.zero_grad(set_to_none=True)
+            xi = x.clone().requires_grad_(True)
+            torch.manual_seed(123)
+            o.KERNEL_TIMER.enable()
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                y = blk(xi)
+            y.backward(cot)
+            s = o.KERNEL_TIMER.summary()
+            o.KERNEL_TIMER.disable()
+            res[mode] = [y.detach().clone(), xi.grad.clone()] + [p.grad.clone() for p in blk.parameters()]
+            launches[mode] = tuple(sum(v["launches"] for n, v in s.items() if n.startswith(k))
+                                   for k in ("dense_nt_kernel<resid>", "scale_residual_fwd"))
+    finally:
+        o.KERNEL_TIMER.disable()
+        OF.NEXT_NORM_FUSED, OF.DENSE_RESID_FUSED = saved
+    assert launches == {True: (2, 0), False: (0, 2)}, launches
+    names = ["out", "dx"] + [n for n, _ in blk.named_parameters()]
+    for n, a, b in zip(names, res[True], res[False]):
+        _close(a, b, 1e-5 if n == "out" else 2e-2, f"block {n} (residual in the GEMM epilogue vs the row pass)")
+
+
+def _census_cases():
+    import make_dense_tail_census as C
+    return list(C.CONFIGS)
+
+
+@pytest.mark.parametrize("config", _census_cases())
+def test_standard_half_launch_census(config):
+    """Which kernels one forward + backward of two linked standard blocks (and, for rows_to, of the ragged pass of a small
+    DINOv2 backbone) launches, and how often, under every routing of the residual tail: equal to the recorded census
+    (tests/golden/dense_tail_census.json, written by tests/golden/make_dense_tail_census.py)."""
+    import json
+    import make_dense_tail_census as C
+    with open(C.PATH) as f:
+        want = json.load(f)[config]
+    got = C.census(config)
+    assert got == want, {k: (got.get(k), want.get(k)) for k in sorted(set(got) | set(want)) if got.get(k) != want.get(k)}

@@ -448,3 +448,15 @@ def test_ragged_mask_pool_statistics():
         per_sample = torch.cat([m[:1200].view(400, 3)[:, 0], m[1200:].view(600, 2)[:, 0]])
         assert torch.equal(rag.row_scale(per_sample), m)     # one value per sample, repeated over its rows
         assert abs(float((per_sample > 0).float().mean()) - keep) < 0.06
+
+
+def test_dense_gemm_ok_is_the_shape_rule_both_call_sites_had():
+    """ops.dense_gemm_ok (behind functional.dense_hip_ok and dispatch._hip_gemm_ok) against the rule written out: K and N
+    multiples of 64 and at least 128, operands within 32-bit byte offsets."""
+    from octic_vits_amd import dispatch, ops
+    for rows in (1, 150, 16448, 2 ** 24):
+        for N in (64, 128, 192, 264, 1280, 5120):
+            for K in (64, 128, 192, 264, 1280, 5120):
+                want = K % 64 == 0 and K >= 128 and N % 64 == 0 and N >= 128 and rows * max(N, K) * 2 < 2 ** 31
+                assert ops.dense_gemm_ok(rows, N, K) is want, (rows, N, K)
+                assert dispatch._hip_gemm_ok(rows, N, K) is want, (rows, N, K)
