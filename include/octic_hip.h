@@ -38,7 +38,7 @@ extern "C" {
 
 #define OCTIC_ABI_VERSION 20
 
-enum { OCTIC_F32 = 0, OCTIC_BF16 = 1 };
+enum { OCTIC_F32 = 0, OCTIC_BF16 = 1, OCTIC_U8 = 2 /* octic_augment_u8's pixel output only */ };
 
 enum {
   OCTIC_OK = 0,
@@ -638,6 +638,44 @@ int octic_mix_targets(const int64_t* labels, const octic_mix_row* table, int B, 
 int octic_mix_bce(const void* logits, int dtype, int64_t ldl, const int64_t* labels, const octic_mix_row* table, int B, int row0,
                   int rows, int num_classes, float on, float off, int binarize, float* loss, const float* gscale,
                   void* dlogits, int64_t ldd, void* workspace, void* stream);
+
+/* ---- 3-Augment of the DeiT-III recipe on uint8 batches (deit/augment.py:90-123 behind the crop) ---------------------------
+ * RandomHorizontalFlip, RandomChoice(grayscale, solarize, Gaussian blur), ColorJitter(brightness, contrast, saturation),
+ * ToTensor and Normalize as one call on the decoded, cropped batch.  As for the mix the host draws the per-sample parameters
+ * and uploads them as a DEVICE table of B rows; the kernels take everything about the draw from it.  A row whose op is not
+ * 0..3, or a blur row whose box radius is not 0 or 1, gets no op; a jitter entry outside 0..2, or one that repeats an earlier
+ * entry, is skipped.  The arithmetic is PIL's (Pillow's ImageOps / ImageFilter / ImageEnhance), rounding for rounding, with a
+ * uint8 image between all stages:
+ *   flip       x -> W-1-x
+ *   grayscale  L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 in all three channels
+ *   solarize   v < 128 ? v : 255 - v
+ *   blur       three passes along x, then three along y, per channel, of
+ *              out[x] = (ww sum_{|d| <= r} in[clamp(x+d)] + fw (in[clamp(x-r-1)] + in[clamp(x+r+1)]) + (1 << 23)) >> 24,
+ *              clamp to the line.  The host computes the constants in FLOAT32, one rounding per operation, from the radius:
+ *              s2 = radius radius / 3, L = sqrtf(12 s2 + 1), l = floorf((L - 1) / 2),
+ *              a = (2l + 1)(l (l + 1) - 3 s2) / (6 (s2 - (l + 1)^2)), fr = l + a; r = (int)fr,
+ *              ww = (uint32)((float)(1 << 24) / (fr 2 + 1)), fw = ((1 << 24) - (2r + 1) ww) / 2.  radius <= 2 gives r <= 1.
+ *   jitter     order[0..3] in turn: v = trunc(clip(deg + f (v - deg), 0, 255)) in f32, product and sum rounded separately;
+ *              brightness: deg = 0; saturation: deg = the pixel's L; contrast: deg = (2 S + N) / (2 N) in integers, S = the sum
+ *              of L over the whole image as it is at that point of the chain, N = H W
+ *   output     (v / 255 - mean[c]) / std[c], two correctly rounded f32 divisions                                          */
+typedef struct {
+  int32_t flip;                            /* != 0: mirrored along x                                       */
+  int32_t op;                              /* 0 none, 1 grayscale, 2 solarize, 3 Gaussian blur             */
+  int32_t blur_r, blur_ww, blur_fw;        /* the box pass constants (op 3)                                */
+  int32_t order[4];                        /* jitter ops in application order: 0 brightness, 1 contrast, 2 saturation, -1 skip */
+  float brightness, contrast, saturation;  /* the blend factors                                            */
+  int32_t pad[4];
+} octic_aug_row;
+/* bytes of the workspace of octic_augment_u8 (per-tile sums of L for the contrast op); OCTIC_ESHAPE for non-positive sizes */
+int64_t octic_augment_workspace_bytes(int B, int H, int W);
+/* src: uint8 [B, H, W, 3] (a decoder's layout, and PIL's), left untouched.  dst, by dtype_out: OCTIC_F32 - f32 [B, 3, H, W],
+ * the normalised batch the model takes; OCTIC_U8 - uint8 [B, H, W, 3], the augmented pixels in front of ToTensor.  Any
+ * H, W >= 1 with H W 3 < 2^31.  workspace: octic_augment_workspace_bytes(B, H, W) bytes, 4-byte aligned, always required (the
+ * table decides on the device whether a sample has a contrast op).  src and dst must not overlap (OCTIC_ESHAPE).  Integer
+ * sums only, no atomics: bitwise reproducible.                                                                         */
+int octic_augment_u8(const uint8_t* src, void* dst, int dtype_out, const octic_aug_row* table, float mean0, float mean1,
+                     float mean2, float std0, float std1, float std2, int B, int H, int W, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OCTIC_LIB") or os.path.join(HERE, "liboctic_hip.so")   # OCTIC_LIB: developer A/B builds
 HEADER_PATH = os.path.join(HERE, "..", "include", "octic_hip.h")
 
-F32, BF16 = 0, 1
+F32, BF16, U8 = 0, 1, 2
 ABI_VERSION = 20
 # knobs of octic_route_override (include/octic_hip.h)
 (ROUTE_DENSE_TILE, ROUTE_DENSE_SPLIT, ROUTE_WGRAD_SLABS, ROUTE_WGRAD_TILE, ROUTE_LINEAR_RING, ROUTE_RING_EVEN,
@@ -157,6 +157,8 @@ _PROTOS = {
     "octic_mix_targets": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p]),
     "octic_mix_bce": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
                               c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
+    "octic_augment_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "octic_augment_u8": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_float] * 6 + [c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 

@@ -1362,3 +1362,44 @@ def mix_bce(logits, labels, table, on, off, binarize, row0=0, loss=None, workspa
                               float(on), float(off), int(bool(binarize)), _p(loss), _p(gscale), _p(dlogits),
                               dlogits.stride(0) if dlogits is not None else 0, _p(workspace), _stream(logits)))
     KERNEL_TIMER.stop(t, f"mix_bce_kernel<{_DTN[logits.dtype]}>", logits.numel() * logits.element_size() * (2 if dlogits is not None else 1))
+
+
+# ------------------------------------------------------------------------------------------ 3-Augment on uint8 (csrc/augment.hip)
+def augment_workspace(B, H, W, device):
+    """The int32 workspace octic_augment_u8 needs for a [B, H, W, 3] batch."""
+    n = lib().octic_augment_workspace_bytes(int(B), int(H), int(W))
+    if n < 0:
+        check(int(n))
+    return torch.empty(n // 4, dtype=torch.int32, device=device)
+
+
+def augment_u8(src, table, mean, std, dst, workspace=None):
+    """dst = the uint8 batch src [B, H, W, 3] augmented as the device table (AugParams.table()) says; dst is f32 [B, 3, H, W]
+    (normalised with mean / std, three floats each) or uint8 [B, H, W, 3] (the pixels in front of ToTensor)."""
+    _require_cuda(src)
+    _require_cuda(dst)
+    _require_cuda(table)
+    if src.dim() != 4 or src.shape[3] != 3 or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError("augment_u8: images must be a contiguous uint8 [B, H, W, 3] tensor")
+    B, H, W, _ = src.shape
+    if table.dtype != torch.int32 or tuple(table.shape) != (B, 16) or not table.is_contiguous():
+        raise ValueError(f"augment_u8: the parameter table must be a contiguous int32 [{B}, 16] tensor (AugParams.table())")
+    if dst.dtype == torch.float32:
+        want, code = (B, 3, H, W), _lib.F32
+    elif dst.dtype == torch.uint8:
+        want, code = (B, H, W, 3), _lib.U8
+    else:
+        raise TypeError(f"augment_u8: the output is float32 [B, 3, H, W] or uint8 [B, H, W, 3], got {dst.dtype}")
+    if tuple(dst.shape) != want or not dst.is_contiguous():
+        raise ValueError(f"augment_u8: the {dst.dtype} output must be a contiguous {want} tensor")
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("augment_u8: mean and std take three values each")
+    if workspace is None:
+        workspace = augment_workspace(B, H, W, src.device)
+    elif workspace.dtype != torch.int32 or not workspace.is_cuda or workspace.numel() * 4 < lib().octic_augment_workspace_bytes(B, H, W):
+        raise ValueError("augment_u8: the workspace must be an int32 GPU tensor of augment_workspace(B, H, W)'s size")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_augment_u8(_p(src), _p(dst), code, _p(table), *[float(v) for v in mean], *[float(v) for v in std], B, H, W,
+                                 _p(workspace), _stream(src)))
+    KERNEL_TIMER.stop(t, "augment_kernel", 2 * src.numel() + dst.numel() * dst.element_size())
+    return dst

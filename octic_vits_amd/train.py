@@ -13,6 +13,9 @@ targets -> backward (gradients all-reduced over RCCL by DDP bucket hooks, overla
   * Mixup / CutMix (engine.py:47-54, timm's ``mixup_fn`` + ``targets.gt(0)``) are part of the step when the trainer is given a
     ``mixup.Mixup``: the draw on the host, the mix and the BCE loss as HIP kernels driven by a small device table
     (``Trainer(mixup=...)``); without one the caller passes mixed float targets as before.
+  * 3-Augment behind the crop (deit/augment.py:90-123: flip, grayscale / solarize / blur, ColorJitter, ToTensor, Normalize) is
+    part of the step when the trainer is given an ``augment.ThreeAugment``: the batch comes as uint8 [B, H, W, 3], the draw stays
+    on the host, the pixels are HIP kernels in front of the mix (``Trainer(augment=...)``).
 ``evaluate`` is the reference's evaluation loop (engine.py:98-128) on one GPU.
 """
 import math
@@ -1023,7 +1026,7 @@ class Trainer:
     def __init__(self, model, lr=3e-3, weight_decay=0.02, ema_decay=0.99996, distributed=False, local_rank=0,
                  fused_optimizer=True, tuned_gemms=True, opt_eps=1e-8, accum_steps=1, bf16_buckets=False,
                  autocast=True, check_every=1, device_type=None, bucket_cap_mb=None, segment_graphs=0, ddp_proxy=None,
-                 own_reducer=None, mixup=None, fused_loss=True):
+                 own_reducer=None, mixup=None, fused_loss=True, augment=None):
         """mixup: a ``mixup.Mixup`` (GPU only) - ``step`` / ``capture`` / ``GraphedStep.replay`` then take ``(images, int64 labels
         [B])``: every step draws the Mixup / CutMix parameters on the host, uploads them as one small device table (pinned ring,
         no stream drain), mixes the WHOLE batch once with the HIP kernels of csrc/mixup.hip and takes the recipe's BCE loss
@@ -1031,6 +1034,11 @@ class Trainer:
         come from ``mixup.mix_bce_loss`` without materialised targets; False materialises them (``mixup.mix_targets``) for
         ``nn.BCEWithLogitsLoss``.  Data parallel: every rank owns its ``Mixup``, seeded ``seed + rank`` as the reference seeds
         its ranks.  None: the caller mixes, ``step`` takes float multi-hot targets as before.
+        augment: an ``augment.ThreeAugment`` (GPU only) - ``step`` / ``capture`` / ``GraphedStep.replay`` then take the decoded,
+        cropped batch as uint8 [B, H, W, 3]: every step draws the flip / op / jitter parameters on the host, uploads them as a second
+        small device table and runs the kernels of csrc/augment.hip on the WHOLE batch in front of the mix; their normalised f32
+        [B, 3, H, W] output is what the mix (or, without ``mixup``, the model) reads, and a captured step's input buffer is the uint8
+        batch.  None: ``step`` takes normalised f32 images as before.
         segment_graphs = n > 0 (GPU only): forward and backward run as 2 n hipGraph replays (``SegmentedModel``), the
         loss, the gradient all-reduce hooks and the optimizer stay eager - the cheap-on-the-host step for gradient
         accumulation, where the whole-step graph of ``capture`` does not apply.
@@ -1043,6 +1051,12 @@ class Trainer:
         self.mixup, self.fused_loss, self._mix_tables = mixup, bool(fused_loss), {}
         if mixup is not None and (device_type or next(model.parameters()).device.type) != "cuda":
             raise RuntimeError("Trainer(mixup=...): Mixup / CutMix run on the GPU only (HIP kernels, no CPU fallback)")
+        self.augment, self._aug_tables = augment, {}
+        if augment is not None and (device_type or next(model.parameters()).device.type) != "cuda":
+            raise RuntimeError("Trainer(augment=...): 3-Augment runs on the GPU only (HIP kernels, no CPU fallback)")
+        if augment is not None and segment_graphs:
+            raise RuntimeError("Trainer(augment=..., segment_graphs=n): graphed slices are captured on normalised f32 micro-batches; "
+                               "augment in front of the trainer (ThreeAugment.apply) or use capture()")
         self.segmented = None
         if segment_graphs:
             self.segmented = SegmentedModel(model, segment_graphs)
@@ -1188,9 +1202,27 @@ class Trainer:
             up = self._mix_tables[B] = TableUploader(B, device)
         return up
 
+    def _aug_table(self, B, device):
+        up = self._aug_tables.get(B)
+        if up is None:
+            from .augment import AugTableUploader
+            up = self._aug_tables[B] = AugTableUploader(B, device)
+        return up
+
+    def _aug_draw(self, samples):
+        """A fresh 3-Augment draw for this uint8 batch, on its way to the device table (as ``_mix_draw``)."""
+        return self._aug_table(samples.shape[0], samples.device).upload(self.augment.draw(samples.shape[0]))
+
+    def _aug_batch(self, samples):
+        """The launches of the augmentation (also what ``capture`` records): uint8 [B, H, W, 3] -> normalised f32 [B, 3, H, W]."""
+        return self.augment.launch(samples, self._aug_table(samples.shape[0], samples.device).table)
+
     def _mix_draw(self, samples):
         """A fresh draw for this batch shape, on its way to the device table (stream-ordered, in front of the step)."""
-        B, _, H, W = samples.shape
+        if self.augment is not None and samples.dtype == torch.uint8:     # (the uint8 batch in front of the augmentation)
+            B, H, W, _ = samples.shape
+        else:
+            B, _, H, W = samples.shape
         return self._mix_table(B, samples.device).upload(self.mixup.draw(B, H, W))
 
     def _mix_batch(self, samples, labels):
@@ -1257,6 +1289,8 @@ class Trainer:
         if self._ddp_args is not None and self.model is self.segmented:
             raise RuntimeError("Trainer(distributed=True, segment_graphs=n): call capture_segments(micro_batch) before the "
                                "first step (the slices are captured, then wrapped in DistributedDataParallel)")
+        if self.augment is not None:
+            self.augment.check_batch(samples, "Trainer(augment=...)")
         if self.mixup is not None:
             self._mix_check(samples, targets)
         self.model.train()
@@ -1264,6 +1298,9 @@ class Trainer:
         self._steps += 1
         if self._steps % self.check_every == 0:
             self._watch.check()
+        if self.augment is not None:
+            self._aug_draw(samples)
+            samples = self._aug_batch(samples)
         if self.mixup is not None:
             self._mix_draw(samples)
             samples, targets = self._mix_batch(samples, targets)
@@ -1342,6 +1379,8 @@ class Trainer:
             # sx / sy are the staging images and labels; the parameter table is the third static input (``_mix_table``):
             # ``GraphedStep.replay`` refills all three in front of the replay, the mix kernels and the loss are in the graph
             self._mix_check(samples, targets)
+        if self.augment is not None:                    # sx is the uint8 staging batch; the augmentation table a static input
+            self.augment.check_batch(samples, "Trainer(augment=...)")
         sx, sy = samples.clone(), targets.clone()
         for _ in range(max(1, warmup)):
             self.step(sx, sy)
@@ -1364,6 +1403,8 @@ class Trainer:
 
     def _capture_body(self, graph, mode, sx, sy):
         with torch.cuda.graph(graph, **mode):
+            if self.augment is not None:
+                sx = self._aug_batch(sx)
             if self.mixup is not None:
                 sx, sy = self._mix_batch(sx, sy)
             if self.accum_steps > 1:
@@ -1441,11 +1482,15 @@ class GraphedStep:
         if t._steps % t.check_every == 0:
             t._watch.check()
         if samples is not None and samples.data_ptr() != self.samples.data_ptr():
+            if t.augment is not None:
+                t.augment.check_batch(samples, "Trainer(augment=...)")
             self.samples.copy_(samples, non_blocking=True)
         if targets is not None and targets.data_ptr() != self.targets.data_ptr():
             if t.mixup is not None:
                 t._mix_check(self.samples, targets)
             self.targets.copy_(targets, non_blocking=True)
+        if t.augment is not None:                       # this step's 3-Augment draw, likewise
+            t._aug_draw(self.samples)
         if t.mixup is not None:                         # this step's Mixup / CutMix draw: the captured kernels read the table
             t._mix_draw(self.samples)
         # a schedule's new lr / weight decay / EMA decay: copied in front of the replay (the captured kernels read them)
@@ -1470,7 +1515,8 @@ def evaluate(model, batches, graphed=True):
     cross-entropy sum and the top-1 / top-5 counts accumulate ON THE DEVICE (``ops.probe_ce`` with one head); the host reads
     them once at the end.  Returns {"loss": mean over the images, "acc1", "acc5": percentages} as the reference's
     ``global_avg`` meters (weighted by batch size).  graphed: batches of the first batch's shape run through
-    ``serve.GraphedForward``, a ragged last batch eagerly."""
+    ``serve.GraphedForward``, a ragged last batch eagerly.  Images may also come as uint8 [B, H, W, 3] (decoded, cropped): they
+    go through ``augment.to_tensor`` (ToTensor + Normalize on the device, ImageNet's mean / std as in deit/datasets.py:134-135)."""
     from . import ops
     model.eval()
     gf = None
@@ -1481,6 +1527,9 @@ def evaluate(model, batches, graphed=True):
         ops._require_cuda(labels)
         if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] != images.shape[0]:
             raise ValueError("evaluate: labels must be int64 class indices [B]")
+        if images.dtype == torch.uint8:
+            from .augment import to_tensor
+            images = to_tensor(images)
         if loss_sum is None:
             loss_sum = torch.zeros(1, dtype=torch.float32, device=images.device)
             topk = torch.zeros(2, dtype=torch.int32, device=images.device)
