@@ -59,8 +59,13 @@ const char* octic_strerror(int code);
 
 /* ---- routing overrides (measurement / tests) --------------------------------------------------
  * Every entry point chooses its kernel and tiling from the shapes alone.  The alternatives it chooses between are all
- * shipped and parity-tested; this ONE call forces a choice so that an A/B or a test can run the other kernel on the
- * same operands.  It is the library's only process-global mutable state: not thread-safe against concurrent launches,
+ * shipped; this ONE call forces a choice so that an A/B or a test can run the other kernel on the same operands.
+ * Parity-tested under a forced value (tests/): DENSE_TILE, WGRAD_TILE, LINEAR_RING, DENSE_IMAGE, DENSE_CLS2, ATTN_STREAM
+ * and the three attention knobs ATTN_LEGACY, ATTN_ONLINE, ATTN_BWD_PAIR (tests/test_attn_resident_gpu.py).  NOT set by
+ * any test: DENSE_SPLIT, WGRAD_SLABS and RING_EVEN - the tests reach those alternatives only where the automatic
+ * choice picks them; the forced values are exercised by the A/B tools (tools/ab_dense_tile.py, tools/bench_tn.py,
+ * tools/wreg_check.py) alone.
+ * It is the library's only process-global mutable state: not thread-safe against concurrent launches,
  * value 0 = automatic (the default), returns the previous value (OCTIC_ESHAPE for an unknown knob).              */
 enum {
   OCTIC_ROUTE_DENSE_TILE = 0,      /* octic_dense_gemm_nt plain mode: 4 = 256 x 256 tile, 5 = 256 x 320 tile              */

@@ -510,13 +510,16 @@ def prep_views(flat, cin, cout, transposed):
     return out
 
 
-def attn_fwd(q, k, v, scale):
-    """q,k,v: [B,H,T,hd] bf16 views with a common stride set (last dim contiguous) -> (o [B,H,T,hd], lse [B,H,T])"""
+def attn_fwd(q, k, v, scale, out=None):
+    """q,k,v: [B,H,T,hd] bf16 views with a common stride set (last dim contiguous) -> (o [B,H,T,hd], lse [B,H,T]);
+    out: an optional [B,H,T,hd] view (last dim contiguous, strides multiples of 8) that receives o"""
     B, H, T, hd = q.shape
     st = q.stride()
     if st[3] != 1 or k.stride() != st or v.stride() != st:
         raise ValueError("attn_fwd: q, k, v must share strides and be contiguous in the last dim")
-    o = torch.empty((B, H, T, hd), dtype=q.dtype, device=q.device)
+    if out is not None and (out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or out.stride(3) != 1):
+        raise ValueError("attn_fwd: out must match q in shape, dtype and device and be contiguous in the last dim")
+    o = out if out is not None else torch.empty((B, H, T, hd), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
     t = KERNEL_TIMER.start()
     check(lib().octic_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, T, hd, st[0], st[1], st[2],
@@ -533,14 +536,18 @@ def attn_supported(T, hd, dtype):
     return dtype == torch.bfloat16 and 0 < T <= ATTN_MAX_T and hd % 16 == 0 and 0 < hd <= 128
 
 
-def attn_streams(T, hd):
+def attn_streams(T, hd, backward=False):
     """True where the entry points run the streaming kernels (csrc/attn_stream.hip: K / V through LDS in blocks):
-    T > 320, a head whose K and V do not fit in LDS at once, or every shape under ROUTE_ATTN_STREAM = 1."""
+    T > 320, a head whose images do not fit in LDS at once (attn_fwd_launch: K and V; attn_bwd_launch: two row images and
+    the delta partials or the statistics - more per row, so the backward streams from fewer tokens on: head_dim 112 from
+    257, the forward from 289), or every shape under ROUTE_ATTN_STREAM = 1."""
     if T > 320 or _lib.ROUTES.get(_lib.ROUTE_ATTN_STREAM, 0) == 1:
         return True
     tp = (T + 31) // 32 * 32
-    cols = max((hd + 31) // 32 * 32, hd)
-    return 2 * tp * (cols * 2 + 16) + 2 * tp * 4 > 160 * 1024
+    cols = (hd + 31) // 32 * 32
+    if backward:
+        return 2 * tp * (cols * 2 + 16) + max(tp * (hd // 8) * 4, 2 * tp * 4) > 160 * 1024
+    return tp * ((hd * 2 + 16) + (cols * 2 + (64 if cols % 64 == 0 else 0))) > 160 * 1024
 
 
 def _attn_fwd_name(T, hd):
@@ -554,7 +561,7 @@ ATTN_BWD_FUSED = True
 
 def _attn_bwd_phases(T, hd):
     """(phase, timer name, algorithmic bytes per element of q, flops per B H T^2 hd) of the backward launches."""
-    if attn_streams(T, hd):                               # phase 1: dq (3 products), phase 2: dk, dv (4 products)
+    if attn_streams(T, hd, backward=True):                # phase 1: dq (3 products), phase 2: dk, dv (4 products)
         return ((1, "attn_bwd_dq_stream_kernel", 6, 6.0), (2, "attn_bwd_dkv_stream_kernel", 6, 8.0))
     if ATTN_BWD_FUSED and hd == 80 and (T == 257 or 192 < T <= 256 or T <= 64):    # csrc/attn80_bwd.hip: attn80_bwd_ok
         return ((3, "attn_bwd_kernel", 8, 10.0),)         # reads q k v o dO, writes dq dk dv
