@@ -261,6 +261,32 @@ int octic_attn_bwd(const void* q, const void* k, const void* v, const void* o, c
                    int64_t sT, int64_t oB, int64_t oH, int64_t oT, int64_t gB, int64_t gH, int64_t gT, float scale,
                    int phase, void* stream);
 
+/* ---- attention core (float32) ------------------------------------------------------------------
+ * octic_attn_fwd / octic_attn_bwd on float32 operands (q, k, v, o, dout, dq, dk, dv all f32; every stride in f32
+ * elements, rows 16-byte aligned = strides multiples of 4).  Same argument lists, stride sets, lse / delta / phase
+ * meaning and rejections (OCTIC_ENULL, OCTIC_ESHAPE for T outside 1..16384, hd % 16 != 0, hd > 128, non-positive
+ * B / H; OCTIC_EALIGN), all before any launch; scale must be positive and finite (the masking and the running maximum
+ * work on scaled scores): anything else is OCTIC_ESHAPE too.  Arithmetic contract:
+ *  - every product is a chain of v_mfma_f32_16x16x4_f32 = a k-ordered f32 fmaf chain, one rounding per product, no
+ *    reduced precision; scores sum over the head vector in the order d = g hd/4 + s (g = 0..3 the MFMA k index, s the
+ *    step), P V and the gradient products over the rows of a 32-row block in the order 4 g + reg, blocks in
+ *    ascending order;
+ *  - online softmax in the exp2 domain: p = exp2(fl(x scale log2(e)) - m) - the product is rounded before the subtraction,
+ *    no fma, so the exponent of a row's own maximum is exactly 0 - with the running row max m updated once per 32-key
+ *    block, f32 statistics, row sums reduced over the four lanes of a row in a fixed order; lse = m + log2(l); the
+ *    backward recomputes p = exp2(fl(x scale log2(e)) - lse) and uses delta = rowsum(dout * o), summed as the diagonal
+ *    of an MFMA product in the order of the dP entries it is subtracted from;
+ *  - keys beyond T in the last block are masked (-inf forward, p = 0 backward), rows beyond T are staged as zeros, no
+ *    address beyond row T - 1 of any operand is read;
+ *  - every output element is written once, no atomics: results are bitwise repeatable and independent of the strides.
+ * One streaming design for every T: 128 own rows per workgroup, 32 streamed rows per LDS block (csrc/attn_f32.hip). */
+int octic_attn_fwd_f32(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int H, int T, int hd,
+                       int64_t sB, int64_t sH, int64_t sT, int64_t oB, int64_t oH, int64_t oT, float scale, void* stream);
+int octic_attn_bwd_f32(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                       float* delta, void* dq, void* dk, void* dv, int64_t B, int H, int T, int hd, int64_t sB, int64_t sH,
+                       int64_t sT, int64_t oB, int64_t oH, int64_t oT, int64_t gB, int64_t gH, int64_t gT, float scale,
+                       int phase, void* stream);
+
 /* AttentionD8 straight on packed rows - reference octic_vits/d8_layers.py:631-656 (head split of the five-irrep
  * projection output, F.scaled_dot_product_attention, re-assembly of the irreps) WITHOUT the pack / unpack copies:
  * qkv = LinearD8 output [B, T, 3*8c] (row stride ld_qkv elements), o = packed [B, T, 8c] input of the output

@@ -716,7 +716,8 @@ class AttentionD8(nn.Module):
                 on = Octic(OF.AttnPackedFn.apply(qkv.packed, self.num_heads, c, (8 * c // self.num_heads) ** -0.5), c)
         else:
             q, k, v = OF.PackHeadsFn.apply(qkv.packed, self.num_heads, c)
-            # HIP attention core for the shapes it covers (bf16, T <= 16384, no dropout); torch SDPA (== self.att) otherwise
+            # HIP attention core for the shapes it covers (bf16 and float32, T <= 16384, head_dim % 16 == 0, no dropout);
+            # torch SDPA (== self.att) only for dropout > 0, fp16 tensors, other head sizes and CPU tensors
             o = OF.attention_core(q, k, v, dropout_p=drop)
             on = Octic(OF.UnpackHeadsFn.apply(o, c), c)
         if self.proj_drop.active or resid is None:

@@ -624,10 +624,7 @@ def attn_qkv(qkv: Tensor, scale: float) -> Tuple[Tensor, Tensor]:
     q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
     o = torch.empty((B, T, H, hd), dtype=qkv.dtype, device=qkv.device)
     ov = o.permute(0, 2, 1, 3)
-    lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
-    st = q.stride()
-    ops.check(ops.lib().octic_attn_fwd(ops._p(q), ops._p(k), ops._p(v), ops._p(o), ops._p(lse), B, H, T, hd, st[0], st[1],
-                                       st[2], ov.stride(0), ov.stride(1), ov.stride(2), float(scale), ops._stream(qkv)))
+    _, lse = ops.attn_fwd(q, k, v, scale, out=ov)         # bf16 or float32 entry point by qkv.dtype
     return o.view(B, T, H * hd), lse
 
 

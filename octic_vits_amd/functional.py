@@ -48,8 +48,9 @@ RAGGED = None          # ragged.Ragged of the [1, R, .] tensor the blocks are lo
 def compute_dtype(t: torch.Tensor):
     """Operand dtype of the octic kernels for `t` under the ambient autocast state.  bf16 autocast -> bf16 (the fast
     path, BASELINE dtype).  fp16 autocast (the reference's DeiT default, deit/engine.py:56) -> float32: the engine has no
-    fp16 kernels, so the octic half runs on its exact-f32 MFMA path - a superset of fp16's precision, slower than bf16;
-    the standard blocks run the reference's own eager fp16 ops.  Said once on stderr, never silently."""
+    fp16 kernels, so the octic half runs on its exact-f32 MFMA path - a superset of fp16's precision, slower than bf16 -
+    and its attention is on the engine too (octic_attn_*_f32, csrc/attn_f32.hip); the standard blocks run the
+    reference's own eager fp16 ops.  Said once on stderr, never silently."""
     if torch.is_autocast_enabled("cuda"):
         dt = torch.get_autocast_dtype("cuda")
         if dt == torch.bfloat16:
@@ -407,7 +408,8 @@ class UnpackHeadsFn(torch.autograd.Function):
 
 # ------------------------------------------------------------------------------------- attention
 class AttnFn(torch.autograd.Function):
-    """softmax(q k^T / sqrt(hd)) v for separate q, k, v of shape [B,H,T,hd] (bf16) — HIP forward and backward."""
+    """softmax(q k^T / sqrt(hd)) v for separate q, k, v of shape [B,H,T,hd] (bf16, or float32 on the exact-f32 kernels of
+    csrc/attn_f32.hip) — HIP forward and backward."""
 
     @staticmethod
     def forward(ctx, q, k, v, scale):
@@ -458,12 +460,7 @@ class AttnFusedQKVFn(torch.autograd.Function):
         q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
         o = torch.empty((B, T, H, hd), dtype=qkv.dtype, device=qkv.device)
         ov = o.permute(0, 2, 1, 3)
-        lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
-        st = q.stride()
-        t = ops.KERNEL_TIMER.start()
-        ops.check(ops.lib().octic_attn_fwd(ops._p(q), ops._p(k), ops._p(v), ops._p(o), ops._p(lse), B, H, T, hd, st[0], st[1],
-                                           st[2], ov.stride(0), ov.stride(1), ov.stride(2), float(scale), ops._stream(qkv)))
-        ops.KERNEL_TIMER.stop(t, "attn_fwd_kernel", 4 * q.numel() * 2, 4.0 * B * H * T * T * hd)
+        _, lse = ops.attn_fwd(q, k, v, scale, out=ov)     # bf16 or float32 entry point by qkv.dtype
         ctx.save_for_backward(qkv, o, lse)
         ctx.scale = scale
         return o.view(B, T, H * hd)
@@ -481,10 +478,11 @@ class AttnFusedQKVFn(torch.autograd.Function):
 
 
 def attention_core(q, k, v, dropout_p=0.0):
-    """Drop-in for F.scaled_dot_product_attention(q, k, v) on [B,H,T,hd]: HIP kernels for the shapes they cover
-    (bf16, T <= 16384, no dropout), torch SDPA otherwise (f32 exact path, fp16, head sizes that are not multiples of 16)."""
+    """Drop-in for F.scaled_dot_product_attention(q, k, v) on [B,H,T,hd]: HIP kernels for the shapes they cover (bf16 and
+    float32 operands, T <= 16384, head_dim a multiple of 16 up to 128, no dropout); torch SDPA only for attention dropout
+    > 0, fp16 tensors, head sizes that are not multiples of 16 and CPU tensors."""
     B, H, T, hd = q.shape
-    if dropout_p == 0.0 and q.is_cuda and ops.attn_supported(T, hd, q.dtype):
+    if dropout_p == 0.0 and q.is_cuda and (ops.attn_supported(T, hd, q.dtype) or ops.attn_f32_supported(T, hd, q.dtype)):
         return AttnFn.apply(q, k, v, hd ** -0.5)
     o = torch.nn.functional.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p)
     return o if o.dtype == q.dtype else o.to(q.dtype)       # fp16 autocast hands back fp16: the octic rows stay in q's dtype

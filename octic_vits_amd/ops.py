@@ -511,8 +511,9 @@ def prep_views(flat, cin, cout, transposed):
 
 
 def attn_fwd(q, k, v, scale, out=None):
-    """q,k,v: [B,H,T,hd] bf16 views with a common stride set (last dim contiguous) -> (o [B,H,T,hd], lse [B,H,T]);
-    out: an optional [B,H,T,hd] view (last dim contiguous, strides multiples of 8) that receives o"""
+    """q,k,v: [B,H,T,hd] bf16 or float32 views with a common stride set (last dim contiguous) -> (o [B,H,T,hd],
+    lse [B,H,T]); out: an optional [B,H,T,hd] view (last dim contiguous, 16-byte rows) that receives o.  float32
+    operands run octic_attn_fwd_f32 (csrc/attn_f32.hip)."""
     B, H, T, hd = q.shape
     st = q.stride()
     if st[3] != 1 or k.stride() != st or v.stride() != st:
@@ -521,10 +522,13 @@ def attn_fwd(q, k, v, scale, out=None):
         raise ValueError("attn_fwd: out must match q in shape, dtype and device and be contiguous in the last dim")
     o = out if out is not None else torch.empty((B, H, T, hd), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
+    f32 = q.dtype == torch.float32
+    fn = lib().octic_attn_fwd_f32 if f32 else lib().octic_attn_fwd
     t = KERNEL_TIMER.start()
-    check(lib().octic_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, T, hd, st[0], st[1], st[2],
-                               o.stride(0), o.stride(1), o.stride(2), float(scale), _stream(q)))
-    KERNEL_TIMER.stop(t, _attn_fwd_name(T, hd), 4 * q.numel() * 2, 4.0 * B * H * T * T * hd)
+    check(fn(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, T, hd, st[0], st[1], st[2],
+             o.stride(0), o.stride(1), o.stride(2), float(scale), _stream(q)))
+    KERNEL_TIMER.stop(t, "attn_f32_fwd_kernel" if f32 else _attn_fwd_name(T, hd), 4 * q.numel() * q.element_size(),
+                      4.0 * B * H * T * T * hd)
     return o, lse
 
 
@@ -534,6 +538,16 @@ ATTN_MAX_T = 16384      # octic_attn_*: longest sequence of the streaming kernel
 def attn_supported(T, hd, dtype):
     """Shapes the HIP attention core handles (others keep torch SDPA): bf16, 0 < T <= 16384, hd % 16 == 0, hd <= 128."""
     return dtype == torch.bfloat16 and 0 < T <= ATTN_MAX_T and hd % 16 == 0 and 0 < hd <= 128
+
+
+ATTN_F32_ROWS = 128     # csrc/attn_f32.hip, kF32Rows: own rows (queries / keys) of a workgroup
+ATTN_F32_BLK = 32       # csrc/attn_f32.hip, kF32Blk: streamed rows per LDS block
+
+
+def attn_f32_supported(T, hd, dtype):
+    """Shapes of octic_attn_{fwd,bwd}_f32 (exact-f32 MFMA, one streaming design): float32, 0 < T <= 16384, hd % 16 == 0,
+    hd <= 128.  attn_supported / attn_packed_ok stay bf16-only predicates."""
+    return dtype == torch.float32 and 0 < T <= ATTN_MAX_T and hd % 16 == 0 and 0 < hd <= 128
 
 
 def attn_streams(T, hd, backward=False):
@@ -568,19 +582,26 @@ def _attn_bwd_phases(T, hd):
     return ((1, "attn_bwd_dq_kernel", 6, 6.0), (2, "attn_bwd_dkv_kernel", 6, 8.0))
 
 
+_ATTN_F32_BWD_PHASES = ((1, "attn_f32_dq_kernel", 6, 6.0), (2, "attn_f32_dkv_kernel", 6, 8.0))
+
+
 def attn_bwd(q, k, v, o, dout, lse, scale, dq, dk, dv):
-    """All tensors are [B,H,T,hd] views; q/k/v share strides, o/dout share strides, dq/dk/dv share strides."""
+    """All tensors are [B,H,T,hd] views (bf16, or all float32: octic_attn_bwd_f32); q/k/v share strides, o/dout share
+    strides, dq/dk/dv share strides."""
     B, H, T, hd = q.shape
     st, so, sg = q.stride(), o.stride(), dq.stride()
     if k.stride() != st or v.stride() != st or dout.stride() != so or dk.stride() != sg or dv.stride() != sg:
         raise ValueError("attn_bwd: stride sets differ")
     delta = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
-    for phase, name, nbytes, flops in _attn_bwd_phases(T, hd):
+    f32 = q.dtype == torch.float32
+    fn = lib().octic_attn_bwd_f32 if f32 else lib().octic_attn_bwd
+    phases = _ATTN_F32_BWD_PHASES if f32 else _attn_bwd_phases(T, hd)
+    for phase, name, nbytes, flops in phases:
         t = KERNEL_TIMER.start()
-        check(lib().octic_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, H,
-                                   T, hd, st[0], st[1], st[2], so[0], so[1], so[2], sg[0], sg[1], sg[2], float(scale),
-                                   phase, _stream(q)))
-        KERNEL_TIMER.stop(t, name, nbytes * q.numel() * 2, flops * B * H * T * T * hd)
+        check(fn(_p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, H,
+                 T, hd, st[0], st[1], st[2], so[0], so[1], so[2], sg[0], sg[1], sg[2], float(scale),
+                 phase, _stream(q)))
+        KERNEL_TIMER.stop(t, name, nbytes * q.numel() * q.element_size(), flops * B * H * T * T * hd)
 
 
 def attn_packed_ok(T, c, H, dtype):

@@ -147,8 +147,10 @@ class Attention(nn.Module):
         hd = C // self.num_heads
         qkv = self.qkv(x)
         drop = self.attn_drop.p if self.training else 0.
-        if self.fused_attn and drop == 0. and qkv.is_cuda and _ops.attn_supported(N, hd, qkv.dtype):
-            # HIP attention core reading q/k/v through strides of the fused projection output and writing [B,N,C]
+        if (self.fused_attn and drop == 0. and qkv.is_cuda
+                and (_ops.attn_supported(N, hd, qkv.dtype) or _ops.attn_f32_supported(N, hd, qkv.dtype))):
+            # HIP attention core (bf16 or float32) reading q/k/v through strides of the fused projection output and
+            # writing [B,N,C]
             x = _OF.AttnFusedQKVFn.apply(qkv.view(B, N, 3, self.num_heads, hd), hd ** -0.5)
             return self.proj_drop(self.proj(x))
         qkv = qkv.reshape(B, N, 3, self.num_heads, hd).permute(2, 0, 3, 1, 4)
