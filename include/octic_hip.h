@@ -299,6 +299,32 @@ int octic_attn_bwd_packed(const void* qkv, const void* o, const void* dout, cons
                           int64_t B, int H, int T, int c, int64_t ld_qkv, int64_t ld_o, int64_t ld_g, float scale,
                           int phase, void* stream);
 
+/* ---- attention core: samples dropped by stochastic depth ------------------------------------------
+ * The four bf16 entry points with one more argument in front of `stream`: sample_scale, nullable, B floats on the
+ * device - the per-sample factor the CALLER multiplies this attention branch's output with (x + scale * f(x)); exactly
+ * 0.0f for a sample whose branch is dropped.  The existing entry points are these with sample_scale = NULL.
+ * Contract: for a sample with sample_scale[b] == 0 a kernel MAY skip the sample.  If it does, it writes +0 to every
+ * element of that sample's o rows and lse (forward), of its dq, dk, dv rows and delta (backward), and reads none of the
+ * sample's operands.  The caller guarantees that the branch output is multiplied by the same factor, so the skipped o never
+ * reaches the result and dout is zero for those samples (dq = dk = dv = 0 is then what the full computation gives).  A
+ * kernel that does not skip computes the sample as without the argument.  NULL, or factors that are all non-zero, give
+ * the results of the plain entry points bit for bit.  Which kernels skip: the persistent one-shot
+ * forward at 257 / 258 tokens, head_dim 80 (up to 512 samples per launch), and the single-pass backward for head_dim 80
+ * (257, 193 .. 256 and <= 64 tokens); every other route ignores the argument.  sample_scale must be 4-byte aligned
+ * (OCTIC_EALIGN); all other rejections as in the plain entry points.                                                    */
+int octic_attn_fwd_skip(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int H, int T, int hd,
+                        int64_t sB, int64_t sH, int64_t sT, int64_t oB, int64_t oH, int64_t oT, float scale,
+                        const float* sample_scale, void* stream);
+int octic_attn_bwd_skip(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                        float* delta, void* dq, void* dk, void* dv, int64_t B, int H, int T, int hd, int64_t sB, int64_t sH,
+                        int64_t sT, int64_t oB, int64_t oH, int64_t oT, int64_t gB, int64_t gH, int64_t gT, float scale,
+                        int phase, const float* sample_scale, void* stream);
+int octic_attn_fwd_packed_skip(const void* qkv, void* o, float* lse, int64_t B, int H, int T, int c, int64_t ld_qkv,
+                               int64_t ld_o, float scale, const float* sample_scale, void* stream);
+int octic_attn_bwd_packed_skip(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
+                               int64_t B, int H, int T, int c, int64_t ld_qkv, int64_t ld_o, int64_t ld_g, float scale,
+                               int phase, const float* sample_scale, void* stream);
+
 /* ---- octic -> standard hand-off (model.py:196-200) ---------------------------------------------
  * hybrid:    dense[m, :] = cat(A1,A2,B1,B2, E[0,:c], E[1,:c], E[0,c:], E[1,c:])   (8-tuple order,
  *            d8_utils.py:370-385; the following standard blocks' weights depend on it)

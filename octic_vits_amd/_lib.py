@@ -104,6 +104,11 @@ _PROTOS = {
     "octic_attn_fwd_packed": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int, c_int, c_i64, c_i64, c_float, c_void_p]),
     "octic_attn_bwd_packed": (c_int, [c_void_p] * 6 + [c_i64, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_float, c_int, c_void_p]),
     "octic_attn_bwd": (c_int, [c_void_p] * 10 + [c_i64, c_int, c_int, c_int] + [c_i64] * 9 + [c_float, c_int, c_void_p]),
+    # the four above with sample_scale (nullable [B] f32: 0 = the sample's branch is dropped) in front of the stream
+    "octic_attn_fwd_skip": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_int, c_int] + [c_i64] * 6 + [c_float, c_void_p, c_void_p]),
+    "octic_attn_bwd_skip": (c_int, [c_void_p] * 10 + [c_i64, c_int, c_int, c_int] + [c_i64] * 9 + [c_float, c_int, c_void_p, c_void_p]),
+    "octic_attn_fwd_packed_skip": (c_int, [c_void_p] * 3 + [c_i64, c_int, c_int, c_int, c_i64, c_i64, c_float, c_void_p, c_void_p]),
+    "octic_attn_bwd_packed_skip": (c_int, [c_void_p] * 6 + [c_i64, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_float, c_int, c_void_p, c_void_p]),
     "octic_attn_fwd_f32": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_int, c_int] + [c_i64] * 6 + [c_float, c_void_p]),
     "octic_attn_bwd_f32": (c_int, [c_void_p] * 10 + [c_i64, c_int, c_int, c_int] + [c_i64] * 9 + [c_float, c_int, c_void_p]),
     "octic_attn_pack_heads": (c_int, [VP, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p]),

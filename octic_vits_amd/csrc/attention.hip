@@ -784,6 +784,13 @@ __global__ __launch_bounds__(MAXT) void attn_bwd_dq_kernel(AttnBwdArgs a, int rs
   ATRACE(1, 0);
   DqRows<KS> mine, shared;                          // the shared tile's rows are fetched up front too
   const HeadMaps hm = head_maps(a, h);
+  // a sample stochastic depth drops (AttnBwdArgs::sample_scale; a forward that skipped it left o = lse = 0): +0 to dq and
+  // delta, nothing is loaded
+  if (a.sample_scale != nullptr && a.sample_scale[b] == 0.f) {
+    zero_head_rows(dqb, a.gT, T, hd / 8, hm.q, tid, blockDim.x);
+    zero_stats(a.delta + stat_off, T, tid, blockDim.x);
+    return;
+  }
   // Prologue in ONE memory round trip: Q, dO, O, K and V of the head are all requested before anything is used.
   //  * the wave's own 32 query rows (Q, dO fragments; delta = <dO, O>) come out of LDS images of Q and dO staged with
   //    row-contiguous requests, not from fragment-shaped global loads (lane (r, half) taking 16 bytes of row r = 32
@@ -955,6 +962,11 @@ __global__ __launch_bounds__(MAXT) void attn_bwd_dkv_kernel(AttnBwdArgs a, int r
   ATRACE(2, 0);
   KvRows<KS> kv;
   const HeadMaps hm = head_maps(a, h);
+  if (a.sample_scale != nullptr && a.sample_scale[b] == 0.f) {      // a dropped sample (attn_bwd_dq_kernel): +0 to dk and dv
+    zero_head_rows(dkb, a.gT, T, hd / 8, hm.k, tid, blockDim.x);
+    zero_head_rows(dvb, a.gT, T, hd / 8, hm.v, tid, blockDim.x);
+    return;
+  }
   // Prologue in one memory round trip (see attn_bwd_dq_kernel): K, V, Q and dO are all requested up front; the own key
   // rows' fragments are read from the LDS images of K and V, which are then overwritten with Q and dO.
   const int kc = hd / 8;
@@ -1081,7 +1093,15 @@ extern "C" {
 
 int octic_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int H, int T, int hd,
                    int64_t sB, int64_t sH, int64_t sT, int64_t oB, int64_t oH, int64_t oT, float scale, void* stream) {
+  return octic_attn_fwd_skip(q, k, v, o, lse, B, H, T, hd, sB, sH, sT, oB, oH, oT, scale, nullptr, stream);
+}
+
+// sample_scale (nullable, [B] f32): 0.0f marks a sample whose branch stochastic depth drops - see AttnArgs::sample_scale
+int octic_attn_fwd_skip(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int H, int T, int hd,
+                        int64_t sB, int64_t sH, int64_t sT, int64_t oB, int64_t oH, int64_t oT, float scale,
+                        const float* sample_scale, void* stream) {
   if (!q || !k || !v || !o) return OCTIC_ENULL;
+  if (((uintptr_t)sample_scale) & 3) return OCTIC_EALIGN;
   if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o)) & 15) return OCTIC_EALIGN;
   if ((sB | sH | sT | oB | oH | oT) & 7) return OCTIC_EALIGN;   // rows must stay 16-byte aligned (8 bf16)
@@ -1093,6 +1113,7 @@ int octic_attn_fwd(const void* q, const void* k, const void* v, void* o, float* 
   a.H = H; a.T = T; a.hd = hd;
   a.scale_log2 = scale * 1.4426950408889634f;
   a.cv_in = a.cv_out = a.c = 0;
+  a.sample_scale = sample_scale;
   hipStream_t s = (hipStream_t)stream;
   if (attn_stream_route(T)) return attn_stream_fwd_launch(a, B, s);
   switch (hd / 16) {
@@ -1111,7 +1132,16 @@ int octic_attn_bwd(const void* q, const void* k, const void* v, const void* o, c
                    float* delta, void* dq, void* dk, void* dv, int64_t B, int H, int T, int hd, int64_t sB, int64_t sH,
                    int64_t sT, int64_t oB, int64_t oH, int64_t oT, int64_t gB, int64_t gH, int64_t gT, float scale,
                    int phase, void* stream) {
+  return octic_attn_bwd_skip(q, k, v, o, dout, lse, delta, dq, dk, dv, B, H, T, hd, sB, sH, sT, oB, oH, oT, gB, gH, gT, scale,
+                             phase, nullptr, stream);
+}
+
+int octic_attn_bwd_skip(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                        float* delta, void* dq, void* dk, void* dv, int64_t B, int H, int T, int hd, int64_t sB, int64_t sH,
+                        int64_t sT, int64_t oB, int64_t oH, int64_t oT, int64_t gB, int64_t gH, int64_t gT, float scale,
+                        int phase, const float* sample_scale, void* stream) {
   if (!q || !k || !v || !o || !dout || !lse || !delta || !dq || !dk || !dv) return OCTIC_ENULL;
+  if (((uintptr_t)sample_scale) & 3) return OCTIC_EALIGN;
   if (phase < 1 || phase > 3) return OCTIC_ESHAPE;
   if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o) | ((uintptr_t)dout) | ((uintptr_t)dq) |
@@ -1127,6 +1157,7 @@ int octic_attn_bwd(const void* q, const void* k, const void* v, const void* o, c
   a.scale = scale;
   a.scale_log2 = scale * 1.4426950408889634f;
   a.cv_in = a.cv_out = a.c = 0;
+  a.sample_scale = sample_scale;
   hipStream_t s = (hipStream_t)stream;
   if (attn_stream_route(T)) return attn_stream_bwd_launch(a, B, phase, s);
   switch (hd / 16) {
@@ -1148,7 +1179,13 @@ int octic_attn_bwd(const void* q, const void* k, const void* v, const void* o, c
 // whole piece - A1, A2, B1, B2, two halves of each E row - so only the g < 8 branch of HeadMap is used), bf16.
 int octic_attn_fwd_packed(const void* qkv, void* o, float* lse, int64_t B, int H, int T, int c, int64_t ld_qkv,
                           int64_t ld_o, float scale, void* stream) {
+  return octic_attn_fwd_packed_skip(qkv, o, lse, B, H, T, c, ld_qkv, ld_o, scale, nullptr, stream);
+}
+
+int octic_attn_fwd_packed_skip(const void* qkv, void* o, float* lse, int64_t B, int H, int T, int c, int64_t ld_qkv,
+                               int64_t ld_o, float scale, const float* sample_scale, void* stream) {
   if (!qkv || !o) return OCTIC_ENULL;
+  if (((uintptr_t)sample_scale) & 3) return OCTIC_EALIGN;
   if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || c <= 0 || (c != 10 * H && c != 8 * H)) return OCTIC_ESHAPE;
   if (((((uintptr_t)qkv) | ((uintptr_t)o)) & 15) || ((ld_qkv | ld_o) & 7) || ld_qkv < 24 * c || ld_o < 8 * c) return OCTIC_EALIGN;
   AttnArgs a;
@@ -1159,6 +1196,7 @@ int octic_attn_fwd_packed(const void* qkv, void* o, float* lse, int64_t B, int H
   a.H = H; a.T = T; a.hd = 8 * (c / H);
   a.scale_log2 = scale * 1.4426950408889634f;
   a.cv_in = 3 * c; a.cv_out = c; a.c = c;
+  a.sample_scale = sample_scale;
   if (attn_stream_route(T)) return attn_stream_fwd_launch(a, B, (hipStream_t)stream);
   if (a.hd == 64) return attn_fwd_launch<4, 2>(a, B, (hipStream_t)stream);
   return attn_fwd_launch<5, 3>(a, B, (hipStream_t)stream);
@@ -1168,7 +1206,14 @@ int octic_attn_fwd_packed(const void* qkv, void* o, float* lse, int64_t B, int H
 int octic_attn_bwd_packed(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
                           int64_t B, int H, int T, int c, int64_t ld_qkv, int64_t ld_o, int64_t ld_g, float scale,
                           int phase, void* stream) {
+  return octic_attn_bwd_packed_skip(qkv, o, dout, lse, delta, dqkv, B, H, T, c, ld_qkv, ld_o, ld_g, scale, phase, nullptr, stream);
+}
+
+int octic_attn_bwd_packed_skip(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
+                               int64_t B, int H, int T, int c, int64_t ld_qkv, int64_t ld_o, int64_t ld_g, float scale,
+                               int phase, const float* sample_scale, void* stream) {
   if (!qkv || !o || !dout || !lse || !delta || !dqkv) return OCTIC_ENULL;
+  if (((uintptr_t)sample_scale) & 3) return OCTIC_EALIGN;
   if (phase < 1 || phase > 3) return OCTIC_ESHAPE;
   if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || c <= 0 || (c != 10 * H && c != 8 * H)) return OCTIC_ESHAPE;
   if (((((uintptr_t)qkv) | ((uintptr_t)o) | ((uintptr_t)dout) | ((uintptr_t)dqkv)) & 15) || ((ld_qkv | ld_o | ld_g) & 7) ||
@@ -1183,6 +1228,7 @@ int octic_attn_bwd_packed(const void* qkv, const void* o, const void* dout, cons
   a.scale = scale;
   a.scale_log2 = scale * 1.4426950408889634f;
   a.cv_in = 3 * c; a.cv_out = c; a.c = c;
+  a.sample_scale = sample_scale;
   if (attn_stream_route(T)) return attn_stream_bwd_launch(a, B, phase, (hipStream_t)stream);
   if (a.hd == 64) return attn_bwd_launch<4, 2>(a, B, phase, (hipStream_t)stream);
   return attn_bwd_launch<5, 3>(a, B, phase, (hipStream_t)stream);

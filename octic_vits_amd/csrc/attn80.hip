@@ -267,7 +267,34 @@ __device__ __forceinline__ bf16x8 trfrag_ones(const char* tile, const FragAddr& 
   return __builtin_bit_cast(bf16x8, v);
 }
 
+// Kept / dropped sample lists of a launch with a stochastic-depth mask (AttnArgs::sample_scale), built by every workgroup for
+// itself: order[0 .. n_kept) = the kept samples (scale != 0) in ascending order, order[B - 1 - j] = the j-th dropped one,
+// order[kSkipMaxB] = n_kept.  Wave 0 walks the samples 64 at a time (one ballot per word); returns n_kept to every wave after
+// one barrier.
+constexpr int kSkipMaxB = 512;                                    // launches with more samples run without skipping
+constexpr int kSkipLds = (kSkipMaxB + 8) * 2;
+__device__ __forceinline__ int skip_table(unsigned short* order, const float* scale, int B, int wid, int lane) {
+  if (wid == 0) {
+    int nk = 0, ndrop = 0;
+    for (int b0 = 0; b0 < B; b0 += 64) {
+      const int b = b0 + lane;
+      const bool in = b < B;
+      const bool kept = in && scale[b] != 0.f;
+      const unsigned long long mk = __builtin_amdgcn_ballot_w64(kept), md = __builtin_amdgcn_ballot_w64(in && !kept);
+      const unsigned long long below = (1ull << lane) - 1ull;
+      if (kept) order[nk + __builtin_popcountll(mk & below)] = (unsigned short)b;
+      else if (in) order[B - 1 - (ndrop + __builtin_popcountll(md & below))] = (unsigned short)b;
+      nk += __builtin_popcountll(mk);
+      ndrop += __builtin_popcountll(md);
+    }
+    if (lane == 0) order[kSkipMaxB] = (unsigned short)nk;
+  }
+  __syncthreads();
+  return __builtin_amdgcn_readfirstlane((int)order[kSkipMaxB]);
+}
+
 // LDS: [3 image buffers x nt tiles][extra rows][ones block 128 B][P of the extra rows: 8 waves x 2 KiB][partials][m, l]
+// [sample order table, skip_table]
 __global__ __launch_bounds__(512) void fwd_os_kernel(AttnArgs a, int units) {
   constexpr int nt = MAXNT;                                       // nine tiles exactly (T = 257, 258): static register indexing
   constexpr int W = WAVES;
@@ -283,6 +310,7 @@ __global__ __launch_bounds__(512) void fwd_os_kernel(AttnArgs a, int units) {
   char* const pxs = ones + 128;                                   // [8 waves][64 lanes][32 B]
   float* const parts = (float*)(pxs + W * 2048 + 1024);          // + wave 0's block for keys 256..
   float* const ml = parts + W * 2 * DC;
+  unsigned short* const order = (unsigned short*)(ml + 2 * W * 2);   // [kSkipMaxB] sample ids + the kept count (skip_table)
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   const int G = gridDim.x;
   const bool shared_rows = a.sH < a.sT;
@@ -291,10 +319,22 @@ __global__ __launch_bounds__(512) void fwd_os_kernel(AttnArgs a, int units) {
   LeanStager st;
   st.setup(wid, W, lane, a.sT, a.cv_in, nt, T);
 
+  // Stochastic depth (AttnArgs::sample_scale): the persistent loop runs over the (b, h) units of the KEPT samples only -
+  // `units` becomes n_kept H, dealt by the same unit_of (every XCD still works on whole samples) - and the dropped samples'
+  // units are zero-filled after it.  Null pointer: the identity, as before.
+  const bool skip = a.sample_scale != nullptr;
+  const int nB = units / a.H;
+  int n_kept = nB;
+  if (skip) {
+    n_kept = skip_table(order, a.sample_scale, nB, wid, lane);
+    units = n_kept * a.H;
+  }
+
   auto head_of = [&](int idx, int64_t& in_off, int64_t& o_off, int64_t& st_off, int& h) {
     const int u = unit_of(idx, units, shared_rows);
-    const int b = u / a.H;
-    h = u - b * a.H;
+    const int kb = u / a.H;
+    h = u - kb * a.H;
+    const int b = skip ? __builtin_amdgcn_readfirstlane((int)order[kb]) : kb;
     in_off = b * a.sB + h * a.sH;
     o_off = b * a.oB + h * a.oH;
     st_off = ((int64_t)b * a.H + h) * T;
@@ -324,22 +364,23 @@ __global__ __launch_bounds__(512) void fwd_os_kernel(AttnArgs a, int units) {
   if (tid < 32) ((unsigned*)ones)[tid] = (tid & 7) == 0 ? 0x3F80u : 0u;
 
   int u = blockIdx.x;
-  int64_t in_off, o_off, st_off;
-  int hh;
-  head_of(u, in_off, o_off, st_off, hh);
+  int64_t in_off = 0, o_off = 0, st_off = 0;
+  int hh = 0;
+  const bool any = u < units;                                     // (fewer kept units than workgroups: nothing to prefetch)
+  if (any) head_of(u, in_off, o_off, st_off, hh);
   HeadMaps hm = head_maps(a, hh);
   int bK = 0, bV = 1, bS = 2;                                     // buffer roles
-  {
+  bf16x8 qf[KS];
+  u32x4 xq = {0, 0, 0, 0};
+  if (any) {
     const i32x4 rk = make_rs(a.k, in_off, a.sT, T, a.cv_in), rv = make_rs(a.v, in_off, a.sT, T, a.cv_in);
     for (int j = 0; j < nt; ++j) {
       st.issue(j, lds0 + bK * IMG, rk, hm.k.bs);
       st.issue(j, lds0 + bV * IMG, rv, hm.v.bs);
     }
+    load_rows(qf, a.q + in_off, a.sT, wid, T, lane, hm.q);
+    if (wid == 1 && lane < 10 * nx) xq = hm_load16(a.q + in_off + (int64_t)(32 * W + lane / 10) * a.sT, lane % 10, hm.q);
   }
-  bf16x8 qf[KS];
-  load_rows(qf, a.q + in_off, a.sT, wid, T, lane, hm.q);
-  u32x4 xq = {0, 0, 0, 0};
-  if (wid == 1 && lane < 10 * nx) xq = hm_load16(a.q + in_off + (int64_t)(32 * W + lane / 10) * a.sT, lane % 10, hm.q);
   bf16* p_ob = nullptr;                                           // the previous head (its extra rows are merged one head late)
   float* p_lse = nullptr;
   HeadMap p_hmo = hm.o;
@@ -573,6 +614,17 @@ __global__ __launch_bounds__(512) void fwd_os_kernel(AttnArgs a, int units) {
   }
   __syncthreads();
   if (wid == 0 && p_ob != nullptr) merge_extra(p_ob, p_lse, p_hmo);
+  if (skip) {
+    // the dropped samples' units, dealt from the last workgroup down (those ran the fewest kept units): +0 to o and lse
+    const int nd = (nB - n_kept) * a.H;
+    for (int d = G - 1 - (int)blockIdx.x; d < nd; d += G) {
+      const int ud = unit_of(d, nd, shared_rows);                 // whole samples per XCD: a shared line is filled from one L2
+      const int jb = ud / a.H, h = ud - jb * a.H;
+      const int b = __builtin_amdgcn_readfirstlane((int)order[nB - 1 - jb]);
+      zero_head_rows(a.o + (b * a.oB + h * a.oH), a.oT, T, HD / 8, head_maps(a, h).o, tid, 512);
+      if (a.lse) zero_stats(a.lse + ((int64_t)b * a.H + h) * T, T, tid, 512);
+    }
+  }
 }
 
 
@@ -757,7 +809,7 @@ __global__ __launch_bounds__((NT < 4 ? 4 : NT) * 64) void fwd_oss_kernel(AttnArg
 inline size_t fwd_oss_lds(int nt) { return (size_t)3 * nt * TILE_B + 128; }
 
 inline size_t fwd_os_lds(int nt) {
-  return (size_t)3 * nt * TILE_B + 2 * HD * 2 + 128 + (WAVES * 2048 + 1024) + (size_t)(WAVES * 2 * (DT * 32 + kPartPad) + 2 * WAVES * 2) * sizeof(float);
+  return (size_t)3 * nt * TILE_B + 2 * HD * 2 + 128 + (WAVES * 2048 + 1024) + (size_t)(WAVES * 2 * (DT * 32 + kPartPad) + 2 * WAVES * 2) * sizeof(float) + kSkipLds;
 }
 
 inline size_t fwd_lds(int nt) {
@@ -795,7 +847,10 @@ int attn80_fwd_launch(const AttnArgs& a_, int64_t B, hipStream_t s) {
   }
   const int grid = units < cus ? units : cus;
   const bool one_shot = (route(OCTIC_ROUTE_ATTN_ONLINE) & 15) == 0;
-  if (one_shot && nt == MAXNT) fwd_os_kernel<<<grid, 512, fwd_os_lds(nt), s>>>(a, units);
+  if (one_shot && nt == MAXNT) {
+    if (B > kSkipMaxB) a.sample_scale = nullptr;                  // the order table holds 512 samples: larger launches do not skip
+    fwd_os_kernel<<<grid, 512, fwd_os_lds(nt), s>>>(a, units);
+  }
   else if (one_shot && a.T <= 32 * nt && nt <= 8) {               // every token inside a tile: the T <= 256 one-shot kernels
     switch (nt) {
 #define OSS(n) case n: { static DeviceOnce o##n; if (o##n.first()) { (void)hipFuncSetAttribute((const void*)fwd_oss_kernel<n>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); (void)hipGetLastError(); } \

@@ -105,7 +105,8 @@ __device__ __forceinline__ const char* tile_chunk(const char* tile, int row, int
 // NKT = key tiles (= waves that own one); XKEY: one more key / query row past them (T = 32 NKT + 1: ViT-H/14's 257).  Round 5:
 // T <= 256 runs the same kernel with XKEY = false - every token inside a tile, the last tile possibly partial (its keys past T
 // are masked out of P and dS, their rows arrive as zeros), waves past NKT own no key tile and only stage, reduce and compute dQ.
-template <int NKT, bool XKEY>
+// SKIP: the launch carries a stochastic-depth mask (AttnBwdArgs::sample_scale); without one the kernel is compiled as before.
+template <int NKT, bool XKEY, bool SKIP>
 __global__ __launch_bounds__(512) void bwd_kernel(AttnBwdArgs a) {
   constexpr int nt = XKEY ? NKT + 1 : NKT, W = WAVES;
   const int T = a.T;
@@ -125,10 +126,24 @@ __global__ __launch_bounds__(512) void bwd_kernel(AttnBwdArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, half = lane >> 5;
-  const int bh = unit_of(blockIdx.x, gridDim.x, a.sH < a.sT), b = bh / a.H, h = bh - b * a.H;
+  int b, h;
+  bool dropped = false;
+  if constexpr (SKIP) {                              // kept samples' units first, evenly over the XCDs (skip_unit)
+    skip_unit(a.sample_scale, gridDim.x / a.H, a.H, blockIdx.x, a.sH < a.sT, lane, b, h, dropped);
+  } else {
+    const int bh = unit_of(blockIdx.x, gridDim.x, a.sH < a.sT);
+    b = bh / a.H;
+    h = bh - b * a.H;
+  }
   const int64_t in_off = b * a.sB + h * a.sH, o_off = b * a.oB + h * a.oH, g_off = b * a.gB + h * a.gH;
   const int64_t stat_off = ((int64_t)b * a.H + h) * T;
   const HeadMaps hm = head_maps(a, h);
+  // stochastic depth dropped this sample (AttnBwdArgs::sample_scale): its cotangent is zero, so are dq, dk, dv and delta -
+  // stored as such, nothing is loaded, and the CU takes its next workgroup
+  if (dropped) {
+    zero_bwd_unit(a, g_off, stat_off, hm, HD / 8, tid, 512);
+    return;
+  }
 
 #ifdef A80_TRACE
   unsigned long long bwt_ph[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -461,7 +476,7 @@ __global__ __launch_bounds__(512) void bwd_kernel(AttnBwdArgs a) {
 // quarters, no extra-row machinery).  50.5 KiB of LDS at NKT = 2: three workgroups per CU.  (V rows and the delta chunks
 // straight from global memory - 38.5 KiB, four workgroups per CU - timed the same on strided rows, 77 against 76 us, and lost on
 // packed rows, whose 16-byte chunks straddle irrep pieces: the DMA stager's piece addressing is the cheaper path there.)
-template <int NKT>
+template <int NKT, bool SKIP>
 __global__ __launch_bounds__(64 * NKT) void bwd_small_kernel(AttnBwdArgs a) {
   constexpr int nt = NKT, W = NKT;
   constexpr int IMG = NKT * TILE_B;
@@ -481,10 +496,22 @@ __global__ __launch_bounds__(64 * NKT) void bwd_small_kernel(AttnBwdArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = wid_of();
   const int r = lane & 31, half = lane >> 5;
-  const int bh = unit_of(blockIdx.x, gridDim.x, a.sH < a.sT), b = bh / a.H, h = bh - b * a.H;
+  int b, h;
+  bool dropped = false;
+  if constexpr (SKIP) {                              // kept samples' units first, evenly over the XCDs (skip_unit)
+    skip_unit(a.sample_scale, gridDim.x / a.H, a.H, blockIdx.x, a.sH < a.sT, lane, b, h, dropped);
+  } else {
+    const int bh = unit_of(blockIdx.x, gridDim.x, a.sH < a.sT);
+    b = bh / a.H;
+    h = bh - b * a.H;
+  }
   const int64_t in_off = b * a.sB + h * a.sH, o_off = b * a.oB + h * a.oH, g_off = b * a.gB + h * a.gH;
   const int64_t stat_off = ((int64_t)b * a.H + h) * T;
   const HeadMaps hm = head_maps(a, h);
+  if (dropped) {                                     // a dropped sample (bwd_kernel): zeros, no loads
+    zero_bwd_unit(a, g_off, stat_off, hm, HD / 8, tid, 64 * NKT);
+    return;
+  }
   FragAddr fa;
   fa.setup(lane);
 
@@ -634,22 +661,29 @@ int attn80_bwd_ok(const AttnBwdArgs& a) {
           (int64_t)a.T * a.gT * 2 < 0x7FFFFFF0ll) ? 1 : 0;
 }
 
-int attn80_bwd_launch(const AttnBwdArgs& a, int64_t B, hipStream_t s) {
-  using namespace a80;
+namespace a80 {
+template <bool SKIP>
+static int bwd_launch(const AttnBwdArgs& a, int64_t B, hipStream_t s) {
   static DeviceOnce once;
   if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)bwd_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)bwd_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)bwd_kernel<7, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)bwd_kernel<8, true, SKIP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)bwd_kernel<8, false, SKIP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)bwd_kernel<7, false, SKIP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipGetLastError();
   }
   const int grid = (int)(B * a.H);
-  if (a.T <= 32) { bwd_small_kernel<1><<<grid, 64, 5 * TILE_B + 2 * 32 * 4, s>>>(a); return launch_status(); }
-  if (a.T <= 64) { bwd_small_kernel<2><<<grid, 128, 10 * TILE_B + 2 * 64 * 4, s>>>(a); return launch_status(); }
-  if (a.T == BW_T) bwd_kernel<8, true><<<grid, 512, BW_LDS, s>>>(a);
-  else if (a.T > 224) bwd_kernel<8, false><<<grid, 512, BW_LDS, s>>>(a);
-  else bwd_kernel<7, false><<<grid, 512, BW_LDS, s>>>(a);
+  if (a.T <= 32) { bwd_small_kernel<1, SKIP><<<grid, 64, 5 * TILE_B + 2 * 32 * 4, s>>>(a); return launch_status(); }
+  if (a.T <= 64) { bwd_small_kernel<2, SKIP><<<grid, 128, 10 * TILE_B + 2 * 64 * 4, s>>>(a); return launch_status(); }
+  if (a.T == BW_T) bwd_kernel<8, true, SKIP><<<grid, 512, BW_LDS, s>>>(a);
+  else if (a.T > 224) bwd_kernel<8, false, SKIP><<<grid, 512, BW_LDS, s>>>(a);
+  else bwd_kernel<7, false, SKIP><<<grid, 512, BW_LDS, s>>>(a);
   return launch_status();
+}
+}  // namespace a80
+
+int attn80_bwd_launch(const AttnBwdArgs& a, int64_t B, hipStream_t s) {
+  using namespace a80;
+  return a.sample_scale != nullptr ? bwd_launch<true>(a, B, s) : bwd_launch<false>(a, B, s);
 }
 
 }  // namespace octic

@@ -18,6 +18,10 @@ struct AttnArgs {
   // [B,T,8c] input of the output projection; cv = irrep block width of a row (3c / c), c = channels per irrep.
   int cv_in, cv_out, c;
   int dbg = 0;           // developer probes (csrc/attn80.hip): 1 = K / V descriptors with zero records (their DMA is dropped)
+  // nullable, [B] f32: the factor the caller multiplies sample b's branch output with (stochastic depth).  Exactly 0.0f = the
+  // sample is dropped: a kernel may skip it - it then writes +0 to the sample's o rows and lse and reads none of its operands
+  // (include/octic_hip.h, octic_attn_*_skip)
+  const float* sample_scale = nullptr;
 };
 
 // ---- head-vector addressing ------------------------------------------------------------------------------------------
@@ -103,6 +107,19 @@ __device__ __forceinline__ int hm_elem(int e, const HeadMap m) {
 
 __device__ inline int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
+// +0 to the T head vectors (nc 16-byte chunks each) of one (b, h) of a tensor, by all `nthr` threads of the workgroup:
+// the store of a unit whose sample the stochastic-depth mask drops (AttnArgs::sample_scale)
+__device__ __forceinline__ void zero_head_rows(bf16* base, int64_t row_stride, int T, int nc, const HeadMap m, int tid, int nthr) {
+  const u32x4 z = {0u, 0u, 0u, 0u};
+  for (int i = tid; i < T * nc; i += nthr) {
+    const int row = i / nc;
+    hm_store16(base + (int64_t)row * row_stride, i - row * nc, z, m);
+  }
+}
+__device__ __forceinline__ void zero_stats(float* p, int T, int tid, int nthr) {
+  for (int i = tid; i < T; i += nthr) p[i] = 0.f;
+}
+
 __device__ inline bf16x8 pack8(const float* p) {
   bf16x8 r;
 #pragma unroll
@@ -133,6 +150,7 @@ struct AttnBwdArgs {
   int H, T, hd;
   float scale, scale_log2;
   int cv_in, cv_out, c;                                                   // packed mode, see AttnArgs
+  const float* sample_scale = nullptr;                                    // see AttnArgs: a skipped sample gets +0 in dq, dk, dv, delta
 };
 
 
@@ -260,6 +278,51 @@ __device__ __forceinline__ void load_kv_rows(KvRows<KS>& R, const AttnBwdArgs& a
   }
 }
 
+
+// A workgroup that owns ONE (b, h) of a backward launch and whose sample is dropped: +0 to the unit's dq, dk, dv rows and its
+// delta, before any load - the caller returns right after.  nc = head_dim / 8.
+__device__ __forceinline__ void zero_bwd_unit(const AttnBwdArgs& a, int64_t g_off, int64_t stat_off, const HeadMaps& hm, int nc,
+                                              int tid, int nthr) {
+  zero_head_rows(a.dq + g_off, a.gT, a.T, nc, hm.q, tid, nthr);
+  zero_head_rows(a.dk + g_off, a.gT, a.T, nc, hm.k, tid, nthr);
+  zero_head_rows(a.dv + g_off, a.gT, a.T, nc, hm.v, tid, nthr);
+  zero_stats(a.delta + stat_off, a.T, tid, nthr);
+}
+
+// Block index -> (b, h) of a one-unit-per-workgroup backward launch with a stochastic-depth mask: the units of the KEPT samples
+// come first - dealt by unit_of over n_kept H units, so the kept work fills whole rounds of workgroups evenly over the XCDs
+// (dealing all B H units and leaving the dropped ones early made an XCD with many kept samples the tail of the launch:
+// E max_x Binomial(8, 1/2) = 6.3 of its 8 samples at batch 64) - and the dropped samples' units after them.  Every wave works
+// the mapping out for itself from the B factors, 64 samples per ballot word, in registers: no LDS, no barrier.
+__device__ __forceinline__ int nth_set_bit(unsigned long long m, int n, int lane) {
+  const bool hit = ((m >> lane) & 1ull) && __builtin_popcountll(m & ((1ull << lane) - 1ull)) == n;
+  return __builtin_ctzll(__builtin_amdgcn_ballot_w64(hit));
+}
+__device__ __forceinline__ void skip_unit(const float* scale, int B, int H, int idx, bool shared_rows, int lane, int& b, int& h,
+                                          bool& dropped) {
+  int nk = 0;
+  for (int b0 = 0; b0 < B; b0 += 64) {
+    const bool kept = b0 + lane < B && scale[b0 + lane] != 0.f;
+    nk += __builtin_popcountll(__builtin_amdgcn_ballot_w64(kept));
+  }
+  const int uk = nk * H;
+  dropped = idx >= uk;
+  // (the dropped units too: the heads of a sample share cache lines, and a line zero-filled from one XCD's L2 is written once)
+  const int u = dropped ? unit_of(idx - uk, B * H - uk, shared_rows) : unit_of(idx, uk, shared_rows);
+  int want = u / H;                                  // ordinal among the kept (dropped) samples
+  h = u - want * H;
+  b = 0;
+  for (int b0 = 0; b0 < B; b0 += 64) {
+    const bool in = b0 + lane < B;
+    const bool kept = in && scale[b0 + lane] != 0.f;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(dropped ? in && !kept : kept);
+    const int cnt = __builtin_popcountll(m);
+    if (want < cnt) { b = b0 + nth_set_bit(m, want, lane); break; }
+    want -= cnt;
+  }
+  b = __builtin_amdgcn_readfirstlane(b);
+  h = __builtin_amdgcn_readfirstlane(h);
+}
 
 // csrc/attn80.hip: persistent head_dim-80 kernels (all operands by LDS-DMA, one head ahead)
 int attn80_fwd_ok(const AttnArgs& a);

@@ -713,7 +713,10 @@ class AttentionD8(nn.Module):
                 from . import dispatch as _D   # noqa: F401
                 on = Octic(torch.ops.octic.attn_packed(qkv.packed, self.num_heads, c, (8 * c // self.num_heads) ** -0.5)[0], c)
             else:
-                on = Octic(OF.AttnPackedFn.apply(qkv.packed, self.num_heads, c, (8 * c // self.num_heads) ** -0.5), c)
+                # rs multiplies this branch's output in the tail below: the kernels may skip the samples it drops (the compacted
+                # batch already holds kept samples only: nothing to skip there)
+                on = Octic(OF.AttnPackedFn.apply(qkv.packed, self.num_heads, c, (8 * c // self.num_heads) ** -0.5,
+                                                 None if (COMPACT_DROP_PATH or resid is None) else rs), c)
         else:
             q, k, v = OF.PackHeadsFn.apply(qkv.packed, self.num_heads, c)
             # HIP attention core for the shapes it covers (bf16 and float32, T <= 16384, head_dim % 16 == 0, no dropout);

@@ -11,6 +11,8 @@ path (used for the reference's fp32 equivariance tolerances); under
 accumulation while the residual stream, LayerNorm statistics and parameter gradients stay f32
 (that is what autocast does to the reference).
 """
+import os
+
 import torch
 
 from . import ops
@@ -428,24 +430,46 @@ class AttnFn(torch.autograd.Function):
         return dq, dk, dv, None
 
 
+# Stochastic depth: a block draws its per-sample factor rs[b] (0 or 1 / keep) BEFORE the attention branch runs and the branch's
+# tail multiplies the branch output with it, so everything the softmax core computes for a dropped sample is discarded in the
+# forward and meets a zero cotangent in the backward.  With ATTN_SKIP_DROPPED the factor travels to the attention kernels, which
+# skip those samples where their work is dealt per (sample, head) - same launch shapes, so it lives inside a captured step
+# (include/octic_hip.h: octic_attn_*_skip).  Read once at import from OCTIC_ATTN_SKIP (0 = off).
+def _attn_skip_from_env():
+    return os.environ.get("OCTIC_ATTN_SKIP", "1").strip() != "0"
+
+
+ATTN_SKIP_DROPPED = _attn_skip_from_env()
+
+
+def skip_scale(rs, B):
+    """rs as the attention kernels' sample_scale: the block's per-sample factor when the switch is on and rs is one float32
+    entry per sample on the GPU (not the per-row factors of a ragged row tensor, not a traced value); None otherwise."""
+    if (not ATTN_SKIP_DROPPED or rs is None or not rs.is_cuda or rs.dtype != torch.float32 or rs.dim() != 1
+            or rs.numel() != B or not rs.is_contiguous()):
+        return None
+    return rs.detach()
+
+
 class AttnPackedFn(torch.autograd.Function):
     """AttentionD8's core on packed rows (reference d8_layers.py:631-656): qkv [B,T,3*8c] -> o [B,T,8c].  The head
     vectors are gathered from / scattered to the irrep pieces inside the attention kernels, so the four pack / unpack
     passes of a training step (and their 0.5 GB of traffic per block) do not exist."""
 
     @staticmethod
-    def forward(ctx, qkv, H, c, scale):
+    def forward(ctx, qkv, H, c, scale, sample_scale=None):
         qkv = _c(qkv)
-        o, lse = ops.attn_fwd_packed(qkv, H, c, scale)
-        ctx.save_for_backward(qkv, o, lse)
+        ss = skip_scale(sample_scale, qkv.shape[0])
+        o, lse = ops.attn_fwd_packed(qkv, H, c, scale, sample_scale=ss)
+        ctx.save_for_backward(qkv, o, lse, ss)
         ctx.meta = (H, c, scale)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse = ctx.saved_tensors
+        qkv, o, lse, ss = ctx.saved_tensors
         H, c, scale = ctx.meta
-        return ops.attn_bwd_packed(qkv, o, _c(do), lse, H, c, scale), None, None, None
+        return ops.attn_bwd_packed(qkv, o, _c(do), lse, H, c, scale, sample_scale=ss), None, None, None, None
 
 
 class AttnFusedQKVFn(torch.autograd.Function):
@@ -454,27 +478,28 @@ class AttnFusedQKVFn(torch.autograd.Function):
     [B,T,3,H,hd] tensor (no permute copies, no zero-fill + add of three partial gradients)."""
 
     @staticmethod
-    def forward(ctx, qkv, scale):
+    def forward(ctx, qkv, scale, sample_scale=None):
         qkv = _c(qkv)
         B, T, _, H, hd = qkv.shape
+        ss = skip_scale(sample_scale, B) if qkv.dtype == torch.bfloat16 else None
         q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
         o = torch.empty((B, T, H, hd), dtype=qkv.dtype, device=qkv.device)
         ov = o.permute(0, 2, 1, 3)
-        _, lse = ops.attn_fwd(q, k, v, scale, out=ov)     # bf16 or float32 entry point by qkv.dtype
-        ctx.save_for_backward(qkv, o, lse)
+        _, lse = ops.attn_fwd(q, k, v, scale, out=ov, sample_scale=ss)     # bf16 or float32 entry point by qkv.dtype
+        ctx.save_for_backward(qkv, o, lse, ss)
         ctx.scale = scale
         return o.view(B, T, H * hd)
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse = ctx.saved_tensors
+        qkv, o, lse, ss = ctx.saved_tensors
         B, T, _, H, hd = qkv.shape
         do = _c(do).view(B, T, H, hd)
         dqkv = torch.empty_like(qkv)
         q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
         dq, dk, dv = (dqkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-        ops.attn_bwd(q, k, v, o.permute(0, 2, 1, 3), do.permute(0, 2, 1, 3), lse, ctx.scale, dq, dk, dv)
-        return dqkv, None
+        ops.attn_bwd(q, k, v, o.permute(0, 2, 1, 3), do.permute(0, 2, 1, 3), lse, ctx.scale, dq, dk, dv, sample_scale=ss)
+        return dqkv, None, None
 
 
 def attention_core(q, k, v, dropout_p=0.0):

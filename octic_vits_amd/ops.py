@@ -510,10 +510,22 @@ def prep_views(flat, cin, cout, transposed):
     return out
 
 
-def attn_fwd(q, k, v, scale, out=None):
+def _sample_scale(sample_scale, B, ref):
+    """The [B] float32 stochastic-depth factors of a launch as the kernels read them, or None (octic_attn_*_skip)."""
+    if sample_scale is None:
+        return None
+    if (sample_scale.dtype != torch.float32 or sample_scale.device != ref.device or sample_scale.numel() != B
+            or not sample_scale.is_contiguous()):
+        raise ValueError("attention: sample_scale must be a contiguous float32 tensor of B entries on the operands' device")
+    return sample_scale
+
+
+def attn_fwd(q, k, v, scale, out=None, sample_scale=None):
     """q,k,v: [B,H,T,hd] bf16 or float32 views with a common stride set (last dim contiguous) -> (o [B,H,T,hd],
     lse [B,H,T]); out: an optional [B,H,T,hd] view (last dim contiguous, 16-byte rows) that receives o.  float32
-    operands run octic_attn_fwd_f32 (csrc/attn_f32.hip)."""
+    operands run octic_attn_fwd_f32 (csrc/attn_f32.hip).  sample_scale ([B] f32, bf16 operands only): the factor the caller
+    multiplies each sample's branch output with - a kernel may skip the samples whose factor is 0 and write zeros
+    (include/octic_hip.h, octic_attn_fwd_skip)."""
     B, H, T, hd = q.shape
     st = q.stride()
     if st[3] != 1 or k.stride() != st or v.stride() != st:
@@ -523,10 +535,15 @@ def attn_fwd(q, k, v, scale, out=None):
     o = out if out is not None else torch.empty((B, H, T, hd), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
     f32 = q.dtype == torch.float32
-    fn = lib().octic_attn_fwd_f32 if f32 else lib().octic_attn_fwd
     t = KERNEL_TIMER.start()
-    check(fn(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, T, hd, st[0], st[1], st[2],
-             o.stride(0), o.stride(1), o.stride(2), float(scale), _stream(q)))
+    if f32:
+        check(lib().octic_attn_fwd_f32(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, T, hd, st[0], st[1], st[2],
+                                       o.stride(0), o.stride(1), o.stride(2), float(scale), _stream(q)))
+    else:
+        ss = _sample_scale(sample_scale, B, q)
+        check(lib().octic_attn_fwd_skip(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, T, hd, st[0], st[1], st[2],
+                                        o.stride(0), o.stride(1), o.stride(2), float(scale), _p(ss), _stream(q)))
+    # (bytes and FLOP stay the full batch's with a sample_scale: the host does not know the kept count without a sync)
     KERNEL_TIMER.stop(t, "attn_f32_fwd_kernel" if f32 else _attn_fwd_name(T, hd), 4 * q.numel() * q.element_size(),
                       4.0 * B * H * T * T * hd)
     return o, lse
@@ -585,22 +602,25 @@ def _attn_bwd_phases(T, hd):
 _ATTN_F32_BWD_PHASES = ((1, "attn_f32_dq_kernel", 6, 6.0), (2, "attn_f32_dkv_kernel", 6, 8.0))
 
 
-def attn_bwd(q, k, v, o, dout, lse, scale, dq, dk, dv):
+def attn_bwd(q, k, v, o, dout, lse, scale, dq, dk, dv, sample_scale=None):
     """All tensors are [B,H,T,hd] views (bf16, or all float32: octic_attn_bwd_f32); q/k/v share strides, o/dout share
-    strides, dq/dk/dv share strides."""
+    strides, dq/dk/dv share strides.  sample_scale: as in attn_fwd (a skipped sample gets zeros in dq, dk, dv)."""
     B, H, T, hd = q.shape
     st, so, sg = q.stride(), o.stride(), dq.stride()
     if k.stride() != st or v.stride() != st or dout.stride() != so or dk.stride() != sg or dv.stride() != sg:
         raise ValueError("attn_bwd: stride sets differ")
     delta = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
     f32 = q.dtype == torch.float32
-    fn = lib().octic_attn_bwd_f32 if f32 else lib().octic_attn_bwd
     phases = _ATTN_F32_BWD_PHASES if f32 else _attn_bwd_phases(T, hd)
+    ss = None if f32 else _sample_scale(sample_scale, B, q)
     for phase, name, nbytes, flops in phases:
         t = KERNEL_TIMER.start()
-        check(fn(_p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, H,
-                 T, hd, st[0], st[1], st[2], so[0], so[1], so[2], sg[0], sg[1], sg[2], float(scale),
-                 phase, _stream(q)))
+        args = (_p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, H,
+                T, hd, st[0], st[1], st[2], so[0], so[1], so[2], sg[0], sg[1], sg[2], float(scale), phase)
+        if f32:
+            check(lib().octic_attn_bwd_f32(*args, _stream(q)))
+        else:
+            check(lib().octic_attn_bwd_skip(*args, _p(ss), _stream(q)))
         KERNEL_TIMER.stop(t, name, nbytes * q.numel() * q.element_size(), flops * B * H * T * T * hd)
 
 
@@ -609,27 +629,30 @@ def attn_packed_ok(T, c, H, dtype):
     return dtype == torch.bfloat16 and c in (10 * H, 8 * H) and attn_supported(T, 8 * (c // H), dtype)
 
 
-def attn_fwd_packed(qkv, H, c, scale, out=None):
-    """qkv packed [B,T,3*8c] bf16 -> (o packed [B,T,8c], lse [B,H,T]); no head pack / unpack copies."""
+def attn_fwd_packed(qkv, H, c, scale, out=None, sample_scale=None):
+    """qkv packed [B,T,3*8c] bf16 -> (o packed [B,T,8c], lse [B,H,T]); no head pack / unpack copies.  sample_scale: as in
+    attn_fwd."""
     B, T = qkv.shape[0], qkv.shape[1]
     o = out if out is not None else torch.empty((B, T, 8 * c), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
     t = KERNEL_TIMER.start()
-    check(lib().octic_attn_fwd_packed(_p(qkv), _p(o), _p(lse), B, H, T, c, qkv.stride(1), o.stride(1), float(scale),
-                                      _stream(qkv)))
+    check(lib().octic_attn_fwd_packed_skip(_p(qkv), _p(o), _p(lse), B, H, T, c, qkv.stride(1), o.stride(1), float(scale),
+                                           _p(_sample_scale(sample_scale, B, qkv)), _stream(qkv)))
     KERNEL_TIMER.stop(t, _attn_fwd_name(T, 8 * (c // H)), 4 * B * T * 8 * c * 2, 4.0 * B * T * T * 8 * c)
     return o, lse
 
 
-def attn_bwd_packed(qkv, o, dout, lse, H, c, scale, out=None):
-    """-> dqkv packed [B,T,3*8c] (dq | dk | dv in the layout of qkv)."""
+def attn_bwd_packed(qkv, o, dout, lse, H, c, scale, out=None, sample_scale=None):
+    """-> dqkv packed [B,T,3*8c] (dq | dk | dv in the layout of qkv).  sample_scale: as in attn_bwd."""
     B, T = qkv.shape[0], qkv.shape[1]
     dqkv = out if out is not None else torch.empty_like(qkv)
     delta = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
+    ss = _sample_scale(sample_scale, B, qkv)
     for phase, name, nbytes, flops in _attn_bwd_phases(T, 8 * (c // H)):
         t = KERNEL_TIMER.start()
-        check(lib().octic_attn_bwd_packed(_p(qkv), _p(o), _p(dout), _p(lse), _p(delta), _p(dqkv), B, H, T, c, qkv.stride(1),
-                                          o.stride(1), dqkv.stride(1), float(scale), phase, _stream(qkv)))
+        check(lib().octic_attn_bwd_packed_skip(_p(qkv), _p(o), _p(dout), _p(lse), _p(delta), _p(dqkv), B, H, T, c,
+                                               qkv.stride(1), o.stride(1), dqkv.stride(1), float(scale), phase, _p(ss),
+                                               _stream(qkv)))
         KERNEL_TIMER.stop(t, name, nbytes * B * T * 8 * c * 2, flops * B * T * T * 8 * c)
     return dqkv
 

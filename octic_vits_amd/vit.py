@@ -130,7 +130,11 @@ class Attention(nn.Module):
             from . import ragged as _R
             a = _R.AttnQKVRaggedFn.apply(qkv, rag, self.num_heads, hd ** -0.5)
         else:
-            a = _OF.AttnFusedQKVFn.apply(qkv.view(B, N, 3, self.num_heads, hd), hd ** -0.5)
+            # rs multiplies this branch's output in the tail below: the kernels may skip the samples it drops (the compacted
+            # batch of d8_layers.COMPACT_DROP_PATH already holds kept samples only: nothing to skip there)
+            from . import d8_layers as _L
+            a = _OF.AttnFusedQKVFn.apply(qkv.view(B, N, 3, self.num_heads, hd), hd ** -0.5,
+                                         None if _L.COMPACT_DROP_PATH else rs)
         rps = _rows_per_scale(y, rs)
         hip = bf and self.rows_ok(y)
         if rows_to is not None and (not hip or next_norm is not None):
