@@ -299,6 +299,28 @@ int octic_attn_bwd_packed(const void* qkv, const void* o, const void* dout, cons
                           int64_t B, int H, int T, int c, int64_t ld_qkv, int64_t ld_o, int64_t ld_g, float scale,
                           int phase, void* stream);
 
+/* What the attention entry points run for a shape, without touching the GPU: the answer of the one routing function of
+ * the library (attn_plan, csrc/attention.hip), under the current octic_route_override table.  dtype: OCTIC_BF16 | OCTIC_F32;
+ * ld_in / ld_out / ld_grad: token strides in elements of q/k/v, of o/dout and of dq/dk/dv (the sT / oT / gT of the entry
+ * points, ld_qkv / ld_o / ld_g of the packed ones; 0 = hd, contiguous heads).  out[0] = forward kernel (OCTIC_ATTN_FWD_*),
+ * out[1] = its waves per workgroup, out[2] = what a backward call with phase 3 runs (OCTIC_ATTN_BWD_*), out[3] = its waves.
+ * OCTIC_ESHAPE exactly where the entry points return it for (T, hd). */
+enum {
+  OCTIC_ATTN_FWD_PERSIST = 0,      /* attn_fwd_persist_kernel: one workgroup per CU walks over its heads                   */
+  OCTIC_ATTN_FWD_A80_ONESHOT = 1,  /* csrc/attn80.hip, head_dim 80: fwd_os_kernel / fwd_oss_kernel<n>, one-shot softmax     */
+  OCTIC_ATTN_FWD_A80_ONLINE = 2,   /* csrc/attn80.hip, head_dim 80: fwd_kernel, online softmax                              */
+  OCTIC_ATTN_FWD_RESIDENT = 3,     /* attn_fwd_kernel<.., 512 | 640>: one workgroup per head, one wave per query tile       */
+  OCTIC_ATTN_FWD_STREAM = 4,       /* csrc/attn_stream.hip: K / V through LDS in blocks                                     */
+  OCTIC_ATTN_FWD_F32 = 5           /* csrc/attn_f32.hip                                                                     */
+};
+enum {
+  OCTIC_ATTN_BWD_SINGLE = 0,       /* csrc/attn80_bwd.hip: dq, dk, dv from one recomputation of P                           */
+  OCTIC_ATTN_BWD_PAIR = 1,         /* attn_bwd_dq_kernel + attn_bwd_dkv_kernel, K / V (Q / dO) of a head resident in LDS    */
+  OCTIC_ATTN_BWD_STREAM = 2,       /* the streaming dq + dkv pair                                                           */
+  OCTIC_ATTN_BWD_F32 = 3           /* the float32 dq + dkv pair                                                             */
+};
+int octic_attn_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int64_t ld_grad, int out[4]);
+
 /* ---- attention core: samples dropped by stochastic depth ------------------------------------------
  * The four bf16 entry points with one more argument in front of `stream`: sample_scale, nullable, B floats on the
  * device - the per-sample factor the CALLER multiplies this attention branch's output with (x + scale * f(x)); exactly

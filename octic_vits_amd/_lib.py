@@ -17,6 +17,10 @@ ABI_VERSION = 20
 (ROUTE_DENSE_TILE, ROUTE_DENSE_SPLIT, ROUTE_WGRAD_SLABS, ROUTE_WGRAD_TILE, ROUTE_LINEAR_RING, ROUTE_RING_EVEN,
  ROUTE_ATTN_LEGACY, ROUTE_ATTN_ONLINE, ROUTE_ATTN_BWD_PAIR, ROUTE_DENSE_IMAGE, ROUTE_DENSE_CLS2, ROUTE_ATTN_STREAM) = range(12)
 
+# kernel ids of octic_attn_plan (include/octic_hip.h)
+(ATTN_FWD_PERSIST, ATTN_FWD_A80_ONESHOT, ATTN_FWD_A80_ONLINE, ATTN_FWD_RESIDENT, ATTN_FWD_STREAM, ATTN_FWD_F32) = range(6)
+ATTN_BWD_SINGLE, ATTN_BWD_PAIR, ATTN_BWD_STREAM, ATTN_BWD_F32 = range(4)
+
 c_i64, c_int, c_float, c_void_p = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 c_double = ctypes.c_double
 
@@ -111,6 +115,7 @@ _PROTOS = {
     "octic_attn_bwd_packed_skip": (c_int, [c_void_p] * 6 + [c_i64, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_float, c_int, c_void_p, c_void_p]),
     "octic_attn_fwd_f32": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_int, c_int] + [c_i64] * 6 + [c_float, c_void_p]),
     "octic_attn_bwd_f32": (c_int, [c_void_p] * 10 + [c_i64, c_int, c_int, c_int] + [c_i64] * 9 + [c_float, c_int, c_void_p]),
+    "octic_attn_plan": (c_int, [c_int, c_int, c_int, c_i64, c_i64, c_i64, ctypes.POINTER(c_int)]),
     "octic_attn_pack_heads": (c_int, [VP, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p]),
     "octic_attn_unpack_heads": (c_int, [c_void_p, VP, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p]),
     "octic_handoff_cat_fwd": (c_int, [VP, c_void_p, c_i64, c_int, c_int, c_void_p]),
@@ -196,18 +201,30 @@ def lib():
     return _LIB
 
 
-# the values set through route_override (the library keeps the authoritative table; this mirror lets the Python side
-# name the launches a forced route runs, e.g. KERNEL_TIMER under ROUTE_ATTN_STREAM)
-ROUTES = {}
-
-
 def route_override(knob: int, value: int) -> int:
     """Force a kernel / tiling choice for an A/B or a test (0 = automatic); returns the previous value."""
     old = lib().octic_route_override(knob, value)
     if old < 0:
         raise ValueError(f"octic_route_override: unknown knob {knob}")
-    ROUTES[knob] = value
+    _ATTN_PLANS.clear()
     return old
+
+
+# octic_attn_plan's answers by argument tuple: the eager step asks per attention call, and without this it measured 1.3 - 1.9 ms
+# per ViT-H step slower than before the query existed (NOTES, 'Attention routing').  An answer holds until the override table
+# changes: route_override drops them all.
+_ATTN_PLANS = {}
+
+
+def attn_plan(T, hd, dtype=BF16, ld_in=0, ld_out=0, ld_grad=0):
+    """octic_attn_plan: (forward kernel, its waves, what a phase-3 backward call runs, its waves) - ATTN_FWD_* / ATTN_BWD_*."""
+    key = (T, hd, dtype, ld_in, ld_out, ld_grad)
+    plan = _ATTN_PLANS.get(key)
+    if plan is None:
+        out = (c_int * 4)()
+        check(lib().octic_attn_plan(dtype, T, hd, ld_in, ld_out, ld_grad, out))
+        plan = _ATTN_PLANS[key] = tuple(out)
+    return plan
 
 
 def check(code: int):

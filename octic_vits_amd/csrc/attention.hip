@@ -15,12 +15,9 @@
 //   * O^T keeps the query on the lane too, so the online-softmax rescale and the final 1/l are lane-local.
 // head_dim must be a multiple of 16 (<= 128).  Bound: MFMA/VALU mix, not HBM (q,k,v,o are 4 x 42 MB per call).
 #include <stdlib.h>
-#include "attn_common.hpp"
+#include "attn80_common.hpp"
 
 namespace octic {
-
-inline int attn_rsk(int hd) { return hd * 2 + 16; }                       // K image row bytes (odd # of 16-B slots)
-inline int attn_rsv(int dp) { int r = dp * 2; return ((r / 4) % 32 == 0) ? r + 64 : r; }   // V image row bytes
 
 // Stage two row images (zero-filled beyond T rows / kcA, kcB source chunks per row) with all global loads of a batch
 // in flight before the first LDS store.  The s_memtime timeline showed 10-20k cycles (a third of the kernel) in
@@ -239,8 +236,6 @@ extern "C" void* octic_dbg_attn_trace(void) {
 #else
 #define ATRACE(kern, slot) do {} while (0)
 #endif
-constexpr int kAttnWaves = 8;
-inline int attn_waves(int nt) { return nt == kAttnWaves + 1 ? kAttnWaves : nt; }
 
 // One pass of the forward over key tiles kt0, kt0+kstep, ... < nt for query tile `qtile`; online softmax state
 // (m, l: per lane = per query, l still split between the half-waves) and O^T accumulators are updated in place.
@@ -679,51 +674,6 @@ __global__ __launch_bounds__(512) void attn_fwd_persist_kernel(AttnArgs a, int r
   }
 }
 
-// routing override OCTIC_ROUTE_ATTN_LEGACY: 1 = round-2 kernels for every shape
-
-template <int KS, int DT>
-static int attn_fwd_launch(const AttnArgs& a, int64_t B, hipStream_t s) {
-  // the forward is light on registers: one wave per tile even for nine tiles (three waves on one SIMD hide the
-  // softmax latency better than the shared-tile split does: 78 vs 85 us at T = 257); the kernel supports both
-  const int rsk = attn_rsk(a.hd), rsv = attn_rsv(DT * 32);
-  if (!route(OCTIC_ROUTE_ATTN_LEGACY) && attn80_fwd_ok(a)) return attn80_fwd_launch(a, B, s);
-  {
-    const int nt = (a.T + 31) / 32, W = nt < 8 ? nt : 8;
-    const int nrows = a.T - W * 32;
-    const int kimg = (nt * 32 * rsk + 1023) & ~1023;
-    const size_t need = 2 * (size_t)kimg + (size_t)nt * 32 * rsv +
-                        (nrows > 0 ? (size_t)W * nrows * (DT * 32 + kPartPad + 2) * sizeof(float) : 0);
-    const bool fits = nt <= 9 && nrows <= 2 && need <= 160 * 1024 && kimg / 1024 <= 8 * W &&
-                      (a.T * 2 * KS + W * 64 - 1) / (W * 64) <= 6 && (a.T - 1) * a.sT * 2 + a.hd * 2 < 0x7FFFFFF0ll;
-    if (fits) {
-      static DeviceOnce once;
-      const int cus = device_cus();
-      if (once.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_fwd_persist_kernel<KS, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-      }
-      const int units = (int)(B * a.H);
-      attn_fwd_persist_kernel<KS, DT><<<units < cus ? units : cus, W * 64, need, s>>>(a, rsk, rsv, nt, units);
-      return launch_status();
-    }
-  }
-  const int nt = (a.T + 31) / 32, W = nt;
-  size_t smem = (size_t)nt * 32 * (rsk + rsv);
-  const size_t comb = ((size_t)W * 32 * (DT * 32 + kPartPad) + (2 * W + 1) * 32) * sizeof(float);
-  if (nt != W && comb > smem) smem = comb;
-  if (smem > 160 * 1024) return attn_stream_fwd_launch(a, B, s);   // K and V of the head do not fit: stream them
-  static DeviceOnce once;
-  if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<KS, DT, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<KS, DT, 640>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-  }
-  if (W <= 8) attn_fwd_kernel<KS, DT, 512><<<(int)(B * a.H), W * 64, smem, s>>>(a, rsk, rsv, nt);
-  else attn_fwd_kernel<KS, DT, 640><<<(int)(B * a.H), W * 64, smem, s>>>(a, rsk, rsv, nt);
-  return launch_status();
-}
-
-
 // =================================================================================================
 // Backward.  P is recomputed from q, k and the saved log-sum-exp (no T x T tensor is ever stored).
 //   dV = P^T dO ;  dP = dO V^T ;  dS = P * (dP - delta),  delta[q] = sum_d dO[q,d] O[q,d] ;  dQ = scale dS K ;  dK = scale dS^T Q
@@ -1043,53 +993,169 @@ __global__ __launch_bounds__(MAXT) void attn_bwd_dkv_kernel(AttnBwdArgs a, int r
   ATRACE(2, 7);
 }
 
-template <int KS, int DT>
-static int attn_bwd_launch(const AttnBwdArgs& a, int64_t B, int phase, hipStream_t s) {
-  // dkv (two accumulator sets) needs the 256-register budget of the eight-wave split (105 vs 156 us with spills);
-  // dq runs the same either way (~106 us) and follows it
-  // both gradients asked for at once: the single-pass kernel (csrc/attn80_bwd.hip) where its shape applies
-  if (phase == 3 && KS == 5 && !route(OCTIC_ROUTE_ATTN_LEGACY) && attn80_bwd_ok(a)) return attn80_bwd_launch(a, B, s);
-  const int nt = (a.T + 31) / 32, W = attn_waves(nt), Wq = W;
-  // the row images are read both by rows (ds_read_b128) and transposed (ds_read_b64_tr_b16); rows are padded so the
-  // b128 reads are conflict-free, the transposed reads then see at most 2-way conflicts.  The tr fragments reach
-  // DT*32 columns, so rows must hold that many (the pad columns meet zero accumulator columns / are discarded).
-  const int cols = DT * 32 > a.hd ? DT * 32 : a.hd;
-  const int rs = cols * 2 + 16;
-  const size_t img = (size_t)2 * nt * 32 * rs;
-  size_t smem_dq = img + (size_t)nt * 32 * (a.hd / 8) * sizeof(float);      // + the delta partials [Tp][hd / 8]
-  size_t smem_kv = img + (size_t)2 * nt * 32 * sizeof(float);
-  const size_t comb = (size_t)W * 32 * (DT * 32 + kPartPad) * sizeof(float);
-  if (nt != W && comb > smem_dq) smem_dq = comb;
-  if (nt != W && comb > smem_kv) smem_kv = comb;
-  if (smem_kv > 160 * 1024 || smem_dq > 160 * 1024) return attn_stream_bwd_launch(a, B, phase, s);   // do not fit: stream
-  static DeviceOnce once;
-  if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<KS, DT, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<KS, DT, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<KS, DT, 640>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<KS, DT, 640>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
+// ---- the routing: every condition that picks an attention kernel is in this function ------------------------------------
+// (tests/test_attn_plan_host.py holds its answers for every T <= 320 at every head_dim, written out)
+// Knobs: OCTIC_ROUTE_ATTN_STREAM = 1: the streaming kernels for every T; OCTIC_ROUTE_ATTN_LEGACY = 1: no csrc/attn80*.hip
+// kernel; OCTIC_ROUTE_ATTN_BWD_PAIR = 1: no single-pass backward; OCTIC_ROUTE_ATTN_ONLINE: 1 = online softmax in the
+// head_dim-80 forward (+16: K / V descriptors with zero records, a timing probe of developer runs).
+int attn_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int64_t ld_grad, AttnPlan* plan) {
+  if (T <= 0 || T > kAttnMaxT || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
+  AttnPlan p = {};
+  if (dtype == OCTIC_F32) {                                   // one streaming design for every shape (csrc/attn_f32.hip)
+    p.fwd = OCTIC_ATTN_FWD_F32;
+    p.bwd = p.pair = OCTIC_ATTN_BWD_F32;
+    p.fwd_waves = p.bwd_waves = p.pair_waves = 4;
+    p.fwd_lds = p.dq_lds = p.dkv_lds = attn_f32_lds(hd);
+    *plan = p;
+    return OCTIC_OK;
   }
-  if (phase & 1) {
-    if (Wq <= 8) attn_bwd_dq_kernel<KS, DT, 512><<<(int)(B * a.H), Wq * 64, smem_dq, s>>>(a, rs, nt);
-    else attn_bwd_dq_kernel<KS, DT, 640><<<(int)(B * a.H), Wq * 64, smem_dq, s>>>(a, rs, nt);
+  if (dtype != OCTIC_BF16) return OCTIC_EDTYPE;
+  const int64_t sT = ld_in ? ld_in : hd, oT = ld_out ? ld_out : hd, gT = ld_grad ? ld_grad : hd;
+  const int KS = hd / 16, DT = (hd + 31) / 32, nt = (T + 31) / 32, Tp = nt * 32;
+  const int rsk = attn_rsk(hd), rsv = attn_rsv(DT * 32), rs = attn_rs(hd);
+  const size_t lds_max = 160 * 1024;
+  const bool stream = T > 320 || route(OCTIC_ROUTE_ATTN_STREAM) == 1;       // K and V of a head stay resident up to 320 tokens
+  const int W8 = nt < 8 ? nt : 8, extra = T - 32 * W8;                      // eight waves, one tile each; rows beyond them
+  // csrc/attn80*.hip address rows with 32-bit buffer offsets
+  const auto off32 = [T](int64_t ld) { return (int64_t)T * ld * 2 < 0x7FFFFFF0ll; };
+  const bool hd80 = hd == a80::HD && !route(OCTIC_ROUTE_ATTN_LEGACY);
+
+  // ---- forward
+  const size_t kimg = ((size_t)Tp * rsk + 1023) & ~(size_t)1023;            // persistent forward: K image in whole DMA instructions
+  const size_t persist = 2 * kimg + (size_t)Tp * rsv + (extra > 0 ? (size_t)W8 * extra * (DT * 32 + kPartPad + 2) * sizeof(float) : 0);
+  const size_t resident = (size_t)Tp * (rsk + rsv);
+  p.fwd = OCTIC_ATTN_FWD_STREAM;                                            // unless K and V of the head fit in LDS at once
+  p.fwd_waves = kStreamWaves;
+  p.fwd_lds = 2 * (size_t)kStreamBlk * (rsk + rsv);                         // <= 74 KiB (head_dim 128)
+  if (!stream && hd80 && nt <= a80::MAXNT && extra <= 2 && off32(sT) && off32(oT)) {   // at most 8 full tiles + 2 extra rows
+    const bool one_shot = (route(OCTIC_ROUTE_ATTN_ONLINE) & 15) == 0;       // nine tiles: fwd_os_kernel, else fwd_oss_kernel<nt>
+    p.fwd = one_shot ? OCTIC_ATTN_FWD_A80_ONESHOT : OCTIC_ATTN_FWD_A80_ONLINE;
+    p.fwd_waves = !one_shot ? W8 : nt == a80::MAXNT ? a80::WAVES : nt < 4 ? 4 : nt;
+    p.fwd_lds = !one_shot ? a80::fwd_lds(nt) : nt == a80::MAXNT ? a80::fwd_os_lds(nt) : a80::fwd_oss_lds(nt);
+    p.fwd_dbg = route(OCTIC_ROUTE_ATTN_ONLINE) >> 4;
+  } else if (!stream && nt <= 9 && extra <= 2 && persist <= lds_max && (int)(kimg / 1024) <= 8 * W8 &&
+             (T * 2 * KS + W8 * 64 - 1) / (W8 * 64) <= 6 && (T - 1) * sT * 2 + hd * 2 < 0x7FFFFFF0ll) {
+    // persistent forward: the images and the shared rows' partials fit, at most 8 K DMA instructions and 6 V chunks per
+    // lane, 32-bit K offsets
+    p.fwd = OCTIC_ATTN_FWD_PERSIST;
+    p.fwd_waves = W8;
+    p.fwd_lds = persist;
+  } else if (!stream && resident <= lds_max) {                                        // one wave per query tile
+    p.fwd = OCTIC_ATTN_FWD_RESIDENT;
+    p.fwd_waves = nt;
+    p.fwd_lds = resident;
   }
-  if (phase & 2) {
-    if (W <= 8) attn_bwd_dkv_kernel<KS, DT, 512><<<(int)(B * a.H), W * 64, smem_kv, s>>>(a, rs, nt);
-    else attn_bwd_dkv_kernel<KS, DT, 640><<<(int)(B * a.H), W * 64, smem_kv, s>>>(a, rs, nt);
+
+  // ---- backward, phases 1 and 2: the dq + dkv pair, resident (nine tiles on eight waves: the ninth is shared) or streaming
+  const int W = nt == kAttnWaves + 1 ? kAttnWaves : nt;
+  const size_t img = (size_t)2 * Tp * rs;
+  const size_t comb = nt != W ? (size_t)W * 32 * (DT * 32 + kPartPad) * sizeof(float) : 0;   // the shared tile's partials
+  size_t dq = img + (size_t)Tp * (hd / 8) * sizeof(float);                  // + the delta partials [Tp][hd / 8]
+  size_t dkv = img + (size_t)2 * Tp * sizeof(float);                        // + lse, delta
+  if (comb > dq) dq = comb;
+  if (comb > dkv) dkv = comb;
+  p.pair = OCTIC_ATTN_BWD_STREAM;
+  p.pair_waves = kStreamWaves;
+  p.dq_lds = 4 * (size_t)kStreamBlk * rs;
+  p.dkv_lds = p.dq_lds + 4 * kStreamBlk * sizeof(float);                    // <= 69 KiB (head_dim 128)
+  if (!stream && dq <= lds_max && dkv <= lds_max) {
+    p.pair = OCTIC_ATTN_BWD_PAIR;
+    p.pair_waves = W;
+    p.dq_lds = dq;
+    p.dkv_lds = dkv;
   }
-  return launch_status();
+  // ---- phase 3: the single-pass backward at 257 tokens (8 key tiles + one extra row), 193 .. 256 (7 - 8 key tiles, every
+  // token inside one: DINOv2 ViT-H/16's 197) or <= 64 (bwd_small_kernel: the 37-token local crops); 65 .. 192 tokens would
+  // leave most of the eight waves without a key tile (and those instantiations spill) and stay on the pair
+  if (!stream && hd80 && !route(OCTIC_ROUTE_ATTN_BWD_PAIR) && (T == a80::BW_T || (T > 192 && T <= 256) || T <= 64) &&
+      off32(sT) && off32(oT) && off32(gT)) {
+    p.bwd = OCTIC_ATTN_BWD_SINGLE;
+    p.bwd_waves = T <= 64 ? nt : a80::WAVES;
+    p.bwd_lds = T <= 64 ? a80::bwd_small_lds(nt) : a80::BW_LDS;
+  } else {
+    p.bwd = p.pair;
+    p.bwd_waves = p.pair_waves;
+  }
+  *plan = p;
+  return OCTIC_OK;
 }
 
-// T > 320, or every T under OCTIC_ROUTE_ATTN_STREAM = 1: the streaming kernels (csrc/attn_stream.hip)
-static bool attn_stream_route(int T) { return T > 320 || route(OCTIC_ROUTE_ATTN_STREAM) == 1; }
-constexpr int kAttnMaxT = 16384;
+// The resident forward is light on registers: one wave per tile even for nine tiles (three waves on one SIMD hide the softmax
+// latency better than the shared-tile split does: 78 vs 85 us at T = 257); attn_fwd_kernel supports both.
+static int attn_fwd_run(const AttnArgs& a, int64_t B, const AttnPlan& p, hipStream_t s) {
+  if (p.fwd == OCTIC_ATTN_FWD_STREAM) return attn_stream_fwd_launch(a, B, p, s);
+  if (p.fwd == OCTIC_ATTN_FWD_A80_ONESHOT || p.fwd == OCTIC_ATTN_FWD_A80_ONLINE) return attn80_fwd_launch(a, B, p, s);
+  const int nt = (a.T + 31) / 32, W = p.fwd_waves, units = (int)(B * a.H);
+  return attn_dispatch(a.hd, [&](auto c) {
+    constexpr int KS = decltype(c)::KS, DT = decltype(c)::DT;
+    const int rsk = attn_rsk(a.hd), rsv = attn_rsv(DT * 32);
+    static DeviceOnce once;
+    attn_lds_optin(once, attn_fwd_persist_kernel<KS, DT>, attn_fwd_kernel<KS, DT, 512>, attn_fwd_kernel<KS, DT, 640>);
+    if (p.fwd == OCTIC_ATTN_FWD_PERSIST) {
+      const int cus = device_cus();
+      attn_fwd_persist_kernel<KS, DT><<<units < cus ? units : cus, W * 64, p.fwd_lds, s>>>(a, rsk, rsv, nt, units);
+    } else if (W <= 8) attn_fwd_kernel<KS, DT, 512><<<units, W * 64, p.fwd_lds, s>>>(a, rsk, rsv, nt);
+    else attn_fwd_kernel<KS, DT, 640><<<units, W * 64, p.fwd_lds, s>>>(a, rsk, rsv, nt);
+    return launch_status();
+  });
+}
+
+// Resident pair: dkv (two accumulator sets) needs the 256-register budget of the eight-wave split (105 vs 156 us with spills);
+// dq runs the same either way (~106 us) and follows it.
+static int attn_bwd_run(const AttnBwdArgs& a, int64_t B, int phase, const AttnPlan& p, hipStream_t s) {
+  // both gradients asked for at once: the single-pass kernel where the plan has it
+  if (phase == 3 && p.bwd == OCTIC_ATTN_BWD_SINGLE) return attn80_bwd_launch(a, B, p, s);
+  if (p.pair == OCTIC_ATTN_BWD_STREAM) return attn_stream_bwd_launch(a, B, phase, p, s);
+  const int nt = (a.T + 31) / 32, W = p.pair_waves, rs = attn_rs(a.hd), units = (int)(B * a.H);
+  return attn_dispatch(a.hd, [&](auto c) {
+    constexpr int KS = decltype(c)::KS, DT = decltype(c)::DT;
+    static DeviceOnce once;
+    attn_lds_optin(once, attn_bwd_dq_kernel<KS, DT, 512>, attn_bwd_dkv_kernel<KS, DT, 512>, attn_bwd_dq_kernel<KS, DT, 640>,
+                   attn_bwd_dkv_kernel<KS, DT, 640>);
+    if ((phase & 1) && W <= 8) attn_bwd_dq_kernel<KS, DT, 512><<<units, W * 64, p.dq_lds, s>>>(a, rs, nt);
+    else if (phase & 1) attn_bwd_dq_kernel<KS, DT, 640><<<units, W * 64, p.dq_lds, s>>>(a, rs, nt);
+    if ((phase & 2) && W <= 8) attn_bwd_dkv_kernel<KS, DT, 512><<<units, W * 64, p.dkv_lds, s>>>(a, rs, nt);
+    else if (phase & 2) attn_bwd_dkv_kernel<KS, DT, 640><<<units, W * 64, p.dkv_lds, s>>>(a, rs, nt);
+    return launch_status();
+  });
+}
+
+// The fields AttnArgs and AttnBwdArgs share.  [B,H,T,hd] views with one stride set per tensor group: c = 0.  Packed rows
+// (c > 0 channels per irrep): q == k == v = the LinearD8 output [B, T, 3*8c], o the packed [B, T, 8c], sH = oH = 0 (HeadMap).
+template <typename A>
+static A attn_args(const void* q, const void* k, const void* v, const void* o, int H, int T, int hd, int64_t sB, int64_t sH,
+                   int64_t sT, int64_t oB, int64_t oH, int64_t oT, float scale, int c, const float* sample_scale) {
+  A a;
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.sB = sB; a.sH = sH; a.sT = sT;
+  a.o = (bf16*)o; a.oB = oB; a.oH = oH; a.oT = oT;
+  a.H = H; a.T = T; a.hd = hd;
+  a.scale_log2 = scale * 1.4426950408889634f;
+  a.cv_in = 3 * c; a.cv_out = c; a.c = c;
+  a.sample_scale = sample_scale;
+  return a;
+}
+// what only the backward has
+static void attn_bwd_rest(AttnBwdArgs& a, const void* dout, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                          int64_t gB, int64_t gH, int64_t gT, float scale) {
+  a.dout = (const bf16*)dout;
+  a.lse = lse; a.delta = delta;
+  a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.gB = gB; a.gH = gH; a.gT = gT;
+  a.scale = scale;
+}
 
 }  // namespace octic
 
 using namespace octic;
 
 extern "C" {
+
+int octic_attn_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int64_t ld_grad, int out[4]) {
+  if (!out) return OCTIC_ENULL;
+  AttnPlan p;
+  if (const int rc = attn_plan(dtype, T, hd, ld_in, ld_out, ld_grad, &p)) return rc;
+  out[0] = p.fwd; out[1] = p.fwd_waves; out[2] = p.bwd; out[3] = p.bwd_waves;
+  return OCTIC_OK;
+}
 
 int octic_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int H, int T, int hd,
                    int64_t sB, int64_t sH, int64_t sT, int64_t oB, int64_t oH, int64_t oT, float scale, void* stream) {
@@ -1100,32 +1166,15 @@ int octic_attn_fwd(const void* q, const void* k, const void* v, void* o, float* 
 int octic_attn_fwd_skip(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int H, int T, int hd,
                         int64_t sB, int64_t sH, int64_t sT, int64_t oB, int64_t oH, int64_t oT, float scale,
                         const float* sample_scale, void* stream) {
+  AttnPlan p;
   if (!q || !k || !v || !o) return OCTIC_ENULL;
   if (((uintptr_t)sample_scale) & 3) return OCTIC_EALIGN;
-  if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
+  if (B <= 0 || H <= 0 || attn_plan(OCTIC_BF16, T, hd, sT, oT, 0, &p)) return OCTIC_ESHAPE;
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o)) & 15) return OCTIC_EALIGN;
   if ((sB | sH | sT | oB | oH | oT) & 7) return OCTIC_EALIGN;   // rows must stay 16-byte aligned (8 bf16)
-  AttnArgs a;
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v;
-  a.sB = sB; a.sH = sH; a.sT = sT;
-  a.o = (bf16*)o; a.oB = oB; a.oH = oH; a.oT = oT;
+  AttnArgs a = attn_args<AttnArgs>(q, k, v, o, H, T, hd, sB, sH, sT, oB, oH, oT, scale, 0, sample_scale);
   a.lse = lse;
-  a.H = H; a.T = T; a.hd = hd;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  a.cv_in = a.cv_out = a.c = 0;
-  a.sample_scale = sample_scale;
-  hipStream_t s = (hipStream_t)stream;
-  if (attn_stream_route(T)) return attn_stream_fwd_launch(a, B, s);
-  switch (hd / 16) {
-    case 1: return attn_fwd_launch<1, 1>(a, B, s);
-    case 2: return attn_fwd_launch<2, 1>(a, B, s);
-    case 3: return attn_fwd_launch<3, 2>(a, B, s);
-    case 4: return attn_fwd_launch<4, 2>(a, B, s);
-    case 5: return attn_fwd_launch<5, 3>(a, B, s);
-    case 6: return attn_fwd_launch<6, 3>(a, B, s);
-    case 7: return attn_fwd_launch<7, 4>(a, B, s);
-    default: return attn_fwd_launch<8, 4>(a, B, s);
-  }
+  return attn_fwd_run(a, B, p, (hipStream_t)stream);
 }
 
 int octic_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
@@ -1140,36 +1189,18 @@ int octic_attn_bwd_skip(const void* q, const void* k, const void* v, const void*
                         float* delta, void* dq, void* dk, void* dv, int64_t B, int H, int T, int hd, int64_t sB, int64_t sH,
                         int64_t sT, int64_t oB, int64_t oH, int64_t oT, int64_t gB, int64_t gH, int64_t gT, float scale,
                         int phase, const float* sample_scale, void* stream) {
+  AttnPlan p;
   if (!q || !k || !v || !o || !dout || !lse || !delta || !dq || !dk || !dv) return OCTIC_ENULL;
   if (((uintptr_t)sample_scale) & 3) return OCTIC_EALIGN;
   if (phase < 1 || phase > 3) return OCTIC_ESHAPE;
-  if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
+  if (B <= 0 || H <= 0 || attn_plan(OCTIC_BF16, T, hd, sT, oT, gT, &p)) return OCTIC_ESHAPE;
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o) | ((uintptr_t)dout) | ((uintptr_t)dq) |
        ((uintptr_t)dk) | ((uintptr_t)dv)) & 15)
     return OCTIC_EALIGN;
   if ((sB | sH | sT | oB | oH | oT | gB | gH | gT) & 7) return OCTIC_EALIGN;
-  AttnBwdArgs a;
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.sB = sB; a.sH = sH; a.sT = sT;
-  a.o = (const bf16*)o; a.dout = (const bf16*)dout; a.oB = oB; a.oH = oH; a.oT = oT;
-  a.lse = lse; a.delta = delta;
-  a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.gB = gB; a.gH = gH; a.gT = gT;
-  a.H = H; a.T = T; a.hd = hd;
-  a.scale = scale;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  a.cv_in = a.cv_out = a.c = 0;
-  a.sample_scale = sample_scale;
-  hipStream_t s = (hipStream_t)stream;
-  if (attn_stream_route(T)) return attn_stream_bwd_launch(a, B, phase, s);
-  switch (hd / 16) {
-    case 1: return attn_bwd_launch<1, 1>(a, B, phase, s);
-    case 2: return attn_bwd_launch<2, 1>(a, B, phase, s);
-    case 3: return attn_bwd_launch<3, 2>(a, B, phase, s);
-    case 4: return attn_bwd_launch<4, 2>(a, B, phase, s);
-    case 5: return attn_bwd_launch<5, 3>(a, B, phase, s);
-    case 6: return attn_bwd_launch<6, 3>(a, B, phase, s);
-    case 7: return attn_bwd_launch<7, 4>(a, B, phase, s);
-    default: return attn_bwd_launch<8, 4>(a, B, phase, s);
-  }
+  AttnBwdArgs a = attn_args<AttnBwdArgs>(q, k, v, o, H, T, hd, sB, sH, sT, oB, oH, oT, scale, 0, sample_scale);
+  attn_bwd_rest(a, dout, lse, delta, dq, dk, dv, gB, gH, gT, scale);
+  return attn_bwd_run(a, B, phase, p, (hipStream_t)stream);
 }
 
 // AttentionD8 on PACKED rows (reference d8_layers.py:631-656 without the pack / unpack copies): qkv is the LinearD8
@@ -1184,22 +1215,16 @@ int octic_attn_fwd_packed(const void* qkv, void* o, float* lse, int64_t B, int H
 
 int octic_attn_fwd_packed_skip(const void* qkv, void* o, float* lse, int64_t B, int H, int T, int c, int64_t ld_qkv,
                                int64_t ld_o, float scale, const float* sample_scale, void* stream) {
+  AttnPlan p;
   if (!qkv || !o) return OCTIC_ENULL;
   if (((uintptr_t)sample_scale) & 3) return OCTIC_EALIGN;
-  if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || c <= 0 || (c != 10 * H && c != 8 * H)) return OCTIC_ESHAPE;
+  if (B <= 0 || H <= 0 || c <= 0 || (c != 10 * H && c != 8 * H) || attn_plan(OCTIC_BF16, T, 8 * (c / H), ld_qkv, ld_o, 0, &p))
+    return OCTIC_ESHAPE;
   if (((((uintptr_t)qkv) | ((uintptr_t)o)) & 15) || ((ld_qkv | ld_o) & 7) || ld_qkv < 24 * c || ld_o < 8 * c) return OCTIC_EALIGN;
-  AttnArgs a;
-  a.q = a.k = a.v = (const bf16*)qkv;
-  a.sB = (int64_t)T * ld_qkv; a.sH = 0; a.sT = ld_qkv;
-  a.o = (bf16*)o; a.oB = (int64_t)T * ld_o; a.oH = 0; a.oT = ld_o;
+  AttnArgs a = attn_args<AttnArgs>(qkv, qkv, qkv, o, H, T, 8 * (c / H), (int64_t)T * ld_qkv, 0, ld_qkv, (int64_t)T * ld_o, 0, ld_o,
+                                       scale, c, sample_scale);
   a.lse = lse;
-  a.H = H; a.T = T; a.hd = 8 * (c / H);
-  a.scale_log2 = scale * 1.4426950408889634f;
-  a.cv_in = 3 * c; a.cv_out = c; a.c = c;
-  a.sample_scale = sample_scale;
-  if (attn_stream_route(T)) return attn_stream_fwd_launch(a, B, (hipStream_t)stream);
-  if (a.hd == 64) return attn_fwd_launch<4, 2>(a, B, (hipStream_t)stream);
-  return attn_fwd_launch<5, 3>(a, B, (hipStream_t)stream);
+  return attn_fwd_run(a, B, p, (hipStream_t)stream);
 }
 
 // Backward of the above: dqkv (packed like qkv, row stride ld_g) receives dq | dk | dv; dout packed like o.
@@ -1212,26 +1237,19 @@ int octic_attn_bwd_packed(const void* qkv, const void* o, const void* dout, cons
 int octic_attn_bwd_packed_skip(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
                                int64_t B, int H, int T, int c, int64_t ld_qkv, int64_t ld_o, int64_t ld_g, float scale,
                                int phase, const float* sample_scale, void* stream) {
+  AttnPlan p;
   if (!qkv || !o || !dout || !lse || !delta || !dqkv) return OCTIC_ENULL;
   if (((uintptr_t)sample_scale) & 3) return OCTIC_EALIGN;
   if (phase < 1 || phase > 3) return OCTIC_ESHAPE;
-  if (B <= 0 || H <= 0 || T <= 0 || T > kAttnMaxT || c <= 0 || (c != 10 * H && c != 8 * H)) return OCTIC_ESHAPE;
+  if (B <= 0 || H <= 0 || c <= 0 || (c != 10 * H && c != 8 * H) || attn_plan(OCTIC_BF16, T, 8 * (c / H), ld_qkv, ld_o, ld_g, &p))
+    return OCTIC_ESHAPE;
   if (((((uintptr_t)qkv) | ((uintptr_t)o) | ((uintptr_t)dout) | ((uintptr_t)dqkv)) & 15) || ((ld_qkv | ld_o | ld_g) & 7) ||
       ld_qkv < 24 * c || ld_g < 24 * c || ld_o < 8 * c)
     return OCTIC_EALIGN;
-  AttnBwdArgs a;
-  a.q = a.k = a.v = (const bf16*)qkv; a.sB = (int64_t)T * ld_qkv; a.sH = 0; a.sT = ld_qkv;
-  a.o = (const bf16*)o; a.dout = (const bf16*)dout; a.oB = (int64_t)T * ld_o; a.oH = 0; a.oT = ld_o;
-  a.lse = lse; a.delta = delta;
-  a.dq = a.dk = a.dv = (bf16*)dqkv; a.gB = (int64_t)T * ld_g; a.gH = 0; a.gT = ld_g;
-  a.H = H; a.T = T; a.hd = 8 * (c / H);
-  a.scale = scale;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  a.cv_in = 3 * c; a.cv_out = c; a.c = c;
-  a.sample_scale = sample_scale;
-  if (attn_stream_route(T)) return attn_stream_bwd_launch(a, B, phase, (hipStream_t)stream);
-  if (a.hd == 64) return attn_bwd_launch<4, 2>(a, B, phase, (hipStream_t)stream);
-  return attn_bwd_launch<5, 3>(a, B, phase, (hipStream_t)stream);
+  AttnBwdArgs a = attn_args<AttnBwdArgs>(qkv, qkv, qkv, o, H, T, 8 * (c / H), (int64_t)T * ld_qkv, 0, ld_qkv, (int64_t)T * ld_o, 0, ld_o,
+                                             scale, c, sample_scale);
+  attn_bwd_rest(a, dout, lse, delta, dqkv, dqkv, dqkv, (int64_t)T * ld_g, 0, ld_g, scale);
+  return attn_bwd_run(a, B, phase, p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -271,8 +271,6 @@ __device__ __forceinline__ bf16x8 trfrag_ones(const char* tile, const FragAddr& 
 // itself: order[0 .. n_kept) = the kept samples (scale != 0) in ascending order, order[B - 1 - j] = the j-th dropped one,
 // order[kSkipMaxB] = n_kept.  Wave 0 walks the samples 64 at a time (one ballot per word); returns n_kept to every wave after
 // one barrier.
-constexpr int kSkipMaxB = 512;                                    // launches with more samples run without skipping
-constexpr int kSkipLds = (kSkipMaxB + 8) * 2;
 __device__ __forceinline__ int skip_table(unsigned short* order, const float* scale, int B, int wid, int lane) {
   if (wid == 0) {
     int nk = 0, ndrop = 0;
@@ -806,61 +804,31 @@ __global__ __launch_bounds__((NT < 4 ? 4 : NT) * 64) void fwd_oss_kernel(AttnArg
   }
 }
 
-inline size_t fwd_oss_lds(int nt) { return (size_t)3 * nt * TILE_B + 128; }
-
-inline size_t fwd_os_lds(int nt) {
-  return (size_t)3 * nt * TILE_B + 2 * HD * 2 + 128 + (WAVES * 2048 + 1024) + (size_t)(WAVES * 2 * (DT * 32 + kPartPad) + 2 * WAVES * 2) * sizeof(float) + kSkipLds;
-}
-
-inline size_t fwd_lds(int nt) {
-  return (size_t)2 * nt * TILE_B + 2 * HD * 2 + (size_t)(WAVES * 2 * (DT * 32 + kPartPad) + 2 * WAVES * 2) * sizeof(float);
-}
-
-// shapes these kernels take: head_dim 80, at most 8 full tiles + 2 extra rows, 32-bit buffer offsets
-inline bool shape_ok(int T, int hd, int64_t sT, int64_t oT) {
-  const int nt = (T + 31) / 32, W = nt < 8 ? nt : 8;
-  return hd == HD && nt <= MAXNT && T - 32 * W <= 2 && (int64_t)T * sT * 2 < 0x7FFFFFF0ll && (int64_t)T * oT * 2 < 0x7FFFFFF0ll;
-}
-
-static int cu_count() {
-  return device_cus();
-}
-
 }  // namespace a80
 
-// routing override OCTIC_ROUTE_ATTN_ONLINE: 0 = one-shot softmax where it applies, 1 = online softmax everywhere
-// (+16: K / V descriptors with zero records, a timing probe of developer runs)
-
-int attn80_fwd_ok(const AttnArgs& a) { return a80::shape_ok(a.T, a.hd, a.sT, a.oT) ? 1 : 0; }
-
-int attn80_fwd_launch(const AttnArgs& a_, int64_t B, hipStream_t s) {
+// p.fwd: the one-shot softmax (nine tiles: fwd_os_kernel; every token inside one of <= 8 tiles: fwd_oss_kernel) or the online one
+int attn80_fwd_launch(const AttnArgs& a_, int64_t B, const AttnPlan& p, hipStream_t s) {
   using namespace a80;
   AttnArgs a = a_;
-  a.dbg = route(OCTIC_ROUTE_ATTN_ONLINE) >> 4;
-  const int nt = (a.T + 31) / 32, W = nt < 8 ? nt : 8;
-  const int units = (int)(B * a.H), cus = cu_count();
+  a.dbg = p.fwd_dbg;
+  const int nt = (a.T + 31) / 32;
+  const int units = (int)(B * a.H), cus = device_cus();
   static DeviceOnce once;
-  if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)fwd_os_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-  }
+  attn_lds_optin(once, fwd_kernel, fwd_os_kernel);
   const int grid = units < cus ? units : cus;
-  const bool one_shot = (route(OCTIC_ROUTE_ATTN_ONLINE) & 15) == 0;
-  if (one_shot && nt == MAXNT) {
+  if (p.fwd == OCTIC_ATTN_FWD_A80_ONLINE) fwd_kernel<<<grid, p.fwd_waves * 64, p.fwd_lds, s>>>(a, nt, units);
+  else if (nt == MAXNT) {
     if (B > kSkipMaxB) a.sample_scale = nullptr;                  // the order table holds 512 samples: larger launches do not skip
-    fwd_os_kernel<<<grid, 512, fwd_os_lds(nt), s>>>(a, units);
-  }
-  else if (one_shot && a.T <= 32 * nt && nt <= 8) {               // every token inside a tile: the T <= 256 one-shot kernels
+    fwd_os_kernel<<<grid, p.fwd_waves * 64, p.fwd_lds, s>>>(a, units);
+  } else {
+    const int wgs = cus * (8 / p.fwd_waves);                      // short sequences: two workgroups per CU (8 waves)
     switch (nt) {
-#define OSS(n) case n: { static DeviceOnce o##n; if (o##n.first()) { (void)hipFuncSetAttribute((const void*)fwd_oss_kernel<n>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); (void)hipGetLastError(); } \
-                 constexpr int wv = n < 4 ? 4 : n;                   /* waves per workgroup */ \
-                 const int wgs = cus * (8 / wv);                     /* short sequences: two workgroups per CU (8 waves) */ \
-                 fwd_oss_kernel<n><<<units < wgs ? units : wgs, wv * 64, fwd_oss_lds(n), s>>>(a, units); break; }
+#define OSS(n) case n: { static DeviceOnce o##n; attn_lds_optin(o##n, fwd_oss_kernel<n>); \
+                 fwd_oss_kernel<n><<<units < wgs ? units : wgs, p.fwd_waves * 64, p.fwd_lds, s>>>(a, units); break; }
       OSS(1) OSS(2) OSS(3) OSS(4) OSS(5) OSS(6) OSS(7) OSS(8)
 #undef OSS
     }
-  } else fwd_kernel<<<grid, W * 64, fwd_lds(nt), s>>>(a, nt, units);
+  }
   return launch_status();
 }
 

@@ -54,20 +54,6 @@ extern "C" void* octic_dbg_a80_bwd_trace(void) {
 namespace octic {
 namespace a80 {
 
-constexpr int BW_T = 257, BW_NT = 9;
-constexpr int BW_NSTG = 4;                        // ring stages: tile t is multiplied while t + 1, t + 2 have landed and t + 3 flies
-constexpr int BW_STG = 3 * TILE_B;                // one ring stage: Q | dO | O tile
-constexpr int BW_RING = BW_NSTG * BW_STG;
-constexpr int BW_KIMG = 8 * TILE_B;
-constexpr int BW_DST = 2048;                      // a wave's dS tile: [key 32][64 B]
-constexpr int BW_DS = 2 * WAVES * BW_DST;         // double-buffered (one barrier per tile)
-constexpr int BW_PQ = 2 * 2 * 4 * 64 * 16;        // f32 key quarters of dQ blocks 8 and 9, double-buffered
-constexpr int BW_STAT = 2 * 288 * 4;              // lse_s, del_s
-constexpr int BW_XK = 384;                        // K row 256 | V row 256 (160 B each)
-constexpr int BW_PX = 2 * 2 * 32 * 4;             // p and dS of key 256 for the queries of a tile, double-buffered
-constexpr int BW_ACC = 160 * 4;                   // dK[256] | dV[256] running sums
-constexpr int BW_LDS = BW_RING + BW_KIMG + BW_DS + BW_PQ + BW_STAT + BW_XK + BW_PX + BW_ACC;
-static_assert(BW_LDS <= 160 * 1024, "LDS budget");
 static_assert(8 * TILE_B <= BW_DS + BW_PQ, "the V image borrows the dS / quarter buffers during the prologue");
 
 __device__ __forceinline__ float bf_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
@@ -646,44 +632,24 @@ __global__ __launch_bounds__(64 * NKT) void bwd_small_kernel(AttnBwdArgs a) {
   }
 }
 
-}  // namespace a80
-
-// routing override OCTIC_ROUTE_ATTN_BWD_PAIR: 1 = the round-2 dq + dkv pair for every shape
-
-// shapes of the single-pass backward: head_dim 80; 257 tokens (8 key tiles + one extra row), 193 .. 256 tokens (7 - 8 key
-// tiles, every token inside one: DINOv2 ViT-H/16's 197) or <= 64 tokens (bwd_small_kernel: the 37-token local crops); 65 .. 192
-// tokens would leave most of the eight waves without a key tile (and those instantiations spill) and stay on the dq + dkv
-// pair; 32-bit offsets
-int attn80_bwd_ok(const AttnBwdArgs& a) {
-  using namespace a80;
-  return (!route(OCTIC_ROUTE_ATTN_BWD_PAIR) && a.hd == HD && (a.T == BW_T || (a.T > 192 && a.T <= 256) || a.T <= 64) &&
-          (int64_t)a.T * a.sT * 2 < 0x7FFFFFF0ll && (int64_t)a.T * a.oT * 2 < 0x7FFFFFF0ll &&
-          (int64_t)a.T * a.gT * 2 < 0x7FFFFFF0ll) ? 1 : 0;
-}
-
-namespace a80 {
+// p.bwd_waves: one or two waves for <= 64 tokens (bwd_small_kernel), eight otherwise
 template <bool SKIP>
-static int bwd_launch(const AttnBwdArgs& a, int64_t B, hipStream_t s) {
+static int bwd_launch(const AttnBwdArgs& a, int64_t B, const AttnPlan& p, hipStream_t s) {
   static DeviceOnce once;
-  if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)bwd_kernel<8, true, SKIP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)bwd_kernel<8, false, SKIP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)bwd_kernel<7, false, SKIP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-  }
-  const int grid = (int)(B * a.H);
-  if (a.T <= 32) { bwd_small_kernel<1, SKIP><<<grid, 64, 5 * TILE_B + 2 * 32 * 4, s>>>(a); return launch_status(); }
-  if (a.T <= 64) { bwd_small_kernel<2, SKIP><<<grid, 128, 10 * TILE_B + 2 * 64 * 4, s>>>(a); return launch_status(); }
-  if (a.T == BW_T) bwd_kernel<8, true, SKIP><<<grid, 512, BW_LDS, s>>>(a);
-  else if (a.T > 224) bwd_kernel<8, false, SKIP><<<grid, 512, BW_LDS, s>>>(a);
-  else bwd_kernel<7, false, SKIP><<<grid, 512, BW_LDS, s>>>(a);
+  attn_lds_optin(once, bwd_kernel<8, true, SKIP>, bwd_kernel<8, false, SKIP>, bwd_kernel<7, false, SKIP>);
+  const int grid = (int)(B * a.H), threads = p.bwd_waves * 64;
+  if (p.bwd_waves == 1) bwd_small_kernel<1, SKIP><<<grid, threads, p.bwd_lds, s>>>(a);
+  else if (p.bwd_waves == 2) bwd_small_kernel<2, SKIP><<<grid, threads, p.bwd_lds, s>>>(a);
+  else if (a.T == BW_T) bwd_kernel<8, true, SKIP><<<grid, threads, p.bwd_lds, s>>>(a);
+  else if (a.T > 224) bwd_kernel<8, false, SKIP><<<grid, threads, p.bwd_lds, s>>>(a);
+  else bwd_kernel<7, false, SKIP><<<grid, threads, p.bwd_lds, s>>>(a);
   return launch_status();
 }
 }  // namespace a80
 
-int attn80_bwd_launch(const AttnBwdArgs& a, int64_t B, hipStream_t s) {
+int attn80_bwd_launch(const AttnBwdArgs& a, int64_t B, const AttnPlan& p, hipStream_t s) {
   using namespace a80;
-  return a.sample_scale != nullptr ? bwd_launch<true>(a, B, s) : bwd_launch<false>(a, B, s);
+  return a.sample_scale != nullptr ? bwd_launch<true>(a, B, p, s) : bwd_launch<false>(a, B, p, s);
 }
 
 }  // namespace octic

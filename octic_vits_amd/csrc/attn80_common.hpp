@@ -264,5 +264,32 @@ __device__ __forceinline__ void store_rows16(bf16* row, const f32x16 (&acc)[DT],
   }
 }
 
+// ---- dynamic LDS of the launches (attn_plan, csrc/attention.hip, hands them to the launchers) ---------------------------
+constexpr int kSkipMaxB = 512;                    // stochastic-depth order table: launches with more samples run without skipping
+constexpr int kSkipLds = (kSkipMaxB + 8) * 2;
+inline size_t fwd_oss_lds(int nt) { return (size_t)3 * nt * TILE_B + 128; }
+inline size_t fwd_os_lds(int nt) {
+  return (size_t)3 * nt * TILE_B + 2 * HD * 2 + 128 + (WAVES * 2048 + 1024) + (size_t)(WAVES * 2 * (DT * 32 + kPartPad) + 2 * WAVES * 2) * sizeof(float) + kSkipLds;
+}
+inline size_t fwd_lds(int nt) {
+  return (size_t)2 * nt * TILE_B + 2 * HD * 2 + (size_t)(WAVES * 2 * (DT * 32 + kPartPad) + 2 * WAVES * 2) * sizeof(float);
+}
+// single-pass backward (csrc/attn80_bwd.hip)
+constexpr int BW_T = 257, BW_NT = 9;
+constexpr int BW_NSTG = 4;                        // ring stages: tile t is multiplied while t + 1, t + 2 have landed and t + 3 flies
+constexpr int BW_STG = 3 * TILE_B;                // one ring stage: Q | dO | O tile
+constexpr int BW_RING = BW_NSTG * BW_STG;
+constexpr int BW_KIMG = 8 * TILE_B;
+constexpr int BW_DST = 2048;                      // a wave's dS tile: [key 32][64 B]
+constexpr int BW_DS = 2 * WAVES * BW_DST;         // double-buffered (one barrier per tile)
+constexpr int BW_PQ = 2 * 2 * 4 * 64 * 16;        // f32 key quarters of dQ blocks 8 and 9, double-buffered
+constexpr int BW_STAT = 2 * 288 * 4;              // lse_s, del_s
+constexpr int BW_XK = 384;                        // K row 256 | V row 256 (160 B each)
+constexpr int BW_PX = 2 * 2 * 32 * 4;             // p and dS of key 256 for the queries of a tile, double-buffered
+constexpr int BW_ACC = 160 * 4;                   // dK[256] | dV[256] running sums
+constexpr int BW_LDS = BW_RING + BW_KIMG + BW_DS + BW_PQ + BW_STAT + BW_XK + BW_PX + BW_ACC;
+static_assert(BW_LDS <= 160 * 1024, "LDS budget");
+inline size_t bwd_small_lds(int nt) { return (size_t)nt * (5 * TILE_B + 2 * 32 * 4); }   // bwd_small_kernel: nt = 1, 2 tiles
+
 }  // namespace a80
 }  // namespace octic

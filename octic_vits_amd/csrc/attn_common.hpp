@@ -324,14 +324,70 @@ __device__ __forceinline__ void skip_unit(const float* scale, int B, int H, int 
   h = __builtin_amdgcn_readfirstlane(h);
 }
 
-// csrc/attn80.hip: persistent head_dim-80 kernels (all operands by LDS-DMA, one head ahead)
-int attn80_fwd_ok(const AttnArgs& a);
-int attn80_fwd_launch(const AttnArgs& a, int64_t B, hipStream_t s);
-// csrc/attn80_bwd.hip: single-pass backward (dq, dk, dv from ONE recomputation of P) for head_dim 80, T = 257
-int attn80_bwd_ok(const AttnBwdArgs& a);
-int attn80_bwd_launch(const AttnBwdArgs& a, int64_t B, hipStream_t s);
-// csrc/attn_stream.hip: K / V (Q / dO) streamed through LDS in blocks, any T (the entry points allow T <= 16384)
-int attn_stream_fwd_launch(const AttnArgs& a, int64_t B, hipStream_t s);
-int attn_stream_bwd_launch(const AttnBwdArgs& a, int64_t B, int phase, hipStream_t s);
+// ---- LDS row images: bytes per row, shared by the resident and the streaming kernels -------------------------------
+inline int attn_rsk(int hd) { return hd * 2 + 16; }                       // K image (odd # of 16-B slots)
+inline int attn_rsv(int dp) { int r = dp * 2; return ((r / 4) % 32 == 0) ? r + 64 : r; }   // V image, dp = DT * 32 columns
+// backward images, read both by rows (ds_read_b128) and transposed (ds_read_b64_tr_b16): rows are padded so the b128 reads
+// are conflict-free, the transposed reads then see at most 2-way conflicts.  The tr fragments reach DT * 32 columns, so
+// rows must hold that many (the pad columns meet zero accumulator columns / are discarded).
+inline int attn_rs(int hd) { return (hd + 31) / 32 * 32 * 2 + 16; }
+
+constexpr int kAttnMaxT = 16384;                   // longest sequence of the entry points
+constexpr int kAttnWaves = 8;                      // resident backward: eight waves own tiles 0-7 and share a ninth
+constexpr int kStreamWaves = 4;                    // csrc/attn_stream.hip: waves per workgroup
+constexpr int kStreamRows = kStreamWaves * 32;     // own rows per workgroup
+constexpr int kStreamBlk = 64;                     // streamed rows per LDS block
+constexpr int kStreamThreads = kStreamWaves * 64;
+
+// ---- which kernels an attention call runs -------------------------------------------------------------------------------
+// attn_plan (csrc/attention.hip) is the ONE place that decides; octic_attn_plan reports it, the entry points launch it.  The
+// launchers take every workgroup size and dynamic-LDS byte count from the plan: the number that decided is the number launched.
+struct AttnPlan {
+  int fwd, fwd_waves;          // OCTIC_ATTN_FWD_*
+  size_t fwd_lds;
+  int fwd_dbg;                 // developer probe of the head_dim-80 forward (OCTIC_ROUTE_ATTN_ONLINE >> 4)
+  int bwd, bwd_waves;          // OCTIC_ATTN_BWD_*: what a phase-3 call runs
+  size_t bwd_lds;              // SINGLE only
+  int pair, pair_waves;        // phases 1 and 2 (and phase 3 unless bwd is SINGLE): OCTIC_ATTN_BWD_PAIR | STREAM | F32
+  size_t dq_lds, dkv_lds;
+};
+// Pure host arithmetic, no HIP call.  ld_*: token strides in elements of q/k/v, o/dout, dq/dk/dv (0: hd).  OCTIC_ESHAPE for
+// the (T, hd) no kernel takes - the shape check of every attention entry point.
+int attn_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int64_t ld_grad, AttnPlan* plan);
+
+// KS = hd / 16 k-steps of the score product, DT = ceil(hd / 32) d-tiles of the output: f(KsDt<KS, DT>{})
+template <int KS_, int DT_>
+struct KsDt { static constexpr int KS = KS_, DT = DT_; };
+template <typename F>
+inline int attn_dispatch(int hd, F&& f) {
+  switch (hd / 16) {
+    case 1: return f(KsDt<1, 1>{});
+    case 2: return f(KsDt<2, 1>{});
+    case 3: return f(KsDt<3, 2>{});
+    case 4: return f(KsDt<4, 2>{});
+    case 5: return f(KsDt<5, 3>{});
+    case 6: return f(KsDt<6, 3>{});
+    case 7: return f(KsDt<7, 4>{});
+    default: return f(KsDt<8, 4>{});
+  }
+}
+
+// dynamic-LDS opt-in (up to the CU's 160 KiB) of a launcher's kernels, once per device
+template <typename... K>
+inline void attn_lds_optin(DeviceOnce& once, K... kernels) {
+  if (!once.first()) return;
+  ((void)hipFuncSetAttribute((const void*)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), ...);
+  (void)hipGetLastError();
+}
+
+// csrc/attn80.hip: persistent head_dim-80 forwards (all operands by LDS-DMA, one head ahead), one-shot or online softmax
+int attn80_fwd_launch(const AttnArgs& a, int64_t B, const AttnPlan& p, hipStream_t s);
+// csrc/attn80_bwd.hip: single-pass backward (dq, dk, dv from ONE recomputation of P) for head_dim 80
+int attn80_bwd_launch(const AttnBwdArgs& a, int64_t B, const AttnPlan& p, hipStream_t s);
+// csrc/attn_stream.hip: K / V (Q / dO) streamed through LDS in blocks, any T
+int attn_stream_fwd_launch(const AttnArgs& a, int64_t B, const AttnPlan& p, hipStream_t s);
+int attn_stream_bwd_launch(const AttnBwdArgs& a, int64_t B, int phase, const AttnPlan& p, hipStream_t s);
+// csrc/attn_f32.hip: dynamic LDS of its three kernels
+size_t attn_f32_lds(int hd);
 
 }  // namespace octic

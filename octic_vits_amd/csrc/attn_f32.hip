@@ -21,7 +21,7 @@
 //   * keys of the last block beyond T are masked to -inf (forward) / P = 0 (backward); rows beyond T are staged as zeros
 //     so that P = 0 never meets a non-finite operand; no address beyond row T - 1 of any operand is read;
 //   * every output element is written once by one lane, in a fixed order: no atomics, bitwise repeatable.
-#include "octic_common.hpp"
+#include "attn_common.hpp"
 
 namespace octic {
 
@@ -29,7 +29,6 @@ constexpr int kF32Waves = 4;                       // waves per workgroup
 constexpr int kF32Rows = kF32Waves * 32;           // own rows per workgroup
 constexpr int kF32Blk = 32;                        // streamed rows per LDS block
 constexpr int kF32Threads = kF32Waves * 64;
-constexpr int kF32MaxT = 16384;
 
 struct AttnF32Args {
   const float* q; const float* k; const float* v; int64_t sB, sH, sT;   // element (b,h,t,d) at base + b*sB + h*sH + t*sT + d
@@ -451,14 +450,14 @@ __global__ __launch_bounds__(kF32Threads) void attn_f32_dkv_kernel(AttnF32Args a
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------
-inline size_t f32_smem_bytes(int hd) { return 2 * (size_t)f32_buf_floats(hd + 4) * sizeof(float); }   // <= 66.5 KiB
+size_t attn_f32_lds(int hd) { return 2 * (size_t)f32_buf_floats(hd + 4) * sizeof(float); }   // <= 66.5 KiB
 
 // dynamic-LDS opt-in of a kernel on the current device (head_dim 128 needs 66.5 KiB); a failure is reported as the
 // positive hipError_t and tried again by the next call
 template <typename K>
 static int f32_lds_optin(K kernel, DeviceOnce& once) {
   if (!once.first()) return OCTIC_OK;
-  const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f32_smem_bytes(128));
+  const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_f32_lds(128));
   if (e == hipSuccess) return OCTIC_OK;
   (void)hipGetLastError();
   once.mask = 0;
@@ -466,26 +465,26 @@ static int f32_lds_optin(K kernel, DeviceOnce& once) {
 }
 
 template <int KC>
-static int f32_fwd(const AttnF32Args& a, int64_t B, hipStream_t s) {
+static int f32_fwd(const AttnF32Args& a, int64_t B, const AttnPlan& p, hipStream_t s) {
   const int nqt = (a.T + kF32Rows - 1) / kF32Rows;
   const int64_t grid = (int64_t)nqt * B * a.H;
   if (grid > 0x7FFFFFFF) return OCTIC_ESHAPE;
   static DeviceOnce once;
   if (const int rc = f32_lds_optin(attn_f32_fwd_kernel<KC>, once)) return rc;
-  attn_f32_fwd_kernel<KC><<<(int)grid, kF32Threads, f32_smem_bytes(a.hd), s>>>(a, nqt);
+  attn_f32_fwd_kernel<KC><<<(int)grid, kF32Threads, p.fwd_lds, s>>>(a, nqt);
   return launch_status();
 }
 
 template <int KC>
-static int f32_bwd(const AttnF32Args& a, int64_t B, int phase, hipStream_t s) {
+static int f32_bwd(const AttnF32Args& a, int64_t B, int phase, const AttnPlan& p, hipStream_t s) {
   const int ntile = (a.T + kF32Rows - 1) / kF32Rows;
   const int64_t grid = (int64_t)ntile * B * a.H;
   if (grid > 0x7FFFFFFF) return OCTIC_ESHAPE;
   static DeviceOnce once_dq, once_dkv;
   if (const int rc = f32_lds_optin(attn_f32_dq_kernel<KC>, once_dq)) return rc;
   if (const int rc = f32_lds_optin(attn_f32_dkv_kernel<KC>, once_dkv)) return rc;
-  if (phase & 1) attn_f32_dq_kernel<KC><<<(int)grid, kF32Threads, f32_smem_bytes(a.hd), s>>>(a, ntile);
-  if (phase & 2) attn_f32_dkv_kernel<KC><<<(int)grid, kF32Threads, f32_smem_bytes(a.hd), s>>>(a, ntile);
+  if (phase & 1) attn_f32_dq_kernel<KC><<<(int)grid, kF32Threads, p.dq_lds, s>>>(a, ntile);
+  if (phase & 2) attn_f32_dkv_kernel<KC><<<(int)grid, kF32Threads, p.dkv_lds, s>>>(a, ntile);
   return launch_status();
 }
 
@@ -502,7 +501,8 @@ extern "C" {
 int octic_attn_fwd_f32(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int H, int T, int hd,
                        int64_t sB, int64_t sH, int64_t sT, int64_t oB, int64_t oH, int64_t oT, float scale, void* stream) {
   if (!q || !k || !v || !o) return OCTIC_ENULL;
-  if (B <= 0 || H <= 0 || T <= 0 || T > kF32MaxT || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
+  AttnPlan p;
+  if (B <= 0 || H <= 0 || attn_plan(OCTIC_F32, T, hd, sT, oT, 0, &p)) return OCTIC_ESHAPE;
   if (!f32_scale_ok(scale)) return OCTIC_ESHAPE;
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o)) & 15) return OCTIC_EALIGN;
   if (!f32_rows_aligned(sB | sH | sT | oB | oH | oT)) return OCTIC_EALIGN;
@@ -514,16 +514,7 @@ int octic_attn_fwd_f32(const void* q, const void* k, const void* v, void* o, flo
   a.scale = scale;
   a.scale_log2 = scale * 1.4426950408889634f;
   hipStream_t s = (hipStream_t)stream;
-  switch (hd / 16) {
-    case 1: return f32_fwd<1>(a, B, s);
-    case 2: return f32_fwd<2>(a, B, s);
-    case 3: return f32_fwd<3>(a, B, s);
-    case 4: return f32_fwd<4>(a, B, s);
-    case 5: return f32_fwd<5>(a, B, s);
-    case 6: return f32_fwd<6>(a, B, s);
-    case 7: return f32_fwd<7>(a, B, s);
-    default: return f32_fwd<8>(a, B, s);
-  }
+  return attn_dispatch(hd, [&](auto c) { return f32_fwd<decltype(c)::KS>(a, B, p, s); });
 }
 
 int octic_attn_bwd_f32(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
@@ -532,7 +523,8 @@ int octic_attn_bwd_f32(const void* q, const void* k, const void* v, const void* 
                        int phase, void* stream) {
   if (!q || !k || !v || !o || !dout || !lse || !delta || !dq || !dk || !dv) return OCTIC_ENULL;
   if (phase < 1 || phase > 3) return OCTIC_ESHAPE;
-  if (B <= 0 || H <= 0 || T <= 0 || T > kF32MaxT || hd <= 0 || (hd % 16) || hd > 128) return OCTIC_ESHAPE;
+  AttnPlan p;
+  if (B <= 0 || H <= 0 || attn_plan(OCTIC_F32, T, hd, sT, oT, 0, &p)) return OCTIC_ESHAPE;
   if (!f32_scale_ok(scale)) return OCTIC_ESHAPE;
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o) | ((uintptr_t)dout) | ((uintptr_t)dq) |
        ((uintptr_t)dk) | ((uintptr_t)dv)) & 15)
@@ -547,16 +539,7 @@ int octic_attn_bwd_f32(const void* q, const void* k, const void* v, const void* 
   a.scale = scale;
   a.scale_log2 = scale * 1.4426950408889634f;
   hipStream_t s = (hipStream_t)stream;
-  switch (hd / 16) {
-    case 1: return f32_bwd<1>(a, B, phase, s);
-    case 2: return f32_bwd<2>(a, B, phase, s);
-    case 3: return f32_bwd<3>(a, B, phase, s);
-    case 4: return f32_bwd<4>(a, B, phase, s);
-    case 5: return f32_bwd<5>(a, B, phase, s);
-    case 6: return f32_bwd<6>(a, B, phase, s);
-    case 7: return f32_bwd<7>(a, B, phase, s);
-    default: return f32_bwd<8>(a, B, phase, s);
-  }
+  return attn_dispatch(hd, [&](auto c) { return f32_bwd<decltype(c)::KS>(a, B, phase, p, s); });
 }
 
 }  // extern "C"

@@ -17,10 +17,7 @@
 
 namespace octic {
 
-constexpr int kStreamWaves = 4;                    // waves per workgroup
-constexpr int kStreamRows = kStreamWaves * 32;     // own rows per workgroup
-constexpr int kStreamBlk = 64;                     // streamed rows per LDS block
-constexpr int kStreamThreads = kStreamWaves * 64;
+// (kStreamWaves = 4 waves per workgroup, kStreamRows = 128 own rows, kStreamBlk = 64 streamed rows per LDS block: attn_common.hpp)
 
 // One block of rows of two tensors in flight through registers: thread (row t0 + it * tstep, 16-byte chunk c).
 template <int KS>
@@ -371,70 +368,32 @@ __global__ __launch_bounds__(kStreamThreads) void attn_bwd_dkv_stream_kernel(Att
   }
 }
 
-// ---- launchers -------------------------------------------------------------------------------------------------
-inline int stream_rsk(int hd) { return hd * 2 + 16; }                                       // as attn_rsk
-inline int stream_rsv(int dp) { int r = dp * 2; return ((r / 4) % 32 == 0) ? r + 64 : r; }  // as attn_rsv
-inline int stream_rs(int hd, int DT) { return (DT * 32 > hd ? DT * 32 : hd) * 2 + 16; }     // row + transposed reads
-
-template <int KS, int DT>
-static int fwd_stream(const AttnArgs& a, int64_t B, hipStream_t s) {
-  const int rsk = stream_rsk(a.hd), rsv = stream_rsv(DT * 32);
+// ---- launchers: the dynamic LDS comes with the plan (attn_plan, csrc/attention.hip) ------------------------------------
+int attn_stream_fwd_launch(const AttnArgs& a, int64_t B, const AttnPlan& p, hipStream_t s) {
   const int nqt = (a.T + kStreamRows - 1) / kStreamRows;
   const int64_t grid = (int64_t)nqt * B * a.H;
   if (grid > 0x7FFFFFFF) return OCTIC_ESHAPE;
-  const size_t smem = 2 * (size_t)kStreamBlk * (rsk + rsv);         // <= 74 KiB (head_dim 128)
-  static DeviceOnce once;
-  if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_stream_kernel<KS, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-  }
-  attn_fwd_stream_kernel<KS, DT><<<(int)grid, kStreamThreads, smem, s>>>(a, rsk, rsv, nqt);
-  return launch_status();
+  return attn_dispatch(a.hd, [&](auto c) {
+    constexpr int KS = decltype(c)::KS, DT = decltype(c)::DT;
+    static DeviceOnce once;
+    attn_lds_optin(once, attn_fwd_stream_kernel<KS, DT>);
+    attn_fwd_stream_kernel<KS, DT><<<(int)grid, kStreamThreads, p.fwd_lds, s>>>(a, attn_rsk(a.hd), attn_rsv(DT * 32), nqt);
+    return launch_status();
+  });
 }
 
-template <int KS, int DT>
-static int bwd_stream(const AttnBwdArgs& a, int64_t B, int phase, hipStream_t s) {
-  const int rs = stream_rs(a.hd, DT);
-  const int ntile = (a.T + kStreamRows - 1) / kStreamRows;
+int attn_stream_bwd_launch(const AttnBwdArgs& a, int64_t B, int phase, const AttnPlan& p, hipStream_t s) {
+  const int rs = attn_rs(a.hd), ntile = (a.T + kStreamRows - 1) / kStreamRows;
   const int64_t grid = (int64_t)ntile * B * a.H;
   if (grid > 0x7FFFFFFF) return OCTIC_ESHAPE;
-  const size_t smem_dq = 4 * (size_t)kStreamBlk * rs;
-  const size_t smem_kv = smem_dq + 4 * kStreamBlk * sizeof(float);   // <= 69 KiB (head_dim 128)
-  static DeviceOnce once;
-  if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_stream_kernel<KS, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_stream_kernel<KS, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-  }
-  if (phase & 1) attn_bwd_dq_stream_kernel<KS, DT><<<(int)grid, kStreamThreads, smem_dq, s>>>(a, rs, ntile);
-  if (phase & 2) attn_bwd_dkv_stream_kernel<KS, DT><<<(int)grid, kStreamThreads, smem_kv, s>>>(a, rs, ntile);
-  return launch_status();
-}
-
-int attn_stream_fwd_launch(const AttnArgs& a, int64_t B, hipStream_t s) {
-  switch (a.hd / 16) {
-    case 1: return fwd_stream<1, 1>(a, B, s);
-    case 2: return fwd_stream<2, 1>(a, B, s);
-    case 3: return fwd_stream<3, 2>(a, B, s);
-    case 4: return fwd_stream<4, 2>(a, B, s);
-    case 5: return fwd_stream<5, 3>(a, B, s);
-    case 6: return fwd_stream<6, 3>(a, B, s);
-    case 7: return fwd_stream<7, 4>(a, B, s);
-    default: return fwd_stream<8, 4>(a, B, s);
-  }
-}
-
-int attn_stream_bwd_launch(const AttnBwdArgs& a, int64_t B, int phase, hipStream_t s) {
-  switch (a.hd / 16) {
-    case 1: return bwd_stream<1, 1>(a, B, phase, s);
-    case 2: return bwd_stream<2, 1>(a, B, phase, s);
-    case 3: return bwd_stream<3, 2>(a, B, phase, s);
-    case 4: return bwd_stream<4, 2>(a, B, phase, s);
-    case 5: return bwd_stream<5, 3>(a, B, phase, s);
-    case 6: return bwd_stream<6, 3>(a, B, phase, s);
-    case 7: return bwd_stream<7, 4>(a, B, phase, s);
-    default: return bwd_stream<8, 4>(a, B, phase, s);
-  }
+  return attn_dispatch(a.hd, [&](auto c) {
+    constexpr int KS = decltype(c)::KS, DT = decltype(c)::DT;
+    static DeviceOnce once;
+    attn_lds_optin(once, attn_bwd_dq_stream_kernel<KS, DT>, attn_bwd_dkv_stream_kernel<KS, DT>);
+    if (phase & 1) attn_bwd_dq_stream_kernel<KS, DT><<<(int)grid, kStreamThreads, p.dq_lds, s>>>(a, rs, ntile);
+    if (phase & 2) attn_bwd_dkv_stream_kernel<KS, DT><<<(int)grid, kStreamThreads, p.dkv_lds, s>>>(a, rs, ntile);
+    return launch_status();
+  });
 }
 
 }  // namespace octic

@@ -544,7 +544,7 @@ def attn_fwd(q, k, v, scale, out=None, sample_scale=None):
         check(lib().octic_attn_fwd_skip(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, T, hd, st[0], st[1], st[2],
                                         o.stride(0), o.stride(1), o.stride(2), float(scale), _p(ss), _stream(q)))
     # (bytes and FLOP stay the full batch's with a sample_scale: the host does not know the kept count without a sync)
-    KERNEL_TIMER.stop(t, "attn_f32_fwd_kernel" if f32 else _attn_fwd_name(T, hd), 4 * q.numel() * q.element_size(),
+    KERNEL_TIMER.stop(t, _attn_fwd_name(T, hd, dt_code(q.dtype), (st[2], o.stride(2), 0)), 4 * q.numel() * q.element_size(),
                       4.0 * B * H * T * T * hd)
     return o, lse
 
@@ -568,38 +568,35 @@ def attn_f32_supported(T, hd, dtype):
 
 
 def attn_streams(T, hd, backward=False):
-    """True where the entry points run the streaming kernels (csrc/attn_stream.hip: K / V through LDS in blocks):
-    T > 320, a head whose images do not fit in LDS at once (attn_fwd_launch: K and V; attn_bwd_launch: two row images and
-    the delta partials or the statistics - more per row, so the backward streams from fewer tokens on: head_dim 112 from
-    257, the forward from 289), or every shape under ROUTE_ATTN_STREAM = 1."""
-    if T > 320 or _lib.ROUTES.get(_lib.ROUTE_ATTN_STREAM, 0) == 1:
-        return True
-    tp = (T + 31) // 32 * 32
-    cols = (hd + 31) // 32 * 32
-    if backward:
-        return 2 * tp * (cols * 2 + 16) + max(tp * (hd // 8) * 4, 2 * tp * 4) > 160 * 1024
-    return tp * ((hd * 2 + 16) + (cols * 2 + (64 if cols % 64 == 0 else 0))) > 160 * 1024
+    """True where the entry points run the streaming kernels (csrc/attn_stream.hip: K / V through LDS in blocks): what
+    octic_attn_plan says for contiguous bf16 heads under the current route overrides."""
+    plan = _lib.attn_plan(T, hd)
+    return plan[2] == _lib.ATTN_BWD_STREAM if backward else plan[0] == _lib.ATTN_FWD_STREAM
 
 
-def _attn_fwd_name(T, hd):
-    return "attn_fwd_stream_kernel" if attn_streams(T, hd) else "attn_fwd_kernel"
+_ATTN_FWD_NAMES = {_lib.ATTN_FWD_STREAM: "attn_fwd_stream_kernel", _lib.ATTN_FWD_F32: "attn_f32_fwd_kernel"}
 
 
-# Single-pass attention backward (csrc/attn80_bwd.hip: P and dS computed once, 10 T^2 hd FLOP) for head_dim 80, T = 257;
+def _attn_fwd_name(T, hd, dtype=_lib.BF16, ld=(0, 0, 0)):
+    """Timer name of the forward launch octic_attn_plan names; ld = token strides of q/k/v, o, gradients (0: hd)."""
+    return _ATTN_FWD_NAMES.get(_lib.attn_plan(T, hd, dtype, *ld)[0], "attn_fwd_kernel")
+
+
+# Single-pass attention backward (csrc/attn80_bwd.hip: P and dS computed once, 10 T^2 hd FLOP) where octic_attn_plan has it;
 # False = the dq + dkv pair (14 T^2 hd) for every shape (bench --no-fused-attn-bwd)
 ATTN_BWD_FUSED = True
 
 
-def _attn_bwd_phases(T, hd):
-    """(phase, timer name, algorithmic bytes per element of q, flops per B H T^2 hd) of the backward launches."""
-    if attn_streams(T, hd, backward=True):                # phase 1: dq (3 products), phase 2: dk, dv (4 products)
-        return ((1, "attn_bwd_dq_stream_kernel", 6, 6.0), (2, "attn_bwd_dkv_stream_kernel", 6, 8.0))
-    if ATTN_BWD_FUSED and hd == 80 and (T == 257 or 192 < T <= 256 or T <= 64):    # csrc/attn80_bwd.hip: attn80_bwd_ok
+def _attn_bwd_phases(T, hd, dtype=_lib.BF16, ld=(0, 0, 0)):
+    """(phase, timer name, algorithmic bytes per element of q, flops per B H T^2 hd) of the backward launches: one phase-3
+    call exactly where ATTN_BWD_FUSED is on and octic_attn_plan says SINGLE, else phase 1 (dq: 3 products) and phase 2
+    (dk, dv: 4 products), named after the plan."""
+    bwd = _lib.attn_plan(T, hd, dtype, *ld)[2]
+    if ATTN_BWD_FUSED and bwd == _lib.ATTN_BWD_SINGLE:
         return ((3, "attn_bwd_kernel", 8, 10.0),)         # reads q k v o dO, writes dq dk dv
-    return ((1, "attn_bwd_dq_kernel", 6, 6.0), (2, "attn_bwd_dkv_kernel", 6, 8.0))
-
-
-_ATTN_F32_BWD_PHASES = ((1, "attn_f32_dq_kernel", 6, 6.0), (2, "attn_f32_dkv_kernel", 6, 8.0))
+    pre = "attn_f32" if bwd == _lib.ATTN_BWD_F32 else "attn_bwd"
+    suf = "_stream_kernel" if bwd == _lib.ATTN_BWD_STREAM else "_kernel"
+    return ((1, pre + "_dq" + suf, 6, 6.0), (2, pre + "_dkv" + suf, 6, 8.0))
 
 
 def attn_bwd(q, k, v, o, dout, lse, scale, dq, dk, dv, sample_scale=None):
@@ -611,7 +608,7 @@ def attn_bwd(q, k, v, o, dout, lse, scale, dq, dk, dv, sample_scale=None):
         raise ValueError("attn_bwd: stride sets differ")
     delta = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
     f32 = q.dtype == torch.float32
-    phases = _ATTN_F32_BWD_PHASES if f32 else _attn_bwd_phases(T, hd)
+    phases = _attn_bwd_phases(T, hd, dt_code(q.dtype), (st[2], so[2], sg[2]))
     ss = None if f32 else _sample_scale(sample_scale, B, q)
     for phase, name, nbytes, flops in phases:
         t = KERNEL_TIMER.start()
@@ -638,7 +635,8 @@ def attn_fwd_packed(qkv, H, c, scale, out=None, sample_scale=None):
     t = KERNEL_TIMER.start()
     check(lib().octic_attn_fwd_packed_skip(_p(qkv), _p(o), _p(lse), B, H, T, c, qkv.stride(1), o.stride(1), float(scale),
                                            _p(_sample_scale(sample_scale, B, qkv)), _stream(qkv)))
-    KERNEL_TIMER.stop(t, _attn_fwd_name(T, 8 * (c // H)), 4 * B * T * 8 * c * 2, 4.0 * B * T * T * 8 * c)
+    KERNEL_TIMER.stop(t, _attn_fwd_name(T, 8 * (c // H), ld=(qkv.stride(1), o.stride(1), 0)), 4 * B * T * 8 * c * 2,
+                      4.0 * B * T * T * 8 * c)
     return o, lse
 
 
@@ -648,7 +646,7 @@ def attn_bwd_packed(qkv, o, dout, lse, H, c, scale, out=None, sample_scale=None)
     dqkv = out if out is not None else torch.empty_like(qkv)
     delta = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
     ss = _sample_scale(sample_scale, B, qkv)
-    for phase, name, nbytes, flops in _attn_bwd_phases(T, 8 * (c // H)):
+    for phase, name, nbytes, flops in _attn_bwd_phases(T, 8 * (c // H), ld=(qkv.stride(1), o.stride(1), dqkv.stride(1))):
         t = KERNEL_TIMER.start()
         check(lib().octic_attn_bwd_packed_skip(_p(qkv), _p(o), _p(dout), _p(lse), _p(delta), _p(dqkv), B, H, T, c,
                                                qkv.stride(1), o.stride(1), dqkv.stride(1), float(scale), phase, _p(ss),

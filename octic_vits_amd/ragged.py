@@ -179,10 +179,7 @@ class AttnQKVRaggedFn(torch.autograd.Function):
             q5 = qv.view(B, T, 3, H, hd)
             q, k, v = (q5[:, :, i].permute(0, 2, 1, 3) for i in range(3))
             o4 = ov.view(B, T, H, hd).permute(0, 2, 1, 3)
-            lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
-            st = q.stride()
-            ops.check(ops.lib().octic_attn_fwd(ops._p(q), ops._p(k), ops._p(v), ops._p(o4), ops._p(lse), B, H, T, hd, st[0], st[1],
-                                               st[2], o4.stride(0), o4.stride(1), o4.stride(2), float(scale), ops._stream(qkv)))
+            _, lse = ops.attn_fwd(q, k, v, scale, out=o4)
             lses.append(lse)
         ctx.save_for_backward(qkv, o, *lses)
         ctx.meta = (rag, H, hd, scale)

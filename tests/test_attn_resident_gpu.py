@@ -3,29 +3,13 @@ at every head_dim the entry points accept and at the token counts where the laun
 softmax attention on the same bf16-rounded inputs, with NaN guard rows behind every input and sentinel rows behind every
 output.
 
-Which kernel a (T, hd) runs (nt = ceil(T / 32) tiles; _fwd_kernel / _bwd_kernel below mirror attn_fwd_launch /
-attn_bwd_launch, and test_sweep_reaches_every_kernel_a_resident_shape_can_reach holds the sweep to the mirror):
-
-  forward             hd 16 32 48 64   hd 80              hd 96        hd 112               hd 128
-    persist           T <= 258         (LEGACY) T <= 257  T <= 256     T <= 27 min(nt, 8)   -
-    attn80            -                T <= 258           -            -                    -
-    fwd512            -                -                  -            other T <= 256       T <= 256
-    fwd640,  9 waves  259 .. 288       259 .. 288         257 .. 288   257 .. 288           -
-    fwd640, 10 waves  289 .. 320       289 .. 320         289 .. 320   -                    -
-    stream            -                -                  -            289 .. 320           257 .. 320
-  backward            hd 16 32 48 64   hd 80              hd 96        hd 112               hd 128
-    attn80_bwd        -                <= 64, 193 .. 257  -            -                    -
-    pair512           T <= 256         65 .. 192 (*)      T <= 256     T <= 256             T <= 256
-    pair512 + tile 9  257 .. 288       258 .. 288         257 .. 288   -                    -
-    pair640           289 .. 320       289 .. 320         289 .. 320   -                    -
-    stream            -                -                  -            257 .. 320           257 .. 320
-  (*) and every T <= 257 under ROUTE_ATTN_LEGACY / ROUTE_ATTN_BWD_PAIR or ops.ATTN_BWD_FUSED = False.
-  persist: attn_fwd_persist_kernel (at hd 112 its V rows fit the registers for T <= 27 per wave: 1, 33, 65 and 129 of the
-  sweep; at hd 128 its K image is too large for the DMA schedule).  fwd512 / fwd640: attn_fwd_kernel<KS, DT, 512 | 640>, one
-  wave per query tile; the 512 variant has no shape for hd <= 96 (every T <= 256 there fits the persistent kernel) and the
-  640 variant none at hd 128 (K and V of nine tiles do not fit in LDS: streaming).  pair: attn_bwd_dq_kernel +
-  attn_bwd_dkv_kernel; "tile 9": eight waves share the ninth tile (store_partial / combine_store) with T - 256 = 1 .. 32
-  real rows.  stream: csrc/attn_stream.hip, where the head's images exceed 160 KiB.
+Which kernel a (T, hd) runs is written out in tests/test_attn_plan_host.py (FWD / BWD and the knob rows: the table that
+octic_attn_plan, the library's one routing function, is held to on the host); the ids of the sweep below name it, and
+test_sweep_reaches_every_kernel_a_resident_shape_can_reach holds the sweep to the table and the table to the library.
+Names used in the ids: persist = attn_fwd_persist_kernel; attn80 = csrc/attn80.hip; fwd512 / fwd640w<waves> =
+attn_fwd_kernel<KS, DT, 512 | 640>, one wave per query tile; attn80_bwd = the single-pass backward; pair512 / pair640 =
+attn_bwd_dq_kernel + attn_bwd_dkv_kernel; "tile9": eight waves share the ninth tile (store_partial / combine_store) with
+T - 256 = 1 .. 32 real rows; stream = csrc/attn_stream.hip, where the head's images exceed 160 KiB.
 
 Bounds (the project's, test_attention_gpu.py): o max-abs <= 2e-2 max(1, max|ref|); lse <= 2e-3; gradients max-abs <= 3e-2
 max(1, max|ref|); every tensor ||got - ref|| < 1.2e-2 max(||ref||, 1e-3) (the absolute floor is for dq / dk at T = 1, which
@@ -48,6 +32,8 @@ import sys
 import pytest
 import torch
 
+from test_attn_plan_host import PAIR, SINGLE, expected, labels       # the literal table: imports without the built library
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -55,63 +41,25 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 HDS = (16, 32, 48, 64, 80, 96, 112, 128)
 TS = (1, 31, 32, 33, 64, 65, 96, 129, 192, 193, 256, 257, 258, 259, 261, 288, 289, 319, 320)
 SENTINEL = -24576.0                      # exact in bf16; no attention output of these inputs comes near it
-_LDS, _PART_PAD = 160 * 1024, 4
 
 
-# ---- the launch code's choice, for the test ids and the coverage check ------------------------------------------
-
-def _rsv(dp):
-    r = dp * 2
-    return r + 64 if (r // 4) % 32 == 0 else r
-
-
-def _fwd_kernel(T, hd, legacy=False):
-    """attn_fwd_launch (csrc/attention.hip) on contiguous rows."""
-    KS, DT, nt = hd // 16, (hd + 31) // 32, (T + 31) // 32
-    W = min(nt, 8)
-    nrows = T - 32 * W
-    if hd == 80 and not legacy and nt <= 9 and nrows <= 2:
-        return "attn80"
-    rsk, rsv = hd * 2 + 16, _rsv(DT * 32)
-    kimg = (nt * 32 * rsk + 1023) & ~1023
-    need = 2 * kimg + nt * 32 * rsv + (W * nrows * (DT * 32 + _PART_PAD + 2) * 4 if nrows > 0 else 0)
-    if nt <= 9 and nrows <= 2 and need <= _LDS and kimg // 1024 <= 8 * W and (T * 2 * KS + W * 64 - 1) // (W * 64) <= 6:
-        return "persist"
-    if nt * 32 * (rsk + rsv) > _LDS:
-        return "stream"
-    return "fwd512" if nt <= 8 else "fwd640w%d" % nt
-
-
-def _bwd_kernel(T, hd, single_pass=True):
-    """attn_bwd_launch (csrc/attention.hip) / attn80_bwd_ok (csrc/attn80_bwd.hip)."""
-    DT, nt = (hd + 31) // 32, (T + 31) // 32
-    if single_pass and hd == 80 and (T == 257 or 192 < T <= 256 or T <= 64):
-        return "attn80_bwd"
-    W = 8 if nt == 9 else nt
-    rs = max(DT * 32, hd) * 2 + 16
-    img = 2 * nt * 32 * rs
-    dq, kv = img + nt * 32 * (hd // 8) * 4, img + 2 * nt * 32 * 4
-    if nt != W:
-        comb = W * 32 * (DT * 32 + _PART_PAD) * 4
-        dq, kv = max(dq, comb), max(kv, comb)
-    if dq > _LDS or kv > _LDS:
-        return "stream"
-    return "pair512" if nt <= 8 else "pair512tile9" if nt == 9 else "pair640"
-
+# ---- the routing table: test ids and the coverage check ----------------------------------------------------------------
 
 def test_sweep_reaches_every_kernel_a_resident_shape_can_reach():
-    """TS holds, for every head_dim, a token count for each kernel that some T <= 320 runs at that head_dim."""
-    from octic_vits_amd import ops
+    """TS holds, for every head_dim, a token count for each kernel that some T <= 320 runs at that head_dim - by the table,
+    and the library plans every shape of the sweep as the table says."""
+    from octic_vits_amd import _lib, ops
     for hd in HDS:
-        for kern in (_fwd_kernel, _bwd_kernel):
-            every = [kern(T, hd) for T in range(1, 321)]
-            assert {kern(T, hd) for T in TS} == set(every), (hd, kern.__name__)
-        for T in TS:                                                # the Python side's launch names and phase plan agree
-            assert ops.attn_streams(T, hd) == (_fwd_kernel(T, hd) == "stream"), (T, hd)
-            assert ops.attn_streams(T, hd, backward=True) == (_bwd_kernel(T, hd) == "stream"), (T, hd)
-            assert (ops._attn_bwd_phases(T, hd)[0][0] == 3) == (_bwd_kernel(T, hd) == "attn80_bwd"), (T, hd)
-    assert [_fwd_kernel(T, 80, legacy=True) for T in (37, 197, 257, 258)] == ["persist"] * 3 + ["fwd640w9"]
-    assert {_bwd_kernel(T, 80, single_pass=False) for T in (37, 197, 257, 258)} == {"pair512", "pair512tile9"}
+        for side in (0, 1):
+            every = {labels(T, hd)[side] for T in range(1, 321)}
+            assert {labels(T, hd)[side] for T in TS} == every, (hd, side)
+        for T in TS:                                                # the library, and the Python side's launch names and phase plan
+            assert _lib.attn_plan(T, hd) == expected(T, hd), (T, hd)
+            assert ops.attn_streams(T, hd) == (labels(T, hd)[0] == "stream"), (T, hd)
+            assert ops.attn_streams(T, hd, backward=True) == (labels(T, hd)[1] == "stream"), (T, hd)
+            assert (ops._attn_bwd_phases(T, hd)[0][0] == 3) == (labels(T, hd)[1] == "attn80_bwd"), (T, hd)
+    assert [labels(T, 80, "LEGACY")[0] for T in (37, 197, 257, 258)] == ["persist"] * 3 + ["fwd640w9"]
+    assert {labels(T, 80, "BWD_PAIR")[1] for T in (37, 197, 257, 258)} == {"pair512", "pair512tile9"}
 
 
 # ---- references -----------------------------------------------------------------------------------------------
@@ -269,7 +217,7 @@ def _bwd_fused(value):
 
 # ---- 1 + 2: every head_dim x every token edge, behind guard rows ------------------------------------------------
 
-@pytest.mark.parametrize("T,hd", [pytest.param(T, hd, id=f"hd{hd}-T{T}-{_fwd_kernel(T, hd)}-{_bwd_kernel(T, hd)}")
+@pytest.mark.parametrize("T,hd", [pytest.param(T, hd, id="hd%d-T%d-%s-%s" % ((hd, T) + labels(T, hd)))
                                   for hd in HDS for T in TS])
 def test_sweep_matches_fp64_behind_guard_rows(T, hd):
     """o, lse, dq, dk, dv of whatever kernel the routing picks (named in the test id) against float64, whole and on the
@@ -366,7 +314,7 @@ def test_persistent_forward_at_head_dim_64_walks_over_several_heads(T):
     while it computes the current one; at T = 257 / 258 with one / two rows in the shared ninth tile."""
     from octic_vits_amd import ops
     B, H, hd = 17, 16, 64
-    assert _fwd_kernel(T, hd) == "persist"
+    assert labels(T, hd)[0] == "persist"
     (q, k, v, _), ref = _case(B, H, T, hd, T, grads=False)
     o, lse = ops.attn_fwd(q.cuda(), k.cuda(), v.cuda(), hd ** -0.5)
     _check({"o": o, "lse": lse}, ref, T, names=("o", "lse"))
@@ -411,20 +359,32 @@ def test_route_attn_online_at_head_dim_80(T):
 
 @pytest.mark.parametrize("T", KNOB_TS)
 def test_route_attn_bwd_pair_at_head_dim_80(T):
-    """ROUTE_ATTN_BWD_PAIR = 1 under ops.ATTN_BWD_FUSED = True: Python sends phase 3 wherever the single-pass kernel
-    would run and the library runs dq then dkv in that one call - the same two kernels as ATTN_BWD_FUSED = False with
-    the knob at 0 runs in two calls, so bit-identical to it."""
+    """ROUTE_ATTN_BWD_PAIR = 1: a phase-3 call to the C entry point (ops plans no such call under the knob: it names the dq
+    and dkv kernels and sends two) runs dq then dkv in that one call - the same two kernels as the two calls of ops.attn_bwd,
+    so bit-identical to them."""
     from octic_vits_amd import _lib, ops
     inputs, ref = _knob_case(T)
+    scale = 80 ** -0.5
     with _bwd_fused(True), _route(_lib.ROUTE_ATTN_BWD_PAIR, 1):
-        assert ops._attn_bwd_phases(T, 80)[0][0] == (1 if T == 258 else 3)
-        got, _ = _launch(inputs)
+        for t in KNOB_TS:
+            assert [p[:2] for p in ops._attn_bwd_phases(t, 80)] == [(1, "attn_bwd_dq_kernel"), (2, "attn_bwd_dkv_kernel")]
+        two, _ = _launch(inputs)                                     # phase 1, then phase 2
+        q, k, v, do = (t.cuda() for t in inputs)
+        dq, dk, dv = (torch.full_like(q, SENTINEL) for _ in range(3))
+        delta = torch.empty(q.shape[:3], dtype=torch.float32, device="cuda")
+        st = q.stride()
+        _lib.check(_lib.lib().octic_attn_bwd(*(ops._p(t) for t in (q, k, v, two["o"], do, two["lse"], delta, dq, dk, dv)),
+                                             *q.shape, *(st[:3] * 3), scale, 3, ops._stream(q)))
+        torch.cuda.synchronize()
     assert _lib.route_override(_lib.ROUTE_ATTN_BWD_PAIR, 0) == 0
-    with _bwd_fused(False):
-        two, _ = _launch(inputs)
+    got = dict(two, dq=dq, dk=dk, dv=dv)
     _check(got, ref, T, inputs)
-    for n in ("o", "lse", "dq", "dk", "dv"):
+    for n in ("dq", "dk", "dv"):
         assert torch.equal(got[n], two[n]), f"{n}: one call with phase 3 differs from the two calls"
+    with _bwd_fused(False):                                         # and the two calls of ATTN_BWD_FUSED = False, knob at 0
+        unfused, _ = _launch(inputs)
+    for n in ("o", "lse", "dq", "dk", "dv"):
+        assert torch.equal(unfused[n], two[n]), f"{n}: the pair under the knob differs from the pair without it"
 
 
 # ---- 7: repeatability -----------------------------------------------------------------------------------------------
@@ -439,3 +399,37 @@ def test_two_launches_are_bitwise_equal(T, hd):
     two, _ = _launch(inputs)
     for n in ("o", "lse", "dq", "dk", "dv"):
         assert torch.equal(one[n], two[n]), n
+
+
+# ---- 8: KERNEL_TIMER books what the plan says ----------------------------------------------------------------------------
+
+_FWD_TIMER = {"stream": "attn_fwd_stream_kernel"}
+_BWD_TIMER = {"attn80_bwd": ["attn_bwd_kernel"], "stream": ["attn_bwd_dq_stream_kernel", "attn_bwd_dkv_stream_kernel"]}
+
+
+@pytest.mark.parametrize("T,hd,knob", [(37, 80, None), (257, 80, None), (258, 80, None), (289, 112, None), (257, 128, None),
+                                       (257, 80, "STREAM"), (257, 80, "LEGACY"), (257, 80, "BWD_PAIR"), (257, 80, "ONLINE")])
+def test_kernel_timer_names_what_the_plan_says(T, hd, knob):
+    """The launches ops.attn_fwd / ops.attn_bwd book in KERNEL_TIMER, and their FLOP, are those of the library's plan - under
+    the knobs too (ROUTE_ATTN_LEGACY / ROUTE_ATTN_BWD_PAIR: two calls booked as dq and dkv at 14 T^2 hd, where a single
+    phase-3 call used to be booked as the single-pass kernel at 10)."""
+    from octic_vits_amd import _lib, ops
+    f, b = labels(T, hd, knob)
+    want = [_FWD_TIMER.get(f, "attn_fwd_kernel")] + _BWD_TIMER.get(b, ["attn_bwd_dq_kernel", "attn_bwd_dkv_kernel"])
+    inputs = _inputs(2, 2, T, hd, T + hd)
+    try:
+        if knob:
+            _lib.route_override(getattr(_lib, "ROUTE_ATTN_" + knob), 1)
+        plan = _lib.attn_plan(T, hd)
+        ops.KERNEL_TIMER.enable()
+        _launch(inputs)
+        records = list(ops.KERNEL_TIMER.records)
+    finally:
+        ops.KERNEL_TIMER.disable()
+        if knob:
+            _lib.route_override(getattr(_lib, "ROUTE_ATTN_" + knob), 0)
+    assert plan == expected(T, hd, knob)
+    assert [r[0] for r in records] == want
+    unit = 2 * 2 * T * T * hd
+    assert [r[4] / unit for r in records] == [4.0] + ([10.0] if plan[2] == SINGLE else [6.0, 8.0])
+    assert (plan[2] == SINGLE) == (b == "attn80_bwd") and (plan[2] == PAIR) == b.startswith("pair")
