@@ -176,6 +176,17 @@ int octic_linear_d8_prep_batch(const octic_prep_item* items_dev, int n_items, in
 /* Output-tile width (32*NT) the launcher picks for this problem; the kernel instantiation that runs is
  * linear_d8_kernel<TIN, TOUT, NT> — exposed so profilers/benchmarks can name it.                 */
 int octic_linear_d8_tile_n(int64_t M, int cin, int cout);
+/* Host-only query (no device call): what octic_linear_d8_fwd runs for this problem, as decided by the one routing function
+ * of the library (linear_plan, csrc/gemm.hip) under the current octic_route_override table.  fused: whether the call passes a
+ * residual, a per-sample scale or column scales.  out[0] = kernel (OCTIC_LINEAR_*), out[1] = columns per output tile (0 for
+ * the W-stationary kernel, which sizes its column chunks per irrep), out[2] = 1 when the fused-epilogue instantiation runs,
+ * out[3] = 0.  OCTIC_ESHAPE / OCTIC_EDTYPE exactly where the entry point returns them for (M, cin, cout, dtype, out_dtype). */
+enum {
+  OCTIC_LINEAR_WREG = 0,     /* csrc/gemm_wreg.hip linear_d8_wreg_kernel<TOUT, fused>: bf16, cin a multiple of 32 in 32 .. 160 */
+  OCTIC_LINEAR_RING = 1,     /* linear_d8_ring_kernel<TIN, TOUT, fused, ..>: cin a multiple of 32 (bf16) | 16 (f32); tile 80 | 160 */
+  OCTIC_LINEAR_CLASSIC = 2   /* linear_d8_kernel<TIN, TOUT, NT>: register-staged, tile 32 NT, any legal cin                  */
+};
+int octic_linear_d8_plan(int64_t M, int cin, int cout, int dtype, int out_dtype, int fused, int out[4]);
 /* Host-only query (no device call): the workgroup -> item order of a long-K ("ring") launch.  A launch is `ngroups` (<= 5)
  * item classes, class g with items[g] items of ksteps[g] K-steps each (class 0 = the long one, the E irrep); workgroups are
  * dispatched in blockIdx order round-robin over the 8 XCDs to slots_per_xcd slots each, so the order is a schedule.
@@ -197,6 +208,14 @@ int octic_linear_d8_ring_order(int ngroups, const int* items, const int* ksteps,
  * irrep's dY (the bias gradient) in the workspace; _finish then takes them when called with dysum == NULL and
  * octic_colsum_a1 is not needed.                                                                       */
 int octic_linear_d8_wgrad_has_colsum(int cin, int cout, int dtype);
+/* Host-only query: what octic_linear_d8_wgrad runs for this problem (wgrad_plan, csrc/wgrad.hip).  out[0] = kernel
+ * (OCTIC_WGRAD_*), out[1] = tile width (32 TT; 160 on every ring shape), out[2] = the `splits` to pass, out[3] = 1 when the
+ * launch leaves the A1 column sums in the workspace.  _has_colsum, _splits and _tile below are its single answers. */
+enum {
+  OCTIC_WGRAD_RING = 0,      /* wgrad_ring_kernel: bf16, cin and cout multiples of 160 */
+  OCTIC_WGRAD_TILED = 1      /* wgrad_kernel<TIN, TT>                                  */
+};
+int octic_linear_d8_wgrad_plan(int64_t M, int cin, int cout, int dtype, int out[4]);
 int64_t octic_linear_d8_wgrad_workspace_bytes(int cin, int cout, int splits);
 int octic_linear_d8_wgrad_splits(int64_t M, int cin, int cout);
 int octic_linear_d8_wgrad_tile(int64_t M, int cin, int cout);   /* tile width 32*TT of wgrad_kernel<TIN, TT> */
@@ -583,6 +602,11 @@ int64_t octic_dense_wgrad_workspace_bytes(int M, int N, int K);
 /* Tile width along K the launch will use: 256 (256 x 256 tiles, whenever K % 256 == 0) or 320 (256 x 320 tiles: K % 320 == 0
  * only), 64 on the narrow path, 0 for a shape no path takes.  Informational (profilers see dense_tn_kernel<4> / <5>). */
 int octic_dense_wgrad_tile(int M, int N, int K);
+/* Host-only query: the accept-and-plan function of the TN launchers (dw_route, csrc/dense_wgrad.hip).  One problem (N1 = 0) or
+ * the pair [N0 | N1] of octic_dense_wgrad_tn_pair; ld_max = the largest operand row stride in elements (0 = not known: the
+ * stride bound is not checked).  out[0] = tile width (64 | 256 | 320), out[1] = output tiles, out[2] = row slabs, out[3] = 0.
+ * OCTIC_ESHAPE for what the launchers refuse by shape or stride bound (pointer alignment and ld % 8 are theirs to check). */
+int octic_dense_wgrad_plan(int M, int N0, int N1, int K, int64_t ld_max, int out[4]);
 int octic_dense_wgrad_tn(const void* dY, const void* X, int M, int N, int K, int64_t ldy, int64_t ldx, float* dW,
                          void* workspace, void* stream);
 /* Two weight gradients that share the token rows M and K as ONE launch (tile list = [problem 0 | problem 1], row slabs chosen

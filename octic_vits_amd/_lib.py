@@ -20,6 +20,9 @@ ABI_VERSION = 20
 # kernel ids of octic_attn_plan (include/octic_hip.h)
 (ATTN_FWD_PERSIST, ATTN_FWD_A80_ONESHOT, ATTN_FWD_A80_ONLINE, ATTN_FWD_RESIDENT, ATTN_FWD_STREAM, ATTN_FWD_F32) = range(6)
 ATTN_BWD_SINGLE, ATTN_BWD_PAIR, ATTN_BWD_STREAM, ATTN_BWD_F32 = range(4)
+# kernel ids of octic_linear_d8_plan and octic_linear_d8_wgrad_plan
+LINEAR_WREG, LINEAR_RING, LINEAR_CLASSIC = range(3)
+WGRAD_RING, WGRAD_TILED = range(2)
 
 c_i64, c_int, c_float, c_void_p = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 c_double = ctypes.c_double
@@ -50,6 +53,7 @@ _PROTOS = {
     "octic_linear_d8_fwd": (c_int, [VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int,
                                     c_int, c_int, c_void_p]),
     "octic_linear_d8_tile_n": (c_int, [c_i64, c_int, c_int]),
+    "octic_linear_d8_plan": (c_int, [c_i64, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "octic_linear_d8_ring_order": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "octic_linear_d8_wgrad_tile": (c_int, [c_i64, c_int, c_int]),
     "octic_linear_d8_wgrad_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
@@ -59,6 +63,7 @@ _PROTOS = {
                                              c_void_p, c_void_p, c_void_p, c_void_p]),
     "octic_linear_d8_wgrad_finish_batch": (c_int, [c_void_p, c_int, c_void_p]),
     "octic_linear_d8_wgrad_has_colsum": (c_int, [c_int, c_int, c_int]),
+    "octic_linear_d8_wgrad_plan": (c_int, [c_i64, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "octic_lamb_workspace_floats": (c_i64, [c_int, c_int]),
     "octic_lamb_step": (c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_float,
                                                   c_int, c_float, c_void_p, c_void_p]),
@@ -142,6 +147,7 @@ _PROTOS = {
     "octic_dense_colsum": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p]),
     "octic_dense_wgrad_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
     "octic_dense_wgrad_tile": (c_int, [c_int, c_int, c_int]),
+    "octic_dense_wgrad_plan": (c_int, [c_int, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_int)]),
     "octic_dense_wgrad_tn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "octic_dense_wgrad_pair_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "octic_dense_wgrad_tn_pair": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_i64,
@@ -206,25 +212,35 @@ def route_override(knob: int, value: int) -> int:
     old = lib().octic_route_override(knob, value)
     if old < 0:
         raise ValueError(f"octic_route_override: unknown knob {knob}")
-    _ATTN_PLANS.clear()
+    _PLANS.clear()
     return old
 
 
-# octic_attn_plan's answers by argument tuple: the eager step asks per attention call, and without this it measured 1.3 - 1.9 ms
-# per ViT-H step slower than before the query existed (NOTES, 'Attention routing').  An answer holds until the override table
-# changes: route_override drops them all.
-_ATTN_PLANS = {}
+# The answers of the library's plan queries by (query, arguments): the eager step asks per call, and without this the attention
+# query alone measured 1.3 - 1.9 ms per ViT-H step slower than before it existed (NOTES, 'Attention routing'; 3.6 us a query).
+# An answer holds until the override table changes: route_override drops them all.
+_PLANS = {}
+
+
+def plan(query, *args):
+    """The four ints an octic_*_plan query writes for these arguments, or None where it refuses them with OCTIC_ESHAPE."""
+    key = (query, args)
+    answer = _PLANS.get(key, 0)
+    if answer == 0:
+        out = (c_int * 4)()
+        code = getattr(lib(), query)(*args, out)
+        if code not in (0, -1):
+            check(code)
+        _PLANS[key] = answer = tuple(out) if code == 0 else None
+    return answer
 
 
 def attn_plan(T, hd, dtype=BF16, ld_in=0, ld_out=0, ld_grad=0):
     """octic_attn_plan: (forward kernel, its waves, what a phase-3 backward call runs, its waves) - ATTN_FWD_* / ATTN_BWD_*."""
-    key = (T, hd, dtype, ld_in, ld_out, ld_grad)
-    plan = _ATTN_PLANS.get(key)
-    if plan is None:
-        out = (c_int * 4)()
-        check(lib().octic_attn_plan(dtype, T, hd, ld_in, ld_out, ld_grad, out))
-        plan = _ATTN_PLANS[key] = tuple(out)
-    return plan
+    answer = plan("octic_attn_plan", dtype, T, hd, ld_in, ld_out, ld_grad)
+    if answer is None:
+        check(-1)
+    return answer
 
 
 def check(code: int):

@@ -585,8 +585,7 @@ static int dw_launch(DwArgs& a, hipStream_t s) {
 
 extern "C" {
 
-// The narrow path (dense_tn_narrow_kernel): taken where the wide tiles do not divide the shape; N, K multiples of 64.
-static bool dwn_shape(int N, int K) { return N % DWN_T == 0 && K % DWN_T == 0 && ((N % DW_T) || ((K % 256) && (K % 320))); }
+// The narrow path (dense_tn_narrow_kernel): taken where the wide tiles do not divide the shape (dw_route below).
 static int dwn_slabs(int tiles, int M) {
   const int steps = (M + DWN_R - 1) / DWN_R;
   int S = (2 * device_cus() + tiles - 1) / tiles;                 // about two workgroups per CU
@@ -594,14 +593,9 @@ static int dwn_slabs(int tiles, int M) {
   S = S > steps / 4 ? steps / 4 : S;                               // at least four stages per slab
   return S < 1 ? 1 : S;
 }
-static int64_t dwn_workspace_bytes(int M, int N, int K) {
-  const int tiles = (N / DWN_T) * (K / DWN_T);
-  return (int64_t)tiles * dwn_slabs(tiles, M) * DWN_T * DWN_T * 4 + 4096;
-}
-static int dwn_launch(const bf16* Y, const bf16* X, int64_t ldy, int64_t ldx, int M, int N, int K, float* dW, void* workspace,
-                      hipStream_t s) {
-  const int tiles_k = K / DWN_T, tiles = (N / DWN_T) * tiles_k;
-  const int S = dwn_slabs(tiles, M);
+static int dwn_launch(const bf16* Y, const bf16* X, int64_t ldy, int64_t ldx, int M, int N, int K, int tiles, int S, float* dW,
+                      void* workspace, hipStream_t s) {
+  const int tiles_k = K / DWN_T;
   float* part = (float*)((char*)workspace + 4096);                 // (the wide kernel's ticket region stays untouched)
   dense_tn_narrow_kernel<<<dim3(tiles, S), 256, 0, s>>>(Y, X, ldy, ldx, M, N, K, tiles_k, S, S == 1 ? dW : part);
   if (S > 1) {
@@ -655,95 +649,116 @@ static DwPlan dw_plan(int M, int N, int K) {
     p.S = dw_slabs(p.tiles, steps);
     return p;
   };
-  const bool ok4 = K % 256 == 0, ok5 = K % 320 == 0;          // (the entry points refuse K that fits neither)
+  const bool ok4 = K % 256 == 0, ok5 = K % 320 == 0;          // (dw_route refuses K that fits neither)
   if (ok5 && (!ok4 || route(OCTIC_ROUTE_WGRAD_TILE) == 320)) return make(5);
   return make(4);
 }
 
-int octic_dense_wgrad_tile(int M, int N, int K) {      // tile width the launch uses (256 | 320; 64 = the narrow path)
-  if (M > 0 && N > 0 && K > 0 && dwn_shape(N, K)) return DWN_T;
-  if (M <= 0 || N <= 0 || K <= 0 || (N % DW_T) || ((K % 256) && (K % 320))) return 0;
-  return dw_plan(M, N, K).kw * 64;
+// ---- accept and plan: the one place that says which problems the TN launchers take and what they launch.  One problem
+// (N1 = 0) or the pair [N0 | N1] over the same M token rows and K; ld_max = the largest operand row stride in elements (0: not
+// known yet - the shape-only queries).  kw = 1: the narrow 64 x 64 path, for a single problem with N, K multiples of 64 that the
+// wide tiles do not divide; kw = 4 | 5: 256 x 256 | 256 x 320 tiles, N (N0, N1) % 256 == 0 and K % 256 == 0 or K % 320 == 0, at
+// most 1024 tiles (the ticket region), M * ld_max * 2 < 2^31 (32-bit buffer offsets).  Anything else: err = OCTIC_ESHAPE.
+struct DwRoute { int err; DwPlan plan; };
+static DwRoute dw_route(int M, int N0, int N1, int K, int64_t ld_max) {
+  DwRoute r = {OCTIC_ESHAPE, {}};
+  if (M <= 0 || N0 <= 0 || N1 < 0 || K <= 0) return r;
+  const bool wide = N0 % DW_T == 0 && N1 % DW_T == 0 && (K % 256 == 0 || K % 320 == 0);
+  if (!wide) {
+    if (N1 || N0 % DWN_T || K % DWN_T) return r;
+    r.plan.kw = 1;
+    r.plan.tiles_k = K / DWN_T;
+    r.plan.tiles = (N0 / DWN_T) * r.plan.tiles_k;
+    r.plan.S = dwn_slabs(r.plan.tiles, M);
+  } else {
+    if ((int64_t)M * ld_max * 2 >= (1ll << 31)) return r;
+    r.plan = dw_plan(M, N0 + N1, K);                          // tiles and slabs of the joint tile list
+    if (r.plan.tiles > 1024) return r;
+  }
+  r.err = OCTIC_OK;
+  return r;
 }
 
-int64_t octic_dense_wgrad_workspace_bytes(int M, int N, int K) {
-  if (M > 0 && dwn_shape(N, K)) return dwn_workspace_bytes(M, N, K);
+int octic_dense_wgrad_plan(int M, int N0, int N1, int K, int64_t ld_max, int out[4]) {
+  if (!out) return OCTIC_ENULL;
+  const DwRoute r = dw_route(M, N0, N1, K, ld_max);
+  if (r.err) return r.err;
+  out[0] = r.plan.kw * 64;
+  out[1] = r.plan.tiles;
+  out[2] = r.plan.S;
+  out[3] = 0;
+  return OCTIC_OK;
+}
+
+int octic_dense_wgrad_tile(int M, int N, int K) {      // tile width the launch uses (256 | 320; 64 = the narrow path)
+  const DwRoute r = dw_route(M, N, 0, K, 0);
+  return r.err ? 0 : r.plan.kw * 64;
+}
+
+int64_t octic_dense_wgrad_pair_workspace_bytes(int M, int N0, int N1, int K) {
+  const DwRoute r = dw_route(M, N0, N1, K, 0);
+  if (r.err) return 4096;
+  if (r.plan.kw == 1) return (int64_t)r.plan.tiles * r.plan.S * DWN_T * DWN_T * 4 + 4096;
   // room for either width and any forced slab count: [4 KiB tickets (<= 1024 tiles) | slabs]
   const int steps = (M + DW_BR - 1) / DW_BR;
   int64_t need = 0;
   for (int kw = 4; kw <= 5; ++kw) {
     if (K % (64 * kw)) continue;
-    const int tiles = (N / DW_T) * (K / (64 * kw));
+    const int tiles = ((N0 + N1) / DW_T) * (K / (64 * kw));
     const int S = route(OCTIC_ROUTE_WGRAD_SLABS) > 0 ? 16 : dw_slabs(tiles, steps);
     const int64_t b = (int64_t)tiles * S * (DW_T * 64 * kw) * 4;
     need = b > need ? b : need;
   }
   return need + 4096;
 }
+int64_t octic_dense_wgrad_workspace_bytes(int M, int N, int K) { return octic_dense_wgrad_pair_workspace_bytes(M, N, 0, K); }
+
+// the wide launch of a planned problem (single: N1 = 0 and the second operand set unused)
+static int dw_launch_plan(DwArgs& a, const DwPlan& pl, void* workspace, hipStream_t s) {
+  a.tiles_k = pl.tiles_k;
+  a.tiles = pl.tiles;
+  a.tiles8 = (a.tiles + 7) / 8 * 8;
+  a.steps = (a.M + DW_BR - 1) / DW_BR;
+  a.S = pl.S;
+  a.tickets = (int*)workspace;
+  a.slabs = (float*)((char*)workspace + 4096);   // fixed ticket region: a workspace shared by several shapes keeps its zeros
+  return pl.kw == 5 ? dw_launch<5>(a, s) : dw_launch<4>(a, s);
+}
 
 int octic_dense_wgrad_tn(const void* dY, const void* X, int M, int N, int K, int64_t ldy, int64_t ldx, float* dW,
                          void* workspace, void* stream) {
   if (!dY || !X || !dW || !workspace) return OCTIC_ENULL;
-  if (M > 0 && N > 0 && K > 0 && dwn_shape(N, K)) {
-    if ((ldy % 8) || (ldx % 8) || ldy < N || ldx < K) return OCTIC_ESHAPE;
-    if ((((uintptr_t)dY) | ((uintptr_t)X) | ((uintptr_t)dW)) & 15) return OCTIC_EALIGN;
-    return dwn_launch((const bf16*)dY, (const bf16*)X, ldy, ldx, M, N, K, dW, workspace, (hipStream_t)stream);
-  }
-  if (M <= 0 || N <= 0 || K <= 0 || (N % DW_T) || ((K % 256) && (K % 320)) || (ldy % 8) || (ldx % 8)) return OCTIC_ESHAPE;
-  if ((int64_t)M * ldy * 2 >= (1ll << 31) || (int64_t)M * ldx * 2 >= (1ll << 31)) return OCTIC_ESHAPE;   // 32-bit buffer offsets
+  const DwRoute r = dw_route(M, N, 0, K, ldy > ldx ? ldy : ldx);
+  if (r.err) return r.err;
+  if ((ldy % 8) || (ldx % 8) || (r.plan.kw == 1 && (ldy < N || ldx < K))) return OCTIC_ESHAPE;
   if ((((uintptr_t)dY) | ((uintptr_t)X) | ((uintptr_t)dW)) & 15) return OCTIC_EALIGN;
-  const DwPlan pl = dw_plan(M, N, K);
-  if (pl.tiles > 1024) return OCTIC_ESHAPE;                   // ticket region
+  if (r.plan.kw == 1)
+    return dwn_launch((const bf16*)dY, (const bf16*)X, ldy, ldx, M, N, K, r.plan.tiles, r.plan.S, dW, workspace, (hipStream_t)stream);
   DwArgs a = {};
   a.Y = (const bf16*)dY; a.X = (const bf16*)X; a.ldy = ldy; a.ldx = ldx; a.M = M; a.N = N; a.K = K;
   a.W = dW;
-  a.tiles_k = pl.tiles_k;
-  a.tiles = pl.tiles;
-  a.tiles8 = (a.tiles + 7) / 8 * 8;
-  a.steps = (M + DW_BR - 1) / DW_BR;
-  a.S = pl.S;
-  a.tickets = (int*)workspace;
-  char* p = (char*)workspace + 4096;         // fixed ticket region: a workspace shared by several shapes keeps its zeros
-  a.slabs = (float*)p;
-  hipStream_t s = (hipStream_t)stream;
-  return pl.kw == 5 ? dw_launch<5>(a, s) : dw_launch<4>(a, s);
+  return dw_launch_plan(a, r.plan, workspace, (hipStream_t)stream);
 }
-
 
 // Two weight gradients with the same token rows M and the same K as ONE launch: dW0[N0,K] = dY0^T X0, dW1[N1,K] = dY1^T X1.
 // The tile list is [tiles of problem 0 | tiles of problem 1], row slabs chosen for the sum: the qkv and proj weight gradients
 // of a standard block (3840 x 1280 and 1280 x 1280 at ViT-H) become one 100-tile, two-slab launch - the shape of an MLP
 // weight gradient - instead of a 75-tile one and a 25-tile one that needs eight slabs to fill the chip.
-int64_t octic_dense_wgrad_pair_workspace_bytes(int M, int N0, int N1, int K) {
-  return octic_dense_wgrad_workspace_bytes(M, N0 + N1, K);
-}
-
 int octic_dense_wgrad_tn_pair(const void* dY0, const void* X0, int N0, int64_t ldy0, int64_t ldx0, float* dW0,
                               const void* dY1, const void* X1, int N1, int64_t ldy1, int64_t ldx1, float* dW1, int M, int K,
                               void* workspace, void* stream) {
   if (!dY0 || !X0 || !dW0 || !dY1 || !X1 || !dW1 || !workspace) return OCTIC_ENULL;
-  if (M <= 0 || N0 <= 0 || N1 <= 0 || K <= 0 || (N0 % DW_T) || (N1 % DW_T) || ((K % 256) && (K % 320)) || (ldy0 % 8) ||
-      (ldx0 % 8) || (ldy1 % 8) || (ldx1 % 8))
-    return OCTIC_ESHAPE;
-  const int64_t lim = 1ll << 31;
-  if ((int64_t)M * ldy0 * 2 >= lim || (int64_t)M * ldx0 * 2 >= lim || (int64_t)M * ldy1 * 2 >= lim || (int64_t)M * ldx1 * 2 >= lim)
-    return OCTIC_ESHAPE;
+  if (N1 <= 0) return OCTIC_ESHAPE;
+  const int64_t ld0 = ldy0 > ldx0 ? ldy0 : ldx0, ld1 = ldy1 > ldx1 ? ldy1 : ldx1;
+  const DwRoute r = dw_route(M, N0, N1, K, ld0 > ld1 ? ld0 : ld1);
+  if (r.err) return r.err;
+  if ((ldy0 % 8) || (ldx0 % 8) || (ldy1 % 8) || (ldx1 % 8)) return OCTIC_ESHAPE;
   if ((((uintptr_t)dY0) | ((uintptr_t)X0) | ((uintptr_t)dW0) | ((uintptr_t)dY1) | ((uintptr_t)X1) | ((uintptr_t)dW1)) & 15) return OCTIC_EALIGN;
-  const DwPlan pl = dw_plan(M, N0 + N1, K);                   // tiles and slabs of the joint tile list
-  if (pl.tiles > 1024) return OCTIC_ESHAPE;
   DwArgs a = {};
   a.Y = (const bf16*)dY0; a.X = (const bf16*)X0; a.ldy = ldy0; a.ldx = ldx0; a.M = M; a.N = N0; a.K = K; a.W = dW0;
   a.Y1 = (const bf16*)dY1; a.X1 = (const bf16*)X1; a.ldy1 = ldy1; a.ldx1 = ldx1; a.N1 = N1; a.W1 = dW1;
-  a.tiles_k = pl.tiles_k;
-  a.tiles = pl.tiles;
-  a.tiles0 = (N0 / DW_T) * pl.tiles_k;
-  a.tiles8 = (a.tiles + 7) / 8 * 8;
-  a.steps = (M + DW_BR - 1) / DW_BR;
-  a.S = pl.S;
-  a.tickets = (int*)workspace;
-  a.slabs = (float*)((char*)workspace + 4096);
-  hipStream_t s = (hipStream_t)stream;
-  return pl.kw == 5 ? dw_launch<5>(a, s) : dw_launch<4>(a, s);
+  a.tiles0 = (N0 / DW_T) * r.plan.tiles_k;
+  return dw_launch_plan(a, r.plan, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

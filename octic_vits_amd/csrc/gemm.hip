@@ -801,10 +801,9 @@ inline bool plan_ring(GemmArgs& a, int nwg, int slots_per_xcd) {
 }
 
 template <typename TIN, typename TOUT, int NT, int S, int BM = 128>
-int launch_ring_nt(GemmArgs& a, hipStream_t s) {
+int launch_ring_nt(GemmArgs& a, bool fused, hipStream_t s) {
   constexpr int BN = 16 * NT;
   int t = 0;
-  bool fused = a.rs != nullptr || a.lift_np > 0;
   for (int i = 0; i < a.ngroups; ++i) {
     a.g[i].n_tiles = (a.g[i].N + BN - 1) / BN;
     a.g[i].m_tiles = (int)((a.g[i].rows + BM - 1) / BM);
@@ -812,7 +811,6 @@ int launch_ring_nt(GemmArgs& a, hipStream_t s) {
     a.g[i].n_chunks = a.g[i].n_tiles;  // of the kernel relies on it: the ring is idle when the tile is complete)
     a.g[i].tile_begin = t;
     t += a.g[i].n_chunks * a.g[i].m_tiles;
-    fused = fused || a.g[i].cs || a.g[i].resid;
   }
   a.total_tiles = t;
   const size_t smem = (size_t)S * (BM + BN) * 128;
@@ -831,20 +829,18 @@ int launch_ring_nt(GemmArgs& a, hipStream_t s) {
   return launch_status();
 }
 
-template <typename TIN, typename TOUT>
-int launch_ring(GemmArgs& a, hipStream_t s) {
-  // wide tile when every group's N is a multiple of 160 and the problem is long in K (the X panel dominates)
-  bool ok = sizeof(TIN) == 2 && a.lift_np == 0;
-  for (int i = 0; i < a.ngroups; ++i) ok = ok && (a.g[i].N % 160) == 0 && a.g[i].K >= 2 * a.g[i].N;
-  if (ok) return launch_ring_nt<TIN, TOUT, 10, 2>(a, s);
-  return launch_ring_nt<TIN, TOUT, 5, 3>(a, s);
-}
-
 inline bool ring_ok(const GemmArgs& a, int dtype) {
   const int kstep = dtype == OCTIC_BF16 ? 32 : 16;
   for (int i = 0; i < a.ngroups; ++i)
     if (a.g[i].K % kstep) return false;
   return true;
+}
+
+// wide ring tile when every group's N is a multiple of 160 and the problem is long in K (the X panel dominates)
+inline bool ring_wide(const GemmArgs& a, int dtype) {
+  bool ok = dtype == OCTIC_BF16 && a.lift_np == 0;
+  for (int i = 0; i < a.ngroups; ++i) ok = ok && (a.g[i].N % 160) == 0 && a.g[i].K >= 2 * a.g[i].N;
+  return ok;
 }
 
 inline int pick_nt(const GemmArgs& a) {
@@ -867,8 +863,7 @@ inline int pick_nt(const GemmArgs& a) {
 }
 
 template <typename TIN, typename TOUT>
-int launch_gemm(GemmArgs& a, hipStream_t s) {
-  const int nt = pick_nt(a);
+int launch_gemm(GemmArgs& a, int nt, hipStream_t s) {
   const int bn = 32 * nt;
   int t = 0;
   for (int i = 0; i < a.ngroups; ++i) {
@@ -906,21 +901,52 @@ int launch_gemm(GemmArgs& a, hipStream_t s) {
   return launch_status();
 }
 
+// ---- routing.  Which kernel a LinearD8 / lift GEMM runs is decided here and nowhere else: host arithmetic on the shape facts of
+// the argument block (rows / K / N / pair of the groups, lift_np), the dtype pair and whether the launch has a fused tail.
+// dispatch_gemm launches what the plan holds; octic_linear_d8_plan reports it.
+struct LinearPlan {
+  int err;      // OCTIC_OK | OCTIC_EDTYPE
+  int kernel;   // OCTIC_LINEAR_WREG (gemm_wreg.hip) | _RING | _CLASSIC (the register-staged kernel)
+  int nt, s;    // RING: 16-column MFMA tiles per wave and ring stages (10, 2 | 5, 3); CLASSIC: tile = 32 nt columns (pick_nt)
+  bool fused;   // WREG / RING: the EPI = 1 instantiation (per-sample scale, column scale, residual or the lift addressing)
+};
+
+inline bool gemm_fused(const GemmArgs& a) {
+  bool fused = a.rs != nullptr || a.lift_np > 0;
+  for (int i = 0; i < a.ngroups; ++i) fused = fused || a.g[i].cs || a.g[i].resid;
+  return fused;
+}
+
+// (classic_only: octic_linear_d8_tile_n names the register-staged kernel's tile whatever kernel the shape runs)
+inline LinearPlan linear_plan(const GemmArgs& a, bool fused, int dtype, int out_dtype, bool classic_only = false) {
+  LinearPlan p = {OCTIC_OK, OCTIC_LINEAR_CLASSIC, 0, 0, fused};
+  const bool bf = dtype == OCTIC_BF16;
+  if (!(bf ? out_dtype == OCTIC_BF16 || out_dtype == OCTIC_F32 : dtype == OCTIC_F32 && out_dtype == OCTIC_F32)) {
+    p.err = OCTIC_EDTYPE;
+  } else if (!classic_only && bf && !route(OCTIC_ROUTE_LINEAR_RING) && wreg_ok(a)) {   // knob = 1: never the W-stationary kernel
+    p.kernel = OCTIC_LINEAR_WREG;
+  } else if (!classic_only && ring_ok(a, dtype)) {
+    p.kernel = OCTIC_LINEAR_RING;
+    p.nt = ring_wide(a, dtype) ? 10 : 5;
+    p.s = p.nt == 10 ? 2 : 3;
+  } else {
+    p.nt = pick_nt(a);
+  }
+  return p;
+}
+
+template <typename TIN, typename TOUT>
+int launch_plan(GemmArgs& a, const LinearPlan& p, hipStream_t s) {
+  if (p.kernel == OCTIC_LINEAR_CLASSIC) return launch_gemm<TIN, TOUT>(a, p.nt, s);
+  return p.nt == 10 ? launch_ring_nt<TIN, TOUT, 10, 2>(a, p.fused, s) : launch_ring_nt<TIN, TOUT, 5, 3>(a, p.fused, s);
+}
+
 inline int dispatch_gemm(GemmArgs& a, int dtype, int out_dtype, hipStream_t s) {
-  if (dtype == OCTIC_BF16) {
-    const int rw = launch_wreg(a, out_dtype, s);   // short-K problems: W-stationary streaming kernel (gemm_wreg.hip)
-    if (rw != -100) return rw;
-  }
-  if (ring_ok(a, dtype)) {
-    if (dtype == OCTIC_F32 && out_dtype == OCTIC_F32) return launch_ring<float, float>(a, s);
-    if (dtype == OCTIC_BF16 && out_dtype == OCTIC_BF16) return launch_ring<bf16, bf16>(a, s);
-    if (dtype == OCTIC_BF16 && out_dtype == OCTIC_F32) return launch_ring<bf16, float>(a, s);
-    return OCTIC_EDTYPE;
-  }
-  if (dtype == OCTIC_F32 && out_dtype == OCTIC_F32) return launch_gemm<float, float>(a, s);
-  if (dtype == OCTIC_BF16 && out_dtype == OCTIC_BF16) return launch_gemm<bf16, bf16>(a, s);
-  if (dtype == OCTIC_BF16 && out_dtype == OCTIC_F32) return launch_gemm<bf16, float>(a, s);
-  return OCTIC_EDTYPE;
+  const LinearPlan p = linear_plan(a, gemm_fused(a), dtype, out_dtype);
+  if (p.err) return p.err;
+  if (p.kernel == OCTIC_LINEAR_WREG) return launch_wreg(a, out_dtype, p.fused, s);
+  if (dtype == OCTIC_F32) return launch_plan<float, float>(a, p, s);
+  return out_dtype == OCTIC_BF16 ? launch_plan<bf16, bf16>(a, p, s) : launch_plan<bf16, float>(a, p, s);
 }
 
 }  // namespace octic
@@ -968,16 +994,12 @@ int octic_linear_d8_fwd(const octic_view* x, const void* const w[5], const float
     for (int i = 0; i < 5; ++i)
       if (!cs[i]) return OCTIC_ENULL;
   GemmArgs a = {};
-  a.ngroups = 5;
   a.rs = rs;
   a.rps = rs ? rows_per_sample : 1;
-  a.lift_np = 0;
-  a.lift_tok0 = 0;
-  // group order: E first (its tiles carry 2x the K work), then the four one-dimensional irreps
+  d8_group_table(a, M, cin, cout);
   for (int gidx = 0; gidx < 5; ++gidx) {
-    const int irrep = gidx == 0 ? 4 : gidx - 1;
+    const int irrep = d8_group_irrep(gidx);
     GemmGroup& g = a.g[gidx];
-    const bool isE = irrep == 4;
     g.a = (const char*)x->ptr[irrep];
     g.a_ld = x->ld[irrep];
     g.w = (const char*)w[irrep];
@@ -987,26 +1009,30 @@ int octic_linear_d8_fwd(const octic_view* x, const void* const w[5], const float
     g.r_ld = resid ? resid->ld[irrep] : 0;
     g.bias = (irrep == 0) ? bias : nullptr;
     g.cs = cs ? cs[irrep] : nullptr;
-    g.rows = isE ? 2 * M : M;
-    g.K = isE ? 2 * cin : cin;
-    g.N = isE ? 2 * cout : cout;
-    g.pair = isE ? 1 : 0;
   }
-  if (cs)
-    for (int i = 0; i < 5; ++i)
-      if (!cs[i]) return OCTIC_ENULL;
   return dispatch_gemm(a, dtype, out_dtype, (hipStream_t)stream);
+}
+
+int octic_linear_d8_plan(int64_t M, int cin, int cout, int dtype, int out_dtype, int fused, int out[4]) {
+  if (!out) return OCTIC_ENULL;
+  int e;
+  if ((e = check_c_dt(cin, dtype)) || (e = check_c_dt(cout, dtype)) || (e = check_c_dt(cout, out_dtype))) return e;
+  if (M <= 0) return OCTIC_ESHAPE;
+  GemmArgs a = {};
+  d8_group_table(a, M, cin, cout);
+  const LinearPlan p = linear_plan(a, fused != 0, dtype, out_dtype);
+  if (p.err) return p.err;
+  out[0] = p.kernel;
+  out[1] = p.kernel == OCTIC_LINEAR_RING ? 16 * p.nt : 32 * p.nt;   // (0: the W-stationary kernel sizes its column chunks per group)
+  out[2] = p.kernel == OCTIC_LINEAR_CLASSIC ? 0 : (int)p.fused;     // (the register-staged kernel has one instantiation)
+  out[3] = 0;
+  return OCTIC_OK;
 }
 
 int octic_linear_d8_tile_n(int64_t M, int cin, int cout) {
   GemmArgs a = {};
-  a.ngroups = 5;
-  for (int i = 0; i < 5; ++i) {
-    a.g[i].rows = i == 0 ? 2 * M : M;
-    a.g[i].K = i == 0 ? 2 * cin : cin;
-    a.g[i].N = i == 0 ? 2 * cout : cout;
-  }
-  return 32 * pick_nt(a);
+  d8_group_table(a, M, cin, cout);
+  return 32 * linear_plan(a, false, OCTIC_F32, OCTIC_F32, true).nt;
 }
 
 int octic_lift_gemm(const void* patches, const void* w, const float* bias, const float* pos, float* out, int64_t B,

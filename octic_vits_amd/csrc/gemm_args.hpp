@@ -55,7 +55,9 @@ __device__ __forceinline__ void landed(bf16x8& v) {   // at most N younger LDS r
   asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N) : "memory");
 }
 
-// W-stationary streaming kernel (gemm_wreg.hip); returns -100 when the problem does not qualify.
-int launch_wreg(GemmArgs& a, int out_dtype, hipStream_t s);
+// W-stationary streaming kernel (gemm_wreg.hip).  wreg_ok: the problems it takes (bf16 operands are the caller's to check);
+// asked by linear_plan (gemm.hip) and by nobody else.  launch_wreg: out_dtype bf16 | f32, fused = the EPI = 1 instantiation.
+bool wreg_ok(const GemmArgs& a);
+int launch_wreg(GemmArgs& a, int out_dtype, bool fused, hipStream_t s);
 
 }  // namespace octic

@@ -66,8 +66,6 @@ __device__ unsigned long long g_trace[1024 * 4 * 128];
 #define WTRACE(slot) do {} while (0)
 #endif
 
-// routing override OCTIC_ROUTE_LINEAR_RING: 1 = never take this kernel (A/B against the ring kernel)
-
 template <typename TOUT>
 __device__ __forceinline__ void stage_out4(char* p, f32x4 v);
 template <>
@@ -420,21 +418,25 @@ static int cu_count() {
   return device_cus();
 }
 
-template <typename TOUT>
-int launch_t(GemmArgs& a, hipStream_t s) {
-  constexpr int ES = (int)sizeof(TOUT);
-  if (a.lift_np > 0 || route(OCTIC_ROUTE_LINEAR_RING)) return -100;
+// The problems the kernel takes: no lift addressing, every group's K cut into k-chunks (two for the pair group) of one common
+// length, a multiple of 32 in 32 .. 32 KSC, and row counts that fit the kernel's 32-bit row arithmetic.
+static bool eligible(const GemmArgs& a) {
+  if (a.lift_np > 0) return false;
   int Kc = 0;
-  bool fused = a.rs != nullptr;
   for (int i = 0; i < a.ngroups; ++i) {
     const GemmGroup& g = a.g[i];
     const int nch = g.pair ? 2 : 1;
-    if (g.K % (32 * nch) || g.rows <= 0 || g.rows >= (1ll << 31)) return -100;
-    if (Kc && g.K / nch != Kc) return -100;
+    if (g.K % (32 * nch) || g.rows <= 0 || g.rows >= (1ll << 31)) return false;
+    if (Kc && g.K / nch != Kc) return false;
     Kc = g.K / nch;
-    fused = fused || g.cs || g.resid;
   }
-  if (Kc < 32 || Kc > 32 * KSC) return -100;
+  return Kc >= 32 && Kc <= 32 * KSC;
+}
+
+template <typename TOUT>
+int launch_t(GemmArgs& a, bool fused, hipStream_t s) {
+  constexpr int ES = (int)sizeof(TOUT);
+  const int Kc = a.g[0].K / (a.g[0].pair ? 2 : 1);   // the common k-chunk (eligible)
   // column tiles per wave: what fits next to the accumulators (and the residual registers of the fused epilogue)
   const int NTW_A = ES == 2 ? (fused ? 4 : 5) : 3, NTW_E = ES == 2 ? (fused ? 3 : 4) : 3, NTW_MAX = NTW_A;
   // column chunks, and a time model of one workgroup of a chunk in cycles (from the s_memtime timeline,
@@ -502,10 +504,10 @@ int launch_t(GemmArgs& a, hipStream_t s) {
 
 }  // namespace wr
 
-int launch_wreg(GemmArgs& a, int out_dtype, hipStream_t s) {
-  if (out_dtype == OCTIC_BF16) return wr::launch_t<bf16>(a, s);
-  if (out_dtype == OCTIC_F32) return wr::launch_t<float>(a, s);
-  return -100;
+bool wreg_ok(const GemmArgs& a) { return wr::eligible(a); }
+
+int launch_wreg(GemmArgs& a, int out_dtype, bool fused, hipStream_t s) {
+  return out_dtype == OCTIC_BF16 ? wr::launch_t<bf16>(a, fused, s) : wr::launch_t<float>(a, fused, s);
 }
 
 }  // namespace octic

@@ -193,6 +193,22 @@ inline int check_c_dt(int c, int dtype) {
   return (c % (dtype == OCTIC_F32 ? 4 : 8)) == 0 ? OCTIC_OK : OCTIC_ESHAPE;
 }
 
+// ---- the five sub-problems of a LinearD8 launch (GemmArgs of gemm_args.hpp, WgArgs of wgrad.hip), in launch order: group 0 is
+// the two-dimensional irrep E - the two E rows of a token are two GEMM rows sharing W_E: 2M rows, K = 2 cin, N = 2 cout, its
+// tiles carry twice the K work and go first - then the four one-dimensional irreps A1, A2, B1, B2 with M rows, cin, cout.
+inline int d8_group_irrep(int gidx) { return gidx == 0 ? 4 : gidx - 1; }   // index into octic_view / w[5] / cs[5]
+template <typename Args>
+inline void d8_group_table(Args& a, int64_t M, int cin, int cout) {
+  a.ngroups = 5;
+  for (int gidx = 0; gidx < 5; ++gidx) {
+    const int two = gidx == 0 ? 2 : 1;
+    a.g[gidx].rows = two * M;
+    a.g[gidx].K = two * cin;
+    a.g[gidx].N = two * cout;
+    a.g[gidx].pair = two - 1;
+  }
+}
+
 inline int launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? OCTIC_OK : (int)e;

@@ -484,15 +484,6 @@ int launch_wgrad_tt(WgArgs& a, hipStream_t s) {
   return launch_status();
 }
 
-inline bool wgrad_ring_ok(const WgArgs& a) {
-  for (int i = 0; i < a.ngroups; ++i) {
-    const WgGroup& g = a.g[i];
-    if ((g.K % 160) || (g.N % 160)) return false;
-    if ((((uintptr_t)g.x) | ((uintptr_t)g.dy)) & 15) return false;
-  }
-  return true;
-}
-
 inline int launch_wgrad_ring(WgArgs& a, hipStream_t s) {
   int t = 0;
   for (int i = 0; i < a.ngroups; ++i) {
@@ -511,10 +502,41 @@ inline int launch_wgrad_ring(WgArgs& a, hipStream_t s) {
   return launch_status();
 }
 
+// ---- routing.  What a weight-gradient launch runs is decided here and nowhere else, from the groups' rows / K / N and the
+// operand dtype; launch_wgrad launches it, octic_linear_d8_wgrad_plan and the older single-answer queries report it.
+//   RING   wgrad_ring_kernel: bf16, every K and N a multiple of its 160 x 160 tile (operand alignment is not asked again:
+//          check_view has refused unaligned views, octic_lift_wgrad unaligned pointers); a group with a colsum pointer (A1) also
+//          gets its partial column sums written - the bias gradient
+//   TILED  wgrad_kernel<TIN, tt>, 32 tt x 32 tt tiles, tt = 2 .. 5 by least padded work (5 on every RING shape)
+// splits: enough row splits of the E group for two workgroups per CU, bounded so the f32 slabs stay a fraction of the activation
+// bytes the kernel has to read anyway (what the callers of octic_linear_d8_wgrad pass as `splits`).
+#ifndef OCTIC_WG_TARGET
+#define OCTIC_WG_TARGET 512.0
+#endif
+struct WgPlan {
+  int kernel;   // OCTIC_WGRAD_*
+  int tt;
+  int splits;
+};
+inline WgPlan wgrad_plan(const WgArgs& a, int dtype) {
+  WgPlan p = {dtype == OCTIC_BF16 ? OCTIC_WGRAD_RING : OCTIC_WGRAD_TILED, pick_tt(a), 1};
+  for (int i = 0; i < a.ngroups; ++i)
+    if ((a.g[i].K % 160) || (a.g[i].N % 160)) p.kernel = OCTIC_WGRAD_TILED;
+  const int bw = 32 * p.tt;
+  double tiles = 0;                                            // in tiles of the E group: the others take half its splits
+  for (int i = 0; i < a.ngroups; ++i) tiles += (i == 0 ? 1.0 : 0.5) * (((a.g[i].K + bw - 1) / bw) * ((a.g[i].N + bw - 1) / bw));
+  const int64_t max_by_rows = (a.g[0].rows + 255) / 256;
+  int s = (int)((OCTIC_WG_TARGET / tiles) + 0.5);
+  s = s > max_by_rows ? (int)max_by_rows : s;
+  p.splits = s > 32 ? 32 : (s < 1 ? 1 : s);
+  return p;
+}
+
 template <typename TIN>
 int launch_wgrad(WgArgs& a, hipStream_t s) {
-  if (sizeof(TIN) == 2 && wgrad_ring_ok(a)) return launch_wgrad_ring(a, s);
-  switch (pick_tt(a)) {
+  const WgPlan p = wgrad_plan(a, sizeof(TIN) == 2 ? OCTIC_BF16 : OCTIC_F32);
+  if (p.kernel == OCTIC_WGRAD_RING) return launch_wgrad_ring(a, s);
+  switch (p.tt) {
     case 2: return launch_wgrad_tt<TIN, 2>(a, s);
     case 3: return launch_wgrad_tt<TIN, 3>(a, s);
     case 4: return launch_wgrad_tt<TIN, 4>(a, s);
@@ -540,44 +562,34 @@ int64_t octic_linear_d8_wgrad_workspace_bytes(int cin, int cout, int splits) {
   return (colsum_off_elems(cin, cout, splits) + (int64_t)splits * cout) * 4;
 }
 
+int octic_linear_d8_wgrad_plan(int64_t M, int cin, int cout, int dtype, int out[4]) {
+  if (!out) return OCTIC_ENULL;
+  int e;
+  if ((e = check_c_dt(cin, dtype)) || (e = check_c_dt(cout, dtype))) return e;
+  if (M <= 0) return OCTIC_ESHAPE;
+  WgArgs a = {};
+  d8_group_table(a, M, cin, cout);
+  const WgPlan p = wgrad_plan(a, dtype);
+  out[0] = p.kernel;
+  out[1] = 32 * p.tt;
+  out[2] = p.splits;
+  out[3] = p.kernel == OCTIC_WGRAD_RING;      // octic_linear_d8_wgrad hands the A1 group its colsum pointer
+  return OCTIC_OK;
+}
+
+// the single answers of the plan (older queries; the dtype-less ones ask as f32 - every legal width - since the operand dtype
+// decides neither tt nor splits)
 int octic_linear_d8_wgrad_has_colsum(int cin, int cout, int dtype) {
-  return dtype == OCTIC_BF16 && (cin % 160) == 0 && (cout % 160) == 0;
+  int out[4];
+  return octic_linear_d8_wgrad_plan(1, cin, cout, dtype, out) == OCTIC_OK && out[3];
 }
-
 int octic_linear_d8_wgrad_tile(int64_t M, int cin, int cout) {
-  WgArgs a = {};
-  a.ngroups = 5;
-  for (int i = 0; i < 5; ++i) {
-    a.g[i].K = i == 0 ? 2 * cin : cin;
-    a.g[i].N = i == 0 ? 2 * cout : cout;
-    a.g[i].rows = i == 0 ? 2 * M : M;
-  }
-  return 32 * pick_tt(a);
+  int out[4];
+  return octic_linear_d8_wgrad_plan(M, cin, cout, OCTIC_F32, out) == OCTIC_OK ? out[1] : 0;
 }
-
 int octic_linear_d8_wgrad_splits(int64_t M, int cin, int cout) {
-  // enough row-splits to give every CU two workgroups, bounded so the f32 slabs stay a fraction of the activation
-  // bytes the kernel has to read anyway
-  WgArgs a = {};
-  a.ngroups = 5;
-  for (int i = 0; i < 5; ++i) {
-    a.g[i].K = i == 0 ? 2 * cin : cin;
-    a.g[i].N = i == 0 ? 2 * cout : cout;
-    a.g[i].rows = i == 0 ? 2 * M : M;
-  }
-  const int bw = 32 * pick_tt(a);
-  const int tiles_e = ((2 * cin + bw - 1) / bw) * ((2 * cout + bw - 1) / bw);
-  const int tiles_1 = 4 * ((cin + bw - 1) / bw) * ((cout + bw - 1) / bw);
-#ifndef OCTIC_WG_TARGET
-#define OCTIC_WG_TARGET 512.0
-#endif
-  constexpr double target = OCTIC_WG_TARGET;
-  int s = (int)((target / (tiles_e + 0.5 * tiles_1)) + 0.5);
-  const int64_t max_by_rows = (2 * M + 255) / 256;
-  if (s > max_by_rows) s = (int)max_by_rows;
-  if (s > 32) s = 32;
-  if (s < 1) s = 1;
-  return s;
+  int out[4];
+  return octic_linear_d8_wgrad_plan(M, cin, cout, OCTIC_F32, out) == OCTIC_OK ? out[2] : 1;
 }
 
 int octic_linear_d8_wgrad(const octic_view* x, const octic_view* dy, int64_t M, int cin, int cout, int dtype,
@@ -588,22 +600,18 @@ int octic_linear_d8_wgrad(const octic_view* x, const octic_view* dy, int64_t M, 
   if (!workspace) return OCTIC_ENULL;
   if (M <= 0 || splits <= 0) return OCTIC_ESHAPE;
   WgArgs a = {};
-  a.ngroups = 5;
   a.slab_elems = linear_slab_elems(cin, cout);
   a.slabs = workspace;
+  d8_group_table(a, M, cin, cout);
   // slab layout: [W_A1 | W_A2 | W_B1 | W_B2 | W_E]; launch order E first
   for (int gidx = 0; gidx < 5; ++gidx) {
-    const int irrep = gidx == 0 ? 4 : gidx - 1;
+    const int irrep = d8_group_irrep(gidx);
     const bool isE = irrep == 4;
     WgGroup& g = a.g[gidx];
     g.x = (const char*)x->ptr[irrep];
     g.x_ld = x->ld[irrep];
     g.dy = (const char*)dy->ptr[irrep];
     g.dy_ld = dy->ld[irrep];
-    g.rows = isE ? 2 * M : M;
-    g.K = isE ? 2 * cin : cin;
-    g.N = isE ? 2 * cout : cout;
-    g.pair = isE ? 1 : 0;
     g.splits = group_splits(splits, isE);
     g.slab_off = isE ? (int64_t)4 * cin * cout : (int64_t)irrep * cin * cout;
     g.colsum = irrep == 0 ? workspace + colsum_off_elems(cin, cout, splits) : nullptr;
@@ -684,6 +692,7 @@ int octic_lift_wgrad(const void* patches, const void* dout, float* dw, float* wo
                      int Kpad, int D, int dtype, void* stream) {
   if (!patches || !dout || !dw || !workspace) return OCTIC_ENULL;
   if (rows <= 0 || splits <= 0 || Kpad <= 0 || (Kpad % 8) || D <= 0 || (D % 8)) return OCTIC_ESHAPE;
+  if ((((uintptr_t)patches) | ((uintptr_t)dout)) & 15) return OCTIC_EALIGN;
   WgArgs a = {};
   a.ngroups = 1;
   a.slab_elems = (int64_t)Kpad * D;

@@ -854,8 +854,8 @@ def wgrad_slabs(M, N, K):
 
 
 # Weight gradients of the standard half on csrc/dense_wgrad.hip (dW = dY^T X straight from the row-major operands, f32
-# result, fixed-order slab reduction) wherever the kernel takes the shape (ops.dense_wgrad_ok: N, K multiples of 256, at
-# most 256 output tiles - ViT-H/14, ViT-L/16, ...), not for a literal list of shapes (round-3 review).  Measured against
+# result, fixed-order slab reduction) wherever the kernel takes the shape (ops.dense_wgrad_ok: the library's plan and
+# a cap of 256 output tiles - ViT-H/14, ViT-L/16, ...), not for a literal list of shapes (round-3 review).  Measured against
 # the library's batched row slabs on one MI355X (tools/bench_tn.py): 5120x1280 224-234 vs 296 us, 1280x5120 211 vs 246,
 # 3840x1280 156 vs 187, 1280x1280 93 vs 100.  False = every weight gradient on the BLAS library (bench.py --lib-wgrad).
 WGRAD_HIP = True
@@ -866,8 +866,8 @@ def _wgrad_lib(g2, x2, wparam=None):
     parameter this is the gradient of - under DDP the result is written into its bucket view (ops.GRAD_DEST)."""
     M, N, K = g2.shape[0], g2.shape[1], x2.shape[1]
     if (WGRAD_HIP and g2.is_cuda and g2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16
-            and g2.stride(1) == 1 and x2.stride(1) == 1 and ops.dense_wgrad_ok(M, N, K)
-            and M * max(g2.stride(0), x2.stride(0)) * 2 < 2 ** 31):
+            and g2.stride(1) == 1 and x2.stride(1) == 1
+            and ops.dense_wgrad_ok(M, N, K, max(g2.stride(0), x2.stride(0)))):
         dest = ops.grad_dest(wparam, (N, K))
         dw = ops.dense_wgrad_tn(g2, x2, out=dest)
         if dest is not None:

@@ -6,6 +6,7 @@ through the C ABI (include/octic_hip.h) via ctypes.  Tensors are described to th
 and the engine's packed ``[B, T, 8c]`` rows are handled by the same kernels without a copy.
 """
 import ctypes
+import operator
 
 import torch
 
@@ -294,12 +295,28 @@ def dense_gemm_ok(rows, N, K):
     return K % 64 == 0 and K >= 128 and N % 64 == 0 and N >= 128 and rows * max(N, K) * 2 < 2 ** 31
 
 
-def dense_wgrad_ok(M, N, K):
-    """Shapes csrc/dense_wgrad.hip takes: the 256 x (256 | 320) tiles where they divide N x K (at most 256 of them), else
-    the 64 x 64 narrow path for N, K multiples of 64 (the standard blocks of DeiT-III tiny / small: D = 192, 384)."""
-    wide = N % 256 == 0 and (K % 256 == 0 or K % 320 == 0)
-    narrow = N % 64 == 0 and K % 64 == 0 and not wide
-    return M > 0 and ((wide and (N // 256) * (K // 256) <= 256) or narrow)
+# Routing policy of this side, stricter than the kernel's 1024-tile limit: the wide TN tiles run only where N x K is at most
+# this many 256 x 256 blocks (larger weight gradients stay with the framework's GEMM).
+DENSE_WGRAD_MAX_BLOCKS = 256
+
+
+@torch.compiler.assume_constant_result
+def _dense_wgrad_query(M, N0, N1, K, ld_max):
+    return _lib.plan("octic_dense_wgrad_plan", M, N0, N1, K, ld_max)
+
+
+def _dense_wgrad_plan(M, N0, N1, K, ld_max):
+    """octic_dense_wgrad_plan's answer, or None for a refusal.  vit._mlp traces through dense_wgrad_ok under torch.compile: the
+    tracer keeps the query's answer as a constant instead of tracing into ctypes, and a symbolic row count is pinned to its value
+    (operator.index) - the plan is per shape."""
+    return _dense_wgrad_query(operator.index(M), N0, N1, K, ld_max)
+
+
+def dense_wgrad_ok(M, N, K, ld_max=0):
+    """The library's TN launcher takes the problem (octic_dense_wgrad_plan; ld_max: the largest operand row stride, 0 = not
+    known yet) and, on the wide tiles, the routing cap holds."""
+    plan = _dense_wgrad_plan(M, N, 0, K, ld_max)
+    return plan is not None and (plan[0] == 64 or (N // 256) * (K // 256) <= DENSE_WGRAD_MAX_BLOCKS)
 
 
 # Where a weight gradient is to be WRITTEN (train.Trainer under DistributedDataParallel, one micro-batch): parameter address ->
@@ -347,8 +364,9 @@ def dense_wgrad_tn(dy, x, name=None, out=None):
 
 
 def dense_wgrad_pair_ok(M, N0, N1, K):
-    return (N0 % 256 == 0 and N1 % 256 == 0 and (K % 256 == 0 or K % 320 == 0) and M > 0
-            and ((N0 + N1) // 256) * (K // 256) <= 256)
+    """dense_wgrad_ok for the joint launch of two problems over the same token rows."""
+    return (N1 > 0 and _dense_wgrad_plan(M, N0, N1, K, 0) is not None
+            and ((N0 + N1) // 256) * (K // 256) <= DENSE_WGRAD_MAX_BLOCKS)
 
 
 def dense_wgrad_tn_pair(dy0, x0, dy1, x1, dw1=None, dw0=None):
@@ -385,15 +403,15 @@ def linear_fwd(xv, w5, bias, yv, M, cin, cout, dtype, out_dtype, ref, resid_v=No
         es, eo = (2 if dtype == torch.bfloat16 else 4), (2 if out_dtype == torch.bfloat16 else 4)
         nbytes = M * 8 * cin * es + M * 8 * cout * eo * (2 if resid_v is not None else 1) + 8 * cin * cout * es
         fused = int(resid_v is not None or rs is not None or cs5 is not None)
-        KERNEL_TIMER.stop(t, linear_kernel_name(cin, dtype, out_dtype, fused), nbytes, 24.0 * M * cin * cout)
+        KERNEL_TIMER.stop(t, linear_kernel_name(cin, cout, dtype, out_dtype, fused, M), nbytes, 24.0 * M * cin * cout)
 
 
-def linear_kernel_name(cin, dtype, out_dtype, fused):
-    """Name of the kernel instantiation octic_linear_d8_fwd dispatches to (mirrors dispatch_gemm in csrc/gemm.hip)."""
-    if dtype == torch.bfloat16 and cin % 32 == 0 and cin <= 160:
+def linear_kernel_name(cin, cout, dtype, out_dtype, fused, M):
+    """Name of the kernel instantiation octic_linear_d8_fwd runs for this call, from the library's plan."""
+    kernel, _, fused, _ = _lib.plan("octic_linear_d8_plan", M, cin, cout, dt_code(dtype), dt_code(out_dtype), int(fused))
+    if kernel == _lib.LINEAR_WREG:
         return f"linear_d8_wreg_kernel<{_DTN[out_dtype]},{fused}>"
-    kstep = 32 if dtype == torch.bfloat16 else 16
-    if cin % kstep == 0:
+    if kernel == _lib.LINEAR_RING:
         return f"linear_d8_ring_kernel<{_DTN[dtype]},{_DTN[out_dtype]},{fused}>"
     return f"linear_d8_kernel<{_DTN[dtype]},{_DTN[out_dtype]}>"
 
@@ -404,16 +422,14 @@ def linear_wgrad(xv, dyv, M, cin, cout, dtype, ref, w32=None, cs5=None, bias=Non
     them for non-f32 master weights), so the slab reduction must not be postponed to the end of the backward pass."""
     L = lib()
     dev = ref.device
-    splits = L.octic_linear_d8_wgrad_splits(M, cin, cout)
+    kernel, tile, splits, _ = _lib.plan("octic_linear_d8_wgrad_plan", M, cin, cout, dt_code(dtype))
     ws = torch.empty(L.octic_linear_d8_wgrad_workspace_bytes(cin, cout, splits) // 4, dtype=torch.float32, device=dev)
     t = KERNEL_TIMER.start()
     check(L.octic_linear_d8_wgrad(ctypes.byref(xv), ctypes.byref(dyv), M, cin, cout, dt_code(dtype), _p(ws), splits,
                                   _stream(ref)))
     if t is not None:
         es = 2 if dtype == torch.bfloat16 else 4
-        tt = L.octic_linear_d8_wgrad_tile(M, cin, cout) // 32
-        ring = dtype == torch.bfloat16 and cin % 160 == 0 and cout % 160 == 0      # wgrad.hip: wgrad_ring_ok
-        name = "wgrad_ring_kernel<bf16>" if ring else f"wgrad_kernel<{_DTN[dtype]},{tt}>"
+        name = "wgrad_ring_kernel<bf16>" if kernel == _lib.WGRAD_RING else f"wgrad_kernel<{_DTN[dtype]},{tile // 32}>"
         # slabs: the two-dimensional irrep (half of the 8*cin*cout weights) uses `splits`, the others splits/2
         slab = (splits + (splits + 1) // 2) * 4 * cin * cout * 4
         KERNEL_TIMER.stop(t, name, M * 8 * (cin + cout) * es + slab, 24.0 * M * cin * cout)
@@ -437,7 +453,8 @@ def linear_wgrad(xv, dyv, M, cin, cout, dtype, ref, w32=None, cs5=None, bias=Non
 
 
 def wgrad_has_colsum(cin, cout, dtype):
-    return bool(lib().octic_linear_d8_wgrad_has_colsum(cin, cout, dt_code(dtype)))
+    """Whether the wgrad launch leaves the A1 column sums behind its slabs (the answer does not depend on the row count)."""
+    return bool(_lib.plan("octic_linear_d8_wgrad_plan", 1, cin, cout, dt_code(dtype))[3])
 
 
 def colsum_a1(dyv, M, c, dtype, ref):
@@ -1128,8 +1145,9 @@ def dense_colsum(g):
 
 def dense_plan(M, N, K, mode, tokens):
     """(tile width, colsum slab rows, per-image panels?, main-launch workgroups) of octic_dense_gemm_nt_tokens."""
-    out = (ctypes.c_int * 4)()
-    check(lib().octic_dense_gemm_plan(M, N, K, mode, int(tokens), out))
+    out = _lib.plan("octic_dense_gemm_plan", M, N, K, mode, int(tokens))
+    if out is None:
+        check(-1)
     return out[0], out[1], bool(out[2]), out[3]
 
 

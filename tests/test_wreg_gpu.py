@@ -94,7 +94,7 @@ def test_wreg_and_ring_agree_bitwise_without_bias(M, cin, cout):
 
 
 def test_wreg_is_the_routed_kernel_for_vith_shapes():
-    """ops.linear_kernel_name mirrors dispatch_gemm: the ViT-H short-K problems are timed under the wreg name."""
+    """ops.linear_kernel_name reads the library's plan: the ViT-H short-K problems are timed under the wreg name."""
     from octic_vits_amd import ops
-    assert ops.linear_kernel_name(160, bf, bf, 0).startswith("linear_d8_wreg_kernel")
-    assert ops.linear_kernel_name(640, bf, bf, 0).startswith("linear_d8_ring_kernel")
+    assert ops.linear_kernel_name(160, 480, bf, bf, 0, 16448).startswith("linear_d8_wreg_kernel")
+    assert ops.linear_kernel_name(640, 160, bf, bf, 0, 16448).startswith("linear_d8_ring_kernel")
