@@ -600,7 +600,7 @@ int octic_dense_gemm_plan(int M, int N, int K, int mode, int tokens, int* out4);
  * once at allocation.                                                                                                 */
 int64_t octic_dense_wgrad_workspace_bytes(int M, int N, int K);
 /* Tile width along K the launch will use: 256 (256 x 256 tiles, whenever K % 256 == 0) or 320 (256 x 320 tiles: K % 320 == 0
- * only), 64 on the narrow path, 0 for a shape no path takes.  Informational (profilers see dense_tn_kernel<4> / <5>). */
+ * only), 64 on the narrow path, 0 for a shape no path takes.  Informational (profilers see dense_tn_kernel<4, ..> / <5, ..>). */
 int octic_dense_wgrad_tile(int M, int N, int K);
 /* Host-only query: the accept-and-plan function of the TN launchers (dw_route, csrc/dense_wgrad.hip).  One problem (N1 = 0) or
  * the pair [N0 | N1] of octic_dense_wgrad_tn_pair; ld_max = the largest operand row stride in elements (0 = not known: the
@@ -617,6 +617,20 @@ int64_t octic_dense_wgrad_pair_workspace_bytes(int M, int N0, int N1, int K);
 int octic_dense_wgrad_tn_pair(const void* dY0, const void* X0, int N0, int64_t ldy0, int64_t ldx0, float* dW0,
                               const void* dY1, const void* X1, int N1, int64_t ldy1, int64_t ldx1, float* dW1, int M, int K,
                               void* workspace, void* stream);
+/* The same two launches inside a block with stochastic depth (timm DropPath in deit/vit.py: x + drop_path(gamma * f(norm(x)))).
+ * sample_scale: NULL (= the plain call) or the [M / rows_per_sample] f32 factors (0 or 1 / keep) the block multiplies the
+ * branch with, sample b owning token rows [b rows_per_sample, (b + 1) rows_per_sample); for the pair ONE mask for both
+ * problems.  CONTRACT: sample_scale[b] == 0 promises that every dY row of sample b (dY0 and dY1 of the pair) is zero.  The
+ * 256- / 320-wide kernel may then leave those rows of dY and X unread: it walks only the 64-row reduction steps that touch a
+ * sample with a non-zero factor, inside the same row slabs and with the same slab order in the final sum.  The mask is a hint
+ * only: with the promise kept the result is what the unmasked launch writes (the 64 x 64 path ignores it; so does a launch
+ * whose slabs exceed 16 384 steps).  OCTIC_ESHAPE when the mask is given and rows_per_sample <= 0 or M % rows_per_sample != 0.
+ * Workspace and plan queries: those of the plain calls.                                                                  */
+int octic_dense_wgrad_tn_skip(const void* dY, const void* X, int M, int N, int K, int64_t ldy, int64_t ldx, float* dW,
+                              const float* sample_scale, int rows_per_sample, void* workspace, void* stream);
+int octic_dense_wgrad_tn_pair_skip(const void* dY0, const void* X0, int N0, int64_t ldy0, int64_t ldx0, float* dW0,
+                                   const void* dY1, const void* X1, int N1, int64_t ldy1, int64_t ldx1, float* dW1, int M, int K,
+                                   const float* sample_scale, int rows_per_sample, void* workspace, void* stream);
 
 /* ---- row kernels of the DINOv2 objective over the prototype axis (K % 8 == 0, row strides % 8 == 0) -----
  * octic_softmax_center: out[r, :] = softmax((t[r, :] - center) * inv_temp) in f32 - the teacher's centred, sharpened

@@ -152,6 +152,10 @@ _PROTOS = {
     "octic_dense_wgrad_pair_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "octic_dense_wgrad_tn_pair": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_i64,
                                           c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "octic_dense_wgrad_tn_skip": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p,
+                                          c_void_p]),
+    "octic_dense_wgrad_tn_pair_skip": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_i64,
+                                               c_i64, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "octic_probe_features": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_i64, c_i64, c_int, c_i64, c_int, c_int, c_void_p,
                                      c_i64, c_void_p]),
     "octic_probe_forward": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p]),

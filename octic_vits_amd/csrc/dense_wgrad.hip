@@ -80,7 +80,17 @@ struct DwArgs {
   int N1;
   float* W1;
   int tiles0;
+  // Stochastic depth (octic_dense_wgrad_tn_skip): the branch's per-sample factor, [M / rows_per_sample] f32, or NULL.
+  // sample_scale[b] == 0 PROMISES that every dY row of sample b (of both problems) is zero; dense_tn_kernel<KW, true> then
+  // walks only the reduction steps that touch a kept sample.  A hint: with the promise kept the result is the unmasked one.
+  const float* sample_scale;
+  int rows_per_sample;
 };
+// Live-step bitmap of dense_tn_kernel<KW, true>: one bit per reduction step of the workgroup's slab, 64-step words in LDS
+// BEHIND the ring (2 KiB + the eight per-wave counts; the ring stays at offset 0 and leaves 16 KiB at KW = 5).  A slab with
+// more steps runs the unmasked kernel.
+constexpr int DW_LIVE_WORDS = 256;
+constexpr int DW_LIVE_BYTES = DW_LIVE_WORDS * 8 + 8 * 4;
 
 __device__ inline void dw_wait_vmcnt(int n) {
   switch (n) {
@@ -105,11 +115,11 @@ template <int N> __device__ inline void dw_wait_steady() {          // steady st
   else asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
 }
 
-template <int KW>
+template <int KW, bool SKIP>
 __global__ __launch_bounds__(512, 1) void dense_tn_kernel(DwArgs a) {
   typedef DwGeom<KW> G;
   constexpr int KB = KW - 2;                  // k-tiles of a wave's second k-set (the first has 2)
-  extern __shared__ __attribute__((aligned(16))) char lds[];   // two steps of G::STEP bytes
+  extern __shared__ __attribute__((aligned(16))) char lds[];   // two steps of G::STEP bytes (SKIP: + DW_LIVE_BYTES)
 
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -215,7 +225,40 @@ __global__ __launch_bounds__(512, 1) void dense_tn_kernel(DwArgs a) {
     const int s1 = (int)((int64_t)a.steps * (slab_i + 1) / a.S);
     const int tn = tile_l / a.tiles_k, tk = tile_l - tn * a.tiles_k;
     const int n0 = tn * DW_T, k0 = tk * G::BK;
-    const int nkt = s1 - s0;                                 // >= 1 (the launcher keeps S <= max(1, steps / 2))
+    // Reduction steps this item walks.  Unmasked: all of its slab, >= 1 (the launcher keeps S <= max(1, steps / 2)).
+    // SKIP: the slab's LIVE steps - those with a token row of a sample whose factor is non-zero - in ascending order; the
+    // slab boundaries, and with them the grouping of the f32 sums, stay where they are.  Lane = step: wave w builds words
+    // w, w + 8, .. of the bitmap with one ballot each (a lane reads the factors of the samples its 64 rows touch: two
+    // at 257 rows per sample).  0 live steps (every sample of the slab dropped): no DMA, no loop, the barriers below still
+    // pair up, and the item takes its ticket with zero accumulators like any other.
+    int nkt = s1 - s0;
+    [[maybe_unused]] const unsigned long long* live_bits = nullptr;
+    if constexpr (SKIP) {
+      unsigned long long* const live_words = (unsigned long long*)(lds + G::RING);
+      int* const live_cnt = (int*)(live_words + DW_LIVE_WORDS);
+      const int nwords = (nkt + 63) >> 6;
+      int cnt = 0;
+      for (int w = wid; w < nwords; w += 8) {
+        const int j = w * 64 + lane;
+        bool live = false;
+        if (j < nkt) {
+          const int r0 = (s0 + j) * DW_BR;                   // < M
+          const int r1 = r0 + DW_BR < a.M ? r0 + DW_BR : a.M;
+          const int b1 = (r1 - 1) / a.rows_per_sample;
+          for (int b = r0 / a.rows_per_sample; b <= b1; ++b) live |= a.sample_scale[b] != 0.f;
+        }
+        const unsigned long long m = __ballot(live);
+        if (lane == 0) live_words[w] = m;
+        cnt += __popcll(m);
+      }
+      if (lane == 0) live_cnt[wid] = cnt;
+      __syncthreads();
+      int L = 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) L += live_cnt[i];
+      nkt = __builtin_amdgcn_readfirstlane(L);
+      live_bits = live_words;
+    }
     const int nunits = 4 * nkt;
 
     f32x4 acc[2][KW][4];                 // [n-half][k-tile][n-tile]   (k-tiles 0, 1 = first k-set, 2 .. KW-1 = second)
@@ -232,12 +275,28 @@ __global__ __launch_bounds__(512, 1) void dense_tn_kernel(DwArgs a) {
     const int stepY = (int)(ldy_ * DW_BR * 2), stepX = (int)(ldx_ * DW_BR * 2);
 
     int u_issue = 0;
+    // SKIP: the step (relative to s0) the units being issued come from, and the scalar walk over the bitmap that finds
+    // it: the current word in SGPRs, find-first-set, one LDS read per 64 steps.  Called once per issued step, <= nkt times.
+    [[maybe_unused]] int t_src = 0, live_wi = -1;
+    [[maybe_unused]] unsigned long long live_w = 0;
+    auto next_live = [&]() {
+      while (live_w == 0) {
+        ++live_wi;
+        const unsigned long long v = live_bits[live_wi];
+        live_w = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+                 (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+      }
+      const int j = __builtin_ctzll(live_w);
+      live_w &= live_w - 1;
+      return (live_wi << 6) + j;
+    };
     // KIND 0 / 3: first / second 64-column halves of the dY tile halves; KIND 1 / 2: first / second k-sets of X
     auto issue_unit = [&](auto kind_c) {
       constexpr int KIND = decltype(kind_c)::value;
       constexpr bool isY = KIND == 0 || KIND == 3;
       const unsigned dst = lds0 + ((u_issue >> 2) & 1) * G::STEP + G::unit_off(KIND) + wid * 2048;
-      const int t = u_issue >> 2;
+      if constexpr (SKIP && KIND == 0) t_src = next_live();          // (u_issue & 3) == KIND: a new step begins
+      const int t = SKIP ? t_src : u_issue >> 2;
       if constexpr (isY) {
         const int so = sbY + t * stepY + (KIND == 3 ? 128 : 0);
         dma16(dst, voY[0], so, rsY);
@@ -567,18 +626,18 @@ __global__ __launch_bounds__(256) void dense_tn_narrow_finish(const float* __res
 
 using namespace octic;
 
-template <int KW>
+template <int KW, bool SKIP>
 static int dw_launch(DwArgs& a, hipStream_t s) {
-  const int smem = DwGeom<KW>::RING;
+  const int smem = DwGeom<KW>::RING + (SKIP ? DW_LIVE_BYTES : 0);
   static DeviceOnce once;
   if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)dense_tn_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    (void)hipFuncSetAttribute((const void*)dense_tn_kernel<KW, SKIP>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     (void)hipGetLastError();
   }
 #if DW_MAP == 1
-  dense_tn_kernel<KW><<<(a.tiles * a.S + 255) / 256 * 256, 512, smem, s>>>(a);
+  dense_tn_kernel<KW, SKIP><<<(a.tiles * a.S + 255) / 256 * 256, 512, smem, s>>>(a);
 #else
-  dense_tn_kernel<KW><<<a.tiles8 * a.S, 512, smem, s>>>(a);
+  dense_tn_kernel<KW, SKIP><<<a.tiles8 * a.S, 512, smem, s>>>(a);
 #endif
   return launch_status();
 }
@@ -722,14 +781,25 @@ static int dw_launch_plan(DwArgs& a, const DwPlan& pl, void* workspace, hipStrea
   a.S = pl.S;
   a.tickets = (int*)workspace;
   a.slabs = (float*)((char*)workspace + 4096);   // fixed ticket region: a workspace shared by several shapes keeps its zeros
-  return pl.kw == 5 ? dw_launch<5>(a, s) : dw_launch<4>(a, s);
+  // the mask is a hint: a NULL one, or a slab longer than the live-step bitmap, runs the unmasked instantiation
+  if (a.sample_scale && (a.steps + a.S - 1) / a.S <= DW_LIVE_WORDS * 64)
+    return pl.kw == 5 ? dw_launch<5, true>(a, s) : dw_launch<4, true>(a, s);
+  return pl.kw == 5 ? dw_launch<5, false>(a, s) : dw_launch<4, false>(a, s);
 }
 
-int octic_dense_wgrad_tn(const void* dY, const void* X, int M, int N, int K, int64_t ldy, int64_t ldx, float* dW,
-                         void* workspace, void* stream) {
+// the mask of the _skip entry points: NULL, or one f32 factor per sample of rows_per_sample token rows
+static int dw_mask_status(const float* sample_scale, int rows_per_sample, int M) {
+  if (!sample_scale) return OCTIC_OK;
+  if (rows_per_sample <= 0 || M % rows_per_sample) return OCTIC_ESHAPE;
+  return ((uintptr_t)sample_scale & 3) ? OCTIC_EALIGN : OCTIC_OK;
+}
+
+int octic_dense_wgrad_tn_skip(const void* dY, const void* X, int M, int N, int K, int64_t ldy, int64_t ldx, float* dW,
+                              const float* sample_scale, int rows_per_sample, void* workspace, void* stream) {
   if (!dY || !X || !dW || !workspace) return OCTIC_ENULL;
   const DwRoute r = dw_route(M, N, 0, K, ldy > ldx ? ldy : ldx);
   if (r.err) return r.err;
+  if (const int e = dw_mask_status(sample_scale, rows_per_sample, M)) return e;
   if ((ldy % 8) || (ldx % 8) || (r.plan.kw == 1 && (ldy < N || ldx < K))) return OCTIC_ESHAPE;
   if ((((uintptr_t)dY) | ((uintptr_t)X) | ((uintptr_t)dW)) & 15) return OCTIC_EALIGN;
   if (r.plan.kw == 1)
@@ -737,28 +807,40 @@ int octic_dense_wgrad_tn(const void* dY, const void* X, int M, int N, int K, int
   DwArgs a = {};
   a.Y = (const bf16*)dY; a.X = (const bf16*)X; a.ldy = ldy; a.ldx = ldx; a.M = M; a.N = N; a.K = K;
   a.W = dW;
+  a.sample_scale = sample_scale; a.rows_per_sample = rows_per_sample;
   return dw_launch_plan(a, r.plan, workspace, (hipStream_t)stream);
+}
+int octic_dense_wgrad_tn(const void* dY, const void* X, int M, int N, int K, int64_t ldy, int64_t ldx, float* dW,
+                         void* workspace, void* stream) {
+  return octic_dense_wgrad_tn_skip(dY, X, M, N, K, ldy, ldx, dW, nullptr, 0, workspace, stream);
 }
 
 // Two weight gradients with the same token rows M and the same K as ONE launch: dW0[N0,K] = dY0^T X0, dW1[N1,K] = dY1^T X1.
 // The tile list is [tiles of problem 0 | tiles of problem 1], row slabs chosen for the sum: the qkv and proj weight gradients
 // of a standard block (3840 x 1280 and 1280 x 1280 at ViT-H) become one 100-tile, two-slab launch - the shape of an MLP
 // weight gradient - instead of a 75-tile one and a 25-tile one that needs eight slabs to fill the chip.
-int octic_dense_wgrad_tn_pair(const void* dY0, const void* X0, int N0, int64_t ldy0, int64_t ldx0, float* dW0,
-                              const void* dY1, const void* X1, int N1, int64_t ldy1, int64_t ldx1, float* dW1, int M, int K,
-                              void* workspace, void* stream) {
+int octic_dense_wgrad_tn_pair_skip(const void* dY0, const void* X0, int N0, int64_t ldy0, int64_t ldx0, float* dW0,
+                                   const void* dY1, const void* X1, int N1, int64_t ldy1, int64_t ldx1, float* dW1, int M, int K,
+                                   const float* sample_scale, int rows_per_sample, void* workspace, void* stream) {
   if (!dY0 || !X0 || !dW0 || !dY1 || !X1 || !dW1 || !workspace) return OCTIC_ENULL;
   if (N1 <= 0) return OCTIC_ESHAPE;
   const int64_t ld0 = ldy0 > ldx0 ? ldy0 : ldx0, ld1 = ldy1 > ldx1 ? ldy1 : ldx1;
   const DwRoute r = dw_route(M, N0, N1, K, ld0 > ld1 ? ld0 : ld1);
   if (r.err) return r.err;
+  if (const int e = dw_mask_status(sample_scale, rows_per_sample, M)) return e;
   if ((ldy0 % 8) || (ldx0 % 8) || (ldy1 % 8) || (ldx1 % 8)) return OCTIC_ESHAPE;
   if ((((uintptr_t)dY0) | ((uintptr_t)X0) | ((uintptr_t)dW0) | ((uintptr_t)dY1) | ((uintptr_t)X1) | ((uintptr_t)dW1)) & 15) return OCTIC_EALIGN;
   DwArgs a = {};
   a.Y = (const bf16*)dY0; a.X = (const bf16*)X0; a.ldy = ldy0; a.ldx = ldx0; a.M = M; a.N = N0; a.K = K; a.W = dW0;
   a.Y1 = (const bf16*)dY1; a.X1 = (const bf16*)X1; a.ldy1 = ldy1; a.ldx1 = ldx1; a.N1 = N1; a.W1 = dW1;
   a.tiles0 = (N0 / DW_T) * r.plan.tiles_k;
+  a.sample_scale = sample_scale; a.rows_per_sample = rows_per_sample;
   return dw_launch_plan(a, r.plan, workspace, (hipStream_t)stream);
+}
+int octic_dense_wgrad_tn_pair(const void* dY0, const void* X0, int N0, int64_t ldy0, int64_t ldx0, float* dW0,
+                              const void* dY1, const void* X1, int N1, int64_t ldy1, int64_t ldx1, float* dW1, int M, int K,
+                              void* workspace, void* stream) {
+  return octic_dense_wgrad_tn_pair_skip(dY0, X0, N0, ldy0, ldx0, dW0, dY1, X1, N1, ldy1, ldx1, dW1, M, K, nullptr, 0, workspace, stream);
 }
 
 }  // extern "C"

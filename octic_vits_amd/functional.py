@@ -451,6 +451,28 @@ def skip_scale(rs, B):
     return rs.detach()
 
 
+# The same factor makes every dY row of a dropped sample exactly zero in the branch's four weight gradients (proj and fc2: the
+# tail's rs * gamma * gout; fc1: gelu' * (0 W2); qkv: the attention backward of dO = 0), so half of what csrc/dense_wgrad.hip
+# reduces over multiplies zeros.  With WGRAD_SKIP_DROPPED the factor travels to the TN kernel, which leaves out the reduction
+# steps that only touch dropped samples - same launch shapes, same bits (include/octic_hip.h: octic_dense_wgrad_tn_skip).
+# Read once at import from OCTIC_WGRAD_SKIP (0 = off).
+def _wgrad_skip_from_env():
+    return os.environ.get("OCTIC_WGRAD_SKIP", "1").strip() != "0"
+
+
+WGRAD_SKIP_DROPPED = _wgrad_skip_from_env()
+
+
+def wgrad_skip_scale(rs, rps, M, rows_to=None):
+    """rs as the TN kernel's sample_scale for a weight gradient over M token rows: the branch's per-sample factor when the
+    switch is on and rs is one float32 entry per sample of rps rows on the GPU with rps * B == M; None for compact rows of a
+    stream (rows_to), the per-row factors of a ragged row tensor (rps 1), a traced value, eval and drop_path 0 (rs None)."""
+    if (not WGRAD_SKIP_DROPPED or rs is None or rows_to is not None or torch.compiler.is_compiling() or not rs.is_cuda
+            or rs.dtype != torch.float32 or rs.dim() != 1 or not rs.is_contiguous() or rps < 2 or rs.numel() * rps != M):
+        return None
+    return rs.detach()
+
+
 class AttnPackedFn(torch.autograd.Function):
     """AttentionD8's core on packed rows (reference d8_layers.py:631-656): qkv [B,T,3*8c] -> o [B,T,8c].  The head
     vectors are gathered from / scattered to the irrep pieces inside the attention kernels, so the four pack / unpack
@@ -861,15 +883,16 @@ def wgrad_slabs(M, N, K):
 WGRAD_HIP = True
 
 
-def _wgrad_lib(g2, x2, wparam=None):
+def _wgrad_lib(g2, x2, wparam=None, sample_scale=None, rps=0):
     """dW = g^T x (f32 result): the hand-written TN kernel wherever it takes the shape, else the BLAS library.  wparam: the
-    parameter this is the gradient of - under DDP the result is written into its bucket view (ops.GRAD_DEST)."""
+    parameter this is the gradient of - under DDP the result is written into its bucket view (ops.GRAD_DEST).
+    sample_scale / rps (wgrad_skip_scale): the stochastic-depth mask of g2's branch, for the hand-written kernel only."""
     M, N, K = g2.shape[0], g2.shape[1], x2.shape[1]
     if (WGRAD_HIP and g2.is_cuda and g2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16
             and g2.stride(1) == 1 and x2.stride(1) == 1
             and ops.dense_wgrad_ok(M, N, K, max(g2.stride(0), x2.stride(0)))):
         dest = ops.grad_dest(wparam, (N, K))
-        dw = ops.dense_wgrad_tn(g2, x2, out=dest)
+        dw = ops.dense_wgrad_tn(g2, x2, out=dest, sample_scale=sample_scale, rows_per_sample=rps if sample_scale is not None else 0)
         if dest is not None:
             ops.grad_written(wparam)
         return dw
@@ -914,34 +937,37 @@ class WgradPair:
     def __init__(self):
         self.pending = None
 
-    def park(self, g2, x2, wparam=None):
+    def park(self, g2, x2, wparam=None, sample_scale=None, rps=0):
         """Postpone dW = g2^T x2; returns the (not yet written) result tensor - the registered destination of `wparam`'s
-        gradient where there is one (ops.GRAD_DEST)."""
+        gradient where there is one (ops.GRAD_DEST).  sample_scale / rps: g2's stochastic-depth mask (wgrad_skip_scale),
+        kept with the operands for whichever launch runs them."""
         shape = (g2.shape[1], x2.shape[1])
         dw = ops.grad_dest(wparam, shape)
         landed = wparam if dw is not None else None
         if dw is None:
             dw = torch.empty(shape, dtype=torch.float32, device=g2.device)
         # (storage, not tensor: a second tensor reference would make AccumulateGrad clone the unwritten gradient)
-        self.pending = (g2, x2, dw.untyped_storage(), dw.data_ptr(), tuple(dw.shape), dw.storage_offset(), landed)
+        self.pending = (g2, x2, dw.untyped_storage(), dw.data_ptr(), tuple(dw.shape), dw.storage_offset(), landed,
+                        sample_scale, rps)
         ops.DEFERRED_FINISHES.add_pair(self)
         return dw
 
     def take(self):
-        """(g2, x2, dw, landed): landed = the parameter whose registered gradient destination dw is, or None."""
+        """(g2, x2, dw, landed, sample_scale, rps): landed = the parameter whose registered gradient destination dw is, or
+        None; sample_scale / rps = the mask park() was given."""
         p, self.pending = self.pending, None
         if p is None:
             return None
-        g2, x2, storage, ptr, shape, offset, landed = p
+        g2, x2, storage, ptr, shape, offset, landed, ss, rps = p
         dw = torch.empty(0, dtype=torch.float32, device=g2.device).set_(storage, offset, shape)
         assert dw.data_ptr() == ptr
-        return g2, x2, dw, landed
+        return g2, x2, dw, landed, ss, rps
 
     def flush(self):
         p = self.take()
         if p is not None:
-            g2, x2, dw, landed = p
-            dw.copy_(_wgrad_lib(g2, x2))
+            g2, x2, dw, landed, ss, rps = p
+            dw.copy_(_wgrad_lib(g2, x2, sample_scale=ss, rps=rps))
             ops.grad_written(landed)
 
 
@@ -1037,20 +1063,25 @@ class DenseLinearNTFn(torch.autograd.Function):
     gradient on csrc/dense_gemm.hip.  deit/vit.py:33 (``self.qkv(x)``)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, cache, tag, pair=None):
+    def forward(ctx, x, w, b, cache, tag, pair=None, rs=None, rps=0):
+        """rs / rps: the stochastic-depth factor of the branch this projection opens and the rows per entry, where EVERYTHING
+        computed from the output is multiplied by it (the qkv projection of vit.Attention.forward_fused) - the cotangent rows
+        of a dropped sample are then zero and the weight gradient may skip them (wgrad_skip_scale)."""
         ctx.pair = pair
         ctx.wparam = w
         xb = _c(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16))
         wb, wt = cache.get_nt(w, b, ("d" + tag) in DENSE_HIP and ctx.needs_input_grad[0])
         x2 = xb.reshape(-1, wb.shape[1])
         y = _gemm_fwd(tag, x2, wb, b, cache, "plain", _tok(x.shape))
-        ctx.save_for_backward(x2, wb, wt)          # wt is None unless the input gradient is routed to the HIP kernel
+        ss = wgrad_skip_scale(rs, rps, x2.shape[0])
+        ctx.rps = rps
+        ctx.save_for_backward(x2, wb, wt, ss)      # wt is None unless the input gradient is routed to the HIP kernel
         ctx.meta = (b is not None, x.dtype, x.shape, tag)
         return y.view(*x.shape[:-1], wb.shape[0])
 
     @staticmethod
     def backward(ctx, gy):
-        x2, wb, wt = ctx.saved_tensors
+        x2, wb, wt, ss = ctx.saved_tensors
         has_b, x_dtype, x_shape, tag = ctx.meta
         g2 = _c(gy).reshape(-1, wb.shape[0])
         gx = _gemm_dgrad(g2, wt, wb, x_shape, x_dtype) if ctx.needs_input_grad[0] else None
@@ -1063,13 +1094,17 @@ class DenseLinearNTFn(torch.autograd.Function):
             pg, px = pair.pending[0], pair.pending[1]
             if (_pair_ready(pair, g2, x2) and pg.shape[0] == g2.shape[0] and px.shape[1] == x2.shape[1]
                     and ops.dense_wgrad_pair_ok(g2.shape[0], g2.shape[1], pg.shape[1], x2.shape[1])):
-                pg, px, pdw, landed = pair.take()
+                pg, px, pdw, landed, pss, prps = pair.take()
                 dest = ops.grad_dest(ctx.wparam, (g2.shape[1], x2.shape[1]))
-                dw, _ = ops.dense_wgrad_tn_pair(g2, x2, pg, px, dw1=pdw, dw0=dest)
+                # one mask for both problems: only where both halves carry the same factors
+                both = ss if (ss is not None and pss is not None and prps == ctx.rps and pss.data_ptr() == ss.data_ptr()
+                              and pss.numel() == ss.numel()) else None
+                dw, _ = ops.dense_wgrad_tn_pair(g2, x2, pg, px, dw1=pdw, dw0=dest, sample_scale=both,
+                                                rows_per_sample=ctx.rps if both is not None else 0)
                 ops.grad_written(landed, ctx.wparam if dest is not None else None)
-                return gx, dw, gb, None, None, None
+                return gx, dw, gb, None, None, None, None, None
             pair.flush()
-        return gx, _wgrad_lib(g2, x2, ctx.wparam), gb, None, None, None
+        return gx, _wgrad_lib(g2, x2, ctx.wparam, ss, ctx.rps), gb, None, None, None, None, None
 
 
 class DenseProjResidFn(torch.autograd.Function):
@@ -1100,10 +1135,12 @@ class DenseProjResidFn(torch.autograd.Function):
         gx, gy, dgamma, colsum, dnw, dnb = _resid_tail_bwd(ctx, tail, gout, gyn,
                                                            ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
         ga = _gemm_dgrad(gy, wt, wb, a_shape, a_dtype) if ctx.needs_input_grad[1] else None
+        rps = ctx.tail[1]
+        ss = wgrad_skip_scale(tail[2], rps, gy.shape[0], ctx.rows_to)     # gy = rs * gamma * gout: zero rows where rs is 0
         if _pair_ready(ctx.pair, gy, a2) and ops.dense_wgrad_ok(gy.shape[0], gy.shape[1], a2.shape[1]):
-            dw = ctx.pair.park(gy, a2, ctx.wparam)   # written by the qkv weight gradient's launch (or at the end of the pass)
+            dw = ctx.pair.park(gy, a2, ctx.wparam, ss, rps)   # written by the qkv weight gradient's launch (or at the end of the pass)
         else:
-            dw = _wgrad_lib(gy, a2, ctx.wparam)
+            dw = _wgrad_lib(gy, a2, ctx.wparam, ss, rps)
         return gx, ga, dw, colsum, dgamma, None, None, None, dnw, dnb, None, None, None, None
 
 
@@ -1161,8 +1198,10 @@ class DenseMlpFn(torch.autograd.Function):
                 dh, db1 = ops.dense_gemm_nt(gbr, w2t, md, h=h, name="dense_nt_kernel<dgelu>", tokens=_tok(y_shape)), None
         else:
             dh, db1 = ops.dense_gelu_bwd(h, _mm_lib(gbr, w2b), want_colsum=has_b1)
-        gw2 = _wgrad_lib(gbr, a, ctx.wparams[1])
-        gw1 = _wgrad_lib(dh, y2, ctx.wparams[0])
+        rps = ctx.tail[1]
+        ss = wgrad_skip_scale(tail[2], rps, gbr.shape[0], ctx.rows_to)    # gbr = rs * gamma * gout, dh = gelu' * (gbr W2)
+        gw2 = _wgrad_lib(gbr, a, ctx.wparams[1], ss, rps)
+        gw1 = _wgrad_lib(dh, y2, ctx.wparams[0], ss, rps)
         gy = _gemm_dgrad(dh, w1t, w1b, y_shape, y_dtype) if ctx.needs_input_grad[0] else None
         return gy, gx, gw1, db1, gw2, db2, dgamma, None, None, None, None, dnw, dnb, None, None, None
 

@@ -345,20 +345,38 @@ def grad_written(*params):
                 w(prm.data_ptr())
 
 
-def dense_wgrad_tn(dy, x, name=None, out=None):
-    """dW[N,K] = dy[M,N]^T @ x[M,K] in f32 on csrc/dense_wgrad.hip (out: write it there)."""
+def _wgrad_sample_scale(sample_scale, rows_per_sample, M, ref):
+    """The stochastic-depth mask of a TN launch as the kernel reads it (octic_dense_wgrad_tn_skip): (None, 0), or the
+    contiguous float32 factors - one per sample of rows_per_sample token rows - on the operands' device.  Whether
+    rows_per_sample divides M is the library's check (OCTIC_ESHAPE)."""
+    if sample_scale is None:
+        return None, 0
+    rps = int(rows_per_sample)
+    if (sample_scale.dtype != torch.float32 or sample_scale.device != ref.device or not sample_scale.is_contiguous()
+            or (rps > 0 and M % rps == 0 and sample_scale.numel() != M // rps)):
+        raise ValueError("dense_wgrad_tn: sample_scale must be a contiguous float32 tensor of M / rows_per_sample entries on "
+                         "the operands' device")
+    return sample_scale, rps
+
+
+def dense_wgrad_tn(dy, x, name=None, out=None, sample_scale=None, rows_per_sample=0):
+    """dW[N,K] = dy[M,N]^T @ x[M,K] in f32 on csrc/dense_wgrad.hip (out: write it there).  sample_scale ([M / rows_per_sample]
+    f32): the stochastic-depth factor of the branch dy belongs to - a 0 promises that the sample's dy rows are zero, and the
+    wide kernel leaves the reduction steps out that only touch such samples (same result; include/octic_hip.h)."""
     _require_cuda(dy)
     M, N = dy.shape
     K = x.shape[1]
     if dy.stride(1) != 1 or x.stride(1) != 1 or x.shape[0] != M:
         raise ValueError("dense_wgrad_tn: operands must be [M,N] / [M,K] row-major")
+    ss, rps = _wgrad_sample_scale(sample_scale, rows_per_sample, M, dy)
     need = int(lib().octic_dense_wgrad_workspace_bytes(M, N, K))
     ws = _DW_WS.get(dy.device)
     if ws is None or ws.numel() < need:          # one workspace per device: launches on a stream are serial
         ws = _DW_WS[dy.device] = torch.zeros(need, dtype=torch.uint8, device=dy.device)
     dw = out if out is not None else torch.empty((N, K), dtype=torch.float32, device=dy.device)
     t = KERNEL_TIMER.start()
-    check(lib().octic_dense_wgrad_tn(_p(dy), _p(x), M, N, K, dy.stride(0), x.stride(0), _p(dw), _p(ws), _stream(dy)))
+    check(lib().octic_dense_wgrad_tn_skip(_p(dy), _p(x), M, N, K, dy.stride(0), x.stride(0), _p(dw), _p(ss), rps, _p(ws),
+                                          _stream(dy)))
     KERNEL_TIMER.stop(t, name or f"dense_tn_kernel<{N}x{K}>", 2 * (M * N + M * K) + 4 * N * K, 2.0 * M * N * K)
     return dw
 
@@ -369,15 +387,17 @@ def dense_wgrad_pair_ok(M, N0, N1, K):
             and ((N0 + N1) // 256) * (K // 256) <= DENSE_WGRAD_MAX_BLOCKS)
 
 
-def dense_wgrad_tn_pair(dy0, x0, dy1, x1, dw1=None, dw0=None):
+def dense_wgrad_tn_pair(dy0, x0, dy1, x1, dw1=None, dw0=None, sample_scale=None, rows_per_sample=0):
     """(dW0 [N0,K], dW1 [N1,K]) = (dy0^T x0, dy1^T x1) as ONE launch of csrc/dense_wgrad.hip (same M, same K): the qkv and proj
     weight gradients of a standard block.  dw1: write the second result into this (already handed-out) tensor; dw0: a
-    registered destination of the first (grad_dest)."""
+    registered destination of the first (grad_dest).  sample_scale / rows_per_sample: ONE mask for both problems (qkv and proj
+    belong to the same branch), as in dense_wgrad_tn."""
     _require_cuda(dy0)
     M, N0 = dy0.shape
     N1, K = dy1.shape[1], x0.shape[1]
     if not (dy1.shape[0] == M and x0.shape[0] == M and x1.shape == (M, K) and all(t.stride(1) == 1 for t in (dy0, x0, dy1, x1))):
         raise ValueError("dense_wgrad_tn_pair: operands must be [M,N0] / [M,K] / [M,N1] / [M,K] row-major")
+    ss, rps = _wgrad_sample_scale(sample_scale, rows_per_sample, M, dy0)
     need = int(lib().octic_dense_wgrad_pair_workspace_bytes(M, N0, N1, K))
     ws = _DW_WS.get(dy0.device)
     if ws is None or ws.numel() < need:
@@ -387,8 +407,8 @@ def dense_wgrad_tn_pair(dy0, x0, dy1, x1, dw1=None, dw0=None):
     if dw1 is None:
         dw1 = torch.empty((N1, K), dtype=torch.float32, device=dy0.device)
     t = KERNEL_TIMER.start()
-    check(lib().octic_dense_wgrad_tn_pair(_p(dy0), _p(x0), N0, dy0.stride(0), x0.stride(0), _p(dw0), _p(dy1), _p(x1), N1,
-                                          dy1.stride(0), x1.stride(0), _p(dw1), M, K, _p(ws), _stream(dy0)))
+    check(lib().octic_dense_wgrad_tn_pair_skip(_p(dy0), _p(x0), N0, dy0.stride(0), x0.stride(0), _p(dw0), _p(dy1), _p(x1), N1,
+                                               dy1.stride(0), x1.stride(0), _p(dw1), M, K, _p(ss), rps, _p(ws), _stream(dy0)))
     KERNEL_TIMER.stop(t, f"dense_tn_kernel<{N0}+{N1}x{K}>", 2 * M * (N0 + N1 + 2 * K) + 4 * (N0 + N1) * K, 2.0 * M * (N0 + N1) * K)
     return dw0, dw1
 

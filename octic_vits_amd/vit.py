@@ -122,7 +122,11 @@ class Attention(nn.Module):
         hd = C // self.num_heads
         bf = dtype == torch.bfloat16
         if bf and _OF.dense_hip_ok(y, self.qkv.weight) and ({"qkv", "dqkv"} & _OF.DENSE_HIP):
-            qkv = _OF.DenseLinearNTFn.apply(y, self.qkv.weight, self.qkv.bias, self._c1, "qkv", self._wgpair)
+            # rs multiplies everything that is computed from qkv (the tail below): its cotangent rows are zero for the samples rs
+            # drops and the weight gradient may skip them - whole samples of a plain batch only (functional.wgrad_skip_scale)
+            plain = rows_to is None and not (_OF.RAGGED is not None and _OF.RAGGED.matches(y))
+            qkv = _OF.DenseLinearNTFn.apply(y, self.qkv.weight, self.qkv.bias, self._c1, "qkv", self._wgpair,
+                                            rs if plain else None, _rows_per_scale(y, rs) if plain else 0)
         else:
             qkv = _OF.DenseLinearFn.apply(y, self.qkv.weight, self.qkv.bias, dtype, self._c1)
         rag = _OF.RAGGED
