@@ -545,7 +545,11 @@ int octic_dense_prep_batch(const octic_dense_prep_item* items_dev, int n_items, 
  * The four projections of the reference's standard block (deit/vit.py:14-56 Attention.qkv / .proj, timm Mlp fc1 / fc2
  * used by Layer_scale_init_Block, deit/vit.py:90-134) and their input gradients are "NT" problems
  *     C[M,N] = A[M,K] . B[N,K]^T          A, B bf16 with K contiguous (lda, ldb = row strides in elements),
- * M token rows, f32 accumulation on v_mfma_f32_16x16x32_bf16, K % 128 == 0, N % 4 == 0.  `mode` selects the fused tail:
+ * M token rows, f32 accumulation on v_mfma_f32_16x16x32_bf16.  Taken: K % 64 == 0 with K >= 128 (two K-tiles of 64), N % 8 == 0,
+ * lda, ldb, ldc % 8 == 0 (the epilogues move 16 bytes = 8 bf16 of a row of C / C2 / H per lane: a smaller ldc would misalign
+ * them), A and B 16-byte aligned, M * lda and N * ldb below 2^30 elements (32-bit buffer offsets); anything else is
+ * OCTIC_ESHAPE / OCTIC_EALIGN before any launch.  X / OUT of mode 2 and the colsum slabs are dense (row stride N).
+ * `mode` selects the fused tail:
  *   0 PLAIN : C = acc + bias                                   (qkv forward; input gradients: bias = NULL)
  *   1 GELU  : C = acc + bias (pre-activation, kept for backward), C2 = gelu(C) exact erf (fc1 + nn.GELU, vit.py:131-134)
  *   2 RESID : C = acc + bias (branch output, kept for d gamma),  OUT = X + rs[row / rows_per_sample] * gamma * C

@@ -217,7 +217,22 @@ def route_override(knob: int, value: int) -> int:
     if old < 0:
         raise ValueError(f"octic_route_override: unknown knob {knob}")
     _PLANS.clear()
+    for drop in _ON_OVERRIDE:
+        drop()
     return old
+
+
+# What else was sized or chosen under the override table and so must not outlive it: callables run by every route_override
+# (ops registers the drop of its split-K workspace cache - a workspace sized for a plan that splits nothing is 256 bytes, and a
+# launch planned under a forced split would put tickets and slabs past its end).  Nothing here runs per launch.
+_ON_OVERRIDE = []
+
+
+def on_route_override(drop):
+    """Run drop() after every route_override, with _PLANS already empty."""
+    if drop not in _ON_OVERRIDE:
+        _ON_OVERRIDE.append(drop)
+    return drop
 
 
 # The answers of the library's plan queries by (query, arguments): the eager step asks per call, and without this the attention

@@ -1100,7 +1100,8 @@ int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K
                                const float* X, float* OUT, const void* H, float* colsum, void* workspace, int tokens,
                                void* stream) {
   if (!A || !B || !C) return OCTIC_ENULL;
-  if (M <= 0 || N <= 0 || K <= 0 || (K % DG_BK) || K < 2 * DG_BK || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 4)) return OCTIC_ESHAPE;
+  // (ldc % 8: every epilogue moves 8 bf16 = 16 bytes of a row of C / C2 / H per lane, from column offsets that are multiples of 8)
+  if (M <= 0 || N <= 0 || K <= 0 || (K % DG_BK) || K < 2 * DG_BK || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OCTIC_ESHAPE;
   // buffer descriptors and per-lane offsets are 32-bit: operands of 2 GiB or more are refused (callers fall back to
   // the BLAS library) instead of wrapping
   if ((int64_t)M * lda * 2 >= (1ll << 31) || (int64_t)N * ldb * 2 >= (1ll << 31)) return OCTIC_ESHAPE;

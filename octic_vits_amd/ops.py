@@ -1135,10 +1135,14 @@ def dense_gelu_bwd(h, g, want_colsum=True):
 
 # ------------------------------------------------------------------------------------------ dense MFMA GEMMs
 _DG_WS = {}
+# octic_dense_gemm_workspace_bytes depends on the override table (OCTIC_ROUTE_DENSE_SPLIT makes a problem split that otherwise
+# would not): a workspace sized under one table never serves a launch planned under another
+_lib.on_route_override(_DG_WS.clear)
 
 
 def _dense_ws(M, N, K, dev):
-    """Split-K workspace of one (M,N,K) problem, cached per stream-ordered use (launches on one stream are serial)."""
+    """Split-K workspace of one (M,N,K) problem, cached per stream-ordered use (launches on one stream are serial) until
+    the next _lib.route_override."""
     key = (M, N, K, dev)
     ws = _DG_WS.get(key)
     if ws is None:
