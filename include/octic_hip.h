@@ -94,6 +94,17 @@ int octic_gelu_d8_fwd(const octic_view* x, const octic_view* y, int64_t M, int c
 /* gin = F( gelu'(F^-1 x) * F^-1 g )   (d8_gelu.py:283-321) */
 int octic_gelu_d8_bwd(const octic_view* g, const octic_view* x, const octic_view* gin, int64_t M, int c,
                       int dtype, void* stream);
+/* The same two with the stochastic-depth factor of the branch they sit in: sample_scale[M / rows_per_sample] (f32, device),
+ * one entry per sample of rows_per_sample consecutive token rows; NULL = the plain call.  CONTRACT, for every kernel the
+ * entry points can launch (four or eight channels per thread, bf16 and f32): for a sample whose factor is exactly 0 the
+ * kernel reads NONE of its input rows (x; g and x in the backward) and writes +0 to every element of its output rows (y;
+ * gin) - the caller may hand over rows that were never written, and may rely on the zeros.  Every other row is bit for bit
+ * what the plain call writes.  Same launch shape as the plain call (nothing depends on the mask's values on the host).
+ * OCTIC_ESHAPE when the mask is given and rows_per_sample <= 0 or M % rows_per_sample != 0.                              */
+int octic_gelu_d8_fwd_skip(const octic_view* x, const octic_view* y, int64_t M, int c, int dtype,
+                           const float* sample_scale, int64_t rows_per_sample, void* stream);
+int octic_gelu_d8_bwd_skip(const octic_view* g, const octic_view* x, const octic_view* gin, int64_t M, int c, int dtype,
+                           const float* sample_scale, int64_t rows_per_sample, void* stream);
 
 /* ---- LayerNormD8 (+AffineD8) -----------------------------------------------------------------
  * Replaces LayerNormD8.forward (d8_layers.py:166-186): per-segment mean removal, one shared
@@ -152,6 +163,20 @@ int octic_linear_d8_fwd(const octic_view* x, const void* const w[5], const float
                         const octic_view* resid, const float* rs, int64_t rows_per_sample,
                         const float* const cs[5], int64_t M, int cin, int cout, int dtype, int out_dtype,
                         void* stream);
+/* The same with the stochastic-depth factor of the branch the GEMM sits in: sample_scale[M / skip_rows_per_sample] (f32,
+ * device), one entry per sample of skip_rows_per_sample consecutive token rows; NULL = the plain call.  CONTRACT: a factor of
+ * exactly 0 says that NOBODY will read the output rows of that sample; the kernel may leave those rows unwritten and the sample's
+ * input rows unread.  Every row of a sample whose factor is not 0 is bit for bit what the unmasked launch writes.  The W-stationary
+ * kernel honours the mask per 32-row tile (a tile is left out iff every token row it covers belongs to samples with factor 0)
+ * and deals the remaining tiles evenly over its workgroups; a launch the plan routes to the ring or the register-staged kernel
+ * computes every row, as does one with more than 4096 row tiles in an irrep group - the contract allows both.  The plan
+ * (octic_linear_d8_plan) and the launch shape do not depend on the mask.  OCTIC_ESHAPE for a masked call that also carries a
+ * residual, rs or a non-NULL cs array (a fused tail writes the stream itself: every row has a reader), or with
+ * skip_rows_per_sample <= 0 or M % skip_rows_per_sample != 0.                                                              */
+int octic_linear_d8_fwd_skip(const octic_view* x, const void* const w[5], const float* bias, const octic_view* y,
+                             const octic_view* resid, const float* rs, int64_t rows_per_sample,
+                             const float* const cs[5], int64_t M, int cin, int cout, int dtype, int out_dtype,
+                             const float* sample_scale, int64_t skip_rows_per_sample, void* stream);
 
 /* Compute-dtype copies of the f32 master weights in ONE launch per layer: wb = [W_A1|W_A2|W_B1|W_B2|W_E]
  * (forward), wt = each matrix transposed with the layer-scale folded in, wt_g[k][n] = cs_g[n] W_g[n][k]
@@ -339,6 +364,12 @@ enum {
   OCTIC_ATTN_BWD_F32 = 3           /* the float32 dq + dkv pair                                                             */
 };
 int octic_attn_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int64_t ld_grad, int out[4]);
+/* The same query for stochastic depth: which of the planned kernels SKIP a sample whose sample_scale is 0 - read none of its
+ * operands (q, k, v, and o, dout in the backward) and store +0 - as opposed to computing it, which the contract of the *_skip
+ * entry points also allows.  A caller that leaves operand rows of a dropped sample unwritten needs the former.  out[0] = the
+ * largest batch B at which the forward skips (0: it never does; fwd_os_kernel alone, up to its 512-sample order table),
+ * out[1] = 1 when a backward call with phase 3 skips, out[2] = 1 when the phase-1 + phase-2 pair skips, out[3] = 0.          */
+int octic_attn_skip_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int64_t ld_grad, int out[4]);
 
 /* ---- attention core: samples dropped by stochastic depth ------------------------------------------
  * The four bf16 entry points with one more argument in front of `stream`: sample_scale, nullable, B floats on the

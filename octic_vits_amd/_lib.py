@@ -42,6 +42,8 @@ _PROTOS = {
     "octic_route_override": (c_int, [c_int, c_int]),
     "octic_gelu_d8_fwd": (c_int, [VP, VP, c_i64, c_int, c_int, c_void_p]),
     "octic_gelu_d8_bwd": (c_int, [VP, VP, VP, c_i64, c_int, c_int, c_void_p]),
+    "octic_gelu_d8_fwd_skip": (c_int, [VP, VP, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p]),
+    "octic_gelu_d8_bwd_skip": (c_int, [VP, VP, VP, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p]),
     "octic_layernorm_d8_fwd": (c_int, [VP, VP, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, c_int, c_void_p]),
     "octic_layernorm_d8_bwd_blocks": (c_int, [c_i64]),
     "octic_layernorm_d8_bwd": (c_int, [VP, VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_int, c_int, c_void_p]),
@@ -52,6 +54,8 @@ _PROTOS = {
     "octic_sample_blocks": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p]),
     "octic_linear_d8_fwd": (c_int, [VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int,
                                     c_int, c_int, c_void_p]),
+    "octic_linear_d8_fwd_skip": (c_int, [VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int,
+                                         c_int, c_int, c_void_p, c_i64, c_void_p]),
     "octic_linear_d8_tile_n": (c_int, [c_i64, c_int, c_int]),
     "octic_linear_d8_plan": (c_int, [c_i64, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "octic_linear_d8_ring_order": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -121,6 +125,7 @@ _PROTOS = {
     "octic_attn_fwd_f32": (c_int, [c_void_p] * 5 + [c_i64, c_int, c_int, c_int] + [c_i64] * 6 + [c_float, c_void_p]),
     "octic_attn_bwd_f32": (c_int, [c_void_p] * 10 + [c_i64, c_int, c_int, c_int] + [c_i64] * 9 + [c_float, c_int, c_void_p]),
     "octic_attn_plan": (c_int, [c_int, c_int, c_int, c_i64, c_i64, c_i64, ctypes.POINTER(c_int)]),
+    "octic_attn_skip_plan": (c_int, [c_int, c_int, c_int, c_i64, c_i64, c_i64, ctypes.POINTER(c_int)]),
     "octic_attn_pack_heads": (c_int, [VP, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p]),
     "octic_attn_unpack_heads": (c_int, [c_void_p, VP, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p]),
     "octic_handoff_cat_fwd": (c_int, [VP, c_void_p, c_i64, c_int, c_int, c_void_p]),

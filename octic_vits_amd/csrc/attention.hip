@@ -1033,6 +1033,7 @@ int attn_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int64_t l
     p.fwd_waves = !one_shot ? W8 : nt == a80::MAXNT ? a80::WAVES : nt < 4 ? 4 : nt;
     p.fwd_lds = !one_shot ? a80::fwd_lds(nt) : nt == a80::MAXNT ? a80::fwd_os_lds(nt) : a80::fwd_oss_lds(nt);
     p.fwd_dbg = route(OCTIC_ROUTE_ATTN_ONLINE) >> 4;
+    p.fwd_skip_max_b = one_shot && nt == a80::MAXNT ? a80::kSkipMaxB : 0;   // fwd_os_kernel alone, and only while its order table holds the batch
   } else if (!stream && nt <= 9 && extra <= 2 && persist <= lds_max && (int)(kimg / 1024) <= 8 * W8 &&
              (T * 2 * KS + W8 * 64 - 1) / (W8 * 64) <= 6 && (T - 1) * sT * 2 + hd * 2 < 0x7FFFFFF0ll) {
     // persistent forward: the images and the shared rows' partials fit, at most 8 K DMA instructions and 6 V chunks per
@@ -1060,6 +1061,7 @@ int attn_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int64_t l
   p.dkv_lds = p.dq_lds + 4 * kStreamBlk * sizeof(float);                    // <= 69 KiB (head_dim 128)
   if (!stream && dq <= lds_max && dkv <= lds_max) {
     p.pair = OCTIC_ATTN_BWD_PAIR;
+    p.pair_skips = true;                                                    // attn_bwd_dq_kernel / attn_bwd_dkv_kernel leave early
     p.pair_waves = W;
     p.dq_lds = dq;
     p.dkv_lds = dkv;
@@ -1070,11 +1072,13 @@ int attn_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int64_t l
   if (!stream && hd80 && !route(OCTIC_ROUTE_ATTN_BWD_PAIR) && (T == a80::BW_T || (T > 192 && T <= 256) || T <= 64) &&
       off32(sT) && off32(oT) && off32(gT)) {
     p.bwd = OCTIC_ATTN_BWD_SINGLE;
+    p.bwd_skips = true;                                                     // every csrc/attn80_bwd.hip kernel (skip_unit)
     p.bwd_waves = T <= 64 ? nt : a80::WAVES;
     p.bwd_lds = T <= 64 ? a80::bwd_small_lds(nt) : a80::BW_LDS;
   } else {
     p.bwd = p.pair;
     p.bwd_waves = p.pair_waves;
+    p.bwd_skips = p.pair_skips;
   }
   *plan = p;
   return OCTIC_OK;
@@ -1154,6 +1158,14 @@ int octic_attn_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int
   AttnPlan p;
   if (const int rc = attn_plan(dtype, T, hd, ld_in, ld_out, ld_grad, &p)) return rc;
   out[0] = p.fwd; out[1] = p.fwd_waves; out[2] = p.bwd; out[3] = p.bwd_waves;
+  return OCTIC_OK;
+}
+
+int octic_attn_skip_plan(int dtype, int T, int hd, int64_t ld_in, int64_t ld_out, int64_t ld_grad, int out[4]) {
+  if (!out) return OCTIC_ENULL;
+  AttnPlan p;
+  if (const int rc = attn_plan(dtype, T, hd, ld_in, ld_out, ld_grad, &p)) return rc;
+  out[0] = p.fwd_skip_max_b; out[1] = p.bwd_skips; out[2] = p.pair_skips; out[3] = 0;
   return OCTIC_OK;
 }
 

@@ -818,7 +818,7 @@ int attn80_fwd_launch(const AttnArgs& a_, int64_t B, const AttnPlan& p, hipStrea
   const int grid = units < cus ? units : cus;
   if (p.fwd == OCTIC_ATTN_FWD_A80_ONLINE) fwd_kernel<<<grid, p.fwd_waves * 64, p.fwd_lds, s>>>(a, nt, units);
   else if (nt == MAXNT) {
-    if (B > kSkipMaxB) a.sample_scale = nullptr;                  // the order table holds 512 samples: larger launches do not skip
+    if (B > p.fwd_skip_max_b) a.sample_scale = nullptr;           // the order table holds 512 samples: larger launches do not skip
     fwd_os_kernel<<<grid, p.fwd_waves * 64, p.fwd_lds, s>>>(a, units);
   } else {
     const int wgs = cus * (8 / p.fwd_waves);                      // short sequences: two workgroups per CU (8 waves)

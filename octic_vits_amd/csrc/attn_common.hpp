@@ -350,6 +350,11 @@ struct AttnPlan {
   size_t bwd_lds;              // SINGLE only
   int pair, pair_waves;        // phases 1 and 2 (and phase 3 unless bwd is SINGLE): OCTIC_ATTN_BWD_PAIR | STREAM | F32
   size_t dq_lds, dkv_lds;
+  // Stochastic depth (AttnArgs::sample_scale): which of the planned kernels SKIP a sample whose factor is 0, i.e. read none of
+  // its operands and store +0 - the others compute the sample.  fwd_skip_max_b: the forward skips in launches of up to that
+  // many samples (0: never); bwd_skips / pair_skips: the phase-3 kernel / the phase-1 + phase-2 pair.  octic_attn_skip_plan.
+  int fwd_skip_max_b;
+  bool bwd_skips, pair_skips;
 };
 // Pure host arithmetic, no HIP call.  ld_*: token strides in elements of q/k/v, o/dout, dq/dk/dv (0: hd).  OCTIC_ESHAPE for
 // the (T, hd) no kernel takes - the shape check of every attention entry point.

@@ -28,13 +28,39 @@ template <> struct LoadCH<bf16, 4> {
   static __device__ inline void store(bf16* p, const float v[4]) { *(bf16x4*)p = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]}; }
 };
 
-template <typename T>
-__global__ __launch_bounds__(256, 4) void gelu_fwd4_kernel(View x, View y, int64_t M, int c) {
+// Stochastic depth on the D8-GELU launches (octic_gelu_d8_*_skip): rows of a sample whose factor is exactly 0 are not read,
+// their output rows get +0.  Where registers allow, the factor of the NEXT grid-stride item is fetched before the current
+// item's loads, so the kept rows do not wait for a dependent round trip (only a thread's first item does).
+struct RowMask {
+  const float* ss;
+  int64_t rps;
+  bool small;   // every row index fits 32 bits: one 32-bit division per item instead of a 64-bit one
+  __device__ inline float at(int64_t m) const {
+    return ss[small ? (int64_t)((uint32_t)m / (uint32_t)rps) : m / rps];
+  }
+};
+
+template <typename T, bool SKIP>
+__global__ __launch_bounds__(256, 4) void gelu_fwd4_kernel(View x, View y, int64_t M, int c, RowMask mask) {
   const int c4 = c >> 2;
   const int64_t total = M * c4;
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+  const int64_t step = (int64_t)gridDim.x * 256;
+  int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  float f_next = 1.f;
+  if constexpr (SKIP) f_next = idx < total ? mask.at(idx / c4) : 1.f;
+  for (; idx < total; idx += step) {
     const int64_t m = idx / c4;
     const int j = (int)(idx - m * c4) << 2;
+    const float f_row = f_next;
+    if constexpr (SKIP) f_next = idx + step < total ? mask.at((idx + step) / c4) : 1.f;
+    if (SKIP && f_row == 0.f) {   // a dropped sample: nothing read, +0 written (its own pointer table: the live path keeps its schedule)
+      T* pz[8];
+      comp_ptrs<T>(y, m, j, c, pz);
+      const float z[4] = {};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) LoadCH<T, 4>::store(pz[i], z);
+      continue;
+    }
     T *px[8], *py[8];
     comp_ptrs<T>(x, m, j, c, px);
     comp_ptrs<T>(y, m, j, c, py);
@@ -58,13 +84,26 @@ __global__ __launch_bounds__(256, 4) void gelu_fwd4_kernel(View x, View y, int64
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256, 4) void gelu_bwd4_kernel(View g, View x, View gin, int64_t M, int c) {
+template <typename T, bool SKIP>
+__global__ __launch_bounds__(256, 4) void gelu_bwd4_kernel(View g, View x, View gin, int64_t M, int c, RowMask mask) {
   const int c4 = c >> 2;
   const int64_t total = M * c4;
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+  const int64_t step = (int64_t)gridDim.x * 256;
+  int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  for (; idx < total; idx += step) {
     const int64_t m = idx / c4;
     const int j = (int)(idx - m * c4) << 2;
+    // (no look-ahead here: the kernel sits at its 128-register budget, and a factor carried over the item's arithmetic costs two
+    // scratch stores and a load per item; fetched here, its latency runs beside the address arithmetic of the 16 loads)
+    const float f_row = SKIP ? mask.at(m) : 1.f;
+    if (SKIP && f_row == 0.f) {   // a dropped sample: nothing read, +0 written (its own pointer table: the live path keeps its schedule)
+      T* pz[8];
+      comp_ptrs<T>(gin, m, j, c, pz);
+      const float z[4] = {};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) LoadCH<T, 4>::store(pz[i], z);
+      continue;
+    }
     T *px[8], *pg[8], *po[8];
     comp_ptrs<T>(x, m, j, c, px);
     comp_ptrs<T>(g, m, j, c, pg);
@@ -96,13 +135,27 @@ __global__ __launch_bounds__(256, 4) void gelu_bwd4_kernel(View g, View x, View 
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void gelu_fwd_kernel(View x, View y, int64_t M, int c) {
+template <typename T, bool SKIP>
+__global__ __launch_bounds__(256) void gelu_fwd_kernel(View x, View y, int64_t M, int c, RowMask mask) {
   const int c8 = c >> 3;
   const int64_t total = M * c8;
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+  const int64_t step = (int64_t)gridDim.x * 256;
+  int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  float f_next = 1.f;
+  if constexpr (SKIP) f_next = idx < total ? mask.at(idx / c8) : 1.f;
+  for (; idx < total; idx += step) {
     const int64_t m = idx / c8;
     const int j = (int)(idx - m * c8) << 3;
+    const float f_row = f_next;
+    if constexpr (SKIP) f_next = idx + step < total ? mask.at((idx + step) / c8) : 1.f;
+    if (SKIP && f_row == 0.f) {   // a dropped sample: nothing read, +0 written (its own pointer table: the live path keeps its schedule)
+      T* pz[8];
+      comp_ptrs<T>(y, m, j, c, pz);
+      const float z[8] = {};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) store8<T>(pz[i], z);
+      continue;
+    }
     T *px[8], *py[8];
     comp_ptrs<T>(x, m, j, c, px);
     comp_ptrs<T>(y, m, j, c, py);
@@ -126,13 +179,27 @@ __global__ __launch_bounds__(256) void gelu_fwd_kernel(View x, View y, int64_t M
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void gelu_bwd_kernel(View g, View x, View gin, int64_t M, int c) {
+template <typename T, bool SKIP>
+__global__ __launch_bounds__(256) void gelu_bwd_kernel(View g, View x, View gin, int64_t M, int c, RowMask mask) {
   const int c8 = c >> 3;
   const int64_t total = M * c8;
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+  const int64_t step = (int64_t)gridDim.x * 256;
+  int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  float f_next = 1.f;
+  if constexpr (SKIP) f_next = idx < total ? mask.at(idx / c8) : 1.f;
+  for (; idx < total; idx += step) {
     const int64_t m = idx / c8;
     const int j = (int)(idx - m * c8) << 3;
+    const float f_row = f_next;
+    if constexpr (SKIP) f_next = idx + step < total ? mask.at((idx + step) / c8) : 1.f;
+    if (SKIP && f_row == 0.f) {   // a dropped sample: nothing read, +0 written (its own pointer table: the live path keeps its schedule)
+      T* pz[8];
+      comp_ptrs<T>(gin, m, j, c, pz);
+      const float z[8] = {};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) store8<T>(pz[i], z);
+      continue;
+    }
     T *px[8], *pg[8], *po[8];
     comp_ptrs<T>(x, m, j, c, px);
     comp_ptrs<T>(g, m, j, c, pg);
@@ -690,42 +757,72 @@ const char* octic_strerror(int code) {
   }
 }
 
-int octic_gelu_d8_fwd(const octic_view* x, const octic_view* y, int64_t M, int c, int dtype, void* stream) {
+// sample_scale / rows_per_sample of the *_skip entry points -> the kernels' RowMask; OCTIC_ESHAPE where the rows are not whole samples
+static int gelu_mask(const float* sample_scale, int64_t rows_per_sample, int64_t M, RowMask* mask) {
+  if (sample_scale && (rows_per_sample <= 0 || M % rows_per_sample != 0)) return OCTIC_ESHAPE;
+  *mask = RowMask{sample_scale, sample_scale ? rows_per_sample : 1, M < (1ll << 31)};
+  return OCTIC_OK;
+}
+
+int octic_gelu_d8_fwd_skip(const octic_view* x, const octic_view* y, int64_t M, int c, int dtype, const float* sample_scale,
+                           int64_t rows_per_sample, void* stream) {
   int e;
   if ((e = check_c(c)) || (e = check_view(x, c, dtype)) || (e = check_view(y, c, dtype))) return e;
   if (M <= 0) return OCTIC_ESHAPE;
+  RowMask mk;
+  if ((e = gelu_mask(sample_scale, rows_per_sample, M, &mk))) return e;
+  const bool skip = sample_scale != nullptr;
+  hipStream_t s = (hipStream_t)stream;
   View vx = make_view<void>(x), vy = make_view<void>(y);
   // bf16: four channels per thread (111 VGPRs, four waves per SIMD: 81 -> 62 us in-step at ViT-H); f32 keeps eight
-  constexpr int ch4 = 1;      // four channels per thread (eight: 207-250 VGPRs, slower)
-  if (ch4 && dtype == OCTIC_BF16) {
-    gelu_fwd4_kernel<bf16><<<grid_for(M * (c / 4)), 256, 0, (hipStream_t)stream>>>(vx, vy, M, c);
+  // (eight channels per thread in bf16: 207-250 VGPRs, slower; DESIGN.md section 3 - that instantiation is gone)
+  if (dtype == OCTIC_BF16) {
+    const int grid = grid_for(M * (c / 4));
+    if (skip) gelu_fwd4_kernel<bf16, true><<<grid, 256, 0, s>>>(vx, vy, M, c, mk);
+    else gelu_fwd4_kernel<bf16, false><<<grid, 256, 0, s>>>(vx, vy, M, c, mk);
     return launch_status();
   }
   const int grid = grid_for(M * (c / 8));
-  if (dtype == OCTIC_F32) gelu_fwd_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(vx, vy, M, c);
-  else if (dtype == OCTIC_BF16) gelu_fwd_kernel<bf16><<<grid, 256, 0, (hipStream_t)stream>>>(vx, vy, M, c);
-  else return OCTIC_EDTYPE;
+  if (dtype == OCTIC_F32) {
+    if (skip) gelu_fwd_kernel<float, true><<<grid, 256, 0, s>>>(vx, vy, M, c, mk);
+    else gelu_fwd_kernel<float, false><<<grid, 256, 0, s>>>(vx, vy, M, c, mk);
+  } else return OCTIC_EDTYPE;
   return launch_status();
 }
 
-int octic_gelu_d8_bwd(const octic_view* g, const octic_view* x, const octic_view* gin, int64_t M, int c, int dtype,
-                      void* stream) {
+int octic_gelu_d8_fwd(const octic_view* x, const octic_view* y, int64_t M, int c, int dtype, void* stream) {
+  return octic_gelu_d8_fwd_skip(x, y, M, c, dtype, nullptr, 0, stream);
+}
+
+int octic_gelu_d8_bwd_skip(const octic_view* g, const octic_view* x, const octic_view* gin, int64_t M, int c, int dtype,
+                           const float* sample_scale, int64_t rows_per_sample, void* stream) {
   int e;
   if ((e = check_c(c)) || (e = check_view(g, c, dtype)) || (e = check_view(x, c, dtype)) ||
       (e = check_view(gin, c, dtype)))
     return e;
   if (M <= 0) return OCTIC_ESHAPE;
+  RowMask mk;
+  if ((e = gelu_mask(sample_scale, rows_per_sample, M, &mk))) return e;
+  const bool skip = sample_scale != nullptr;
+  hipStream_t s = (hipStream_t)stream;
   View vg = make_view<void>(g), vx = make_view<void>(x), vo = make_view<void>(gin);
-  constexpr int ch4 = 1;      // four channels per thread (eight: 207-250 VGPRs, slower)
-  if (ch4 && dtype == OCTIC_BF16) {                       // 109 -> 95 us in-step
-    gelu_bwd4_kernel<bf16><<<grid_for(M * (c / 4)), 256, 0, (hipStream_t)stream>>>(vg, vx, vo, M, c);
+  if (dtype == OCTIC_BF16) {                              // four channels per thread: 109 -> 95 us in-step
+    const int grid = grid_for(M * (c / 4));
+    if (skip) gelu_bwd4_kernel<bf16, true><<<grid, 256, 0, s>>>(vg, vx, vo, M, c, mk);
+    else gelu_bwd4_kernel<bf16, false><<<grid, 256, 0, s>>>(vg, vx, vo, M, c, mk);
     return launch_status();
   }
   const int grid = grid_for(M * (c / 8));
-  if (dtype == OCTIC_F32) gelu_bwd_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(vg, vx, vo, M, c);
-  else if (dtype == OCTIC_BF16) gelu_bwd_kernel<bf16><<<grid, 256, 0, (hipStream_t)stream>>>(vg, vx, vo, M, c);
-  else return OCTIC_EDTYPE;
+  if (dtype == OCTIC_F32) {
+    if (skip) gelu_bwd_kernel<float, true><<<grid, 256, 0, s>>>(vg, vx, vo, M, c, mk);
+    else gelu_bwd_kernel<float, false><<<grid, 256, 0, s>>>(vg, vx, vo, M, c, mk);
+  } else return OCTIC_EDTYPE;
   return launch_status();
+}
+
+int octic_gelu_d8_bwd(const octic_view* g, const octic_view* x, const octic_view* gin, int64_t M, int c, int dtype,
+                      void* stream) {
+  return octic_gelu_d8_bwd_skip(g, x, gin, M, c, dtype, nullptr, 0, stream);
 }
 
 int octic_cast_rowscale(const octic_view* x, const octic_view* y, const float* rs, int64_t rows_per_sample, int64_t M,

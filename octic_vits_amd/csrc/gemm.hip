@@ -979,10 +979,14 @@ extern "C" int octic_linear_d8_ring_order(int ngroups, const int* items, const i
 
 extern "C" {
 
-int octic_linear_d8_fwd(const octic_view* x, const void* const w[5], const float* bias, const octic_view* y,
-                        const octic_view* resid, const float* rs, int64_t rows_per_sample, const float* const cs[5],
-                        int64_t M, int cin, int cout, int dtype, int out_dtype, void* stream) {
+int octic_linear_d8_fwd_skip(const octic_view* x, const void* const w[5], const float* bias, const octic_view* y,
+                             const octic_view* resid, const float* rs, int64_t rows_per_sample, const float* const cs[5],
+                             int64_t M, int cin, int cout, int dtype, int out_dtype, const float* sample_scale,
+                             int64_t skip_rows_per_sample, void* stream) {
   int e;
+  // the mask says some output rows have no reader: a fused tail (residual, per-sample or column scale) writes the stream itself
+  // (cs: the array itself - the entry point takes five column scales or none)
+  if (sample_scale && (resid || rs || cs || skip_rows_per_sample <= 0 || M % skip_rows_per_sample != 0)) return OCTIC_ESHAPE;
   if ((e = check_c_dt(cin, dtype)) || (e = check_c_dt(cout, dtype)) || (e = check_c_dt(cout, out_dtype))) return e;
   if ((e = check_view(x, cin, dtype)) || (e = check_view(y, cout, out_dtype))) return e;
   if (resid && (e = check_view(resid, cout, out_dtype))) return e;
@@ -996,6 +1000,8 @@ int octic_linear_d8_fwd(const octic_view* x, const void* const w[5], const float
   GemmArgs a = {};
   a.rs = rs;
   a.rps = rs ? rows_per_sample : 1;
+  a.skip = sample_scale;
+  a.skip_rps = sample_scale ? skip_rows_per_sample : 1;
   d8_group_table(a, M, cin, cout);
   for (int gidx = 0; gidx < 5; ++gidx) {
     const int irrep = d8_group_irrep(gidx);
@@ -1011,6 +1017,12 @@ int octic_linear_d8_fwd(const octic_view* x, const void* const w[5], const float
     g.cs = cs ? cs[irrep] : nullptr;
   }
   return dispatch_gemm(a, dtype, out_dtype, (hipStream_t)stream);
+}
+
+int octic_linear_d8_fwd(const octic_view* x, const void* const w[5], const float* bias, const octic_view* y,
+                        const octic_view* resid, const float* rs, int64_t rows_per_sample, const float* const cs[5],
+                        int64_t M, int cin, int cout, int dtype, int out_dtype, void* stream) {
+  return octic_linear_d8_fwd_skip(x, w, bias, y, resid, rs, rows_per_sample, cs, M, cin, cout, dtype, out_dtype, nullptr, 0, stream);
 }
 
 int octic_linear_d8_plan(int64_t M, int cin, int cout, int dtype, int out_dtype, int fused, int out[4]) {

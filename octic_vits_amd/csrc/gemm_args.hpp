@@ -38,6 +38,11 @@ struct GemmArgs {
   int plan_nshort;    // short groups (1 .. ngroups-1), equal item counts
   int plan_a[8], plan_e[8];
   int plan_eb[8], plan_sb[8];   // first long / short item of XCD x
+  // stochastic-depth mask of a plain launch (octic_linear_d8_fwd_skip): one factor per sample of skip_rps token rows; the output
+  // rows of a sample whose factor is 0 have no reader.  Honoured by the W-stationary kernel, ignored by the others.
+  // (Last in the block: the other kernels' argument offsets stay what they were.)
+  const float* skip;
+  int64_t skip_rps;
 };
 
 // MFMA operand reads as inline asm with hand-counted waits: inside the GEMM loops hipcc protects every MFMA group with

@@ -89,9 +89,21 @@ __device__ __forceinline__ u32x4 add_resid(u32x4 v, u32x4 r) {
   }
 }
 
+constexpr int SKIP_WORDS = 64;   // live-tile bitmap of a group: 64 tiles per word, 4096 tiles (launch_t masks nothing beyond)
+constexpr int SKIP_PRE = 8;      // bitmap words per wave whose factors are fetched ahead of the W fragments (2048 tiles)
+
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+
 // One workgroup's life.  NCH = k-chunks per row tile (1: one-dimensional irreps, 2: the E pair rows), NTW = 16-column
-// MFMA tiles a wave can own.
-template <typename TOUT, int EPI, int NCH, int NTW, bool FULLK>
+// MFMA tiles a wave can own.  SKIP (EPI = 0 only): args.skip holds one stochastic-depth factor per sample of args.skip_rps
+// token rows; a row tile all of whose token rows belong to samples with factor 0 is DEAD - nobody reads its output - and is
+// neither fetched nor multiplied nor stored.  The workgroups of a column chunk share the LIVE tiles of the group evenly:
+// workgroup jw streams live tiles [jw L / wgs, (jw + 1) L / wgs) in ascending order (sibling chunks of one jw take the same
+// tiles, so X is still fetched once per XCD).  Rows of live tiles keep their bits: same fragments, same MFMA order.
+template <typename TOUT, int EPI, int NCH, int NTW, bool FULLK, bool SKIP>
 __device__ __forceinline__ void body(const GemmArgs& args, const GemmGroup& G, const int lt, char* lds) {
   constexpr int ES = (int)sizeof(TOUT);
   constexpr int SRS = NTW * 16 * ES + 16;   // staged output row stride (bytes)
@@ -114,8 +126,8 @@ __device__ __forceinline__ void body(const GemmArgs& args, const GemmGroup& G, c
   const int chunk_id = lt % G.n_chunks, jw = lt / G.n_chunks;
   const int t_begin = (int)((int64_t)jw * G.m_tiles / G.wgs);
   const int t_end = (int)((int64_t)(jw + 1) * G.m_tiles / G.wgs);
-  const int ntiles = t_end - t_begin;
-  const int steps = ntiles * NCH;
+  int ntiles = t_end - t_begin;     // SKIP: the workgroup's share of the live tiles, known once the bitmap stands
+  int steps = ntiles * NCH;
   const int c_first = chunk_id * G.chunk;
   const int ct = (G.n_tiles - c_first) < G.chunk ? (G.n_tiles - c_first) : G.chunk;
   const int cb = ct >> 2, crem = ct & 3;
@@ -127,6 +139,32 @@ __device__ __forceinline__ void body(const GemmArgs& args, const GemmGroup& G, c
   char* const stg = lds + S * stage_b + wid * (TM * SRS);
   float* const lbias = (float*)(lds + S * stage_b + 4 * TM * SRS);
   float* const lcs = lbias + 4 * NTW * 16;
+  uint64_t* const bm = (uint64_t*)(lbias + 2 * 4 * NTW * 16);   // SKIP: live-tile bitmap of the group (SKIP_WORDS words)
+
+  // ---- SKIP: the factors of the tiles this lane answers for (lane = tile, wave wid takes bitmap words wid, wid + 4, ...)
+  // are requested first of all, so that their round trip runs beside the W fragment loads and not in front of them
+  const int m_tiles = SKIP ? G.m_tiles : 0, nwords = (m_tiles + 63) >> 6;
+  const float* const ss = SKIP ? args.skip : nullptr;
+  const int srps = SKIP ? (int)(args.skip_rps < 0x7fffffff ? args.skip_rps : 0x7fffffff) : 1;
+  auto tile_samples = [&](int t, int& s0, int& s1) {     // first / last sample among the token rows of tile t
+    const int64_t r0 = (int64_t)t * TM, r1 = (r0 + TM < G.rows ? r0 + TM : G.rows) - 1;
+    s0 = (int)(kPair ? r0 >> 1 : r0) / srps;
+    s1 = (int)(kPair ? r1 >> 1 : r1) / srps;
+  };
+  float pf0[SKIP_PRE], pf1[SKIP_PRE];
+  if constexpr (SKIP) {
+#pragma unroll
+    for (int k = 0; k < SKIP_PRE; ++k) {
+      const int t = (4 * k + wid) * 64 + lane;
+      pf0[k] = pf1[k] = 0.f;
+      if (t < m_tiles) {
+        int s0, s1;
+        tile_samples(t, s0, s1);
+        pf0[k] = ss[s0];
+        pf1[k] = ss[s1];
+      }
+    }
+  }
 
   // XOR applied to a row's 16-byte chunk index so the B-operand reads (16 rows x one chunk column per lane group) are
   // conflict-free at a row stride of cpr chunks: two bits for cpr = 4 (mod 8), three for 8 (mod 16), four for 0 (mod 16).
@@ -152,10 +190,22 @@ __device__ __forceinline__ void body(const GemmArgs& args, const GemmGroup& G, c
   };
   const int64_t last_row0 = (int64_t)(G.m_tiles - 1) * TM;
   const int rv_last = (int)(G.rows - last_row0) < TM ? (int)(G.rows - last_row0) : TM;
-  const bool partial_last = t_end == G.m_tiles && rv_last < TM;
-  set_xoff(ntiles == 1 && partial_last ? rv_last : TM);
+  const bool partial_last = SKIP ? rv_last < TM : (t_end == G.m_tiles && rv_last < TM);
+  if constexpr (!SKIP) set_xoff(ntiles == 1 && partial_last ? rv_last : TM);
   const char* l_src = G.a + (int64_t)t_begin * tile_stride;
+  const char* const a_base = SKIP ? G.a : nullptr;   // SKIP: kept in registers, no kernel-argument load inside the loop
+  char* const y_base = SKIP ? G.y : nullptr;
   int l_c = 0, l_u = 0, l_stage = 0;
+  // SKIP: two walks over the set bits of the workgroup's share, S - 1 steps apart - [0] the DMA side, [1] the consumer side.
+  // Scalar state: the rest of the current bitmap word and its index; a new word is read from LDS when one runs out.
+  uint64_t wk_bits[2] = {0, 0};
+  int wk_word[2] = {0, 0};
+  auto next_live = [&](int side) {
+    while (wk_bits[side] == 0) wk_bits[side] = uniform64(bm[++wk_word[side]]);
+    const int t = wk_word[side] * 64 + __builtin_ctzll(wk_bits[side]);
+    wk_bits[side] &= wk_bits[side] - 1;
+    return t;
+  };
   auto issue = [&]() {
     char* st = ring + l_stage * stage_b;
 #pragma unroll
@@ -167,13 +217,23 @@ __device__ __forceinline__ void body(const GemmArgs& args, const GemmGroup& G, c
     ++l_u;
     if (++l_c == NCH) {
       l_c = 0;
-      l_src += tile_stride;
-      if (partial_last && l_u == (ntiles - 1) * NCH) set_xoff(rv_last);
+      if constexpr (SKIP) {
+        if (l_u < steps) {                   // the next live tile; the partial last tile is known by its index
+          const int t = next_live(0);
+          l_src = a_base + (int64_t)t * tile_stride;
+          if (partial_last && t == m_tiles - 1) set_xoff(rv_last);
+        }
+      } else {
+        l_src += tile_stride;
+        if (partial_last && l_u == (ntiles - 1) * NCH) set_xoff(rv_last);
+      }
     }
   };
+  if constexpr (!SKIP) {
 #pragma unroll
-  for (int pz = 0; pz < S - 1; ++pz)
-    if (pz < steps) issue();
+    for (int pz = 0; pz < S - 1; ++pz)
+      if (pz < steps) issue();
+  }
 
   // ---- bias / layer-scale columns of the chunk -> LDS (zeros / ones where absent)
   for (int c = threadIdx.x; c < 4 * NTW * 16; c += 256) {
@@ -200,6 +260,67 @@ __device__ __forceinline__ void body(const GemmArgs& args, const GemmGroup& G, c
         } else
           wf[i][c * KSC + ks] = *(const bf16x8*)(wrow + c * Kc + (ks < ksteps ? ks : 0) * 32);
       }
+  }
+  if constexpr (SKIP) {
+    // ---- live-tile bitmap: one ballot per 64 tiles.  The factors fetched above have landed by now (they are older than the
+    // W loads); tiles over more than two samples and words past SKIP_PRE take the loop (small rows_per_sample, > 2048 tiles).
+#pragma unroll
+    for (int k = 0; k < SKIP_PRE; ++k) {
+      const int word = 4 * k + wid;
+      if (word < nwords) {
+        const int t = word * 64 + lane;
+        bool live = pf0[k] != 0.f || pf1[k] != 0.f;
+        if (t < m_tiles) {
+          int s0, s1;
+          tile_samples(t, s0, s1);
+          for (int sidx = s0 + 1; sidx < s1; ++sidx) live = live || ss[sidx] != 0.f;
+        }
+        const uint64_t b = __ballot(live);
+        if (lane == 0) bm[word] = b;
+      }
+    }
+    for (int word = 4 * SKIP_PRE + wid; word < nwords; word += 4) {
+      const int t = word * 64 + lane;
+      bool live = false;
+      if (t < m_tiles) {
+        int s0, s1;
+        tile_samples(t, s0, s1);
+        for (int sidx = s0; sidx <= s1; ++sidx) live = live || ss[sidx] != 0.f;
+      }
+      const uint64_t b = __ballot(live);
+      if (lane == 0) bm[word] = b;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    // ---- the share: lane = word, inclusive prefix popcounts; L live tiles in the group
+    const uint64_t wv = lane < nwords ? bm[lane] : 0;
+    int inc = __builtin_popcountll(wv);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(inc, d);
+      if (lane >= d) inc += up;
+    }
+    const int L = __builtin_amdgcn_readlane(inc, 63);
+    const int lo = (int)((int64_t)jw * L / G.wgs), hi = (int)((int64_t)(jw + 1) * L / G.wgs);
+    ntiles = hi - lo;
+    steps = ntiles * NCH;
+    set_xoff(TM);
+    if (ntiles > 0) {
+      // word of live tile number lo: the first whose inclusive count exceeds lo; drop its live tiles below lo
+      const int w0 = __builtin_popcountll(__ballot(inc <= lo));
+      const int before = w0 ? __builtin_amdgcn_readlane(inc, w0 - 1) : 0;
+      uint64_t bits = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(wv >> 32), w0) << 32) |
+                      (uint32_t)__builtin_amdgcn_readlane((int)wv, w0);
+      for (int d = lo - before; d > 0; --d) bits &= bits - 1;
+      wk_bits[0] = wk_bits[1] = bits;
+      wk_word[0] = wk_word[1] = w0;
+      const int t = next_live(0);
+      l_src = a_base + (int64_t)t * tile_stride;
+      if (partial_last && t == m_tiles - 1) set_xoff(rv_last);
+    }
+#pragma unroll
+    for (int pz = 0; pz < S - 1; ++pz)
+      if (pz < steps) issue();
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   // re-define the fragments: hipcc's waitcnt pass cannot see that loads issued before a loop are complete after its
@@ -276,7 +397,9 @@ __device__ __forceinline__ void body(const GemmArgs& args, const GemmGroup& G, c
 
   asm volatile("" : "+s"(g_rows));
   for (int tile = 0; tile < ntiles; ++tile) {
-    const int row0 = (t_begin + tile) * TM;
+    const int t_idx = SKIP ? next_live(1) : t_begin + tile;
+    if constexpr (SKIP) y_t = y_base + (int64_t)t_idx * y_tile_stride;
+    const int row0 = t_idx * TM;
     const int rows_valid = (g_rows - row0) < TM ? (g_rows - row0) : TM;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -391,8 +514,9 @@ __device__ __forceinline__ void body(const GemmArgs& args, const GemmGroup& G, c
   }
 }
 
-template <typename TOUT, int EPI>
+template <typename TOUT, int EPI, bool SKIP = false>
 __global__ __launch_bounds__(256, 2) void linear_d8_wreg_kernel(GemmArgs args) {
+  static_assert(!SKIP || EPI == 0, "the sample mask is for the plain epilogue: a fused tail has to write every row");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   constexpr int NTW_A = sizeof(TOUT) == 2 ? (EPI ? 4 : 5) : 3, NTW_E = sizeof(TOUT) == 2 ? (EPI ? 3 : 4) : 3;
   // consecutive work items (the column chunks of one row range) share an XCD and its L2
@@ -406,11 +530,11 @@ __global__ __launch_bounds__(256, 2) void linear_d8_wreg_kernel(GemmArgs args) {
   const GemmGroup& G = args.g[gi];
   const bool fullk = G.K == (G.pair ? 2 : 1) * 32 * KSC;
   if (G.pair) {
-    if (fullk) body<TOUT, EPI, 2, NTW_E, true>(args, G, item - G.tile_begin, lds);
-    else body<TOUT, EPI, 2, NTW_E, false>(args, G, item - G.tile_begin, lds);
+    if (fullk) body<TOUT, EPI, 2, NTW_E, true, SKIP>(args, G, item - G.tile_begin, lds);
+    else body<TOUT, EPI, 2, NTW_E, false, SKIP>(args, G, item - G.tile_begin, lds);
   } else {
-    if (fullk) body<TOUT, EPI, 1, NTW_A, true>(args, G, item - G.tile_begin, lds);
-    else body<TOUT, EPI, 1, NTW_A, false>(args, G, item - G.tile_begin, lds);
+    if (fullk) body<TOUT, EPI, 1, NTW_A, true, SKIP>(args, G, item - G.tile_begin, lds);
+    else body<TOUT, EPI, 1, NTW_A, false, SKIP>(args, G, item - G.tile_begin, lds);
   }
 }
 
@@ -490,14 +614,21 @@ int launch_t(GemmArgs& a, bool fused, hipStream_t s) {
     t += a.g[i].wgs * a.g[i].n_chunks;
   }
   a.total_tiles = t;
-  const size_t smem = (size_t)S * TM * Kc * 2 + 4 * TM * (NTW_MAX * 16 * ES + 16) + 2 * 4 * NTW_MAX * 16 * sizeof(float);
+  // the sample mask: plain epilogue only (the entry point refuses the rest), and only while every group's live-tile bitmap
+  // fits - a launch beyond that computes every row, which the contract allows
+  bool skip = a.skip != nullptr && !fused;
+  for (int i = 0; i < a.ngroups; ++i) skip = skip && a.g[i].m_tiles <= 64 * SKIP_WORDS;
+  const size_t smem = (size_t)S * TM * Kc * 2 + 4 * TM * (NTW_MAX * 16 * ES + 16) + 2 * 4 * NTW_MAX * 16 * sizeof(float) +
+                      (skip ? SKIP_WORDS * sizeof(uint64_t) : 0);
   static DeviceOnce once;
   if (once.first()) {
     hipFuncSetAttribute((const void*)linear_d8_wreg_kernel<TOUT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     hipFuncSetAttribute((const void*)linear_d8_wreg_kernel<TOUT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    hipFuncSetAttribute((const void*)linear_d8_wreg_kernel<TOUT, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     (void)hipGetLastError();
   }
   if (fused) linear_d8_wreg_kernel<TOUT, 1><<<t, 256, smem, s>>>(a);
+  else if (skip) linear_d8_wreg_kernel<TOUT, 0, true><<<t, 256, smem, s>>>(a);
   else linear_d8_wreg_kernel<TOUT, 0><<<t, 256, smem, s>>>(a);
   return launch_status();
 }

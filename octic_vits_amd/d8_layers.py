@@ -298,9 +298,11 @@ class LinearD8(nn.Module):
     def weights(self):
         return tuple(getattr(self, "lin_" + n).weight for n in _IRREPS)
 
-    def forward(self, x_batched, resid=None, rs=None, cs=None, next_norm=None):
+    def forward(self, x_batched, resid=None, rs=None, cs=None, next_norm=None, skip_out=None, skip_dx=None):
         """next_norm (a LayerNormD8, only with resid): also return next_norm(result) -> (Octic, Octic or None); on the
-        bf16 GPU path the two are ONE autograd node whose backward skips the cast pass (OF.LinearD8NormFn)."""
+        bf16 GPU path the two are ONE autograd node whose backward skips the cast pass (OF.LinearD8NormFn).
+        skip_out / skip_dx: the branch's stochastic-depth factor as the sample mask of the forward / the input-gradient
+        launch (OF.LinearD8Fn) - the caller's promise that every reader of that output honours the same mask."""
         assert len(x_batched) == 5, "Input should be a 5-tuple"
         xp, cin = as_packed(x_batched)
         if 8 * cin != self.input_channels:
@@ -324,9 +326,10 @@ class LinearD8(nn.Module):
                 and resid.dtype == torch.float32 and type(next_norm) is LayerNormD8):
             a, beta = next_norm.affine()
             y, yn = OF.LinearD8NormFn.apply(xp, *self.weights(), self.lin_A1.bias, resid, rs, *cs5, cin, cout, rps, dtype,
-                                            self._prep, *a, beta, next_norm.eps)
+                                            self._prep, *a, beta, next_norm.eps, skip_dx)
             return Octic(y, cout), Octic(yn, cout)
-        y = OF.LinearD8Fn.apply(xp, *self.weights(), self.lin_A1.bias, resid, rs, *cs5, cin, cout, rps, dtype, self._prep)
+        y = OF.LinearD8Fn.apply(xp, *self.weights(), self.lin_A1.bias, resid, rs, *cs5, cin, cout, rps, dtype, self._prep,
+                                skip_out, skip_dx)
         return Octic(y, cout) if next_norm is None else (Octic(y, cout), None)
 
     def extra_repr(self) -> str:
@@ -427,7 +430,27 @@ class MlpD8(nn.Module):
         self.fc2 = LinearD8(hidden_features, out_features, bias=bias[1])
         self.drop2 = DropoutD8(drop_probs[1])
 
+    def _sample_mask(self, xs, resid, rs):
+        """rs as the sample mask of this MLP's row-local kernels, or None.  The fused tail of fc2 multiplies the whole branch by
+        rs, so for a sample with rs = 0: fc1's output is read by the D8-GELU node alone (forward and backward), the GELU's
+        output by fc2 and its weight gradient (zeros suffice), fc2's input gradient by the GELU backward alone, whose output
+        feeds fc1's gradients (zeros again).  Only for exactly that chain: this class's own layers with nothing in between,
+        the fused tail, whole samples of a plain batch (OF.linear_skip_scale: not the compacted batch, whose rows are all
+        kept; not ragged rows; not a traced call, which stays on the dispatcher ops)."""
+        if not (OF.LINEAR_SKIP_DROPPED and rs is not None and resid is not None and not COMPACT_DROP_PATH
+                and type(self.fc1) is LinearD8 and type(self.fc2) is LinearD8 and type(self.act) is TritonGeluD8
+                and type(self.norm) is nn.Identity and not self.drop1.active and not self.drop2.active
+                and isinstance(xs, Octic) and xs.packed.dim() == 3 and xs.packed.is_cuda):
+            return None
+        xp = xs.packed
+        return OF.linear_skip_scale(rs, xp.shape[1], xp.shape[0] * xp.shape[1])
+
     def forward(self, xs, resid=None, rs=None, cs=None, next_norm=None):
+        mask = self._sample_mask(xs, resid, rs)
+        if mask is not None:
+            h = self.fc1(xs, skip_out=mask)
+            a = Octic(OF.GeluD8PackedFn.apply(h.packed, h.c, mask, h.packed.shape[1]), h.c)
+            return self.fc2(a, resid=resid, rs=rs, cs=cs, next_norm=next_norm, skip_dx=mask)
         xs = self.norm(self.drop1(self.act(self.fc1(xs))))
         if self.drop2.active or resid is None:
             out = _tail(self.drop2(self.fc2(xs)), resid, rs, cs)
@@ -692,13 +715,34 @@ class AttentionD8(nn.Module):
         self.rope = rope
         self.att = F.scaled_dot_product_attention
 
+    def _gemm_mask(self, xp, c, resid, rs, drop, rag):
+        """rs as the sample mask of qkv's forward and of proj's input gradient, or None.  Their only readers are the attention
+        forward and backward (qkv's own gradients read the input and dqkv, which a skipping backward zeroes), so the mask
+        goes out exactly where the packed attention node below gets rs AND both launches it will run skip a dropped sample
+        outright (ops.attn_skips_dropped, from the library's plan) - a kernel that computes the sample must find finite rows."""
+        if not (OF.LINEAR_SKIP_DROPPED and OF.ATTN_SKIP_DROPPED and rs is not None and resid is not None
+                and not COMPACT_DROP_PATH and not (rag is not None and rag.matches(xp)) and OF.ATTN_PACKED and drop == 0.
+                and xp.is_cuda and not torch.compiler.is_compiling() and not self.proj_drop.active
+                and type(self.qkv) is LinearD8 and type(self.proj) is LinearD8):
+            return None
+        B, T, H = xp.shape[0], xp.shape[1], self.num_heads
+        if not OF.ops.attn_packed_ok(T, c, H, compute_dtype(xp)):
+            return None
+        if OF.skip_scale(rs, B) is None or OF.linear_skip_scale(rs, T, B * T) is None:
+            return None
+        # the strides of ops.attn_fwd_packed / attn_bwd_packed: qkv and dqkv rows of 3 * 8c, o and dO rows of 8c
+        if not OF.ops.attn_skips_dropped(B, T, 8 * (c // H), ld=(3 * 8 * c, 8 * c, 3 * 8 * c)):
+            return None
+        return rs
+
     def forward(self, xs, resid=None, rs=None, cs=None, next_norm=None):
         xp, c = as_packed(xs)
         if xp.dim() != 3:
             raise ValueError("AttentionD8 expects [B, N, C] irreps")
-        qkv = self.qkv(xs if isinstance(xs, Octic) else Octic(xp, c))
         drop = self.attn_drop.p if self.training else 0.
         rag = OF.RAGGED
+        gemm_mask = self._gemm_mask(xp, c, resid, rs, drop, rag)
+        qkv = self.qkv(xs if isinstance(xs, Octic) else Octic(xp, c), skip_out=gemm_mask)
         if rag is not None and rag.matches(xp):
             # several crop sets in one row tensor: the softmax core walks the sets, everything around it ran once on all rows
             from . import ragged as _R
@@ -726,7 +770,7 @@ class AttentionD8(nn.Module):
         if self.proj_drop.active or resid is None:
             out = _tail(self.proj_drop(self.proj(on)), resid, rs, cs)
             return out if next_norm is None else (out, None)
-        return self.proj(on, resid=resid, rs=rs, cs=cs, next_norm=next_norm)
+        return self.proj(on, resid=resid, rs=rs, cs=cs, next_norm=next_norm, skip_dx=gemm_mask)
 
 
 def _branch(norm, fn, xs_packed, c, rs, cs, out_dtype, pre=None, next_norm=None):

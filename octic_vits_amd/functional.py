@@ -78,24 +78,31 @@ def _c(t):
 
 # ------------------------------------------------------------------------------------------- GELU
 class GeluD8PackedFn(torch.autograd.Function):
+    """D8-GELU on packed rows.  sample_scale / rps (linear_skip_scale): the stochastic-depth factor of the MLP branch the node
+    sits in, one entry per sample of rps rows.  The kernels then read no row of a dropped sample and write +0 there, in the
+    forward and in the backward (include/octic_hip.h: octic_gelu_d8_*_skip) - the readers of both results (fc2 and its
+    weight gradient; fc1's input and weight gradients) multiply those rows by zero anyway."""
+
     @staticmethod
-    def forward(ctx, x, c):
+    def forward(ctx, x, c, sample_scale=None, rps=0):
         x = _c(x)
         y = torch.empty_like(x)
         M = x.numel() // (8 * c)
-        ops.gelu_fwd(ops.pview(x, c), ops.pview(y, c), M, c, x.dtype, x)
-        ctx.save_for_backward(x)
-        ctx.c = c
+        ss = linear_skip_scale(sample_scale, rps, M)
+        ops.gelu_fwd(ops.pview(x, c), ops.pview(y, c), M, c, x.dtype, x, sample_scale=ss, rows_per_sample=rps)
+        ctx.save_for_backward(x, ss)
+        ctx.c, ctx.rps = c, rps
         return y
 
     @staticmethod
     def backward(ctx, g):
-        (x,) = ctx.saved_tensors
+        x, ss = ctx.saved_tensors
         c = ctx.c
         g = _c(g.to(x.dtype))
         gi = torch.empty_like(x)
-        ops.gelu_bwd(ops.pview(g, c), ops.pview(x, c), ops.pview(gi, c), x.numel() // (8 * c), c, x.dtype, x)
-        return gi, None
+        ops.gelu_bwd(ops.pview(g, c), ops.pview(x, c), ops.pview(gi, c), x.numel() // (8 * c), c, x.dtype, x,
+                     sample_scale=ss, rows_per_sample=ctx.rps)
+        return gi, None, None, None
 
 
 class GeluD8Function(torch.autograd.Function):
@@ -250,7 +257,11 @@ class LinearD8Fn(torch.autograd.Function):
     """y = resid + rs*cs*(x W^T + b)   (resid / rs / cs optional).  See octic_hip.h for the math."""
 
     @staticmethod
-    def forward(ctx, x, wA1, wA2, wB1, wB2, wE, bias, resid, rs, sA1, sA2, sB1, sB2, sE, cin, cout, rps, dtype, prep):
+    def forward(ctx, x, wA1, wA2, wB1, wB2, wE, bias, resid, rs, sA1, sA2, sB1, sB2, sE, cin, cout, rps, dtype, prep,
+                skip_out=None, skip_dx=None):
+        """skip_out / skip_dx: the stochastic-depth factor of the branch this layer sits in, as the sample mask of the forward
+        launch / of the input-gradient launch - given by the caller only where EVERY reader of that launch's output honours the
+        same mask (linear_skip_scale; DESIGN.md 'Routing rules').  The rows of a dropped sample may then stay unwritten."""
         w5 = (wA1, wA2, wB1, wB2, wE)
         cs5 = None if sA1 is None else (sA1, sA2, sB1, sB2, sE)
         ops._require_cuda(x)
@@ -268,16 +279,18 @@ class LinearD8Fn(torch.autograd.Function):
         cs32 = None if cs5 is None else [_c(s.detach().float()) for s in cs5]
         rs32 = None if rs is None else _c(rs.float())
         rv = ops.pview(_c(resid), cout) if fused else None
+        plain = not fused and rs32 is None and cs32 is None
+        ss_out = linear_skip_scale(skip_out, rps, M) if plain else None
         ops.linear_fwd(ops.pview(x, cin), wb, b32, ops.pview(y, cout), M, cin, cout, dtype, out_dtype, x,
-                       resid_v=rv, rs=rs32, rps=rps, cs5=cs32)
-        ctx.save_for_backward(x, rs32, b32, *w5, *(cs32 or []))
+                       resid_v=rv, rs=rs32, rps=rps, cs5=cs32, sample_scale=ss_out, skip_rps=rps)
+        ctx.save_for_backward(x, rs32, b32, linear_skip_scale(skip_dx, rps, M), *w5, *(cs32 or []))
         ctx.meta = (cin, cout, rps, dtype, fused, cs5 is not None, bias is not None, x_in_dtype, wt)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         cin, cout, rps, dtype, fused, has_cs, has_bias, x_in_dtype, wt = ctx.meta
-        x, rs32, b32, *rest = ctx.saved_tensors
+        x, rs32, b32, ss_dx, *rest = ctx.saved_tensors
         w5, cs32 = rest[:5], (rest[5:] if has_cs else None)
         M = x.numel() // (8 * cin)
         dy = _c(dy)
@@ -289,7 +302,7 @@ class LinearD8Fn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(x.shape, dtype=dtype, device=x.device)
-            ops.linear_fwd(gv, wt, None, ops.pview(dx, cin), M, cout, cin, dtype, dtype, x)
+            ops.linear_fwd(gv, wt, None, ops.pview(dx, cin), M, cout, cin, dtype, dtype, x, sample_scale=ss_dx, skip_rps=rps)
             if dx.dtype != x_in_dtype:
                 dx = dx.to(x_in_dtype)
         # bias gradient = column sums of the invariant block of g: the bf16 wgrad kernel produces them on the side
@@ -302,7 +315,7 @@ class LinearD8Fn(torch.autograd.Function):
         if not f32_masters:
             dw = [d.to(w.dtype) for d, w in zip(dw, w5)]
         dcs = dcs if has_cs else [None] * 5
-        return (dx, *dw, dbias, dy if fused else None, None, *dcs, None, None, None, None, None)
+        return (dx, *dw, dbias, dy if fused else None, None, *dcs, None, None, None, None, None, None, None)
 
 
 class LinearD8NormFn(torch.autograd.Function):
@@ -314,7 +327,8 @@ class LinearD8NormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wA1, wA2, wB1, wB2, wE, bias, resid, rs, sA1, sA2, sB1, sB2, sE, cin, cout, rps, dtype, prep,
-                a1, a2, b1, b2, ae, beta, eps):
+                a1, a2, b1, b2, ae, beta, eps, skip_dx=None):
+        """skip_dx: as in LinearD8Fn (the sample mask of the input-gradient launch)."""
         w5 = (wA1, wA2, wB1, wB2, wE)
         cs5 = None if sA1 is None else (sA1, sA2, sB1, sB2, sE)
         ops._require_cuda(x)
@@ -332,7 +346,7 @@ class LinearD8NormFn(torch.autograd.Function):
                        resid_v=ops.pview(_c(resid), cout), rs=rs32, rps=rps, cs5=cs32)
         alpha = None if a1 is None else [_c(t.float()) for t in (a1, a2, b1, b2, ae)]
         yn, stats = ops.layernorm_fwd(y, alpha, None if beta is None else _c(beta.float()), eps, dtype, cout)
-        ctx.save_for_backward(x, rs32, b32, y, stats, *w5, *(cs32 or []), *(alpha or []))
+        ctx.save_for_backward(x, rs32, b32, y, stats, linear_skip_scale(skip_dx, rps, M), *w5, *(cs32 or []), *(alpha or []))
         ctx.meta = (cin, cout, rps, dtype, cs5 is not None, bias is not None, x_in_dtype, wt, alpha is not None,
                     beta is not None)
         ctx.set_materialize_grads(False)
@@ -341,7 +355,7 @@ class LinearD8NormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dyn):
         cin, cout, rps, dtype, has_cs, has_bias, x_in_dtype, wt, has_affine, has_beta = ctx.meta
-        x, rs32, b32, y, stats, *rest = ctx.saved_tensors
+        x, rs32, b32, y, stats, ss_dx, *rest = ctx.saved_tensors
         w5 = rest[:5]
         cs32 = rest[5:10] if has_cs else None
         alpha = rest[(10 if has_cs else 5):] if has_affine else None
@@ -363,7 +377,7 @@ class LinearD8NormFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(x.shape, dtype=dtype, device=x.device)
-            ops.linear_fwd(gv, wt, None, ops.pview(dx, cin), M, cout, cin, dtype, dtype, x)
+            ops.linear_fwd(gv, wt, None, ops.pview(dx, cin), M, cout, cin, dtype, dtype, x, sample_scale=ss_dx, skip_rps=rps)
             if dx.dtype != x_in_dtype:
                 dx = dx.to(x_in_dtype)
         dysum = ops.colsum_a1(gv, M, cout, dtype, x) if (has_bias and not ops.wgrad_has_colsum(cin, cout, dtype)) else None
@@ -374,7 +388,7 @@ class LinearD8NormFn(torch.autograd.Function):
         if not f32_masters:
             dw = [d.to(w.dtype) for d, w in zip(dw, w5)]
         dcs = dcs if has_cs else [None] * 5
-        return (dx, *dw, dbias, dy, None, *dcs, None, None, None, None, None, *dal, dbeta if has_beta else None, None)
+        return (dx, *dw, dbias, dy, None, *dcs, None, None, None, None, None, *dal, dbeta if has_beta else None, None, None)
 
 
 # --------------------------------------------------------------------------------- head packing
@@ -468,6 +482,29 @@ def wgrad_skip_scale(rs, rps, M, rows_to=None):
     switch is on and rs is one float32 entry per sample of rps rows on the GPU with rps * B == M; None for compact rows of a
     stream (rows_to), the per-row factors of a ragged row tensor (rps 1), a traced value, eval and drop_path 0 (rs None)."""
     if (not WGRAD_SKIP_DROPPED or rs is None or rows_to is not None or torch.compiler.is_compiling() or not rs.is_cuda
+            or rs.dtype != torch.float32 or rs.dim() != 1 or not rs.is_contiguous() or rps < 2 or rs.numel() * rps != M):
+        return None
+    return rs.detach()
+
+
+# In the octic MLP the same factor makes the D8-GELU's work on a dropped sample void in both directions: gelu(h) of such a
+# sample is read only by fc2 (whose fused tail multiplies the row by rs = 0) and by fc2's weight gradient (against zero dY rows),
+# dh only by fc1's input and weight gradients, whose results for that sample are zero as well.  With LINEAR_SKIP_DROPPED the
+# factor travels to the GELU kernels, which then move no input bytes for those rows and store zeros (zeros, not nothing: the
+# readers multiply by 0, which is harmless on finite values only) - same launch shapes, same results (DESIGN.md section 3).
+# Read once at import from OCTIC_LINEAR_SKIP (0 = off).
+def _linear_skip_from_env():
+    return os.environ.get("OCTIC_LINEAR_SKIP", "1").strip() != "0"
+
+
+LINEAR_SKIP_DROPPED = _linear_skip_from_env()
+
+
+def linear_skip_scale(rs, rps, M, rows_to=None):
+    """rs as the sample_scale of the octic MLP's row kernels over M token rows - under the conditions of wgrad_skip_scale: the
+    switch is on and rs is one float32 entry per sample of rps rows on the GPU with rps * B == M; None for compact rows
+    (rows_to), the per-row factors of a ragged row tensor (rps 1), a traced value, eval and drop_path 0 (rs None)."""
+    if (not LINEAR_SKIP_DROPPED or rs is None or rows_to is not None or torch.compiler.is_compiling() or not rs.is_cuda
             or rs.dtype != torch.float32 or rs.dim() != 1 or not rs.is_contiguous() or rps < 2 or rs.numel() * rps != M):
         return None
     return rs.detach()

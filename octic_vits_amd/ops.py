@@ -184,15 +184,35 @@ def split_packed(t, c):
 
 
 # ------------------------------------------------------------------------------------------ launches
-def gelu_fwd(xv, yv, M, c, dtype, ref):
+def _row_sample_scale(sample_scale, rows_per_sample, M, ref, what):
+    """(sample_scale, rows_per_sample) as a *_skip row kernel takes them: (None, 0) without a mask; a mask is one float32
+    factor per sample of rows_per_sample consecutive rows on the operands' device."""
+    if sample_scale is None:
+        return None, 0
+    rps = int(rows_per_sample)
+    if (sample_scale.dtype != torch.float32 or sample_scale.device != ref.device or not sample_scale.is_contiguous()
+            or (rps > 0 and M % rps == 0 and sample_scale.numel() != M // rps)):
+        raise ValueError(f"{what}: sample_scale must be a contiguous float32 tensor of M / rows_per_sample entries on the "
+                         "operands' device")
+    return sample_scale, rps
+
+
+def gelu_fwd(xv, yv, M, c, dtype, ref, sample_scale=None, rows_per_sample=0):
+    """sample_scale / rows_per_sample: the stochastic-depth factor of the branch (octic_gelu_d8_fwd_skip) - input rows of a
+    sample whose factor is 0 are not read, its output rows are +0."""
+    ss, rps = _row_sample_scale(sample_scale, rows_per_sample, M, ref, "gelu_fwd")
     t = KERNEL_TIMER.start()
-    check(lib().octic_gelu_d8_fwd(ctypes.byref(xv), ctypes.byref(yv), M, c, dt_code(dtype), _stream(ref)))
+    check(lib().octic_gelu_d8_fwd_skip(ctypes.byref(xv), ctypes.byref(yv), M, c, dt_code(dtype), _p(ss), rps, _stream(ref)))
+    # (bytes stay the full batch's with a sample_scale: the host does not know the kept count without a sync)
     KERNEL_TIMER.stop(t, f"gelu_fwd_kernel<{_DTN[dtype]}>", 2 * M * 8 * c * ref.element_size())
 
 
-def gelu_bwd(gv, xv, ov, M, c, dtype, ref):
+def gelu_bwd(gv, xv, ov, M, c, dtype, ref, sample_scale=None, rows_per_sample=0):
+    """sample_scale / rows_per_sample: as in gelu_fwd (octic_gelu_d8_bwd_skip: neither g nor x is read for a dropped sample)."""
+    ss, rps = _row_sample_scale(sample_scale, rows_per_sample, M, ref, "gelu_bwd")
     t = KERNEL_TIMER.start()
-    check(lib().octic_gelu_d8_bwd(ctypes.byref(gv), ctypes.byref(xv), ctypes.byref(ov), M, c, dt_code(dtype), _stream(ref)))
+    check(lib().octic_gelu_d8_bwd_skip(ctypes.byref(gv), ctypes.byref(xv), ctypes.byref(ov), M, c, dt_code(dtype), _p(ss), rps,
+                                       _stream(ref)))
     KERNEL_TIMER.stop(t, f"gelu_bwd_kernel<{_DTN[dtype]}>", 3 * M * 8 * c * ref.element_size())
 
 
@@ -413,12 +433,17 @@ def dense_wgrad_tn_pair(dy0, x0, dy1, x1, dw1=None, dw0=None, sample_scale=None,
     return dw0, dw1
 
 
-def linear_fwd(xv, w5, bias, yv, M, cin, cout, dtype, out_dtype, ref, resid_v=None, rs=None, rps=1, cs5=None):
+def linear_fwd(xv, w5, bias, yv, M, cin, cout, dtype, out_dtype, ref, resid_v=None, rs=None, rps=1, cs5=None, sample_scale=None,
+               skip_rps=0):
+    """sample_scale / skip_rps (plain launches only): the stochastic-depth factor of the branch, one entry per sample of
+    skip_rps rows, where EVERY reader of the output honours the same mask (octic_linear_d8_fwd_skip: the output rows of a
+    dropped sample may stay unwritten).  Timer name, bytes and FLOP stay the full batch's."""
+    ss, srps = _row_sample_scale(sample_scale, skip_rps, M, ref, "linear_fwd")
     t = KERNEL_TIMER.start()
-    check(lib().octic_linear_d8_fwd(ctypes.byref(xv), _arr5(w5), _p(bias), ctypes.byref(yv),
-                                    ctypes.byref(resid_v) if resid_v is not None else None, _p(rs), int(rps),
-                                    _arr5(cs5) if cs5 is not None else None, M, cin, cout, dt_code(dtype),
-                                    dt_code(out_dtype), _stream(ref)))
+    check(lib().octic_linear_d8_fwd_skip(ctypes.byref(xv), _arr5(w5), _p(bias), ctypes.byref(yv),
+                                         ctypes.byref(resid_v) if resid_v is not None else None, _p(rs), int(rps),
+                                         _arr5(cs5) if cs5 is not None else None, M, cin, cout, dt_code(dtype),
+                                         dt_code(out_dtype), _p(ss), srps, _stream(ref)))
     if t is not None:
         es, eo = (2 if dtype == torch.bfloat16 else 4), (2 if out_dtype == torch.bfloat16 else 4)
         nbytes = M * 8 * cin * es + M * 8 * cout * eo * (2 if resid_v is not None else 1) + 8 * cin * cout * es
@@ -634,6 +659,19 @@ def _attn_bwd_phases(T, hd, dtype=_lib.BF16, ld=(0, 0, 0)):
     pre = "attn_f32" if bwd == _lib.ATTN_BWD_F32 else "attn_bwd"
     suf = "_stream_kernel" if bwd == _lib.ATTN_BWD_STREAM else "_kernel"
     return ((1, pre + "_dq" + suf, 6, 6.0), (2, pre + "_dkv" + suf, 6, 8.0))
+
+
+def attn_skips_dropped(B, T, hd, dtype=_lib.BF16, ld=(0, 0, 0)):
+    """True where BOTH attention launches of a training step - the forward and whatever _attn_bwd_phases runs - SKIP a sample
+    whose sample_scale is 0: they read none of its q / k / v / dO rows (octic_attn_skip_plan, under the current route overrides).
+    Only then may the GEMMs around the softmax core (qkv's forward, proj's input gradient) leave those rows unwritten: a kernel
+    that computes the sample would carry whatever the rows hold into the stream as 0 x NaN."""
+    answer = _lib.plan("octic_attn_skip_plan", dtype, T, hd, *ld)
+    if answer is None:
+        return False
+    fwd_max_b, single, pair, _ = answer
+    bwd = single if _attn_bwd_phases(T, hd, dtype, ld)[0][0] == 3 else pair
+    return bool(0 < B <= fwd_max_b and bwd)
 
 
 def attn_bwd(q, k, v, o, dout, lse, scale, dq, dk, dv, sample_scale=None):
