@@ -177,6 +177,25 @@ int octic_linear_d8_fwd_skip(const octic_view* x, const void* const w[5], const 
                              const octic_view* resid, const float* rs, int64_t rows_per_sample,
                              const float* const cs[5], int64_t M, int cin, int cout, int dtype, int out_dtype,
                              const float* sample_scale, int64_t skip_rows_per_sample, void* stream);
+/* The same with a mask of another kind: dropped[M / dropped_rows_per_sample] (f32, device; a factor of exactly 0 = the sample is
+ * dropped by stochastic depth; NULL = the plain call).  Where _skip says "nobody reads those rows", this says "those rows are
+ * known": the caller promises what makes the dropped samples' work void, and every output row is still defined.  CONTRACT:
+ *   plain launch (no resid / rs / cs): bias must be NULL, and the caller promises that EVERY INPUT ROW of a dropped sample is zero.
+ *     The kernel may leave those rows unread and writes +0 to every output row of a dead tile (a 128-row tile all of whose
+ *     tokens belong to dropped samples).  Kept samples' rows are bit for bit the unmasked launch's; dropped samples' rows
+ *     compare equal to it (zeros either way).
+ *   fused launch: needs resid and rs, and dropped_rows_per_sample == rows_per_sample; the caller promises rs[b] == 0 wherever
+ *     dropped[b] == 0 (the same array will do).  A dead tile's output rows are its resid rows copied, x unread.
+ *   OCTIC_ESHAPE: a plain masked launch with a bias; a fused one without resid or rs or with unequal row counts;
+ *     dropped_rows_per_sample <= 0 or M % dropped_rows_per_sample != 0; a mask with the lift addressing.
+ * Ignoring the mask is always correct under this contract: only the ring kernel's SKIP instantiation (bf16 operands,
+ * linear_d8_ring_kernel<.., SKIP>, at most 1024 row tiles per irrep group) honours it - it runs the live items first, dealt evenly
+ * over the XCDs, and a dead item neither loads nor multiplies; the W-stationary and register-staged kernels and f32 operands
+ * compute every row.  The plan (octic_linear_d8_plan) and the launch shape do not depend on the mask.                          */
+int octic_linear_d8_fwd_dropped(const octic_view* x, const void* const w[5], const float* bias, const octic_view* y,
+                                const octic_view* resid, const float* rs, int64_t rows_per_sample,
+                                const float* const cs[5], int64_t M, int cin, int cout, int dtype, int out_dtype,
+                                const float* dropped, int64_t dropped_rows_per_sample, void* stream);
 
 /* Compute-dtype copies of the f32 master weights in ONE launch per layer: wb = [W_A1|W_A2|W_B1|W_B2|W_E]
  * (forward), wt = each matrix transposed with the layer-scale folded in, wt_g[k][n] = cs_g[n] W_g[n][k]
@@ -219,6 +238,17 @@ int octic_linear_d8_plan(int64_t M, int cin, int cout, int dtype, int out_dtype,
  * applies, 0 for the even spread, negative on bad arguments.                                                            */
 int octic_linear_d8_ring_order(int ngroups, const int* items, const int* ksteps, int slots_per_xcd, int* out_group,
                                int* out_item);
+/* The same for a masked ring launch (octic_linear_d8_fwd_dropped), through the kernel's own mapping function: class g has
+ * items[g] row tiles of n_chunks[g] column chunks each (n_chunks NULL = 1 each; classes 1.. must be equal), dead_long[items[0]] /
+ * dead_short[items[1]] flag the dead row tiles (non-zero = dead; the short classes cover the same rows).  out_group / out_item /
+ * out_dead (nullable), sum(items * n_chunks) entries each: per workgroup the class, the item (row tile * n_chunks + chunk) and
+ * whether it is dead.  In every XCD's dispatch order (workgroups x, x + 8, ..) live long items come first, then live short
+ * ones, then dead ones; live items are shared evenly over the XCDs; the chunks of a long row tile are consecutive workgroups
+ * of one XCD where the launch has ceil(items[0] / 8) * n_chunks[0] rounds.  Returns the number of workgroups, OCTIC_ESHAPE for
+ * a launch the masked kernel does not take (unequal short classes, more than 1024 row tiles).                              */
+int octic_linear_d8_ring_order_dropped(int ngroups, const int* items, const int* ksteps, int slots_per_xcd, const int* n_chunks,
+                                       const unsigned char* dead_long, const unsigned char* dead_short, int* out_group,
+                                       int* out_item, int* out_dead);
 
 /* Weight gradient  G_g[n,k] = sum_rows dy_g[row,n] x_g[row,k]  (E: both rows).  Reduction over the
  * M (2M) rows is split over `splits` row ranges whose f32 partial slabs go to `workspace`

@@ -56,9 +56,13 @@ _PROTOS = {
                                     c_int, c_int, c_void_p]),
     "octic_linear_d8_fwd_skip": (c_int, [VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int,
                                          c_int, c_int, c_void_p, c_i64, c_void_p]),
+    "octic_linear_d8_fwd_dropped": (c_int, [VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int,
+                                            c_int, c_int, c_void_p, c_i64, c_void_p]),
     "octic_linear_d8_tile_n": (c_int, [c_i64, c_int, c_int]),
     "octic_linear_d8_plan": (c_int, [c_i64, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "octic_linear_d8_ring_order": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "octic_linear_d8_ring_order_dropped": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p]),
     "octic_linear_d8_wgrad_tile": (c_int, [c_i64, c_int, c_int]),
     "octic_linear_d8_wgrad_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
     "octic_linear_d8_wgrad_splits": (c_int, [c_i64, c_int, c_int]),

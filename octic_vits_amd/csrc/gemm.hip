@@ -383,7 +383,107 @@ __host__ __device__ inline void ring_item_of(const GemmArgs& args, int nwg, int 
   }
 }
 
-template <typename TIN, typename TOUT, int EPI, int NT, int S, int BM = 128>
+// ---- item order of a masked launch (octic_linear_d8_fwd_dropped).  An m-tile is dead when every token it covers belongs to a
+// dropped sample; a dead item costs a twentieth of a live one, so the planned order - which gives each XCD contiguous m-tiles,
+// about eight whole samples - would make the launch last as long as the XCD that drew the most kept samples.  Here the order is
+// a function of blockIdx and the two live bitmaps (long group; one short group - the short groups cover the same token rows):
+// in every XCD's dispatch order (workgroups x, x + 8, ...) all live long items, then all live short items, then the dead ones.
+//   * live long m-tile of rank r goes to XCD r & 7; its n-chunks are consecutive workgroups of that XCD (X crosses into that L2
+//     once), so XCD x starts with (LL / 8 + (x < LL % 8)) * n_chunks long items;
+//   * the slots that are left, walked row by row (l = bid >> 3, then x), take the live short items (m-tile rank, group, n-chunk),
+//     then the dead long and the dead short ones: every XCD's live count is within one m-tile of the others'.
+// Co-locating the n-chunks needs ceil(m_tiles / 8) * n_chunks rows of workgroups; a launch too small for that (a shape fact, not a
+// mask fact) uses the plain list [live long | live short | dead] with item = blockIdx.
+constexpr int kRingMaskCap = 1024;               // m-tiles per group the bitmaps cover; above it the host launches the unmasked kernel
+constexpr int kRingMaskWords = kRingMaskCap / 64;
+
+__host__ __device__ inline int bm_count(const unsigned long long* bm, int words) {
+  int c = 0;
+  for (int i = 0; i < words; ++i) c += __builtin_popcountll(bm[i]);
+  return c;
+}
+// index of the set (live) or clear (dead) bit of rank r; bits past the group's m-tiles are clear and lie behind every dead tile
+__host__ __device__ inline int bm_select(const unsigned long long* bm, int words, int r, bool set) {
+  for (int i = 0; i < words; ++i) {
+    unsigned long long w = set ? bm[i] : ~bm[i];
+    const int c = __builtin_popcountll(w);
+    if (r < c || i == words - 1) {
+      int pos = 0;
+#pragma unroll
+      for (int sh = 32; sh; sh >>= 1) {
+        const unsigned long long lo = w & ((1ull << sh) - 1);
+        const int cl = __builtin_popcountll(lo);
+        if (r >= cl) {
+          r -= cl;
+          w >>= sh;
+          pos += sh;
+        } else {
+          w = lo;
+        }
+      }
+      return i * 64 + pos;
+    }
+    r -= c;
+  }
+  return 0;
+}
+
+__host__ __device__ inline void ring_item_masked(const GemmArgs& args, int nwg, int bid, const unsigned long long* live_long,
+                                                 const unsigned long long* live_short, int& gi, int& lt, bool& dead) {
+  const int ML = args.g[0].m_tiles, NC0 = args.g[0].n_chunks, MS = args.g[1].m_tiles, NCS = args.g[1].n_chunks;
+  const int nshort = args.ngroups - 1;
+  const int wl = (ML + 63) >> 6, ws = (MS + 63) >> 6;
+  const int LL = bm_count(live_long, wl), LS = bm_count(live_short, ws);
+  const int x = bid & 7, l = bid >> 3;
+  int f;                                         // index of this slot among the slots the live long items leave
+  if (((ML + 7) >> 3) * NC0 <= (nwg >> 3)) {
+    const int c0 = LL >> 3, R = LL & 7;
+    if (l < (c0 + (x < R ? 1 : 0)) * NC0) {
+      const int q = l / NC0;
+      gi = 0;
+      lt = bm_select(live_long, wl, q * 8 + x, true) * NC0 + (l - q * NC0);
+      dead = false;
+      return;
+    }
+    f = l < (c0 + 1) * NC0 ? (l - c0 * NC0) * (8 - R) + (x - R) : NC0 * (8 - R) + (l - (c0 + 1) * NC0) * 8 + x;
+  } else {
+    if (bid < LL * NC0) {
+      const int q = bid / NC0;
+      gi = 0;
+      lt = bm_select(live_long, wl, q, true) * NC0 + (bid - q * NC0);
+      dead = false;
+      return;
+    }
+    f = bid - LL * NC0;
+  }
+  const int per_tile = NCS * nshort;             // short items per m-tile: (group, n-chunk)
+  dead = f >= LS * per_tile;
+  if (dead) f -= LS * per_tile;
+  if (dead && f < (ML - LL) * NC0) {
+    const int q = f / NC0;
+    gi = 0;
+    lt = bm_select(live_long, wl, q, false) * NC0 + (f - q * NC0);
+    return;
+  }
+  if (dead) f -= (ML - LL) * NC0;
+  const int q = f / per_tile, r = f - q * per_tile, g = r / NCS;
+  gi = 1 + g;
+  lt = bm_select(live_short, ws, q, !dead) * NCS + (r - g * NCS);
+}
+
+// the launches ring_item_masked can order: a long group and equal short groups over the same token rows, bitmaps within the cap
+inline bool ring_mask_ok(const GemmArgs& a) {
+  if (a.ngroups < 2 || a.lift_np > 0 || a.dropped_rps <= 0) return false;
+  if (a.g[0].m_tiles > kRingMaskCap || a.g[1].m_tiles > kRingMaskCap || a.g[0].rows >= (1ll << 31) - 256) return false;
+  for (int g = 1; g < a.ngroups; ++g) {
+    if (a.g[g].chunk != 1 || a.g[g].m_tiles != a.g[1].m_tiles || a.g[g].n_chunks != a.g[1].n_chunks || a.g[g].rows != a.g[1].rows ||
+        a.g[g].pair != a.g[1].pair)
+      return false;
+  }
+  return a.g[0].chunk == 1;
+}
+
+template <typename TIN, typename TOUT, int EPI, int NT, int S, int BM = 128, bool SKIP = false>
 __global__ __launch_bounds__(BM * 2, 2) void linear_d8_ring_kernel(GemmArgs args) {
   constexpr int NW = BM / 32;                 // waves: each owns 32 rows x BN columns
   constexpr int EPC = Elem<TIN>::EPC;
@@ -405,7 +505,37 @@ __global__ __launch_bounds__(BM * 2, 2) void linear_d8_ring_kernel(GemmArgs args
   // 95 k .. 200 k cycles for one launch).  Segment k of the order = [share k of group 0 | share k of group 1 | ...].
   (void)tile;                                 // (the timeline build indexes its stamps with it)
   int gi, lt;
-  ring_item_of(args, nwg, bid, gi, lt);
+  bool dead_item = false;
+  if constexpr (SKIP) {
+    // live bitmaps of the long group's and of one short group's m-tiles: lane = m-tile, one ballot per 64 tiles; the factors
+    // are a cache line or two that every workgroup of the launch reads
+    __shared__ unsigned long long live_bm[2 * kRingMaskWords];
+    const int lane0 = threadIdx.x & 63, wid0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wl = (args.g[0].m_tiles + 63) >> 6, ws = (args.g[1].m_tiles + 63) >> 6;
+    const float* dropped = args.dropped;
+    const unsigned rps = (unsigned)args.dropped_rps;
+    for (int w = wid0; w < wl + ws; w += BM / 32) {
+      const bool lg = w < wl;
+      const unsigned rows = (unsigned)(lg ? args.g[0].rows : args.g[1].rows);   // (ring_mask_ok: rows < 2^31)
+      const int psh = lg ? args.g[0].pair : args.g[1].pair;
+      const unsigned r0 = (unsigned)(((lg ? w : w - wl) << 6) + lane0) * (unsigned)BM;
+      bool live = false;
+      if (r0 < rows) {
+        const unsigned r1 = r0 + BM - 1 < rows ? r0 + BM - 1 : rows - 1;
+        const unsigned b1 = (r1 >> psh) / rps;
+        for (unsigned b = (r0 >> psh) / rps; b <= b1; ++b) live = live || dropped[b] != 0.0f;
+      }
+      const unsigned long long m = __ballot(live);
+      if (lane0 == 0) live_bm[lg ? w : kRingMaskWords + (w - wl)] = m;
+    }
+    __syncthreads();
+    ring_item_masked(args, nwg, bid, live_bm, live_bm + kRingMaskWords, gi, lt, dead_item);
+    gi = __builtin_amdgcn_readfirstlane(gi);
+    lt = __builtin_amdgcn_readfirstlane(lt);
+    dead_item = __builtin_amdgcn_readfirstlane((int)dead_item) != 0;
+  } else {
+    ring_item_of(args, nwg, bid, gi, lt);
+  }
   const GemmGroup& G = args.g[gi];
   // work item = (m-tile, chunk of consecutive n-tiles); the DMA ring runs continuously over its (n-tile, k-tile) steps
   const int mt = lt / G.n_chunks, nc = lt - mt * G.n_chunks;
@@ -429,6 +559,34 @@ __global__ __launch_bounds__(BM * 2, 2) void linear_d8_ring_kernel(GemmArgs args
     if (tile < 2048 && lane == 0 && wid < 4) g_ring_trace[(tile * 4 + wid) * 64 + 63] = ((unsigned long long)hwid << 32) | xcc;
   }
 #endif
+
+  if constexpr (SKIP) {
+    // ---- dead item (workgroup-uniform: no barrier below is left unpaired): the tile's inputs are zero rows (plain launch) or
+    // its rs is 0 (fused), so the result is +0 or the residual - no DMA, no K loop; the tile is walked row-wise, 16 bytes per
+    // lane, as the staged epilogue walks it
+    if (dead_item) {
+      constexpr int OPC = 16 / (int)sizeof(TOUT), CPR = BN / OPC;
+      typedef typename std::conditional<sizeof(TOUT) == 4, f32x4, bf16x8>::type piece_t;
+      const int nb = nt_begin * BN;
+      const int pshift = G.pair ? 1 : 0;
+      const int64_t rows = G.rows, y_ld = G.y_ld, r_ld = G.r_ld;
+      TOUT* const yb = (TOUT*)G.y;
+      const TOUT* const rb = (const TOUT*)G.resid;
+#pragma unroll 4
+      for (int p = threadIdx.x; p < BM * CPR; p += BM * 2) {
+        const int r = p / CPR, c = p - r * CPR;
+        const int64_t mm = m0 + r;
+        const int n = nb + c * OPC;
+        if (mm < rows && n < N) {
+          const int64_t tok = mm >> pshift, half = mm & pshift;
+          piece_t v = {};
+          if constexpr (EPI == 1) v = *(const piece_t*)(rb + tok * r_ld + half * N + n);
+          *(piece_t*)(yb + tok * y_ld + half * N + n) = v;
+        }
+      }
+      return;
+    }
+  }
 
   // ---- DMA sources.  A wave-instruction fills 8 LDS rows: lane -> row (lane>>3), chunk position (lane&7), which
   // must hold source chunk (lane&7) ^ (row&7) = (lane&7) ^ (lane>>3).
@@ -822,7 +980,19 @@ int launch_ring_nt(GemmArgs& a, bool fused, hipStream_t s) {
   if (once.first()) {
     (void)hipFuncSetAttribute((const void*)linear_d8_ring_kernel<TIN, TOUT, 0, NT, S, BM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     (void)hipFuncSetAttribute((const void*)linear_d8_ring_kernel<TIN, TOUT, 1, NT, S, BM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if constexpr (std::is_same<TIN, bf16>::value) {
+      (void)hipFuncSetAttribute((const void*)linear_d8_ring_kernel<TIN, TOUT, 0, NT, S, BM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      (void)hipFuncSetAttribute((const void*)linear_d8_ring_kernel<TIN, TOUT, 1, NT, S, BM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    }
     (void)hipGetLastError();
+  }
+  if constexpr (std::is_same<TIN, bf16>::value) {
+    // octic_linear_d8_fwd_dropped: same grid, same plan fields (unused); the SKIP instantiation orders the items by the mask
+    if (a.dropped && ring_mask_ok(a)) {
+      if (fused) linear_d8_ring_kernel<TIN, TOUT, 1, NT, S, BM, true><<<t, BM * 2, smem, s>>>(a);
+      else linear_d8_ring_kernel<TIN, TOUT, 0, NT, S, BM, true><<<t, BM * 2, smem, s>>>(a);
+      return launch_status();
+    }
   }
   if (fused) linear_d8_ring_kernel<TIN, TOUT, 1, NT, S, BM><<<t, BM * 2, smem, s>>>(a);
   else linear_d8_ring_kernel<TIN, TOUT, 0, NT, S, BM><<<t, BM * 2, smem, s>>>(a);
@@ -977,13 +1147,61 @@ extern "C" int octic_linear_d8_ring_order(int ngroups, const int* items, const i
   return a.plan_mode;
 }
 
+// The same for a masked launch (octic_linear_d8_fwd_dropped): items[g] m-tiles of n_chunks[g] n-chunks each (n_chunks NULL = 1), group 0 the
+// long one, groups 1.. equal; dead_long[items[0]] / dead_short[items[1]] flag the dead m-tiles.  out_group / out_item / out_dead
+// (nullable) receive, per workgroup in blockIdx order, what ring_item_masked - the kernel's own mapping - gives it.  Returns the
+// number of workgroups, or OCTIC_ESHAPE for a launch the masked kernel does not take (the unmasked kernel runs it).
+extern "C" int octic_linear_d8_ring_order_dropped(int ngroups, const int* items, const int* ksteps, int slots_per_xcd, const int* n_chunks,
+                                            const unsigned char* dead_long, const unsigned char* dead_short, int* out_group,
+                                            int* out_item, int* out_dead) {
+  if (ngroups < 1 || ngroups > 5 || !items || !ksteps || !dead_long || !dead_short || !out_group || !out_item) return OCTIC_ENULL;
+  (void)slots_per_xcd;   // (the masked order does not depend on the slot count: live work fills whole rounds)
+  GemmArgs a = {};
+  a.ngroups = ngroups;
+  a.dropped_rps = 1;
+  int t = 0;
+  for (int g = 0; g < ngroups; ++g) {
+    if (items[g] <= 0 || (n_chunks && n_chunks[g] <= 0)) return OCTIC_ESHAPE;
+    a.g[g].K = ksteps[g] * 64;
+    a.g[g].n_chunks = n_chunks ? n_chunks[g] : 1;
+    a.g[g].chunk = 1;
+    a.g[g].n_tiles = a.g[g].n_chunks;
+    a.g[g].m_tiles = items[g];
+    a.g[g].rows = (int64_t)items[g] * kBM;
+    a.g[g].tile_begin = t;
+    t += items[g] * a.g[g].n_chunks;
+  }
+  a.total_tiles = t;
+  if (!ring_mask_ok(a)) return OCTIC_ESHAPE;
+  unsigned long long bm[2 * kRingMaskWords] = {};
+  for (int i = 0; i < items[0]; ++i)
+    if (!dead_long[i]) bm[i >> 6] |= 1ull << (i & 63);
+  for (int i = 0; i < items[1]; ++i)
+    if (!dead_short[i]) bm[kRingMaskWords + (i >> 6)] |= 1ull << (i & 63);
+  for (int bid = 0; bid < t; ++bid) {
+    bool dead = false;
+    ring_item_masked(a, t, bid, bm, bm + kRingMaskWords, out_group[bid], out_item[bid], dead);
+    if (out_dead) out_dead[bid] = dead ? 1 : 0;
+  }
+  return t;
+}
+
 extern "C" {
 
-int octic_linear_d8_fwd_skip(const octic_view* x, const void* const w[5], const float* bias, const octic_view* y,
-                             const octic_view* resid, const float* rs, int64_t rows_per_sample, const float* const cs[5],
-                             int64_t M, int cin, int cout, int dtype, int out_dtype, const float* sample_scale,
-                             int64_t skip_rows_per_sample, void* stream) {
+// the three LinearD8 entry points: sample_scale / skip_rows_per_sample of octic_linear_d8_fwd_skip, dropped / dropped_rows_per_sample of
+// octic_linear_d8_fwd_dropped (never both)
+static int linear_d8_launch(const octic_view* x, const void* const w[5], const float* bias, const octic_view* y,
+                            const octic_view* resid, const float* rs, int64_t rows_per_sample, const float* const cs[5],
+                            int64_t M, int cin, int cout, int dtype, int out_dtype, const float* sample_scale,
+                            int64_t skip_rows_per_sample, const float* dropped, int64_t dropped_rows_per_sample, void* stream) {
   int e;
+  if (dropped) {
+    // plain launch: the promise is about zero INPUT rows, which a bias would turn into non-zero output rows; fused launch: the
+    // dead tile's result is the residual, which needs the residual and rs as the mask over the same samples
+    if (dropped_rows_per_sample <= 0 || dropped_rows_per_sample >= (1ll << 31) || M % dropped_rows_per_sample != 0) return OCTIC_ESHAPE;
+    const bool plain = !resid && !rs && !cs;
+    if (plain ? bias != nullptr : (!resid || !rs || dropped_rows_per_sample != rows_per_sample)) return OCTIC_ESHAPE;
+  }
   // the mask says some output rows have no reader: a fused tail (residual, per-sample or column scale) writes the stream itself
   // (cs: the array itself - the entry point takes five column scales or none)
   if (sample_scale && (resid || rs || cs || skip_rows_per_sample <= 0 || M % skip_rows_per_sample != 0)) return OCTIC_ESHAPE;
@@ -1002,6 +1220,8 @@ int octic_linear_d8_fwd_skip(const octic_view* x, const void* const w[5], const 
   a.rps = rs ? rows_per_sample : 1;
   a.skip = sample_scale;
   a.skip_rps = sample_scale ? skip_rows_per_sample : 1;
+  a.dropped = dropped;
+  a.dropped_rps = dropped ? (int)dropped_rows_per_sample : 0;
   d8_group_table(a, M, cin, cout);
   for (int gidx = 0; gidx < 5; ++gidx) {
     const int irrep = d8_group_irrep(gidx);
@@ -1016,7 +1236,24 @@ int octic_linear_d8_fwd_skip(const octic_view* x, const void* const w[5], const 
     g.bias = (irrep == 0) ? bias : nullptr;
     g.cs = cs ? cs[irrep] : nullptr;
   }
+  if (a.dropped && a.lift_np > 0) return OCTIC_ESHAPE;   // (the lift addressing has no per-sample rows; no entry point builds this)
   return dispatch_gemm(a, dtype, out_dtype, (hipStream_t)stream);
+}
+
+int octic_linear_d8_fwd_skip(const octic_view* x, const void* const w[5], const float* bias, const octic_view* y,
+                             const octic_view* resid, const float* rs, int64_t rows_per_sample, const float* const cs[5],
+                             int64_t M, int cin, int cout, int dtype, int out_dtype, const float* sample_scale,
+                             int64_t skip_rows_per_sample, void* stream) {
+  return linear_d8_launch(x, w, bias, y, resid, rs, rows_per_sample, cs, M, cin, cout, dtype, out_dtype, sample_scale,
+                          skip_rows_per_sample, nullptr, 0, stream);
+}
+
+int octic_linear_d8_fwd_dropped(const octic_view* x, const void* const w[5], const float* bias, const octic_view* y,
+                                const octic_view* resid, const float* rs, int64_t rows_per_sample, const float* const cs[5],
+                                int64_t M, int cin, int cout, int dtype, int out_dtype, const float* dropped,
+                                int64_t dropped_rows_per_sample, void* stream) {
+  return linear_d8_launch(x, w, bias, y, resid, rs, rows_per_sample, cs, M, cin, cout, dtype, out_dtype, nullptr, 0, dropped,
+                          dropped_rows_per_sample, stream);
 }
 
 int octic_linear_d8_fwd(const octic_view* x, const void* const w[5], const float* bias, const octic_view* y,

@@ -43,6 +43,11 @@ struct GemmArgs {
   // (Last in the block: the other kernels' argument offsets stay what they were.)
   const float* skip;
   int64_t skip_rps;
+  // stochastic-depth mask of octic_linear_d8_fwd_dropped: one factor per sample of dropped_rps token rows; a factor of 0 promises
+  // that the sample's input rows are zero (plain launch) or that rs is 0 there (fused).  Honoured by the ring kernel's SKIP
+  // instantiation (dead tiles: no DMA, no K loop; live items dealt first), ignored by every other kernel.
+  const float* dropped;
+  int dropped_rps;
 };
 
 // MFMA operand reads as inline asm with hand-counted waits: inside the GEMM loops hipcc protects every MFMA group with

@@ -298,11 +298,13 @@ class LinearD8(nn.Module):
     def weights(self):
         return tuple(getattr(self, "lin_" + n).weight for n in _IRREPS)
 
-    def forward(self, x_batched, resid=None, rs=None, cs=None, next_norm=None, skip_out=None, skip_dx=None):
+    def forward(self, x_batched, resid=None, rs=None, cs=None, next_norm=None, skip_out=None, skip_dx=None, zero_dx=None):
         """next_norm (a LayerNormD8, only with resid): also return next_norm(result) -> (Octic, Octic or None); on the
         bf16 GPU path the two are ONE autograd node whose backward skips the cast pass (OF.LinearD8NormFn).
         skip_out / skip_dx: the branch's stochastic-depth factor as the sample mask of the forward / the input-gradient
-        launch (OF.LinearD8Fn) - the caller's promise that every reader of that output honours the same mask."""
+        launch (OF.LinearD8Fn) - the caller's promise that every reader of that output honours the same mask.
+        zero_dx (plain layers): the same factor as the `dropped` mask of the input-gradient launch - the caller's promise that
+        the cotangent rows of a dropped sample arrive as exact zeros (OF.LinearD8Fn)."""
         assert len(x_batched) == 5, "Input should be a 5-tuple"
         xp, cin = as_packed(x_batched)
         if 8 * cin != self.input_channels:
@@ -329,7 +331,7 @@ class LinearD8(nn.Module):
                                             self._prep, *a, beta, next_norm.eps, skip_dx)
             return Octic(y, cout), Octic(yn, cout)
         y = OF.LinearD8Fn.apply(xp, *self.weights(), self.lin_A1.bias, resid, rs, *cs5, cin, cout, rps, dtype, self._prep,
-                                skip_out, skip_dx)
+                                skip_out, skip_dx, zero_dx)
         return Octic(y, cout) if next_norm is None else (Octic(y, cout), None)
 
     def extra_repr(self) -> str:
@@ -448,7 +450,8 @@ class MlpD8(nn.Module):
     def forward(self, xs, resid=None, rs=None, cs=None, next_norm=None):
         mask = self._sample_mask(xs, resid, rs)
         if mask is not None:
-            h = self.fc1(xs, skip_out=mask)
+            # (fc1's input gradient reads the GELU backward's output: +0 in every row of a dropped sample)
+            h = self.fc1(xs, skip_out=mask, zero_dx=mask)
             a = Octic(OF.GeluD8PackedFn.apply(h.packed, h.c, mask, h.packed.shape[1]), h.c)
             return self.fc2(a, resid=resid, rs=rs, cs=cs, next_norm=next_norm, skip_dx=mask)
         xs = self.norm(self.drop1(self.act(self.fc1(xs))))
@@ -742,7 +745,13 @@ class AttentionD8(nn.Module):
         drop = self.attn_drop.p if self.training else 0.
         rag = OF.RAGGED
         gemm_mask = self._gemm_mask(xp, c, resid, rs, drop, rag)
-        qkv = self.qkv(xs if isinstance(xs, Octic) else Octic(xp, c), skip_out=gemm_mask)
+        # qkv's input gradient reads dqkv, the attention backward of dO = 0 for a dropped sample (proj's tail multiplies the branch
+        # by rs): exact zeros wherever the packed attention node below gets rs, whether its kernels skip the sample or compute it
+        zero_dx = rs if (rs is not None and resid is not None and not COMPACT_DROP_PATH and not (rag is not None and rag.matches(xp))
+                         and OF.ATTN_PACKED and drop == 0. and xp.is_cuda and not torch.compiler.is_compiling()
+                         and not self.proj_drop.active and type(self.qkv) is LinearD8 and type(self.proj) is LinearD8
+                         and OF.ops.attn_packed_ok(xp.shape[1], c, self.num_heads, compute_dtype(xp))) else None
+        qkv = self.qkv(xs if isinstance(xs, Octic) else Octic(xp, c), skip_out=gemm_mask, zero_dx=zero_dx)
         if rag is not None and rag.matches(xp):
             # several crop sets in one row tensor: the softmax core walks the sets, everything around it ran once on all rows
             from . import ragged as _R

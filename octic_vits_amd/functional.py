@@ -258,10 +258,13 @@ class LinearD8Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wA1, wA2, wB1, wB2, wE, bias, resid, rs, sA1, sA2, sB1, sB2, sE, cin, cout, rps, dtype, prep,
-                skip_out=None, skip_dx=None):
+                skip_out=None, skip_dx=None, zero_dx=None):
         """skip_out / skip_dx: the stochastic-depth factor of the branch this layer sits in, as the sample mask of the forward
         launch / of the input-gradient launch - given by the caller only where EVERY reader of that launch's output honours the
-        same mask (linear_skip_scale; DESIGN.md 'Routing rules').  The rows of a dropped sample may then stay unwritten."""
+        same mask (linear_skip_scale; DESIGN.md 'Routing rules').  The rows of a dropped sample may then stay unwritten.
+        zero_dx: the same factor as the `dropped` mask of a plain layer's input-gradient launch (ring_skip_scale) - given only
+        where the cotangent rows of a dropped sample are exactly zero; every row of dx is written (zeros there).  A fused
+        forward hands its own rs to the launch as `dropped`: the tail multiplies those samples' rows by 0."""
         w5 = (wA1, wA2, wB1, wB2, wE)
         cs5 = None if sA1 is None else (sA1, sA2, sB1, sB2, sE)
         ops._require_cuda(x)
@@ -281,16 +284,19 @@ class LinearD8Fn(torch.autograd.Function):
         rv = ops.pview(_c(resid), cout) if fused else None
         plain = not fused and rs32 is None and cs32 is None
         ss_out = linear_skip_scale(skip_out, rps, M) if plain else None
+        dropped = ring_skip_scale(rs32, rps, M) if fused else None
         ops.linear_fwd(ops.pview(x, cin), wb, b32, ops.pview(y, cout), M, cin, cout, dtype, out_dtype, x,
-                       resid_v=rv, rs=rs32, rps=rps, cs5=cs32, sample_scale=ss_out, skip_rps=rps)
-        ctx.save_for_backward(x, rs32, b32, linear_skip_scale(skip_dx, rps, M), *w5, *(cs32 or []))
+                       resid_v=rv, rs=rs32, rps=rps, cs5=cs32, sample_scale=ss_out, skip_rps=rps, dropped=dropped, dropped_rps=rps)
+        ss_dx = linear_skip_scale(skip_dx, rps, M)
+        z_dx = ring_skip_scale(zero_dx, rps, M) if (plain and ss_dx is None) else None
+        ctx.save_for_backward(x, rs32, b32, ss_dx, z_dx, *w5, *(cs32 or []))
         ctx.meta = (cin, cout, rps, dtype, fused, cs5 is not None, bias is not None, x_in_dtype, wt)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         cin, cout, rps, dtype, fused, has_cs, has_bias, x_in_dtype, wt = ctx.meta
-        x, rs32, b32, ss_dx, *rest = ctx.saved_tensors
+        x, rs32, b32, ss_dx, z_dx, *rest = ctx.saved_tensors
         w5, cs32 = rest[:5], (rest[5:] if has_cs else None)
         M = x.numel() // (8 * cin)
         dy = _c(dy)
@@ -302,7 +308,8 @@ class LinearD8Fn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(x.shape, dtype=dtype, device=x.device)
-            ops.linear_fwd(gv, wt, None, ops.pview(dx, cin), M, cout, cin, dtype, dtype, x, sample_scale=ss_dx, skip_rps=rps)
+            ops.linear_fwd(gv, wt, None, ops.pview(dx, cin), M, cout, cin, dtype, dtype, x, sample_scale=ss_dx, skip_rps=rps,
+                           dropped=z_dx, dropped_rps=rps)
             if dx.dtype != x_in_dtype:
                 dx = dx.to(x_in_dtype)
         # bias gradient = column sums of the invariant block of g: the bf16 wgrad kernel produces them on the side
@@ -315,7 +322,7 @@ class LinearD8Fn(torch.autograd.Function):
         if not f32_masters:
             dw = [d.to(w.dtype) for d, w in zip(dw, w5)]
         dcs = dcs if has_cs else [None] * 5
-        return (dx, *dw, dbias, dy if fused else None, None, *dcs, None, None, None, None, None, None, None)
+        return (dx, *dw, dbias, dy if fused else None, None, *dcs, None, None, None, None, None, None, None, None)
 
 
 class LinearD8NormFn(torch.autograd.Function):
@@ -328,7 +335,8 @@ class LinearD8NormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, wA1, wA2, wB1, wB2, wE, bias, resid, rs, sA1, sA2, sB1, sB2, sE, cin, cout, rps, dtype, prep,
                 a1, a2, b1, b2, ae, beta, eps, skip_dx=None):
-        """skip_dx: as in LinearD8Fn (the sample mask of the input-gradient launch)."""
+        """skip_dx: as in LinearD8Fn (the sample mask of the input-gradient launch).  The fused forward hands rs to the launch as
+        its `dropped` mask (ring_skip_scale)."""
         w5 = (wA1, wA2, wB1, wB2, wE)
         cs5 = None if sA1 is None else (sA1, sA2, sB1, sB2, sE)
         ops._require_cuda(x)
@@ -343,7 +351,8 @@ class LinearD8NormFn(torch.autograd.Function):
         cs32 = None if cs5 is None else [_c(s.detach().float()) for s in cs5]
         rs32 = None if rs is None else _c(rs.float())
         ops.linear_fwd(ops.pview(x, cin), wb, b32, ops.pview(y, cout), M, cin, cout, dtype, resid.dtype, x,
-                       resid_v=ops.pview(_c(resid), cout), rs=rs32, rps=rps, cs5=cs32)
+                       resid_v=ops.pview(_c(resid), cout), rs=rs32, rps=rps, cs5=cs32, dropped=ring_skip_scale(rs32, rps, M),
+                       dropped_rps=rps)
         alpha = None if a1 is None else [_c(t.float()) for t in (a1, a2, b1, b2, ae)]
         yn, stats = ops.layernorm_fwd(y, alpha, None if beta is None else _c(beta.float()), eps, dtype, cout)
         ctx.save_for_backward(x, rs32, b32, y, stats, linear_skip_scale(skip_dx, rps, M), *w5, *(cs32 or []), *(alpha or []))
@@ -508,6 +517,24 @@ def linear_skip_scale(rs, rps, M, rows_to=None):
             or rs.dtype != torch.float32 or rs.dim() != 1 or not rs.is_contiguous() or rps < 2 or rs.numel() * rps != M):
         return None
     return rs.detach()
+
+
+# The long-K GEMMs of an octic block (fc2 with its residual tail, the input gradients of fc1 and qkv) run the ring kernel, which
+# writes every row: for them the factor travels as the `dropped` mask of octic_linear_d8_fwd_dropped - a promise about the INPUT (zero
+# rows, or rs itself in a fused tail) instead of one about the output's readers.  The kernel then runs its live 128-row tiles
+# first, dealt evenly over the XCDs, and writes zeros / the residual for the dead ones without loading them.  A switch of its
+# own, effective only while LINEAR_SKIP_DROPPED is on: OCTIC_RING_SKIP (0 = off), read once at import.
+def _ring_skip_from_env():
+    return os.environ.get("OCTIC_RING_SKIP", "1").strip() != "0"
+
+
+RING_SKIP_DROPPED = _ring_skip_from_env()
+
+
+def ring_skip_scale(rs, rps, M):
+    """rs as the `dropped` mask of a ring-routed LinearD8 launch over M token rows: linear_skip_scale's conditions plus the
+    switch above; None otherwise."""
+    return linear_skip_scale(rs, rps, M) if RING_SKIP_DROPPED else None
 
 
 class AttnPackedFn(torch.autograd.Function):

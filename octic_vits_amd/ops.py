@@ -434,16 +434,22 @@ def dense_wgrad_tn_pair(dy0, x0, dy1, x1, dw1=None, dw0=None, sample_scale=None,
 
 
 def linear_fwd(xv, w5, bias, yv, M, cin, cout, dtype, out_dtype, ref, resid_v=None, rs=None, rps=1, cs5=None, sample_scale=None,
-               skip_rps=0):
+               skip_rps=0, dropped=None, dropped_rps=0):
     """sample_scale / skip_rps (plain launches only): the stochastic-depth factor of the branch, one entry per sample of
     skip_rps rows, where EVERY reader of the output honours the same mask (octic_linear_d8_fwd_skip: the output rows of a
-    dropped sample may stay unwritten).  Timer name, bytes and FLOP stay the full batch's."""
+    dropped sample may stay unwritten).  dropped / dropped_rps: the same factor under the other contract
+    (octic_linear_d8_fwd_dropped): the input rows of a dropped sample are zero (plain launch, no bias) or rs is that mask (fused);
+    every output row is written.  One mask per call.  Timer name, bytes and FLOP stay the full batch's."""
     ss, srps = _row_sample_scale(sample_scale, skip_rps, M, ref, "linear_fwd")
+    dr, drps = _row_sample_scale(dropped, dropped_rps, M, ref, "linear_fwd")
+    if ss is not None and dr is not None:
+        raise ValueError("linear_fwd: sample_scale and dropped are two contracts for one mask - pass one of them")
     t = KERNEL_TIMER.start()
-    check(lib().octic_linear_d8_fwd_skip(ctypes.byref(xv), _arr5(w5), _p(bias), ctypes.byref(yv),
-                                         ctypes.byref(resid_v) if resid_v is not None else None, _p(rs), int(rps),
-                                         _arr5(cs5) if cs5 is not None else None, M, cin, cout, dt_code(dtype),
-                                         dt_code(out_dtype), _p(ss), srps, _stream(ref)))
+    entry = lib().octic_linear_d8_fwd_skip if dr is None else lib().octic_linear_d8_fwd_dropped
+    check(entry(ctypes.byref(xv), _arr5(w5), _p(bias), ctypes.byref(yv),
+                ctypes.byref(resid_v) if resid_v is not None else None, _p(rs), int(rps),
+                _arr5(cs5) if cs5 is not None else None, M, cin, cout, dt_code(dtype),
+                dt_code(out_dtype), _p(ss if dr is None else dr), srps if dr is None else drps, _stream(ref)))
     if t is not None:
         es, eo = (2 if dtype == torch.bfloat16 else 4), (2 if out_dtype == torch.bfloat16 else 4)
         nbytes = M * 8 * cin * es + M * 8 * cout * eo * (2 if resid_v is not None else 1) + 8 * cin * cout * es
