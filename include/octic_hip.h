@@ -653,6 +653,31 @@ int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K
  * column-sum slabs of modes 3 / 5, out[2] = 1 when the launch uses per-image panels + the class-token kernel, out[3] =
  * workgroups of the main launch. */
 int octic_dense_gemm_plan(int M, int N, int K, int mode, int tokens, int* out4);
+/* The same launch under a stochastic-depth mask.  sample_scale: [M / rows_per_sample] f32 on the device, may be NULL (then
+ * exactly octic_dense_gemm_nt_tokens); it comes with rows_per_sample.  A factor of 0 means the caller and every reader of the
+ * output accept, for that sample's rows, EITHER the computed result OR +0 - the choice is per tile.  A row panel all of whose
+ * samples have factor 0 is dead: the kernel may leave the rows of A (and of H in modes 3 / 5) that only dead tiles cover unread,
+ * stores every output of a dead tile (C, C2; rows below M, columns below N, row stride ldc) as +0 and, in modes 3 / 5, the
+ * tile's two column-sum slab rows as +0 - outputs are never left unwritten, so they are finite whatever the buffers held.  A
+ * live tile is computed by exactly the code, K range and plan of the unmasked launch (same grid, workspace, tile width, panels
+ * and split-K front; octic_dense_gemm_plan_dropped reports it): kept samples' rows are bit for bit those of the unmasked launch.
+ * Only which workgroup takes which full tile changes: dead tiles first, then the live ones dealt evenly over the XCDs
+ * (octic_dense_gemm_order_dropped is the kernel's own mapping on the host).  Mode 2 and launches of more than 1024 row panels
+ * compute every row, which the contract allows.  The class-token launch of per-image panels computes all its rows.
+ * rows_per_sample <= 0 or M % rows_per_sample != 0 with a mask: OCTIC_ESHAPE. */
+int octic_dense_gemm_nt_tokens_skip(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
+                                    void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs,
+                                    int64_t rows_per_sample_rs, const float* X, float* OUT, const void* H, float* colsum,
+                                    const float* sample_scale, int rows_per_sample, void* workspace, int tokens,
+                                    void* stream);
+/* octic_dense_gemm_plan for a masked launch (today identical to it; OCTIC_ESHAPE for a bad rows_per_sample). */
+int octic_dense_gemm_plan_dropped(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out4);
+/* Host query of the masked launch's item map: sample_scale is a HOST array.  Per workgroup in blockIdx order: out_tm / out_tn
+ * the tile (-1 = padding workgroup), out_part its K part, out_split 1 for an item of the split-K front, out_dead 1 for a dead
+ * tile (each nullable, `cap` entries).  Returns the number of workgroups, or OCTIC_ESHAPE for a launch the masked kernel does
+ * not take (mode 2, more than 1024 panels, bad rows_per_sample) or cap too small. */
+int octic_dense_gemm_order_dropped(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
+                                   int cap, int* out_tm, int* out_tn, int* out_part, int* out_split, int* out_dead);
 
 /* Weight gradient of an nn.Linear of the standard half (the autograd of deit/vit.py:33,46 and of timm Mlp.fc1 / fc2):
  *     dW[N,K] = dY[M,N]^T . X[M,K]     f32, nn.Linear layout

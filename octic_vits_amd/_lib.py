@@ -153,6 +153,12 @@ _PROTOS = {
                                            c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_int, c_void_p]),
     "octic_dense_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    "octic_dense_gemm_nt_tokens_skip": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_i64, c_i64, c_int, c_void_p, c_void_p,
+                                                c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "octic_dense_gemm_plan_dropped": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    "octic_dense_gemm_order_dropped": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p]),
     "octic_dense_colsum": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p]),
     "octic_dense_wgrad_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
     "octic_dense_wgrad_tile": (c_int, [c_int, c_int, c_int]),

@@ -103,12 +103,122 @@ struct DgArgs {
   int tail_pad;       // workgroups in front of the full tiles: the split parts of the remaining tiles, padded to 8
   float* slabs;       // [(tiles - full_tiles) * split] x 256 x 256 f32 partials
   int* tickets;       // [(tiles - full_tiles)] arrival counters (zeroed by the host per launch)
+  // stochastic-depth mask (SKIP kernels only; see dense_item_masked)
+  const float* sample_scale;   // [M / rows_per_sample] f32: 0 = every reader of that sample's output rows accepts +0 for them
+  int rows_per_sample;
 };
 
 enum DgMode { DG_PLAIN = 0, DG_GELU = 1, DG_RESID = 2, DG_DGELU = 3,
               DG_GELUF = 4,    // like GELU, but C = gelu'(pre-activation) in bf16 (the factor the backward multiplies by) instead of it
               DG_DFACT = 5,    // like DGELU with H = that stored factor: C = H * acc, no transcendental in the epilogue
               DG_GELUO = 6 };  // GELU only: C = gelu(pre-activation), nothing kept for a backward (inference passes)
+
+// ---------------------------------------------------------------------------------------------------------------
+// Dropped samples (stochastic depth).  `sample_scale` carries one factor per sample of `rows_per_sample` token rows; a factor of 0
+// is the caller's word that every reader of that sample's output rows accepts either the computed result or +0 for them (the
+// residual tail multiplies them by rs = 0, the attention kernels skip the sample, the cotangent they would be computed from is
+// zero).  A row panel is DEAD when every sample its real rows touch has factor 0: its tiles load nothing and store +0.  A live
+// tile is computed by exactly the code, K range and plan of the unmasked launch (same grid, same workspace, same split front) -
+// only WHICH workgroup takes which full tile changes: the dead full tiles go first (they are pure stores and run beside the
+// first round, the argument that put the split parts in front), then the live full tiles in the unmasked launch's own tile
+// order (groups of 8 panels, column-major inside a group - a group simply has fewer panels), dealt in contiguous chunks to the
+// XCDs, so the per-XCD live counts differ by at most one tile.  The split-K front keeps its place and order; every part of a
+// dead split tile leaves without taking the ticket (it stays armed at 0) and part 0 stores the zeros.
+constexpr int kDgMaskCap = 1024;                 // row panels the bitmap covers; above it the host launches the unmasked kernel
+constexpr int kDgMaskWords = kDgMaskCap / 64;
+
+__host__ __device__ inline bool dg_panel_live(const float* scale, int rps, int M, int m_stride, int m_base, int tm) {
+  const int m0 = tm * m_stride + m_base;
+  if (m0 >= M) return false;
+  const int m1 = (m0 + DG_BM < M ? m0 + DG_BM : M) - 1;
+  const int b1 = m1 / rps;
+  for (int b = m0 / rps; b <= b1; ++b)
+    if (scale[b] != 0.0f) return true;
+  return false;
+}
+// the live (or dead) panels of panel group g as 8 bits; groups of 8 panels are the bytes of the bitmap
+__host__ __device__ inline int dg_group_bits(const unsigned long long* bm, int g, int gsz, bool live) {
+  int b = (int)((bm[g >> 3] >> ((g & 7) * 8)) & 0xffull);
+  if (!live) b = ~b;
+  return b & ((1 << gsz) - 1);
+}
+// how many of the first `cut` tiles of a group (column-major over its gsz panels) lie in the panels of `bits`
+__host__ __device__ inline int dg_group_count(int bits, int gsz, int tiles_n, int cut) {
+  if (cut == gsz * tiles_n) return tiles_n * __builtin_popcount(bits);
+  const int cols = cut / gsz, rest = cut - cols * gsz;
+  return cols * __builtin_popcount(bits) + __builtin_popcount(bits & ((1 << rest) - 1));
+}
+// live full tiles of the launch
+__host__ __device__ inline int dg_live_full(const unsigned long long* bm, int tiles_m, int tiles_n, int full) {
+  const int per_group = 8 * tiles_n;
+  int L = 0;
+  for (int g = 0; g * per_group < full; ++g) {
+    const int gsz = tiles_m - 8 * g < 8 ? tiles_m - 8 * g : 8;
+    const int left = full - g * per_group, cut = left < gsz * tiles_n ? left : gsz * tiles_n;
+    L += dg_group_count(dg_group_bits(bm, g, gsz, true), gsz, tiles_n, cut);
+  }
+  return L;
+}
+// the full tile of rank k among the live (or dead) full tiles, in the unmasked launch's tile order
+__host__ __device__ inline int dg_select_full(const unsigned long long* bm, int tiles_m, int tiles_n, int full, int k, bool live) {
+  const int per_group = 8 * tiles_n;
+  for (int g = 0; g * per_group < full; ++g) {
+    const int gsz = tiles_m - 8 * g < 8 ? tiles_m - 8 * g : 8;
+    const int left = full - g * per_group, cut = left < gsz * tiles_n ? left : gsz * tiles_n;
+    int bits = dg_group_bits(bm, g, gsz, live);
+    const int cnt = dg_group_count(bits, gsz, tiles_n, cut);
+    if (k < cnt) {
+      const int lg = __builtin_popcount(bits);
+      const int col = k / lg;
+      int idx = k - col * lg, pos = 0;
+      for (; pos < 8; ++pos) {
+        if (bits & 1) {
+          if (idx == 0) break;
+          --idx;
+        }
+        bits >>= 1;
+      }
+      return g * per_group + col * gsz + pos;
+    }
+    k -= cnt;
+  }
+  return 0;   // (not reached: k is below the count of its kind)
+}
+// row panel of a tile of the launch's tile order (the mapping at the top of dense_nt_kernel)
+__host__ __device__ inline void dg_tile_panel(int tiles_m, int tiles_n, int tile, int& tm, int& tn) {
+  const int per_group = 8 * tiles_n, gidx = tile / per_group, first_m = gidx * 8;
+  const int gsz = (tiles_m - first_m) < 8 ? (tiles_m - first_m) : 8;
+  const int in_g = tile - gidx * per_group;
+  tm = first_m + in_g % gsz;
+  tn = in_g / gsz;
+}
+// blockIdx + bitmap -> work item: tile (< 0: a padding workgroup), the K part of a split tile (rem_idx >= 0), dead or live.
+// For every mask a permutation of the unmasked launch's items.  The live chunk of workgroup j is (j - D) & 7 with D the
+// number of dead full tiles: a fixed rotation of the workgroup's real XCD, so a chunk still lives in one XCD's L2.
+__host__ __device__ inline void dense_item_masked(int tiles_m, int tiles_n, int full, int split, int tail_pad, int bid,
+                                                  const unsigned long long* bm, int& tile, int& rem_idx, int& part, bool& dead) {
+  tile = -1; rem_idx = -1; part = 0; dead = false;
+  if (bid < tail_pad) {
+    if (bid >= (tiles_m * tiles_n - full) * split) return;       // padding
+    rem_idx = bid / split;
+    part = bid - rem_idx * split;
+    tile = full + rem_idx;
+    int tm, tn;
+    dg_tile_panel(tiles_m, tiles_n, tile, tm, tn);
+    dead = ((bm[tm >> 6] >> (tm & 63)) & 1ull) == 0;
+    return;
+  }
+  const int j = bid - tail_pad;
+  const int L = dg_live_full(bm, tiles_m, tiles_n, full), D = full - L;
+  if (j < D) {
+    tile = dg_select_full(bm, tiles_m, tiles_n, full, j, false);
+    dead = true;
+    return;
+  }
+  const int i = j - D, x = i & 7, q8 = L >> 3, r8 = L & 7;
+  const int rank = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (i >> 3);
+  tile = dg_select_full(bm, tiles_m, tiles_n, full, rank, true);
+}
 
 __device__ inline void dg_wait_vmcnt(int n) {      // n even, wave-uniform; anything unexpected drains (always safe)
   switch (n) {
@@ -205,12 +315,13 @@ __device__ inline void dg_wait_imm() {
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int MODE, int NT>
+template <int MODE, int NT, bool SKIP = false>
 __global__ __launch_bounds__(512, 1) void dense_nt_kernel(DgArgs a) {
   extern __shared__ __attribute__((aligned(16))) char lds[];   // two K-tiles of four units; re-used as 8 staged epilogue tiles
   using GE = DgGeom<NT>;
   constexpr int NA = GE::NA, DG_BN = GE::BN;
   static_assert(NT == 4 || MODE == DG_PLAIN, "the fused tails exist for the 256-wide tile only");
+  static_assert(!SKIP || MODE != DG_RESID, "the fused residual tail never takes a mask");
 
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -236,6 +347,28 @@ __global__ __launch_bounds__(512, 1) void dense_nt_kernel(DgArgs a) {
   const int bid = blockIdx.x;
   int tile, kt_begin, kt_end, part = 0, rem_idx = -1;
   const int nkt_all = a.K / DG_BK;
+  bool dead_item = false;
+  if constexpr (SKIP) {
+    // live bitmap of the row panels, behind the ring: lane = panel, one ballot per 64 panels, before the first DMA (the
+    // factors are a cache line or two that every workgroup of the launch reads)
+    unsigned long long* const live_bm = (unsigned long long*)(lds + GE::LDS);
+    const int words = (a.tiles_m + 63) >> 6;
+    for (int w = wid; w < words; w += 8) {
+      const int p = w * 64 + lane;
+      const bool live = p < a.tiles_m && dg_panel_live(a.sample_scale, a.rows_per_sample, a.M, a.m_stride, a.m_base, p);
+      const unsigned long long m = __ballot(live);
+      if (lane == 0) live_bm[w] = m;
+    }
+    __syncthreads();
+    dense_item_masked(a.tiles_m, a.tiles_n, a.full_tiles, a.split, a.tail_pad, bid, live_bm, tile, rem_idx, part, dead_item);
+    tile = __builtin_amdgcn_readfirstlane(tile);
+    rem_idx = __builtin_amdgcn_readfirstlane(rem_idx);
+    part = __builtin_amdgcn_readfirstlane(part);
+    dead_item = __builtin_amdgcn_readfirstlane((int)dead_item) != 0;
+    if (tile < 0) return;                                                      // padding
+    kt_begin = rem_idx >= 0 ? (int)(((int64_t)nkt_all * part) / a.split) : 0;
+    kt_end = rem_idx >= 0 ? (int)(((int64_t)nkt_all * (part + 1)) / a.split) : nkt_all;
+  } else
   if (bid >= a.tail_pad) {
     // XCD-aware bijective remap over the full tiles (tail_pad is a multiple of 8: j & 7 is still the XCD of this workgroup)
     const int j = bid - a.tail_pad;
@@ -269,6 +402,30 @@ __global__ __launch_bounds__(512, 1) void dense_nt_kernel(DgArgs a) {
     tn = in_g / gsz;
   }
   const int m0 = tm * a.m_stride + a.m_base, n0 = tn * DG_BN;
+  if constexpr (SKIP) {
+    // ---- dead tile (workgroup-uniform, before any ring barrier): no DMA, no K loop, no ticket; +0 to every output the tile
+    // owns - row-wise, 16 bytes per lane, as the staged epilogue walks it - and to its two column-sum slab rows
+    if (dead_item) {
+      if (part != 0) return;
+      constexpr int CPR = DG_BN / 8;
+      const u32x4 z = {0, 0, 0, 0};
+#pragma unroll 4
+      for (int p = threadIdx.x; p < DG_BM * CPR; p += 512) {
+        const int r = p / CPR, c = p - r * CPR;
+        const int m = m0 + r, n = n0 + c * 8;
+        if (m < a.M && n < a.N) {
+          *(u32x4*)(a.C + (int64_t)m * a.ldc + n) = z;
+          if (MODE == DG_GELU || MODE == DG_GELUF) *(u32x4*)(a.C2 + (int64_t)m * a.ldc + n) = z;
+        }
+      }
+      if ((MODE == DG_DGELU || MODE == DG_DFACT) && a.colsum != nullptr) {
+        const int t = threadIdx.x;
+        const int row = t / (DG_BN / 4), n = n0 + (t - row * (DG_BN / 4)) * 4;
+        if (row < 2 && n < a.N) *(f32x4*)(a.colsum + (int64_t)(tm * 2 + row) * a.N + n) = f32x4{0, 0, 0, 0};
+      }
+      return;
+    }
+  }
   const int nkt = kt_end - kt_begin;          // >= 2
   const int nunits = 4 * nkt;
 
@@ -1095,11 +1252,14 @@ int octic_dense_gemm_colsum_rows(int M, int N, int K) {
 // 3 DGELU (C = gelu'(H) * (A B^T); colsum != NULL: octic_dense_gemm_colsum_rows() slabs [N] of column sums of C),
 // 4 GELUF (C = gelu'(pre-activation), C2 = gelu(pre-activation)), 5 DFACT (C = H * (A B^T), H = the factor of mode 4),
 // 6 GELUO (C = gelu(pre-activation) only: passes without a backward).
-int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
-                               void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
-                               const float* X, float* OUT, const void* H, float* colsum, void* workspace, int tokens,
-                               void* stream) {
+// sample_scale / rows_per_sample: the stochastic-depth mask (see dense_item_masked); NULL = the unmasked launch.
+int octic_dense_gemm_nt_tokens_skip(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
+                                    void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
+                                    const float* X, float* OUT, const void* H, float* colsum, const float* sample_scale,
+                                    int rows_per_sample, void* workspace, int tokens, void* stream) {
   if (!A || !B || !C) return OCTIC_ENULL;
+  if (sample_scale && (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0)) return OCTIC_ESHAPE;
+  if (sample_scale && (((uintptr_t)sample_scale) & 3)) return OCTIC_EALIGN;
   // (ldc % 8: every epilogue moves 8 bf16 = 16 bytes of a row of C / C2 / H per lane, from column offsets that are multiples of 8)
   if (M <= 0 || N <= 0 || K <= 0 || (K % DG_BK) || K < 2 * DG_BK || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OCTIC_ESHAPE;
   // buffer descriptors and per-lane offsets are 32-bit: operands of 2 GiB or more are refused (callers fall back to
@@ -1118,6 +1278,10 @@ int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K
   a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.full_tiles = p.full; a.split = p.split; a.tail_pad = p.tail_pad;
   a.m_stride = tp.image ? tokens : DG_BM;
   a.m_base = tp.image ? 1 : 0;
+  // the masked kernels take every mode but the fused residual tail, up to the bitmap's panels; anything else computes every row
+  const bool skip = sample_scale != nullptr && mode != DG_RESID && p.tiles_m <= kDgMaskCap;
+  a.sample_scale = skip ? sample_scale : nullptr;
+  a.rows_per_sample = skip ? rows_per_sample : 0;
   hipStream_t s = (hipStream_t)stream;
   if (p.split > 1) {
     if (!workspace) return OCTIC_ENULL;
@@ -1125,7 +1289,7 @@ int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K
     a.tickets = (int*)workspace;
     a.slabs = (float*)((char*)workspace + DG_TICKET_BYTES);
   }
-  const int smem = DgGeom<4>::LDS, smem5 = DgGeom<5>::LDS;
+  const int smem = DgGeom<4>::LDS, smem5 = DgGeom<5>::LDS, bmb = kDgMaskWords * 8;
   static DeviceOnce once;
   if (once.first()) {
     (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_PLAIN, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
@@ -1136,8 +1300,30 @@ int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K
     (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUF, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_DFACT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUO, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_PLAIN, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_PLAIN, 5, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem5 + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELU, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_DGELU, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUF, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_DFACT, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUO, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
     (void)hipGetLastError();
   }
+  if (skip) {
+    // same plan, same grid; the live bitmap sits behind the ring
+    switch (mode) {
+      case DG_PLAIN:
+        if (p.nt == 5) dense_nt_kernel<DG_PLAIN, 5, true><<<p.grid, 512, smem5 + bmb, s>>>(a);
+        else dense_nt_kernel<DG_PLAIN, 4, true><<<p.grid, 512, smem + bmb, s>>>(a);
+        break;
+      case DG_GELU: dense_nt_kernel<DG_GELU, 4, true><<<p.grid, 512, smem + bmb, s>>>(a); break;
+      case DG_DGELU: dense_nt_kernel<DG_DGELU, 4, true><<<p.grid, 512, smem + bmb, s>>>(a); break;
+      case DG_GELUF: dense_nt_kernel<DG_GELUF, 4, true><<<p.grid, 512, smem + bmb, s>>>(a); break;
+      case DG_DFACT: dense_nt_kernel<DG_DFACT, 4, true><<<p.grid, 512, smem + bmb, s>>>(a); break;
+      case DG_GELUO: dense_nt_kernel<DG_GELUO, 4, true><<<p.grid, 512, smem + bmb, s>>>(a); break;
+      default: return OCTIC_ESHAPE;
+    }
+  } else
   switch (mode) {
     case DG_PLAIN:
       if (p.nt == 5) dense_nt_kernel<DG_PLAIN, 5><<<p.grid, 512, smem5, s>>>(a);
@@ -1176,6 +1362,49 @@ int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K
     }
   }
   return launch_status();
+}
+
+int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
+                               void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
+                               const float* X, float* OUT, const void* H, float* colsum, void* workspace, int tokens,
+                               void* stream) {
+  return octic_dense_gemm_nt_tokens_skip(A, B, M, N, K, lda, ldb, mode, C, C2, ldc, bias, gamma, rs, rps, X, OUT, H, colsum,
+                                         nullptr, 0, workspace, tokens, stream);
+}
+
+// The plan in force for a masked launch: the unmasked launch's (a mask changes which workgroup takes which tile, nothing else).
+int octic_dense_gemm_plan_dropped(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out) {
+  if (!out) return OCTIC_ENULL;
+  if (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0) return OCTIC_ESHAPE;
+  return octic_dense_gemm_plan(M, N, K, mode, tokens, out);
+}
+
+// What a masked launch gives each workgroup, in blockIdx order, by the kernel's own mapping (dense_item_masked): sample_scale is
+// a HOST array here.  out_tm / out_tn = the tile (-1 = a padding workgroup), out_part = K part (0 for full tiles), out_split = 1
+// for an item of the split-K front, out_dead = 1 for a dead tile; each may be NULL.  `cap` = entries the arrays hold.  Returns
+// the number of workgroups; OCTIC_ESHAPE for a launch the masked kernel does not take (the unmasked kernel runs it) or cap < that.
+int octic_dense_gemm_order_dropped(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
+                                   int cap, int* out_tm, int* out_tn, int* out_part, int* out_split, int* out_dead) {
+  if (!sample_scale) return OCTIC_ENULL;
+  if (M <= 0 || N <= 0 || K < 2 * DG_BK || rows_per_sample <= 0 || (M % rows_per_sample) != 0 || mode == DG_RESID) return OCTIC_ESHAPE;
+  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
+  const DgPlan p = tp.p;
+  if (p.tiles_m > kDgMaskCap || cap < p.grid) return OCTIC_ESHAPE;
+  unsigned long long bm[kDgMaskWords] = {};
+  for (int tm = 0; tm < p.tiles_m; ++tm)
+    if (dg_panel_live(sample_scale, rows_per_sample, M, tp.image ? tokens : DG_BM, tp.image ? 1 : 0, tm)) bm[tm >> 6] |= 1ull << (tm & 63);
+  for (int bid = 0; bid < p.grid; ++bid) {
+    int tile, rem_idx, part, tm = -1, tn = -1;
+    bool dead;
+    dense_item_masked(p.tiles_m, p.tiles_n, p.full, p.split, p.tail_pad, bid, bm, tile, rem_idx, part, dead);
+    if (tile >= 0) dg_tile_panel(p.tiles_m, p.tiles_n, tile, tm, tn);
+    if (out_tm) out_tm[bid] = tm;
+    if (out_tn) out_tn[bid] = tn;
+    if (out_part) out_part[bid] = part;
+    if (out_split) out_split[bid] = rem_idx >= 0 ? 1 : 0;
+    if (out_dead) out_dead[bid] = dead ? 1 : 0;
+  }
+  return p.grid;
 }
 
 int octic_dense_gemm_nt(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,

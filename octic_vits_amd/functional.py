@@ -496,6 +496,29 @@ def wgrad_skip_scale(rs, rps, M, rows_to=None):
     return rs.detach()
 
 
+# The eight dense_nt_kernel launches of a standard block (csrc/dense_gemm.hip) compute rows nobody needs for a dropped sample:
+# qkv's output is read by the attention kernels alone, proj's and fc2's meet rs = 0 in the residual tail, fc1's two outputs meet
+# zero dY rows in fc2's gradients, and each of the four input gradients starts from a cotangent that is exactly zero for the
+# sample.  With DENSE_NT_SKIP_DROPPED the branch's factor travels to the kernel as its sample_scale: row panels whose samples
+# are all dropped store +0 instead of being computed, the kept rows keep their bits (include/octic_hip.h:
+# octic_dense_gemm_nt_tokens_skip).  Read once at import from OCTIC_DENSE_SKIP (0 = off).
+def _dense_skip_from_env():
+    return os.environ.get("OCTIC_DENSE_SKIP", "1").strip() != "0"
+
+
+DENSE_NT_SKIP_DROPPED = _dense_skip_from_env()
+
+
+def dense_skip_scale(rs, rps, M, rows_to=None):
+    """rs as the sample_scale of a dense_nt_kernel launch over M token rows - under exactly wgrad_skip_scale's conditions: the
+    switch is on and rs is one float32 entry per sample of rps rows on the GPU with rps * B == M; None for compact rows
+    (rows_to), the per-row factors of a ragged row tensor (rps 1), a traced value, eval and drop_path 0 (rs None)."""
+    if (not DENSE_NT_SKIP_DROPPED or rs is None or rows_to is not None or torch.compiler.is_compiling() or not rs.is_cuda
+            or rs.dtype != torch.float32 or rs.dim() != 1 or not rs.is_contiguous() or rps < 2 or rs.numel() * rps != M):
+        return None
+    return rs.detach()
+
+
 # In the octic MLP the same factor makes the D8-GELU's work on a dropped sample void in both directions: gelu(h) of such a
 # sample is read only by fc2 (whose fused tail multiplies the row by rs = 0) and by fc2's weight gradient (against zero dY rows),
 # dh only by fc1's input and weight gradients, whose results for that sample are zero as well.  With LINEAR_SKIP_DROPPED the
@@ -1048,18 +1071,22 @@ def _tok(shape):
     return int(shape[-2]) if len(shape) >= 3 else 0
 
 
-def _gemm_fwd(tag, x2, wb, b, cache, name, tokens):
+def _gemm_fwd(tag, x2, wb, b, cache, name, tokens, ss=None, rps=0):
     """x2 wb^T + b (bf16): csrc/dense_gemm.hip with a plain epilogue (f32 bias b) where `tag` is routed to it (DENSE_HIP),
-    else the BLAS library with the cache's compute-dtype bias."""
+    else the BLAS library with the cache's compute-dtype bias.  ss / rps: the branch's stochastic-depth mask (dense_skip_scale),
+    for the hand-written kernel only."""
     if tag in DENSE_HIP:
-        return ops.dense_gemm_nt(x2, wb, 0, bias=_f32(b), name=f"dense_nt_kernel<{name}>", tokens=tokens)
+        return ops.dense_gemm_nt(x2, wb, 0, bias=_f32(b), name=f"dense_nt_kernel<{name}>", tokens=tokens, sample_scale=ss,
+                                 rows_per_sample=rps if ss is not None else 0)
     return _linear_lib(x2, wb, None if b is None else cache.b)
 
 
-def _gemm_dgrad(g2, wt, wb, shape, dtype):
+def _gemm_dgrad(g2, wt, wb, shape, dtype, ss=None, rps=0):
     """Input gradient g2 W as `shape` in `dtype`: csrc/dense_gemm.hip on the transposed copy wt where the cache made one (the
-    input gradient is routed to it), else the BLAS library on wb."""
-    gx = (ops.dense_gemm_nt(g2, wt, 0, name="dense_nt_kernel<dgrad>", tokens=_tok(shape)) if wt is not None
+    input gradient is routed to it), else the BLAS library on wb.  ss / rps: the mask under which g2's rows of a dropped sample
+    are exactly zero (dense_skip_scale), for the hand-written kernel only."""
+    gx = (ops.dense_gemm_nt(g2, wt, 0, name="dense_nt_kernel<dgrad>", tokens=_tok(shape), sample_scale=ss,
+                            rows_per_sample=rps if ss is not None else 0) if wt is not None
           else _mm_lib(g2, wb))
     return gx.view(shape).to(dtype)
 
@@ -1075,7 +1102,7 @@ def _resid_tail_fwd(ctx, x, tag, a2, wb, b, cache, tokens, g32, rs32, rps, nw, n
     if neps is None and rows_to is None and tag in DENSE_HIP and DENSE_RESID_FUSED:
         br, out = ops.dense_gemm_nt(a2, wb, 2, bias=_f32(b), gamma=g32, rs=rs32, rps=rps, x=x2, name="dense_nt_kernel<resid>")
         return out.view(x.shape), (br, g32, rs32)
-    br = _gemm_fwd(tag, a2, wb, b, cache, tag, tokens)
+    br = _gemm_fwd(tag, a2, wb, b, cache, tag, tokens, dense_skip_scale(rs32, rps, a2.shape[0], rows_to), rps)   # br meets rs = 0
     if neps is not None:
         nw32, nb32 = _f32(nw), _f32(nb)
         out, yn, stats = ops.dense_resid_layernorm_fwd(x2, br, g32, rs32, rps, nw32, nb32, neps, torch.bfloat16)
@@ -1136,19 +1163,20 @@ class DenseLinearNTFn(torch.autograd.Function):
         xb = _c(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16))
         wb, wt = cache.get_nt(w, b, ("d" + tag) in DENSE_HIP and ctx.needs_input_grad[0])
         x2 = xb.reshape(-1, wb.shape[1])
-        y = _gemm_fwd(tag, x2, wb, b, cache, "plain", _tok(x.shape))
+        ds = dense_skip_scale(rs, rps, x2.shape[0])
+        y = _gemm_fwd(tag, x2, wb, b, cache, "plain", _tok(x.shape), ds, rps)
         ss = wgrad_skip_scale(rs, rps, x2.shape[0])
         ctx.rps = rps
-        ctx.save_for_backward(x2, wb, wt, ss)      # wt is None unless the input gradient is routed to the HIP kernel
+        ctx.save_for_backward(x2, wb, wt, ss, ds)  # wt is None unless the input gradient is routed to the HIP kernel
         ctx.meta = (b is not None, x.dtype, x.shape, tag)
         return y.view(*x.shape[:-1], wb.shape[0])
 
     @staticmethod
     def backward(ctx, gy):
-        x2, wb, wt, ss = ctx.saved_tensors
+        x2, wb, wt, ss, ds = ctx.saved_tensors
         has_b, x_dtype, x_shape, tag = ctx.meta
         g2 = _c(gy).reshape(-1, wb.shape[0])
-        gx = _gemm_dgrad(g2, wt, wb, x_shape, x_dtype) if ctx.needs_input_grad[0] else None
+        gx = _gemm_dgrad(g2, wt, wb, x_shape, x_dtype, ds, ctx.rps) if ctx.needs_input_grad[0] else None
         gb = None
         if has_b:
             gb = (ops.dense_colsum(g2) if g2.is_cuda and g2.dtype == torch.bfloat16 and g2.shape[1] % 8 == 0
@@ -1198,9 +1226,10 @@ class DenseProjResidFn(torch.autograd.Function):
         a_dtype, a_shape = ctx.meta
         gx, gy, dgamma, colsum, dnw, dnb = _resid_tail_bwd(ctx, tail, gout, gyn,
                                                            ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
-        ga = _gemm_dgrad(gy, wt, wb, a_shape, a_dtype) if ctx.needs_input_grad[1] else None
         rps = ctx.tail[1]
-        ss = wgrad_skip_scale(tail[2], rps, gy.shape[0], ctx.rows_to)     # gy = rs * gamma * gout: zero rows where rs is 0
+        ds = dense_skip_scale(tail[2], rps, gy.shape[0], ctx.rows_to)     # gy = rs * gamma * gout: zero rows where rs is 0
+        ga = _gemm_dgrad(gy, wt, wb, a_shape, a_dtype, ds, rps) if ctx.needs_input_grad[1] else None
+        ss = wgrad_skip_scale(tail[2], rps, gy.shape[0], ctx.rows_to)
         if _pair_ready(ctx.pair, gy, a2) and ops.dense_wgrad_ok(gy.shape[0], gy.shape[1], a2.shape[1]):
             dw = ctx.pair.park(gy, a2, ctx.wparam, ss, rps)   # written by the qkv weight gradient's launch (or at the end of the pass)
         else:
@@ -1231,13 +1260,17 @@ class DenseMlpFn(torch.autograd.Function):
         # octic_dense_gemm_nt) - the erf of the backward epilogue is computed once, in the forward, beside gelu's
         factor = GELU_FACTOR and "fc1" in DENSE_HIP and w2t is not None
         ctx.factor = factor
+        # fc1's outputs of a dropped sample are read by fc2 (whose output meets rs = 0) and by gradients whose dY rows are zero
+        ds = dense_skip_scale(rs32, rps, y2.shape[0], rows_to)
+        drps = rps if ds is not None else 0
         if "fc1" in DENSE_HIP and not any(ctx.needs_input_grad):
             # no backward will come (inference, the DINOv2 teacher): gelu(h) only, nothing kept (mode 6)
-            a = ops.dense_gemm_nt(y2, w1b, 6, bias=_f32(b1), name="dense_nt_kernel<gelu-only>", tokens=_tok(y.shape))
+            a = ops.dense_gemm_nt(y2, w1b, 6, bias=_f32(b1), name="dense_nt_kernel<gelu-only>", tokens=_tok(y.shape),
+                                  sample_scale=ds, rows_per_sample=drps)
             h = a
         elif "fc1" in DENSE_HIP:
             h, a = ops.dense_gemm_nt(y2, w1b, 4 if factor else 1, bias=_f32(b1), name="dense_nt_kernel<gelu>",
-                                     tokens=_tok(y.shape))
+                                     tokens=_tok(y.shape), sample_scale=ds, rows_per_sample=drps)
         else:
             h = _linear_lib(y2, w1b, None if b1 is None else c1.b)
             a = torch.nn.functional.gelu(h)
@@ -1253,20 +1286,23 @@ class DenseMlpFn(torch.autograd.Function):
         has_b1, y_dtype, y_shape = ctx.meta
         gx, gbr, dgamma, db2, dnw, dnb = _resid_tail_bwd(ctx, tail, gout, gyn,
                                                          ctx.needs_input_grad[11] or ctx.needs_input_grad[12])
+        rps = ctx.tail[1]
+        ds = dense_skip_scale(tail[2], rps, gbr.shape[0], ctx.rows_to)    # gbr = rs * gamma * gout: zero rows where rs is 0
+        drps = rps if ds is not None else 0
         if w2t is not None:
             md = 5 if ctx.factor else 3
             if has_b1:                                                                  # gelu'(h) * (gbr W2), + db1
                 dh, db1 = ops.dense_gemm_nt(gbr, w2t, md, h=h, name="dense_nt_kernel<dgelu>", want_colsum=True,
-                                            tokens=_tok(y_shape))
+                                            tokens=_tok(y_shape), sample_scale=ds, rows_per_sample=drps)
             else:
-                dh, db1 = ops.dense_gemm_nt(gbr, w2t, md, h=h, name="dense_nt_kernel<dgelu>", tokens=_tok(y_shape)), None
+                dh, db1 = ops.dense_gemm_nt(gbr, w2t, md, h=h, name="dense_nt_kernel<dgelu>", tokens=_tok(y_shape),
+                                            sample_scale=ds, rows_per_sample=drps), None
         else:
             dh, db1 = ops.dense_gelu_bwd(h, _mm_lib(gbr, w2b), want_colsum=has_b1)
-        rps = ctx.tail[1]
         ss = wgrad_skip_scale(tail[2], rps, gbr.shape[0], ctx.rows_to)    # gbr = rs * gamma * gout, dh = gelu' * (gbr W2)
         gw2 = _wgrad_lib(gbr, a, ctx.wparams[1], ss, rps)
         gw1 = _wgrad_lib(dh, y2, ctx.wparams[0], ss, rps)
-        gy = _gemm_dgrad(dh, w1t, w1b, y_shape, y_dtype) if ctx.needs_input_grad[0] else None
+        gy = _gemm_dgrad(dh, w1t, w1b, y_shape, y_dtype, ds, rps) if ctx.needs_input_grad[0] else None   # dh = gelu' * 0
         return gy, gx, gw1, db1, gw2, db2, dgamma, None, None, None, None, dnw, dnb, None, None, None
 
 

@@ -1219,14 +1219,24 @@ def dense_plan(M, N, K, mode, tokens):
     return out[0], out[1], bool(out[2]), out[3]
 
 
+def dense_plan_dropped(M, N, K, mode, tokens, rows_per_sample):
+    """dense_plan for a launch under a stochastic-depth mask (octic_dense_gemm_plan_dropped)."""
+    out = _lib.plan("octic_dense_gemm_plan_dropped", M, N, K, mode, int(tokens), int(rows_per_sample))
+    if out is None:
+        check(-1)
+    return out[0], out[1], bool(out[2]), out[3]
+
+
 def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h=None, name=None, want_colsum=False,
-                  tokens=0):
+                  tokens=0, sample_scale=None, rows_per_sample=0):
     """C[M,N] = a[M,K] @ b[N,K]^T on the hand-written MFMA kernel (csrc/dense_gemm.hip) with a fused tail:
     mode 0 -> c ; 1 -> (c, gelu(c)) ; 2 -> (c, x + rs*gamma*c) ; 3 -> gelu'(h) * c (want_colsum: also the f32 column
     sums of that result) ; 4 -> (gelu'(c), gelu(c)) ; 5 -> h * c with h = the factor of mode 4 (want_colsum as 3) ;
     6 -> gelu(c) only.
     a, b bf16 2-D, K contiguous.  tokens: the rows are whole images of that many tokens ([B, tokens, K] flattened) - 257 lets the
-    launch use per-image row panels + the class-token kernel (octic_dense_gemm_nt_tokens); 0 = unknown."""
+    launch use per-image row panels + the class-token kernel (octic_dense_gemm_nt_tokens); 0 = unknown.
+    sample_scale / rows_per_sample: the stochastic-depth mask of octic_dense_gemm_nt_tokens_skip - f32 [M / rows_per_sample] on
+    the device, 0 = every reader of that sample's output rows accepts the computed result or +0 (never with mode 2)."""
     _require_cuda(a)
     M, K = a.shape
     N = b.shape[0]
@@ -1237,17 +1247,28 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
     out = torch.empty((M, N), dtype=torch.float32, device=a.device) if mode == 2 else None
     ws = _dense_ws(M, N, K, a.device)
     tokens = int(tokens) if (tokens and M % int(tokens) == 0) else 0
-    cs_rows = dense_plan(M, N, K, mode, tokens)[1] if (mode in (3, 5) and want_colsum) else 0
+    if sample_scale is not None and mode == 2:
+        raise ValueError("dense_gemm_nt: the fused residual tail (mode 2) takes no sample_scale")
+    # the plan in force: colsum rows, the timer name and (through the library's own sizing) the workspace belong to it
+    plan = ((lambda: dense_plan(M, N, K, mode, tokens)) if sample_scale is None else
+            (lambda: dense_plan_dropped(M, N, K, mode, tokens, rows_per_sample)))
+    cs_rows = plan()[1] if (mode in (3, 5) and want_colsum) else 0
     cs = torch.empty((cs_rows, N), dtype=torch.float32, device=a.device) if cs_rows else None
     t = KERNEL_TIMER.start()
-    check(lib().octic_dense_gemm_nt_tokens(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias),
-                                           _p(gamma), _p(rs), int(rps), _p(x), _p(out), _p(h), _p(cs), _p(ws), tokens,
-                                           _stream(a)))
+    if sample_scale is None:
+        check(lib().octic_dense_gemm_nt_tokens(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias),
+                                               _p(gamma), _p(rs), int(rps), _p(x), _p(out), _p(h), _p(cs), _p(ws), tokens,
+                                               _stream(a)))
+    else:
+        check(lib().octic_dense_gemm_nt_tokens_skip(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N,
+                                                    _p(bias), _p(gamma), _p(rs), int(rps), _p(x), _p(out), _p(h), _p(cs),
+                                                    _p(sample_scale), int(rows_per_sample), _p(ws), tokens,
+                                                    _stream(a)))
     if t is not None:
         nb = 2 * (M * K + N * K + M * N * (2 if mode in (1, 3, 4, 5) else 1)) + (8 * M * N if mode == 2 else 0)
         # "@320": the launch ran the 256 x 320 tile (kernel symbol dense_nt_kernel<0, 5>), else <mode, 4>
         # (with per-image panels the timed interval also holds the class-token launch behind the panels')
-        wide = "@320" if dense_plan(M, N, K, mode, tokens)[0] == 320 else ""
+        wide = "@320" if plan()[0] == 320 else ""
         KERNEL_TIMER.stop(t, (name or f"dense_nt_kernel<{mode}>") + wide, nb, 2.0 * M * N * K)
     if mode in (1, 4):
         return c, c2

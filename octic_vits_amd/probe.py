@@ -17,6 +17,7 @@ Naming follows the reference's own format expression INCLUDING ITS COLLISIONS: a
 earlier one's position), so the reference trains 48 heads while its optimizer holds 52 parameter groups, four of them
 orphaned.  ``classifier_grid`` does the same; the orphaned groups are not materialised (they own no classifier anybody
 can evaluate)."""
+import gc
 from collections import OrderedDict
 
 import numpy as np
@@ -369,6 +370,7 @@ class CapturedProbeStep:
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         probe.optimizer.push_lr()
+        gc.collect()                              # (as serve.GraphedForward: no collection of dead graphs inside the capture)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss = probe.step(self.images, self.labels)

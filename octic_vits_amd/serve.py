@@ -6,6 +6,8 @@ The reference measures inference throughput with eval / no_grad / autocast forwa
 become one graph launch, the host is out of the loop.  The compute-dtype weight copies the kernels read (LinearD8 preparations,
 the standard half's bf16 / transposed copies) are made by the warm-up forwards and are then FROZEN inside the graph - parameters
 must not change behind it: ``__call__`` checks the parameters' version counters and addresses and refuses stale graphs."""
+import gc
+
 import torch
 
 
@@ -23,6 +25,10 @@ class GraphedForward:
                 self._run()
         torch.cuda.current_stream(example.device).wait_stream(side)
         torch.cuda.synchronize(example.device)
+        # dead Python cycles that still hold captured graphs or their memory pools (an earlier Trainer / GraphedForward) must not be
+        # collected WHILE the capture runs - destroying a graph is not legal on a capturing stream and aborts the process; torch's
+        # own collection in front of a capture is off by default since 2.9 (torch.compiler.config.force_cudagraph_gc)
+        gc.collect()
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph):
             self.static_out = self._run()

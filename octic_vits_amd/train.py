@@ -18,6 +18,7 @@ targets -> backward (gradients all-reduced over RCCL by DDP bucket hooks, overla
     on the host, the pixels are HIP kernels in front of the mix (``Trainer(augment=...)``).
 ``evaluate`` is the reference's evaluation loop (engine.py:98-128) on one GPU.
 """
+import gc
 import math
 import os
 
@@ -1402,6 +1403,7 @@ class Trainer:
         return GraphedStep(self, graph, sx, sy, loss.detach())
 
     def _capture_body(self, graph, mode, sx, sy):
+        gc.collect()                              # (as serve.GraphedForward: no collection of dead graphs inside the capture)
         with torch.cuda.graph(graph, **mode):
             if self.augment is not None:
                 sx = self._aug_batch(sx)

@@ -1,0 +1,68 @@
+"""Warm back-to-back launches of the eight dense_nt_kernel shapes of a standard block (ViT-H/14, batch 64, 257 tokens) under a
+stochastic-depth mask.
+
+    python tools/bench_dense_skip.py [--iters 30] [--json FILE]
+
+Four cases per shape: unmasked (sample_scale None), all kept (prices the bitmap prologue: same tiles, same order), a fixed
+Bernoulli(0.5) mask (seed 0), all dropped (prices the dead tile).  Each case is timed as `iters` launches between two events
+after a warm-up, microseconds per launch."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from octic_vits_amd import ops  # noqa: E402
+
+B, T = 64, 257
+SHAPES = [("qkv forward", 3840, 1280, 0), ("proj", 1280, 1280, 0), ("fc1 + factor", 5120, 1280, 4), ("fc2", 1280, 5120, 0),
+          ("fc2 input gradient", 5120, 1280, 5), ("fc1 input gradient", 1280, 5120, 0), ("proj input gradient", 1280, 1280, 0),
+          ("qkv input gradient", 1280, 3840, 0)]
+
+
+def timed(fn, iters):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(iters):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e3 / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    bern = (torch.rand(B, generator=g, device=dev) < 0.5).float() * 2.0
+    masks = {"unmasked": None, "all kept": torch.full((B,), 2.0, device=dev), "bernoulli": bern,
+             "all dropped": torch.zeros(B, device=dev)}
+    rows = []
+    print(f"kept samples of the Bernoulli mask: {int((bern != 0).sum())} of {B}")
+    print(f"{'launch':22s} " + " ".join(f"{k:>12s}" for k in masks))
+    for name, N, K, mode in SHAPES:
+        a = torch.randn(B * T, K, device=dev).to(torch.bfloat16)
+        w = (torch.randn(N, K, device=dev) * K ** -0.5).to(torch.bfloat16)
+        h = torch.rand(B * T, N, device=dev).to(torch.bfloat16) if mode == 5 else None
+        res = {}
+        for label, ss in masks.items():
+            fn = lambda: ops.dense_gemm_nt(a, w, mode, h=h, want_colsum=mode == 5, tokens=T, sample_scale=ss,
+                                           rows_per_sample=T if ss is not None else 0)
+            res[label] = timed(fn, args.iters)
+        rows.append(dict(launch=name, N=N, K=K, mode=mode, us=res))
+        print(f"{name:22s} " + " ".join(f"{res[k]:12.1f}" for k in masks))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(batch=B, tokens=T, kept=int((bern != 0).sum()), iters=args.iters, rows=rows), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
