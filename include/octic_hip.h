@@ -813,6 +813,35 @@ int octic_seg_patch_mode(const void* labels, int esize, int64_t R, int L, int32_
 int octic_seg_confusion(const void* labels, int esize, int64_t R, int L, const int32_t* pred, const uint8_t* ignore,
                         int64_t* counts, void* stream);
 
+/* ---- the k-NN classifier of the segmentation evaluation (KNNClassifier, eval_segmentation.py:172-278) ------------------
+ * For each of n query rows Q [n, D] (row stride ldq) the kmax nearest of M key rows K [M, D] (row stride ldk, so a
+ * sub-sampled training set is a stride) under the SQUARED L2 distance (|a|^2 + |b|^2) - 2 a.b, the cosine distance
+ * 1 - a.b / (|a| |b|), or both from one pass (metrics: 1 = L2, 2 = cosine, 3 = both).  The distance matrix never reaches
+ * memory.  qnorm [n] / knorm [M] are the squared row norms octic_seg_rownorms writes; skip (nullable, DEVICE uint8 [M]) marks
+ * key rows that must not be listed.
+ * TOTAL ORDER: (distance, key row index): the smaller distance first, on equal distance the lower index.  A NaN distance
+ * counts as +inf; a key at distance +inf is never listed, so a query with fewer than kmax listable keys ends on (+inf, -1).
+ * The distance of a pair is a function of the two rows alone (one fmaf chain over D in a fixed order): idx and dist are bitwise
+ * equal for every split count and every query order or batching.  Exact f32 (f32-input MFMA), no floating-point atomics, 64-bit
+ * row offsets.  Limits: D % 64 == 0, 1 <= kmax <= 32, kmax <= M < 2^31, 0 <= splits <= 64 (anything else: OCTIC_ESHAPE before
+ * any launch; the caller checks that at least kmax keys are not skipped - the skip array lives on the device).
+ * octic_seg_knn_plan: out[0] = key-axis splits of an automatic launch (1 once the query tiles fill the device), out[1] / out[2]
+ * = query rows / keys per tile, out[3] = workspace class (0: the workspace is not read, 1: it holds the splits' partial lists).
+ * octic_seg_knn_workspace_bytes: for `splits` as passed to octic_seg_knn (0 = the plan's); 256-byte aligned.
+ * idx_* int32 / dist_* f32 are [n, kmax] with row stride ldo >= kmax, sorted; columns kmax .. ldo-1 are not written.  The pair
+ * of a metric that is not asked for may be NULL.                                                                          */
+int octic_seg_knn_plan(int64_t n, int64_t M, int D, int kmax, int metrics, int* out);
+int64_t octic_seg_knn_workspace_bytes(int64_t n, int64_t M, int D, int kmax, int metrics, int splits);
+int octic_seg_rownorms(const float* X, int64_t ldx, int64_t N, int D, float* norms, void* stream);
+int octic_seg_knn(const float* Q, int64_t ldq, int64_t n, const float* K, int64_t ldk, int64_t M, int D, const float* qnorm,
+                  const float* knorm, const uint8_t* skip, int kmax, int metrics, int splits, int32_t* idx_l2, float* dist_l2,
+                  int32_t* idx_cos, float* dist_cos, int64_t ldo, void* workspace, void* stream);
+/* out [nk, n, L] (uint8): out[i, r, l] = the most frequent of labels[idx[r, 0 .. ks[i]-1], l], the smallest value on a tie
+ * (torch.mode), over the raw label values (an ignored value can win).  idx has row stride ldi; labels is [R, L] of esize-byte
+ * integers (values 0 .. 255) and an index outside [0, R) casts no vote.  ks: HOST array of nk <= 8 ascending values 1 .. 32.  */
+int octic_seg_knn_vote(const int32_t* idx, int64_t ldi, int64_t n, const void* labels, int esize, int64_t R, int L, const int* ks,
+                       int nk, uint8_t* out, void* stream);
+
 /* ---- Mixup / CutMix and the BCE loss of the DeiT-III recipe (timm/data/mixup.py; deit/engine.py:47-59) -----------------
  * The host draws the per-sample parameters and uploads them as a DEVICE table of B rows; the kernels take everything about
  * the draw from it (never from arguments), so one captured launch serves every replay.  A row whose partner is outside

@@ -190,6 +190,13 @@ _PROTOS = {
     "octic_seg_standardize": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p]),
     "octic_seg_patch_mode": (c_int, [c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p]),
     "octic_seg_confusion": (c_int, [c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "octic_seg_knn_plan": (c_int, [c_i64, c_i64, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    "octic_seg_knn_workspace_bytes": (c_i64, [c_i64, c_i64, c_int, c_int, c_int, c_int]),
+    "octic_seg_rownorms": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p]),
+    "octic_seg_knn": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
+    "octic_seg_knn_vote": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_int, c_i64, c_int, ctypes.POINTER(c_int), c_int, c_void_p,
+                                   c_void_p]),
     "octic_mix_images": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "octic_mix_targets": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p]),
     "octic_mix_bce": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int,

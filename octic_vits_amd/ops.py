@@ -1454,6 +1454,101 @@ def seg_confusion(labels, pred, ignore, counts):
     return counts
 
 
+# ------------------------------------------------------------------------------------------ segmentation k-NN (csrc/segknn.hip)
+KNN_L2, KNN_COSINE, KNN_BOTH = 1, 2, 3
+KNN_KMAX = 32
+
+
+def seg_knn_plan(n, M, D, kmax, metrics=KNN_BOTH):
+    """octic_seg_knn_plan: (key-axis splits, query rows per tile, keys per tile, workspace class)."""
+    answer = _lib.plan("octic_seg_knn_plan", int(n), int(M), int(D), int(kmax), int(metrics))
+    if answer is None:
+        check(-1)
+    return answer
+
+
+def seg_knn_workspace(n, M, D, kmax, metrics, splits, device):
+    """The workspace of seg_knn for this shape and split count (0 = the plan's): the partial lists of the splits."""
+    nbytes = lib().octic_seg_knn_workspace_bytes(n, M, D, kmax, metrics, splits)
+    check(min(nbytes, 0))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def seg_rownorms(X):
+    """f32 [N]: the squared norm of every row of the f32 rows X [N, D], summed in a fixed order."""
+    N, D, ldx = _seg_rows(X)
+    norms = torch.empty(N, dtype=torch.float32, device=X.device)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_seg_rownorms(_p(X), ldx, N, D, _p(norms), _stream(X)))
+    KERNEL_TIMER.stop(t, "seg_rownorms_kernel", 4 * N * (D + 1), 2.0 * N * D)
+    return norms
+
+
+def seg_knn(Q, K, qnorm, knorm, skip, kmax, metrics=KNN_BOTH, splits=0, out=None, workspace=None):
+    """The kmax nearest rows of K for every row of Q under the squared L2 distance (metrics & 1), the cosine distance
+    (metrics & 2) or both, ordered by (distance, key row index).  skip: None or uint8 [M], non-zero = the key is never listed.
+    Returns (idx_l2, dist_l2, idx_cos, dist_cos): int32 / f32 [n, kmax], None for a metric not asked for.  ``out`` may hold
+    those four as 2-d tensors with a common row stride >= kmax (columns past kmax are left alone)."""
+    n, D, ldq = _seg_rows(Q)
+    M, Dk, ldk = _seg_rows(K)
+    if Dk != D or K.device != Q.device:
+        raise ValueError("seg_knn: Q and K must have the same width and device")
+    for v, rows in ((qnorm, n), (knorm, M)):
+        if v.dtype != torch.float32 or v.numel() != rows or not v.is_contiguous() or v.device != Q.device:
+            raise ValueError("seg_knn: qnorm / knorm must be contiguous f32 [n] / [M] on the device of Q")
+    if skip is not None and (skip.dtype != torch.uint8 or skip.numel() != M or not skip.is_contiguous() or skip.device != Q.device):
+        raise ValueError("seg_knn: skip must be a contiguous uint8 [M] on the device of Q")
+    if metrics not in (KNN_L2, KNN_COSINE, KNN_BOTH):
+        raise ValueError("seg_knn: metrics must be KNN_L2, KNN_COSINE or KNN_BOTH")
+    if not 1 <= kmax <= KNN_KMAX:
+        raise ValueError(f"seg_knn: kmax must be in 1 .. {KNN_KMAX}")
+    if out is None:
+        out = [torch.empty(n, kmax, dtype=dt, device=Q.device) if metrics & bit else None
+               for bit in (KNN_L2, KNN_COSINE) for dt in (torch.int32, torch.float32)]
+    given = [o for o in out if o is not None]
+    ldo = given[0].stride(0)
+    for o, dt, bit in zip(out, (torch.int32, torch.float32) * 2, (KNN_L2, KNN_L2, KNN_COSINE, KNN_COSINE)):
+        if o is None:
+            if metrics & bit:
+                raise ValueError("seg_knn: out lacks a tensor of a metric that is asked for")
+            continue
+        if (o.dtype != dt or o.dim() != 2 or o.shape[0] != n or o.shape[1] < kmax or o.stride(1) != 1 or o.stride(0) != ldo
+                or o.device != Q.device):
+            raise ValueError("seg_knn: out tensors must be int32 / f32 [n, >= kmax] rows with one common row stride")
+    if workspace is None:
+        workspace = seg_knn_workspace(n, M, D, kmax, metrics, splits, Q.device)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_seg_knn(_p(Q), ldq, n, _p(K), ldk, M, D, _p(qnorm), _p(knorm), _p(skip), kmax, metrics, splits,
+                              *[_p(o) for o in out], ldo, _p(workspace), _stream(Q)))
+    nl = 2 if metrics == KNN_BOTH else 1
+    # algorithmic bytes: every workgroup streams its share of the keys once per query tile, the queries once per key tile
+    qt, kt = 128, 128
+    KERNEL_TIMER.stop(t, f"seg_knn_kernel<{metrics}>", 4 * D * (M * ((n + qt - 1) // qt) + n * ((M + kt - 1) // kt)) + 8 * nl * n * kmax,
+                      2.0 * n * M * D)
+    return tuple(out)
+
+
+def seg_knn_vote(idx, labels, ks, out=None):
+    """uint8 [len(ks), n, L]: per query row and pixel the most frequent of labels[idx[row, :k], pixel] for every k of the
+    ascending ``ks`` (at most 8 values <= 32), the smallest value on a tie (torch.mode)."""
+    R, L, es = _seg_labels(labels)
+    ks = [int(k) for k in ks]
+    if (idx.dtype != torch.int32 or idx.dim() != 2 or idx.stride(1) != 1 or idx.device != labels.device or not ks
+            or len(ks) > 8 or idx.shape[1] < ks[-1]):
+        raise ValueError("seg_knn_vote: idx must be int32 [n, >= max(ks)] rows on the device of labels, ks 1 .. 8 values")
+    n = idx.shape[0]
+    if out is None:
+        out = torch.empty(len(ks), n, L, dtype=torch.uint8, device=labels.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (len(ks), n, L) or not out.is_contiguous() or out.device != labels.device:
+        raise ValueError("seg_knn_vote: out must be a contiguous uint8 [len(ks), n, L]")
+    if n:
+        t = KERNEL_TIMER.start()
+        check(lib().octic_seg_knn_vote(_p(idx), idx.stride(0), n, _p(labels), es, R, L, (ctypes.c_int * len(ks))(*ks), len(ks),
+                                       _p(out), _stream(labels)))
+        KERNEL_TIMER.stop(t, "seg_knn_vote_kernel", n * (4 * ks[-1] + L * (es * ks[-1] + len(ks))))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ Mixup / CutMix + BCE (csrc/mixup.hip)
 def _mix_table(table, B):
     _require_cuda(table)

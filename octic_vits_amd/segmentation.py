@@ -1,4 +1,4 @@
-"""Linear segmentation evaluation of a frozen DINOv2 backbone: the logreg half of the reference's ``eval_model``
+"""Segmentation evaluation of a frozen DINOv2 backbone: the logreg and k-NN classifiers of the reference's ``eval_model``
 (dinov2/eval/segmentation/eval_segmentation.py:346-470) on ONE GPU with the patch features resident in device memory.
 
 The reference gathers ~20 GB of patch features to the host, fits cuML's L-BFGS logistic regression and scores with
@@ -17,7 +17,16 @@ Stopping rule of ``lbfgs`` (cuML's own rule is not reproducible here and not cla
 objective in ``linesearch_max_iter`` trials - then the best iterate seen is returned.  An f32 objective always ends on
 that last rule: near the optimum the decrease along the search direction falls below the rounding noise of the sum.
 
-Not here: the k-NN classifier, RobustScaler / PCA standardisation, datasets and transforms, multi-rank grid splitting.
+k-NN (``KNNClassifier``, csrc/segknn.hip): the reference materialises ``cdist`` and runs ``topk`` once per grid point; here
+ONE fused pass gives the 32 nearest training patches under both distances (both need only the dot product and the row norms,
+and the lists for fewer neighbours are prefixes), and a vote kernel reads the neighbours' pixel labels from the resident label
+matrix.  Neighbours are ordered by (distance, row index) - ``torch.topk`` leaves ties unspecified.  ``eval_model`` still refuses
+"knn" (its refusal is pinned by earlier tests); the reference's default ``("logreg", "knn")`` runs through ``extract_splits`` +
+``eval_features``, which share one backbone pass.  The final refit is on train + val with the validation rows FIRST in the
+resident matrix (the reference concatenates train then val): row order matters to k-NN only through exact distance ties.
+
+Not here: the L1 / Linf / inner_product distances and more than 32 neighbours, RobustScaler / PCA standardisation, datasets
+and transforms, multi-rank grid splitting.
 CPU tensors raise "GPU only" wherever a kernel is involved; ``lbfgs``, ``patch_labels``, ``upscale``, the metric formulas
 on a confusion matrix, the hyper-parameter names and the label <-> class-index tables are plain host code.
 """
@@ -30,7 +39,8 @@ import torch
 from . import ops
 
 __all__ = ["patch_features", "patch_labels", "Standardizer", "LogregClassifier", "lbfgs", "mIoU", "accuracy",
-           "confusion_matrix", "miou_from_confusion", "accuracy_from_confusion", "class_tables", "hparam_name", "eval_model"]
+           "confusion_matrix", "miou_from_confusion", "accuracy_from_confusion", "class_tables", "hparam_name", "eval_model", "KNNClassifier", "SegSplits", "extract_splits",
+           "eval_features"]
 
 
 # ------------------------------------------------------------------------------------------------ features and labels
@@ -439,7 +449,137 @@ class LogregClassifier:
         return metrics
 
 
-classifiers_dict = {"logreg": LogregClassifier}
+class KNNClassifier:
+    """``KNNClassifier`` of eval_segmentation.py:172-278 with the reference's signature and grids.  ``inference_bs``,
+    ``train_set_chunk_size`` and ``device`` are kept for the signature and not used: the keys are the resident matrix, streamed
+    by one kernel.  ``fit`` keeps views (sub-sampling is a row stride), marks the patches whose mode label is ignored as skipped
+    keys (``Classifier.fit``, :83) and computes the key norms.  The vote is over the neighbours' raw pixel labels, so an ignored
+    value can win a pixel, as in the reference.  Distances "cosine" and "L2"; at most 32 neighbours."""
+
+    DISTANCES = {"L2": ops.KNN_L2, "cosine": ops.KNN_COSINE}
+    # Queries go through the kernels in batches of at most this many rows: the neighbour lists and votes of a batch are a few
+    # hundred bytes per row, and the workspace the library asks for (octic_seg_knn_workspace_bytes) holds partial lists only
+    # while splits x query tiles stays near the CU count, so memory is bounded whatever the number of rows.
+    QUERY_ROWS = 65536
+
+    def __init__(self, ignore_labels: Sequence[int], inference_bs: int = 1024, train_set_chunk_size: Optional[int] = 262144,
+                 train_set_subsampling: int = 1, device: str = "cuda", dtype: str = "float32",
+                 num_neighbors: Sequence[int] = (1, 3, 10, 30), distance: Sequence[str] = ("cosine", "L2")):
+        if dtype != "float32":
+            raise ValueError("KNNClassifier: the HIP engine computes k-NN distances in float32 only")
+        self.device, self.dtype = device, torch.float32
+        self.inference_bs, self.train_set_chunk_size = inference_bs, train_set_chunk_size
+        self.train_set_subsampling = train_set_subsampling
+        self.ignore_labels = ignore_labels
+        self.hparam_grids = {"num_neighbors": tuple(num_neighbors), "distance": tuple(distance)}
+        for k in self.hparam_grids["num_neighbors"]:
+            self._check_k(k)
+        for d in self.hparam_grids["distance"]:
+            self._check_distance(d)
+        for k, grid in self.hparam_grids.items():   # a fit without select_hparams uses the first grid point
+            setattr(self, k, grid[0])
+
+    # ---- host pieces
+    @staticmethod
+    def _check_k(k) -> int:
+        if int(k) != k or not 1 <= int(k) <= ops.KNN_KMAX:
+            raise ValueError(f"KNNClassifier: num_neighbors must be an integer in 1 .. {ops.KNN_KMAX}, got {k!r}")
+        return int(k)
+
+    @classmethod
+    def _check_distance(cls, d) -> int:
+        if d in ("L1", "Linf", "inner_product"):
+            raise NotImplementedError(f"k-NN distance {d!r} is not implemented on the HIP engine")
+        if d not in cls.DISTANCES:
+            raise ValueError(f"unknown k-NN distance {d!r}")
+        return cls.DISTANCES[d]
+
+    def upscale(self, labels: torch.Tensor) -> torch.Tensor:
+        return labels[:, None].expand(-1, self.n_pixels_per_sample)
+
+    def unfit(self) -> None:
+        for k in ("train_X", "train_y", "key_norms_", "skip_", "n_keys_"):
+            if hasattr(self, k):
+                delattr(self, k)
+
+    # ---- device pieces
+    def fit(self, features: torch.Tensor, labels: torch.Tensor) -> None:
+        self.unfit()
+        ops._require_cuda(features)
+        ops._require_cuda(labels)
+        if self.train_set_subsampling > 1:
+            labels = labels[:: self.train_set_subsampling]
+            features = features[:: self.train_set_subsampling]
+        self.n_pixels_per_sample = labels.shape[-1]
+        self.label_dtype = labels.dtype
+        labels = labels.contiguous()                 # a copy only when sub-sampled
+        modes = ops.seg_patch_mode(labels)
+        ignore = torch.zeros(256, dtype=torch.bool, device=labels.device)
+        for v in self.ignore_labels:
+            ignore[int(v) & 255] = True
+        self.skip_ = ignore[modes.long()].to(torch.uint8)
+        self.n_keys_ = int(features.shape[0]) - int(self.skip_.sum())
+        self.train_X, self.train_y = features, labels
+        self.key_norms_ = ops.seg_rownorms(features)
+
+    @torch.no_grad()
+    def predict_grid(self, features: torch.Tensor, ks: Sequence[int], distances: Sequence[str]) -> Dict[Tuple[int, str], torch.Tensor]:
+        """{(k, distance): [n, L] pixel-level predictions on the device} for every pair, from ONE pass over the keys."""
+        ops._require_cuda(features)
+        if not hasattr(self, "train_X"):
+            raise RuntimeError("KNNClassifier.predict before fit")
+        ks = [self._check_k(k) for k in ks]
+        metrics = 0
+        for d in distances:
+            metrics |= self._check_distance(d)
+        kasc = sorted(set(ks))
+        kmax = kasc[-1]
+        if self.n_keys_ < kmax:
+            raise ValueError(f"KNNClassifier: {kmax} neighbours asked for, but only {self.n_keys_} training patches are not ignored")
+        n, L = features.shape[0], self.n_pixels_per_sample
+        dev = features.device
+        votes = {d: torch.empty(len(kasc), n, L, dtype=torch.uint8, device=dev) for d in dict.fromkeys(distances)}
+        M, D = self.train_X.shape
+        bs = min(n, self.QUERY_ROWS)
+        ws = ops.seg_knn_workspace(bs, M, D, kmax, metrics, 0, dev) if n else None
+        for i in range(0, n, bs):
+            q = features[i:i + bs]
+            if q.shape[0] != bs:                     # the last batch: its own plan and workspace
+                ws = ops.seg_knn_workspace(q.shape[0], M, D, kmax, metrics, 0, dev)
+            idx_l2, _, idx_cos, _ = ops.seg_knn(q, self.train_X, ops.seg_rownorms(q), self.key_norms_, self.skip_, kmax, metrics,
+                                                0, workspace=ws)
+            for d, idx in (("L2", idx_l2), ("cosine", idx_cos)):
+                if d in votes:
+                    votes[d][:, i:i + bs] = ops.seg_knn_vote(idx, self.train_y, kasc)
+        return {(k, d): votes[d][kasc.index(k)].to(self.label_dtype) for k in ks for d in distances}
+
+    @torch.no_grad()
+    def predict(self, features: torch.Tensor) -> torch.Tensor:
+        """[n, L] pixel-level predictions on the device for the current (num_neighbors, distance)."""
+        return self.predict_grid(features, (self.num_neighbors,), (self.distance,))[(int(self.num_neighbors), self.distance)]
+
+    def select_hparams(self, features_train, labels_train, features_val, labels_val, metric_name: str = "mIoU") -> Dict[str, float]:
+        names, grids = zip(*self.hparam_grids.items())
+        grid = list(itertools.product(*grids))
+        metrics: Dict[str, float] = {}
+        best = grid[0]
+        if len(grid) > 1:
+            self.fit(features_train, labels_train)
+            preds = self.predict_grid(features_val, self.hparam_grids["num_neighbors"], self.hparam_grids["distance"])
+            scores = []
+            for point in grid:
+                score = metrics_dict[metric_name](labels_val, preds[(int(point[0]), point[1])], self.ignore_labels)
+                scores.append(score)
+                metrics[hparam_name(metric_name, names, point)] = score
+            del preds
+            self.unfit()
+            best = grid[int(np.argmax(scores))]         # the first maximum
+        for k, v in zip(names, best):
+            setattr(self, k, v)
+        return metrics
+
+
+classifiers_dict = {"logreg": LogregClassifier, "knn": KNNClassifier}
 
 
 # ------------------------------------------------------------------------------------------------ eval_model
@@ -470,21 +610,21 @@ def _extract(model, batches, X, L, row0, ps, slots=None):
         i0 += B
 
 
-def eval_model(model, train, test, val=None, classifiers: Sequence[str] = ("logreg",),
-               standardization: Optional[str] = "StandardScaler", ignore_labels: Sequence[int] = (0, 255), val_seed: int = 0,
-               classifiers_kwargs: Optional[Dict[str, Dict[str, Any]]] = None) -> Dict[str, float]:
-    """The logreg half of ``eval_model`` (eval_segmentation.py:346-470).  ``train`` / ``test`` / ``val`` are iterables of
+class SegSplits:
+    """What ``extract_splits`` leaves on the device: X [n_fit P, D] f32 and L [n_fit P, ps^2] uint8 with the ``n_val`` validation
+    images FIRST (so train, val and train + val are row ranges), the test rows Xt / Lt, and P patches per image."""
+    __slots__ = ("X", "L", "Xt", "Lt", "n_val", "P")
+
+    def __init__(self, X, L, Xt, Lt, n_val, P):
+        self.X, self.L, self.Xt, self.Lt, self.n_val, self.P = X, L, Xt, Lt, n_val, P
+
+
+def extract_splits(model, train, test, val=None, standardization: Optional[str] = "StandardScaler", val_seed: int = 0) -> SegSplits:
+    """The feature half of ``eval_model`` (eval_segmentation.py:386-415).  ``train`` / ``test`` / ``val`` are iterables of
     ``(images [B, 3, H, W], labels [B, H, W])`` batches (one resolution; they are walked once, after being listed to count the
     images).  With ``val=None`` a tenth of the training images, drawn by ``numpy.random.RandomState(val_seed).permutation``,
-    is held out (:392-398).  Train and validation features share ONE resident matrix, validation rows first, so the
-    hyper-parameter fits and the final refit on train + val (:441-444) are row ranges of it.  Returns the reference's keys:
-    ``hparam_fitting.logreg.mIoU_C=..._max_iter=..._tol=..._linesearch_max_iter=..._lbfgs_hessian_rank=...``,
-    ``labels_logreg_mIoU``, ``labels_logreg_acc``."""
-    for name in classifiers:
-        if name == "knn":
-            raise NotImplementedError("the k-NN classifier of the segmentation evaluation is not implemented on the HIP engine")
-        if name not in classifiers_dict:
-            raise ValueError(f"unknown classifier {name!r}")
+    is held out (:392-398).  Train and validation features share ONE resident matrix, validation rows first; the
+    standardisation is fitted on the training rows only and applied in place."""
     preproc = Standardizer(standardization) if standardization is not None else None
     dev = next(model.parameters()).device
     if dev.type != "cuda":
@@ -517,11 +657,28 @@ def eval_model(model, train, test, val=None, classifiers: Sequence[str] = ("logr
     Xt = torch.empty(n_test * P, D, dtype=torch.float32, device=dev)
     Lt = torch.empty(n_test * P, ps * ps, dtype=label_dtype, device=dev)
     _extract(model, test, Xt, Lt, 0, ps)
-    Xv, Lv, Xtr, Ltr = X[:n_val * P], L[:n_val * P], X[n_val * P:], L[n_val * P:]
     if preproc is not None:
-        preproc.fit(Xtr)                              # never on val / test
+        preproc.fit(X[n_val * P:])                    # never on val / test
         preproc.transform(X)
         preproc.transform(Xt)
+    return SegSplits(X, L, Xt, Lt, n_val, P)
+
+
+def _check_classifiers(classifiers: Sequence[str]) -> None:
+    for name in classifiers:
+        if name not in classifiers_dict:
+            raise ValueError(f"unknown classifier {name!r}")
+
+
+def eval_features(feats: SegSplits, classifiers: Sequence[str] = ("logreg", "knn"), ignore_labels: Sequence[int] = (0, 255),
+                  classifiers_kwargs: Optional[Dict[str, Dict[str, Any]]] = None) -> Dict[str, float]:
+    """The classifier loop of ``eval_model`` (eval_segmentation.py:417-468) on extracted splits, with the reference's default
+    classifiers: per classifier the hyper-parameter search on train against val (``hparam_fitting.<classifier>.<name>``), the
+    refit on train + val (:441-444) and ``labels_<classifier>_mIoU`` / ``labels_<classifier>_acc`` on test.  The refit sees the
+    validation rows first, the reference train first: for k-NN that changes outcomes only where distances tie exactly."""
+    _check_classifiers(classifiers)
+    X, L, Xt, Lt, nv = feats.X, feats.L, feats.Xt, feats.Lt, feats.n_val * feats.P
+    Xv, Lv, Xtr, Ltr = X[:nv], L[:nv], X[nv:], L[nv:]
     results: Dict[str, float] = {}
     for name in classifiers:
         kw = (classifiers_kwargs or {}).get(name, {})
@@ -534,3 +691,21 @@ def eval_model(model, train, test, val=None, classifiers: Sequence[str] = ("logr
             results[f"labels_{name}_{metric_name}"] = float(metric(Lt, preds, ignore_labels))
         del clf
     return results
+
+
+def eval_model(model, train, test, val=None, classifiers: Sequence[str] = ("logreg",),
+               standardization: Optional[str] = "StandardScaler", ignore_labels: Sequence[int] = (0, 255), val_seed: int = 0,
+               classifiers_kwargs: Optional[Dict[str, Dict[str, Any]]] = None) -> Dict[str, float]:
+    """The logreg half of ``eval_model`` (eval_segmentation.py:346-470): ``extract_splits`` then ``eval_features``.  Train and
+    validation features share ONE resident matrix, validation rows first, so the hyper-parameter fits and the final refit on
+    train + val (:441-444) are row ranges of it.  Returns the reference's keys:
+    ``hparam_fitting.logreg.mIoU_C=..._max_iter=..._tol=..._linesearch_max_iter=..._lbfgs_hessian_rank=...``,
+    ``labels_logreg_mIoU``, ``labels_logreg_acc``.  "knn" is refused HERE (call ``extract_splits`` + ``eval_features`` for the
+    reference's default pair of classifiers)."""
+    for name in classifiers:
+        if name == "knn":
+            raise NotImplementedError("the k-NN classifier of the segmentation evaluation is not implemented on the HIP engine")
+        if name not in classifiers_dict:
+            raise ValueError(f"unknown classifier {name!r}")
+    feats = extract_splits(model, train, test, val=val, standardization=standardization, val_seed=val_seed)
+    return eval_features(feats, classifiers=classifiers, ignore_labels=ignore_labels, classifiers_kwargs=classifiers_kwargs)
