@@ -130,6 +130,21 @@ int octic_layernorm_d8_bwd(const octic_view* g, const octic_view* x, const float
 int octic_layernorm_d8_bwd_cast(const octic_view* g, const octic_view* x, const float* stats, const float* const alpha[5],
                                 const octic_view* dres, const octic_view* dx, float* partials, int64_t M, int c,
                                 const float* rs, int64_t rows_per_sample, void* gcast, void* stream);
+/* octic_layernorm_d8_bwd_skip / octic_layernorm_d8_bwd_cast_skip: the two above with the stochastic-depth factor of the
+ * branch this norm OPENS as a sample mask (sample_scale: one f32 per rows_per_sample rows, NULL = the calls above;
+ * rows_per_sample <= 0 or M % rows_per_sample != 0 with a mask: OCTIC_ESHAPE).  sample_scale[b] == 0 PROMISES that the rows
+ * of g of sample b are zero - the branch's first GEMM stores exact zeros for a dropped sample - and the kernel may then leave
+ * those rows of g, x and stats unread: dx = dres (zeros without dres), gcast = bf16(rs * dres), nothing added to the
+ * partials.  With the promise kept and x finite every output equals the unmasked call, up to the sign of an exact zero
+ * (which no comparison of values sees).  Honoured by the bf16 kernel for packed rows with c <= 160; every other route
+ * reads all rows.                                                                                                   */
+int octic_layernorm_d8_bwd_skip(const octic_view* g, const octic_view* x, const float* stats, const float* const alpha[5],
+                                const octic_view* dres, const octic_view* dx, float* partials, int64_t M, int c, int g_dtype,
+                                const float* sample_scale, int64_t rows_per_sample, void* stream);
+int octic_layernorm_d8_bwd_cast_skip(const octic_view* g, const octic_view* x, const float* stats,
+                                     const float* const alpha[5], const octic_view* dres, const octic_view* dx,
+                                     float* partials, int64_t M, int c, const float* rs, int64_t rows_per_scale, void* gcast,
+                                     const float* sample_scale, int64_t rows_per_sample, void* stream);
 int octic_layernorm_d8_bwd_finish(const float* partials, int nblk, int c, float* const dalpha[5], float* dbeta,
                                   void* stream);
 /* njobs of the reductions above in ceil(njobs / 48) launches, bit-identical to njobs calls (see octic_dense_finish_batch). */
@@ -555,6 +570,17 @@ int octic_dense_finish_batch(const octic_finish_job* jobs, int njobs, void* stre
 int octic_dense_layernorm_bwd_tail(const void* gy, const float* x, const float* w, const float* stats, const float* dres,
                                    float* dx, float* partials, const void* yb, const float* gamma, const float* rs,
                                    int64_t rows_per_scale, void* gyb, float* partials2, int64_t rows, int d, void* stream);
+/* octic_dense_layernorm_bwd_tail_skip: the same with the stochastic-depth factor of the branch this norm OPENS as a sample
+ * mask (sample_scale: one f32 per rows_per_sample rows, NULL = the call above; rows_per_sample <= 0 or rows %
+ * rows_per_sample != 0 with a mask: OCTIC_ESHAPE).  sample_scale[b] == 0 PROMISES that the rows of gy of sample b are zero -
+ * the branch's first GEMM stores exact zeros for a dropped sample - and the kernel may then leave those rows of gy, x and
+ * stats unread: dx = dres (zeros without dres), nothing added to `partials`.  Under a mask the rows with rs == 0 (the factor
+ * of the branch that ENDS here) leave yb unread as well; their zero gyb rows are still stored.  With the promise kept and x
+ * finite every output equals the unmasked call, up to the sign of an exact zero (which no comparison of values sees). */
+int octic_dense_layernorm_bwd_tail_skip(const void* gy, const float* x, const float* w, const float* stats,
+                                        const float* dres, float* dx, float* partials, const void* yb, const float* gamma,
+                                        const float* rs, int64_t rows_per_scale, void* gyb, float* partials2, int64_t rows,
+                                        int d, const float* sample_scale, int64_t rows_per_sample, void* stream);
 /* octic_dense_gelu_bwd: dh = gelu'(h) * g (exact erf GELU, bf16 [rows, d], d % 8 == 0) and, when partials != NULL,
  * octic_dense_gelu_blocks() slabs [d] of column sums of dh (bias gradient of the projection that produced h;
  * reduce with octic_dense_finish(partials, blocks, d/2, out, out + d/2, NULL)).  Replaces GeluBackward + the
@@ -565,6 +591,11 @@ int octic_dense_gelu_bwd(const void* h, const void* g, void* dh, float* partials
  * elements, d % 8 == 0), in a fixed order; reduce with octic_dense_finish as above.  The bias gradient of the fused-qkv
  * projection (autograd of deit/vit.py:33: grad.sum(0) over the token rows).                                      */
 int octic_dense_colsum(const void* g, int64_t rows, int d, int64_t ld, float* partials, void* stream);
+/* octic_dense_colsum_skip: sample_scale[b] == 0 (one f32 per rows_per_sample rows; NULL = the call above; rows_per_sample
+ * <= 0 or rows % rows_per_sample != 0 with a mask: OCTIC_ESHAPE) promises that the rows of sample b are zero; they are not
+ * read and zeros take their place in the same sums.                                                                  */
+int octic_dense_colsum_skip(const void* g, int64_t rows, int d, int64_t ld, float* partials, const float* sample_scale,
+                            int64_t rows_per_sample, void* stream);
 int octic_scale_residual_fwd(const float* x, const void* y, int y_dtype, const float* gamma, const float* rs,
                              int64_t rows_per_scale, float* out, int64_t rows, int d, void* stream);
 int octic_scale_residual_bwd(const float* gout, const void* y, int y_dtype, const float* gamma, const float* rs,

@@ -49,6 +49,10 @@ _PROTOS = {
     "octic_layernorm_d8_bwd": (c_int, [VP, VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_int, c_int, c_void_p]),
     "octic_layernorm_d8_bwd_cast": (c_int, [VP, VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_int, c_void_p, c_i64,
                                             c_void_p, c_void_p]),
+    "octic_layernorm_d8_bwd_skip": (c_int, [VP, VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_int, c_int, c_void_p, c_i64,
+                                            c_void_p]),
+    "octic_layernorm_d8_bwd_cast_skip": (c_int, [VP, VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_int, c_void_p, c_i64,
+                                                 c_void_p, c_void_p, c_i64, c_void_p]),
     "octic_layernorm_d8_bwd_finish": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "octic_layernorm_d8_bwd_finish_batch": (c_int, [c_void_p, c_int, c_void_p]),
     "octic_sample_blocks": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p]),
@@ -89,6 +93,8 @@ _PROTOS = {
     "octic_dense_layernorm_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_i64, c_int, c_void_p]),
     "octic_dense_layernorm_bwd_tail": (c_int, [c_void_p] * 10 + [c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p]),
+    "octic_dense_layernorm_bwd_tail_skip": (c_int, [c_void_p] * 10 + [c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64,
+                                                                      c_void_p]),
     "octic_dense_finish": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "octic_dense_finish_batch": (c_int, [c_void_p, c_int, c_void_p]),
     "octic_dense_gelu_blocks": (c_int, []),
@@ -160,6 +166,7 @@ _PROTOS = {
     "octic_dense_gemm_order_dropped": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p]),
     "octic_dense_colsum": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p]),
+    "octic_dense_colsum_skip": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
     "octic_dense_wgrad_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
     "octic_dense_wgrad_tile": (c_int, [c_int, c_int, c_int]),
     "octic_dense_wgrad_plan": (c_int, [c_int, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_int)]),

@@ -314,13 +314,23 @@ __global__ __launch_bounds__(OCTIC_DLNBWD_WAVES * 64, OCTIC_DLNBWD_WAVES / 4) vo
 //   slabs: dw += gy*xhat, db += gy  |  d gamma += rs*dx*yb, bias gradient / gamma += rs*dx
 // The two separate kernels (dense_ln_bwd_wide + scale_residual_bwd) write dx and read it back: 463 MB per launch at
 // ViT-H, this one 379.  Arithmetic per element is that of the two kernels (dx is used as stored).
-template <typename TG, int NV>
+// SKIP (ns given): ns is the stochastic-depth factor of the branch this norm OPENS, one entry per nrps rows.  ns[b] == 0
+// promises that the rows of gy of sample b are zero (the branch's first GEMM stores exact zeros for a dropped sample); the
+// kernel may then leave those rows of gy, x and stats unread: LN'(0) = 0, so dx = dres and the row adds zeros to dw / db.
+// Where rs, the factor of the branch that ENDS here, is 0, t = dx * 0 and yb is not read either (the zero gyb row and dx are
+// still stored: their readers take all rows).  With the promise kept and x finite every output equals the launch without
+// ns, up to the sign of an exact zero (0 * x, 0 + dres), which no comparison of values sees.  The branches are per row and
+// wave-uniform; row-to-wave assignment, summation order and the slabs do not move.
+template <typename TG, int NV, bool SKIP = false, typename... MASK>      // MASK: (const float* ns, long nrps) under SKIP
 __global__ __launch_bounds__(512, 2) void dense_ln_bwd_tail_kernel(
     const TG* __restrict__ gy, const float* __restrict__ x, const float* __restrict__ w,
     const float* __restrict__ stats, const float* __restrict__ dres, float* __restrict__ dx,
     float* __restrict__ partials, const TG* __restrict__ yb, const float* __restrict__ gamma,
-    const float* __restrict__ rs, long rps, TG* __restrict__ gyb, float* __restrict__ partials2, long rows, int d) {
+    const float* __restrict__ rs, long rps, TG* __restrict__ gyb, float* __restrict__ partials2, long rows, int d,
+    MASK... mask) {
   extern __shared__ float lds[];             // [2][d] slab image | [d] LayerNorm weights | [d] layer scale
+  const float* __restrict__ ns = mask_scale(mask...);
+  const long nrps = mask_rows(mask...);
   const int lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
   const long nw = (long)gridDim.x * nwaves;
   float* wl = lds + 2 * d;
@@ -342,16 +352,41 @@ __global__ __launch_bounds__(512, 2) void dense_ln_bwd_tail_kernel(
     const long o = r * d + lane * 4;
     f32x4 xh[NV], g[NV], dr[NV];
     typename Row4<TG>::vec gr[NV], yr[NV];
+    // SKIP: zeros stand in for what a dead row does not load and the arithmetic below runs on them unchanged - the same
+    // instructions in the same order as the unmasked kernel, so a live row keeps its bits whatever the compiler contracts
+    float mean = 0.f, rstd = 0.f, sc = 1.f;
+    bool live = true, tail = true;
+    if constexpr (SKIP) {
+      sc = rs ? rs[r / rps] : 1.f;
+      live = mask_live(ns[r / nrps]);
+      tail = mask_live(sc);
+    }
+    if (live) {
 #pragma unroll
-    for (int i = 0; i < NV; ++i) xh[i] = *(const f32x4*)(x + o + i * 256);
+      for (int i = 0; i < NV; ++i) xh[i] = *(const f32x4*)(x + o + i * 256);
 #pragma unroll
-    for (int i = 0; i < NV; ++i) gr[i] = Row4<TG>::load_raw(gy + o + i * 256);
+      for (int i = 0; i < NV; ++i) gr[i] = Row4<TG>::load_raw(gy + o + i * 256);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        xh[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        gr[i] = typename Row4<TG>::vec{};
+      }
+    }
 #pragma unroll
     for (int i = 0; i < NV; ++i) dr[i] = dres ? *(const f32x4*)(dres + o + i * 256) : f32x4{0.f, 0.f, 0.f, 0.f};
+    if (tail) {
 #pragma unroll
-    for (int i = 0; i < NV; ++i) yr[i] = Row4<TG>::load_raw(yb + o + i * 256);
-    const float mean = stats[2 * r], rstd = stats[2 * r + 1];
-    const float sc = rs ? rs[r / rps] : 1.f;
+      for (int i = 0; i < NV; ++i) yr[i] = Row4<TG>::load_raw(yb + o + i * 256);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) yr[i] = typename Row4<TG>::vec{};
+    }
+    if (live) {
+      mean = stats[2 * r];
+      rstd = stats[2 * r + 1];
+    }
+    if constexpr (!SKIP) sc = rs ? rs[r / rps] : 1.f;
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -585,8 +620,18 @@ __global__ __launch_bounds__(256) void dense_gelu_bwd_kernel(const bf16* __restr
 // Column sums of a bf16 [rows, d] tensor (row stride ld) in f32: kGeluRowBlocks slabs [d] in a fixed order, reduced by
 // dense_finish_kernel.  The bias gradient of the fused-qkv projection (deit/vit.py:33; autograd's `grad.sum(0)`), whose
 // cotangent comes out of the attention backward and is read by nothing else row-wise.
+// SKIP (ns given): one factor per nrps rows; ns[b] == 0 promises that the rows of sample b are zero, and zeros stand in for
+// their loads in the same expressions (same grouping of the sums: same bits, up to the sign of an exact zero).
+template <bool SKIP, typename... MASK>
+__device__ __forceinline__ bf16x8 colsum_row(const bf16* __restrict__ p, long r, MASK... mask) {
+  if constexpr (SKIP) {                      // (a wave holds one row phase; row numbers fit 32 bits under SKIP)
+    if (!mask_live(mask_scale(mask...)[(unsigned)r / mask_rows(mask...)])) return bf16x8{};
+  }
+  return *(const bf16x8*)p;
+}
+template <bool SKIP = false, typename... MASK>                            // MASK: (const float* ns, unsigned nrps) under SKIP
 __global__ __launch_bounds__(256) void dense_colsum_kernel(const bf16* __restrict__ g, float* __restrict__ partials,
-                                                           long rows, int d, long ld) {
+                                                           long rows, int d, long ld, MASK... mask) {
   __shared__ float red[4][64][8];
   const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6;
   const int col = (blockIdx.x * 64 + cl) * 8;
@@ -596,13 +641,13 @@ __global__ __launch_bounds__(256) void dense_colsum_kernel(const bf16* __restric
   if (col < d) {
     long r = r0 + ph;
     for (; r + 12 < r1; r += 16) {        // four rows per trip: four 16-byte loads in flight per lane
-      const bf16x8 v0 = *(const bf16x8*)(g + r * ld + col), v1 = *(const bf16x8*)(g + (r + 4) * ld + col);
-      const bf16x8 v2 = *(const bf16x8*)(g + (r + 8) * ld + col), v3 = *(const bf16x8*)(g + (r + 12) * ld + col);
+      const bf16x8 v0 = colsum_row<SKIP>(g + r * ld + col, r, mask...), v1 = colsum_row<SKIP>(g + (r + 4) * ld + col, r + 4, mask...);
+      const bf16x8 v2 = colsum_row<SKIP>(g + (r + 8) * ld + col, r + 8, mask...), v3 = colsum_row<SKIP>(g + (r + 12) * ld + col, r + 12, mask...);
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[e] += ((float)v0[e] + (float)v1[e]) + ((float)v2[e] + (float)v3[e]);
     }
     for (; r < r1; r += 4) {
-      const bf16x8 v = *(const bf16x8*)(g + r * ld + col);
+      const bf16x8 v = colsum_row<SKIP>(g + r * ld + col, r, mask...);
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[e] += (float)v[e];
     }
@@ -804,6 +849,15 @@ int octic_dense_layernorm_bwd_rows(const void* gy, int g_dtype, const float* x, 
 int octic_dense_layernorm_bwd_tail(const void* gy, const float* x, const float* w, const float* stats, const float* dres,
                                    float* dx, float* partials, const void* yb, const float* gamma, const float* rs,
                                    int64_t rows_per_scale, void* gyb, float* partials2, int64_t rows, int d, void* stream) {
+  return octic_dense_layernorm_bwd_tail_skip(gy, x, w, stats, dres, dx, partials, yb, gamma, rs, rows_per_scale, gyb,
+                                             partials2, rows, d, nullptr, 0, stream);
+}
+
+int octic_dense_layernorm_bwd_tail_skip(const void* gy, const float* x, const float* w, const float* stats,
+                                        const float* dres, float* dx, float* partials, const void* yb, const float* gamma,
+                                        const float* rs, int64_t rows_per_scale, void* gyb, float* partials2, int64_t rows,
+                                        int d, const float* sample_scale, int64_t rows_per_sample, void* stream) {
+  if (sample_scale && (rows_per_sample <= 0 || rows % rows_per_sample)) return OCTIC_ESHAPE;
   if (rows == 0) return OCTIC_OK;
   if (!gy || !x || !stats || !dx || !yb || !gyb) return OCTIC_ENULL;
   if (int e = dense_check(rows, d)) return e;
@@ -813,6 +867,12 @@ int octic_dense_layernorm_bwd_tail(const void* gy, const float* x, const float* 
   const size_t lds = (size_t)4 * d * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
   const long rps = rs ? rows_per_scale : 1;
+  if (sample_scale) {
+    DENSE_NV_SWITCH(dense_nv(d), (dense_ln_bwd_tail_kernel<bf16, NV, true><<<dim3(blocks), dim3(512), lds, s>>>(
+        (const bf16*)gy, x, w, stats, dres, dx, partials, (const bf16*)yb, gamma, rs, rps, (bf16*)gyb, partials2, rows, d,
+        sample_scale, (long)rows_per_sample)));
+    return launch_status();
+  }
   DENSE_NV_SWITCH(dense_nv(d), (dense_ln_bwd_tail_kernel<bf16, NV><<<dim3(blocks), dim3(512), lds, s>>>(
       (const bf16*)gy, x, w, stats, dres, dx, partials, (const bf16*)yb, gamma, rs, rps, (bf16*)gyb, partials2, rows, d)));
   return launch_status();
@@ -850,11 +910,21 @@ int octic_dense_finish_batch(const octic_finish_job* jobs, int njobs, void* stre
 int octic_dense_gelu_blocks(void) { return kGeluRowBlocks; }
 
 int octic_dense_colsum(const void* g, int64_t rows, int d, int64_t ld, float* partials, void* stream) {
+  return octic_dense_colsum_skip(g, rows, d, ld, partials, nullptr, 0, stream);
+}
+
+int octic_dense_colsum_skip(const void* g, int64_t rows, int d, int64_t ld, float* partials, const float* sample_scale,
+                            int64_t rows_per_sample, void* stream) {
   if (!g || !partials) return OCTIC_ENULL;
   if (rows <= 0 || d <= 0 || (d & 7) || (ld & 7) || ld < d) return OCTIC_ESHAPE;
+  if (sample_scale && (rows_per_sample <= 0 || rows % rows_per_sample)) return OCTIC_ESHAPE;
   if (((uintptr_t)g) & 15) return OCTIC_EALIGN;
-  dense_colsum_kernel<<<dim3((d / 8 + 63) / 64, kGeluRowBlocks), dim3(256), 0, (hipStream_t)stream>>>(
-      (const bf16*)g, partials, rows, d, ld);
+  const dim3 grid((d / 8 + 63) / 64, kGeluRowBlocks);
+  if (sample_scale && rows < ((int64_t)1 << 32))      // (the kernel divides 32-bit row numbers; beyond them: every row read)
+    dense_colsum_kernel<true><<<grid, dim3(256), 0, (hipStream_t)stream>>>((const bf16*)g, partials, rows, d, ld,
+                                                                           sample_scale, (unsigned)rows_per_sample);
+  else
+    dense_colsum_kernel<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>((const bf16*)g, partials, rows, d, ld);
   return launch_status();
 }
 

@@ -427,13 +427,22 @@ __global__ __launch_bounds__(256, 4) void ln_fwd_g8_kernel(const float* __restri
 #ifndef OCTIC_LNBWD_WIDE
 #define OCTIC_LNBWD_WIDE 1
 #endif
-template <typename TG, int NV, bool WIDE = false>
+// SKIP (WIDE only, ns given): ns is the stochastic-depth factor of the branch this norm opens, one entry per nrps rows.
+// ns[b] == 0 promises that the rows of g of sample b are zero (the branch's first GEMM stores exact zeros for a dropped
+// sample); the kernel may then leave those rows of g, x and stats unread: dx = dres, cg = bf16(crs * dres), zeros are added
+// to the d alpha / d beta partials.  With the promise kept and x finite every output equals the launch without ns, up to the
+// sign of an exact zero, which no comparison of values sees.  The branch is per row and wave-uniform; row-to-wave
+// assignment, summation order and the slabs do not move.
+template <typename TG, int NV, bool WIDE = false, bool SKIP = false, typename... MASK>  // MASK: (const float* ns, int64_t nrps) under SKIP
 __global__ __launch_bounds__(kLnBwdWaves * 64, WIDE ? 2 : OCTIC_LNBWD_OCC) void ln_bwd_g8_kernel(
     const TG* __restrict__ g, int64_t ldg, const float* __restrict__ x, int64_t ldx, const float* __restrict__ stats,
     const float* a0, const float* a1, const float* a2, const float* a3, const float* a4,
     const float* __restrict__ dres, int64_t ldr, float* __restrict__ dx, int64_t ldd, float* __restrict__ partials,
     int64_t M, int c, const float* __restrict__ crs = nullptr, int64_t crps = 1, bf16* __restrict__ cg = nullptr,
-    int64_t ldc = 0) {
+    int64_t ldc = 0, MASK... mask) {
+  static_assert(WIDE || !SKIP, "the sample mask exists in the wide kernel only");
+  const float* __restrict__ ns = mask_scale(mask...);
+  const int64_t nrps = mask_rows(mask...);
   // cg (WIDE only): also store bf16(crs[row / crps] * dx) - the drop-path-scaled bf16 cotangent the backward of the
   // residual-fused LinearD8 in front of this norm needs (what cast_rowscale_kernel makes of dx in a pass of its own)
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -462,16 +471,32 @@ __global__ __launch_bounds__(kLnBwdWaves * 64, WIDE ? 2 : OCTIC_LNBWD_OCC) void 
   const float inv_n = lg.isE ? 1.0f / (float)(2 * c) : 1.0f / (float)c;
   const float coefw = lg.isE ? inv_n : 2.0f * inv_n;    // w_s*2/n_s
   for (int64_t m = (int64_t)blockIdx.x * kLnBwdWaves + wid; m < M; m += nwaves) {
-    const float mu = stats[m * 8 + lg.seg], rstd = stats[m * 8 + 6];
+    // SKIP: zeros stand in for what a dead row does not load and the arithmetic below runs on them unchanged - the same
+    // instructions in the same order as the unmasked kernel, so a live row keeps its bits whatever the compiler contracts
+    bool live = true;
+    if constexpr (SKIP) live = mask_live(ns[m / nrps]);
+    float mu = 0.f, rstd = 0.f;
+    if (live) {
+      mu = stats[m * 8 + lg.seg];
+      rstd = stats[m * 8 + 6];
+    }
     f32x4 xc[NV], gh[NV];
     f32x4 dr[WIDE ? NV : 1];
     typedef typename std::conditional<std::is_same<TG, float>::value, f32x4, bf16x4>::type graw;
     graw gr[WIDE ? NV : 1];
     if constexpr (WIDE) {
+      if (live) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) xc[i] = *(const f32x4*)(x + m * ldx + lg.col0 + i * lg.step4);
+        for (int i = 0; i < NV; ++i) xc[i] = *(const f32x4*)(x + m * ldx + lg.col0 + i * lg.step4);
 #pragma unroll
-      for (int i = 0; i < NV; ++i) gr[i] = *(const graw*)(g + m * ldg + lg.col0 + i * lg.step4);
+        for (int i = 0; i < NV; ++i) gr[i] = *(const graw*)(g + m * ldg + lg.col0 + i * lg.step4);
+      } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+          xc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+          gr[i] = graw{};
+        }
+      }
 #pragma unroll
       for (int i = 0; i < NV; ++i)
         dr[i] = dres ? *(const f32x4*)(dres + m * ldr + lg.col0 + i * lg.step4) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -631,8 +656,10 @@ int octic_layernorm_d8_bwd_blocks(int64_t M) { return ln_blocks(M); }
 
 static int ln_bwd_impl(const octic_view* g, const octic_view* x, const float* stats, const float* const alpha[5],
                        const octic_view* dres, const octic_view* dx, float* partials, int64_t M, int c, int g_dtype,
-                       void* stream, const float* crs, int64_t crps, void* cg) {
+                       void* stream, const float* crs, int64_t crps, void* cg, const float* ns = nullptr,
+                       int64_t nrps = 0) {
   int e;
+  if (ns && (nrps <= 0 || M % nrps)) return OCTIC_ESHAPE;
   if ((e = check_c(c)) || (e = check_view(g, c, g_dtype)) || (e = check_view(x, c, OCTIC_F32)) ||
       (e = check_view(dx, c, OCTIC_F32)))
     return e;
@@ -664,8 +691,15 @@ static int ln_bwd_impl(const octic_view* g, const octic_view* x, const float* st
     case 4: LN_BWD_G8(T, 4); break; case 5: LN_BWD_G8(T, 5); break; case 6: LN_BWD_G8(T, 6); break; case 7: LN_BWD_G8(T, 7); break; default: LN_BWD_G8(T, 8); break; }
     if (OCTIC_LNBWD_WIDE && g_dtype == OCTIC_BF16 && c / 32 <= 5) {
 #define LN_BWD_G8W(N) ln_bwd_g8_kernel<bf16, N, true><<<grid, kLnBwdWaves * 64, smem_g8, s>>>((const bf16*)vg.p[0], vg.ld[0], (const float*)vx.p[0], vx.ld[0], stats, a[0], a[1], a[2], a[3], a[4], rp, vr.ld[0], (float*)vd.p[0], vd.ld[0], partials, M, c, crs, crs ? crps : 1, (bf16*)cg, (int64_t)8 * c)
+#define LN_BWD_G8S(N) ln_bwd_g8_kernel<bf16, N, true, true><<<grid, kLnBwdWaves * 64, smem_g8, s>>>((const bf16*)vg.p[0], vg.ld[0], (const float*)vx.p[0], vx.ld[0], stats, a[0], a[1], a[2], a[3], a[4], rp, vr.ld[0], (float*)vd.p[0], vd.ld[0], partials, M, c, crs, crs ? crps : 1, (bf16*)cg, (int64_t)8 * c, ns, nrps)
+      if (ns) {                             // (every other kernel of this function reads all rows: the mask is a permission)
+        switch (c / 32) { case 1: LN_BWD_G8S(1); break; case 2: LN_BWD_G8S(2); break; case 3: LN_BWD_G8S(3); break;
+                          case 4: LN_BWD_G8S(4); break; default: LN_BWD_G8S(5); break; }
+        return launch_status();
+      }
       switch (c / 32) { case 1: LN_BWD_G8W(1); break; case 2: LN_BWD_G8W(2); break; case 3: LN_BWD_G8W(3); break;
                         case 4: LN_BWD_G8W(4); break; default: LN_BWD_G8W(5); break; }
+#undef LN_BWD_G8S
 #undef LN_BWD_G8W
       return launch_status();
     }
@@ -690,13 +724,29 @@ int octic_layernorm_d8_bwd(const octic_view* g, const octic_view* x, const float
   return ln_bwd_impl(g, x, stats, alpha, dres, dx, partials, M, c, g_dtype, stream, nullptr, 1, nullptr);
 }
 
+int octic_layernorm_d8_bwd_skip(const octic_view* g, const octic_view* x, const float* stats, const float* const alpha[5],
+                                const octic_view* dres, const octic_view* dx, float* partials, int64_t M, int c, int g_dtype,
+                                const float* sample_scale, int64_t rows_per_sample, void* stream) {
+  return ln_bwd_impl(g, x, stats, alpha, dres, dx, partials, M, c, g_dtype, stream, nullptr, 1, nullptr, sample_scale,
+                     rows_per_sample);
+}
+
 int octic_layernorm_d8_bwd_cast(const octic_view* g, const octic_view* x, const float* stats, const float* const alpha[5],
                                 const octic_view* dres, const octic_view* dx, float* partials, int64_t M, int c,
                                 const float* rs, int64_t rows_per_sample, void* gcast, void* stream) {
+  return octic_layernorm_d8_bwd_cast_skip(g, x, stats, alpha, dres, dx, partials, M, c, rs, rows_per_sample, gcast, nullptr,
+                                          0, stream);
+}
+
+int octic_layernorm_d8_bwd_cast_skip(const octic_view* g, const octic_view* x, const float* stats,
+                                     const float* const alpha[5], const octic_view* dres, const octic_view* dx,
+                                     float* partials, int64_t M, int c, const float* rs, int64_t rows_per_scale, void* gcast,
+                                     const float* sample_scale, int64_t rows_per_sample, void* stream) {
   if (!gcast) return OCTIC_ENULL;
-  if (rs && rows_per_sample <= 0) return OCTIC_ESHAPE;
+  if (rs && rows_per_scale <= 0) return OCTIC_ESHAPE;
   if (((uintptr_t)gcast) & 15) return OCTIC_EALIGN;
-  return ln_bwd_impl(g, x, stats, alpha, dres, dx, partials, M, c, OCTIC_BF16, stream, rs, rows_per_sample, gcast);
+  return ln_bwd_impl(g, x, stats, alpha, dres, dx, partials, M, c, OCTIC_BF16, stream, rs, rows_per_scale, gcast,
+                     sample_scale, rows_per_sample);
 }
 
 int octic_layernorm_d8_bwd_finish(const float* partials, int nblk, int c, float* const dalpha[5], float* dbeta,

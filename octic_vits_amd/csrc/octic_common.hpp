@@ -125,6 +125,15 @@ __device__ inline float total_from16(float v16) {  // uniform: sum over the wave
 __device__ inline float wave_total(float v) { return total_from16(sum16_from8(sum8(v))); }
 __device__ inline float wave_sum(float v) { return wave_total(v); }
 
+// A row kernel's optional sample mask as a trailing parameter pack: (const float* scale, rows per entry) under its SKIP
+// template flag, nothing otherwise - the unmasked instantiation then keeps its kernel-argument layout and its code.
+__device__ __forceinline__ const float* mask_scale() { return nullptr; }
+template <typename R> __device__ __forceinline__ const float* mask_scale(const float* s, R) { return s; }
+__device__ __forceinline__ long mask_rows() { return 1; }
+template <typename R> __device__ __forceinline__ R mask_rows(const float*, R rows) { return rows; }
+// (a row is wave-uniform in these kernels: the test becomes a scalar branch)
+__device__ __forceinline__ bool mask_live(float s) { return __builtin_amdgcn_readfirstlane(__float_as_int(s) << 1) != 0; }
+
 
 // LDS-DMA of 16 bytes per lane (global_load_lds_dwordx4) as inline asm: lane L's 16 bytes land at lds_dst + 16 L
 // (lds_dst wave-uniform).  Why not __builtin_amdgcn_global_load_lds: hipcc tracks the builtin as a pending LDS write and

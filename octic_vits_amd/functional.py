@@ -148,6 +148,7 @@ class LayerNormD8Fn(torch.autograd.Function):
         ctx.save_for_backward(x, stats, *(alpha or []))
         ctx.c, ctx.has_affine, ctx.has_beta = c, alpha is not None, beta is not None
         ctx.set_materialize_grads(False)
+        row_skip_attach(ctx, y)
         return y, xin.view_as(xin)
 
     @staticmethod
@@ -157,7 +158,9 @@ class LayerNormD8Fn(torch.autograd.Function):
             return (gres,) + (None,) * 9
         alpha = alpha if ctx.has_affine else None
         dres = None if gres is None else _c(gres.float())
-        dx, dal, dbeta = ops.layernorm_bwd(_c(g), x, stats, alpha, dres, ctx.c, want_param_grads=ctx.has_affine)
+        ns, nrps = row_skip_get(ctx, x.numel() // (8 * ctx.c))
+        dx, dal, dbeta = ops.layernorm_bwd(_c(g), x, stats, alpha, dres, ctx.c, want_param_grads=ctx.has_affine,
+                                           sample_scale=ns, rows_per_sample=nrps)
         if dal is None:
             dal = [None] * 5
         return (dx, *dal, dbeta if ctx.has_beta else None, None, None, None)
@@ -271,6 +274,7 @@ class LinearD8Fn(torch.autograd.Function):
         fused = resid is not None
         out_dtype = resid.dtype if fused else dtype
         x_in_dtype = x.dtype
+        handed = x
         if x.dtype != dtype:
             x = ops.cast_rowscale(_c(x.float()), None, 1, dtype, cin)
         x = _c(x)
@@ -289,6 +293,8 @@ class LinearD8Fn(torch.autograd.Function):
                        resid_v=rv, rs=rs32, rps=rps, cs5=cs32, sample_scale=ss_out, skip_rps=rps, dropped=dropped, dropped_rps=rps)
         ss_dx = linear_skip_scale(skip_dx, rps, M)
         z_dx = ring_skip_scale(zero_dx, rps, M) if (plain and ss_dx is None) else None
+        # zero cotangent rows in, zero dx rows out (computed or stored, every row written): the norm in front may skip them
+        row_skip_fill(handed, row_skip_scale(zero_dx, rps, M) if (plain and ss_dx is None) else None, rps, M)
         ctx.save_for_backward(x, rs32, b32, ss_dx, z_dx, *w5, *(cs32 or []))
         ctx.meta = (cin, cout, rps, dtype, fused, cs5 is not None, bias is not None, x_in_dtype, wt)
         return y
@@ -359,6 +365,7 @@ class LinearD8NormFn(torch.autograd.Function):
         ctx.meta = (cin, cout, rps, dtype, cs5 is not None, bias is not None, x_in_dtype, wt, alpha is not None,
                     beta is not None)
         ctx.set_materialize_grads(False)
+        row_skip_attach(ctx, yn)
         return y, yn
 
     @staticmethod
@@ -373,11 +380,13 @@ class LinearD8NormFn(torch.autograd.Function):
         if dyn is not None:
             dres = None if dy is None else _c(dy.float())
             gn = _c(dyn)
+            ns, nrps = row_skip_get(ctx, M)
             if ops.layernorm_bwd_cast_ok(gn, y, cout) and dtype == torch.bfloat16:
                 dy, dal_, dbeta, g = ops.layernorm_bwd_cast(gn, y, stats, alpha, dres, cout, rs32, rps,
-                                                            want_param_grads=has_affine)
+                                                            want_param_grads=has_affine, sample_scale=ns, rows_per_sample=nrps)
             else:
-                dy, dal_, dbeta = ops.layernorm_bwd(gn, y, stats, alpha, dres, cout, want_param_grads=has_affine)
+                dy, dal_, dbeta = ops.layernorm_bwd(gn, y, stats, alpha, dres, cout, want_param_grads=has_affine,
+                                                    sample_scale=ns, rows_per_sample=nrps)
             dal = dal_ if dal_ is not None else dal
         dy = _c(dy)
         if g is None:
@@ -558,6 +567,69 @@ def ring_skip_scale(rs, rps, M):
     """rs as the `dropped` mask of a ring-routed LinearD8 launch over M token rows: linear_skip_scale's conditions plus the
     switch above; None otherwise."""
     return linear_skip_scale(rs, rps, M) if RING_SKIP_DROPPED else None
+
+
+# The LayerNorm that opens a branch receives its cotangent from the branch's first GEMM (qkv or fc1), whose input gradient is
+# exactly zero in the rows of a sample the branch drops: LN'(0) = 0, so the norm's backward row pass needs neither those rows
+# of the cotangent nor the stream rows and statistics that belong to them, and the rows add nothing to the norm's parameter
+# gradients.  The same zeros make up half of what the qkv bias gradient sums.  With ROW_SKIP_DROPPED the factor travels to
+# the backward row kernels (include/octic_hip.h: octic_dense_layernorm_bwd_tail_skip, octic_layernorm_d8_bwd*_skip,
+# octic_dense_colsum_skip) - same launch shapes, same values.  Read once at import from OCTIC_ROW_SKIP (0 = off).
+def _row_skip_from_env():
+    return os.environ.get("OCTIC_ROW_SKIP", "1").strip() != "0"
+
+
+ROW_SKIP_DROPPED = _row_skip_from_env()
+
+
+def row_skip_scale(rs, rps, M, rows_to=None):
+    """rs as the sample_scale of a backward row kernel over M token rows - under exactly wgrad_skip_scale's conditions: the
+    switch is on and rs is one float32 entry per sample of rps rows on the GPU with rps * B == M; None for compact rows
+    (rows_to), the per-row factors of a ragged row tensor (rps 1), a traced value, eval and drop_path 0 (rs None)."""
+    if (not ROW_SKIP_DROPPED or rs is None or rows_to is not None or torch.compiler.is_compiling() or not rs.is_cuda
+            or rs.dtype != torch.float32 or rs.dim() != 1 or not rs.is_contiguous() or rps < 2 or rs.numel() * rps != M):
+        return None
+    return rs.detach()
+
+
+class RowSkipSlot:
+    """One-slot holder through which the first GEMM of a branch hands the branch's stochastic-depth factor BACK to the node
+    that produced its normalised input: that node runs before the factor is drawn, its backward after the consumer's forward.
+    The producer keeps the slot on its ctx and attaches it to the normalised tensor (`_octic_row_skip`); a consumer that knows
+    its input gradient is exactly zero in the rows of a dropped sample fills it in its forward (row_skip_fill); the
+    producer's backward reads it (get).  Empty - nobody called row_skip_fill, a second call, another row count - means no
+    mask.  What the slot cannot see is a reader that does NOT call row_skip_fill beside one that does (a plain torch op or
+    user code on the same normalised tensor): its cotangent rows would be added to the promised zeros and dropped.  The
+    guarantee is therefore for the paths of this package, where the normalised tensor goes to exactly one node (qkv or fc1,
+    also through `_octic_prenorm` / `_prenorm`); code that hands it to anything else sets OCTIC_ROW_SKIP=0."""
+    __slots__ = ("scale", "rps", "rows", "fills")
+
+    def __init__(self):
+        self.scale, self.rps, self.rows, self.fills = None, 0, 0, 0
+
+    def get(self, rows):
+        if self.fills != 1 or self.scale is None or self.rows != rows:
+            return None, 0
+        return self.scale, self.rps
+
+
+def row_skip_attach(ctx, yn):
+    """Producer side: a fresh slot on ctx and on the normalised tensor."""
+    ctx.row_skip = yn._octic_row_skip = RowSkipSlot()
+
+
+def row_skip_fill(x, scale, rps, rows):
+    """Consumer side: x is the tensor the node was handed; scale = row_skip_scale(...) of the branch (None voids nothing: an
+    unfilled slot already means no mask, but the visit counts - two readers of one normalised tensor sum their cotangents)."""
+    slot = getattr(x, "_octic_row_skip", None)
+    if slot is not None:
+        slot.fills += 1
+        slot.scale, slot.rps, slot.rows = scale, rps, rows
+
+
+def row_skip_get(ctx, rows):
+    slot = getattr(ctx, "row_skip", None)
+    return (None, 0) if slot is None else slot.get(rows)
 
 
 class AttnPackedFn(torch.autograd.Function):
@@ -1107,7 +1179,9 @@ def _resid_tail_fwd(ctx, x, tag, a2, wb, b, cache, tokens, g32, rs32, rps, nw, n
         nw32, nb32 = _f32(nw), _f32(nb)
         out, yn, stats = ops.dense_resid_layernorm_fwd(x2, br, g32, rs32, rps, nw32, nb32, neps, torch.bfloat16)
         ctx.set_materialize_grads(False)
-        return (out.view(x.shape), yn.view(x.shape)), (br, g32, rs32, out, stats, nw32)
+        yn = yn.view(x.shape)
+        row_skip_attach(ctx, yn)
+        return (out.view(x.shape), yn), (br, g32, rs32, out, stats, nw32)
     if rows_to is not None:
         ops.scale_residual_fwd_rows_(stream, rows_to.rowmap, x2, br, g32, rs32, rps)
         ctx.mark_dirty(stream)
@@ -1130,9 +1204,10 @@ def _resid_tail_bwd(ctx, tail, gout, gyn, want_norm):
             dres = None if gout is None else _c(gout.float()).view(out.shape)
             g2 = _c(gyn).view(out.shape)
             if LN_TAIL_FUSED and ops.dense_ln_bwd_tail_ok(g2, br, out.shape[-1]):
+                ns, nrps = row_skip_get(ctx, g2.shape[0])
                 gout, dnw, dnb, gbr, dgamma, colsum = ops.dense_layernorm_bwd_tail(
                     g2, out, nw32, stats, dres, br, g32, rs32, rps, want_param_grads=want, want_gamma=has_gamma,
-                    want_colsum=has_b)
+                    want_colsum=has_b, sample_scale=ns, rows_per_sample=nrps)
             else:
                 gout, dnw, dnb = ops.dense_layernorm_bwd(g2, out, nw32, stats, dres, want_param_grads=want)
             dnw, dnb = (dnw if has_nw else None), (dnb if has_nb else None)
@@ -1166,20 +1241,25 @@ class DenseLinearNTFn(torch.autograd.Function):
         ds = dense_skip_scale(rs, rps, x2.shape[0])
         y = _gemm_fwd(tag, x2, wb, b, cache, "plain", _tok(x.shape), ds, rps)
         ss = wgrad_skip_scale(rs, rps, x2.shape[0])
+        # zero cotangent rows in (the attention backward of dO = 0), zero input-gradient rows out: the bias column sums and the
+        # backward of the norm that produced x may skip them
+        rk = row_skip_scale(rs, rps, x2.shape[0])
+        row_skip_fill(x, rk, rps, x2.shape[0])
         ctx.rps = rps
-        ctx.save_for_backward(x2, wb, wt, ss, ds)  # wt is None unless the input gradient is routed to the HIP kernel
+        ctx.save_for_backward(x2, wb, wt, ss, ds, rk)  # wt is None unless the input gradient is routed to the HIP kernel
         ctx.meta = (b is not None, x.dtype, x.shape, tag)
         return y.view(*x.shape[:-1], wb.shape[0])
 
     @staticmethod
     def backward(ctx, gy):
-        x2, wb, wt, ss, ds = ctx.saved_tensors
+        x2, wb, wt, ss, ds, rk = ctx.saved_tensors
         has_b, x_dtype, x_shape, tag = ctx.meta
         g2 = _c(gy).reshape(-1, wb.shape[0])
         gx = _gemm_dgrad(g2, wt, wb, x_shape, x_dtype, ds, ctx.rps) if ctx.needs_input_grad[0] else None
         gb = None
         if has_b:
-            gb = (ops.dense_colsum(g2) if g2.is_cuda and g2.dtype == torch.bfloat16 and g2.shape[1] % 8 == 0
+            gb = (ops.dense_colsum(g2, rk, ctx.rps if rk is not None else 0)
+                  if g2.is_cuda and g2.dtype == torch.bfloat16 and g2.shape[1] % 8 == 0
                   else g2.sum(0, dtype=torch.float32))
         pair = ctx.pair
         if pair is not None and pair.pending is not None:
@@ -1263,6 +1343,9 @@ class DenseMlpFn(torch.autograd.Function):
         # fc1's outputs of a dropped sample are read by fc2 (whose output meets rs = 0) and by gradients whose dY rows are zero
         ds = dense_skip_scale(rs32, rps, y2.shape[0], rows_to)
         drps = rps if ds is not None else 0
+        # fc1's input gradient is dh W1 with dh = gelu' * (gbr W2) and gbr = rs * gamma * gout: zero rows where rs is 0, so
+        # the backward of the norm that produced y may skip them
+        row_skip_fill(y, row_skip_scale(rs32, rps, y2.shape[0], rows_to), rps, y2.shape[0])
         if "fc1" in DENSE_HIP and not any(ctx.needs_input_grad):
             # no backward will come (inference, the DINOv2 teacher): gelu(h) only, nothing kept (mode 6)
             a = ops.dense_gemm_nt(y2, w1b, 6, bias=_f32(b1), name="dense_nt_kernel<gelu-only>", tokens=_tok(y.shape),

@@ -86,10 +86,11 @@ class KernelTimer:
     def summary(self):
         out = {}
         for k, a in sorted(self._agg().items(), key=lambda kv: -kv[1]["total_us"]):
+            us = a["avg_us"] or float("inf")      # (every launch at or below the event pair's own overhead: no rate to report)
             out[k] = {"launches": a["launches"], "total_us": round(a["total_us"], 1), "avg_us": round(a["avg_us"], 2),
-                      "GBps": round(a["alg_bytes_per_launch"] / a["avg_us"] / 1e3, 1)}
+                      "GBps": round(a["alg_bytes_per_launch"] / us / 1e3, 1)}
             if a["flops_per_launch"]:
-                out[k]["TFLOPs"] = round(a["flops_per_launch"] / a["avg_us"] / 1e6, 1)
+                out[k]["TFLOPs"] = round(a["flops_per_launch"] / us / 1e6, 1)
         return out
 
 
@@ -229,8 +230,10 @@ def layernorm_fwd(x, alpha5, beta, eps, out_dtype, c, want_stats=True):
     return y, stats
 
 
-def layernorm_bwd(g, x, stats, alpha5, dres, c, want_param_grads=True):
-    """Returns (dx f32 packed, dalpha5 or None, dbeta or None).  dx = dres + LN'(g)."""
+def layernorm_bwd(g, x, stats, alpha5, dres, c, want_param_grads=True, sample_scale=None, rows_per_sample=0):
+    """Returns (dx f32 packed, dalpha5 or None, dbeta or None).  dx = dres + LN'(g).
+    sample_scale / rows_per_sample: the factor of the branch this norm opens, a promise that the rows of g are zero where it
+    is 0 (octic_layernorm_d8_bwd_skip: those rows of g, x and stats stay unread)."""
     M = x.numel() // (8 * c)
     dx = torch.empty_like(x)
     nblk = lib().octic_layernorm_d8_bwd_blocks(M)
@@ -238,9 +241,14 @@ def layernorm_bwd(g, x, stats, alpha5, dres, c, want_param_grads=True):
     gv, xv, dv = pview(g, c), pview(x, c), pview(dx, c)
     rv = pview(dres, c) if dres is not None else None
     t = KERNEL_TIMER.start()
-    check(lib().octic_layernorm_d8_bwd(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
-                                       ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
-                                       M, c, dt_code(g.dtype), _stream(x)))
+    if sample_scale is not None:
+        check(lib().octic_layernorm_d8_bwd_skip(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
+                                                ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
+                                                M, c, dt_code(g.dtype), _p(sample_scale), int(rows_per_sample), _stream(x)))
+    else:
+        check(lib().octic_layernorm_d8_bwd(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
+                                           ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
+                                           M, c, dt_code(g.dtype), _stream(x)))
     KERNEL_TIMER.stop(t, f"ln_bwd_kernel<{_DTN[g.dtype]}>", M * 8 * c * (g.element_size() + 8 + (4 if dres is not None else 0)))
     if not want_param_grads or alpha5 is None:
         return dx, None, None
@@ -285,8 +293,9 @@ def layernorm_bwd_cast_ok(g, x, c):
     return g.dtype == torch.bfloat16 and x.dtype == torch.float32 and c % 32 == 0 and c <= 160
 
 
-def layernorm_bwd_cast(g, x, stats, alpha5, dres, c, rs, rps, want_param_grads=True):
-    """layernorm_bwd that also returns bf16(rs[row // rps] * dx): (dx, dalpha5, dbeta, gcast)."""
+def layernorm_bwd_cast(g, x, stats, alpha5, dres, c, rs, rps, want_param_grads=True, sample_scale=None, rows_per_sample=0):
+    """layernorm_bwd that also returns bf16(rs[row // rps] * dx): (dx, dalpha5, dbeta, gcast).  sample_scale / rows_per_sample:
+    as in layernorm_bwd (the factor of the branch this norm opens; rs is that of the branch that ends in front of it)."""
     M = x.numel() // (8 * c)
     dx = torch.empty_like(x)
     gc = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
@@ -295,9 +304,15 @@ def layernorm_bwd_cast(g, x, stats, alpha5, dres, c, rs, rps, want_param_grads=T
     gv, xv, dv = pview(g, c), pview(x, c), pview(dx, c)
     rv = pview(dres, c) if dres is not None else None
     t = KERNEL_TIMER.start()
-    check(lib().octic_layernorm_d8_bwd_cast(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
-                                            ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
-                                            M, c, _p(rs), int(rps), _p(gc), _stream(x)))
+    if sample_scale is not None:
+        check(lib().octic_layernorm_d8_bwd_cast_skip(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
+                                                     ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv),
+                                                     _p(partials), M, c, _p(rs), int(rps), _p(gc), _p(sample_scale),
+                                                     int(rows_per_sample), _stream(x)))
+    else:
+        check(lib().octic_layernorm_d8_bwd_cast(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
+                                                ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
+                                                M, c, _p(rs), int(rps), _p(gc), _stream(x)))
     KERNEL_TIMER.stop(t, "ln_bwd_kernel<bf16>", M * 8 * c * (2 + 8 + (4 if dres is not None else 0) + 2))
     if not want_param_grads or alpha5 is None:
         return dx, None, None, gc
@@ -1032,9 +1047,11 @@ def dense_ln_bwd_tail_ok(gy, yb, d):
 
 
 def dense_layernorm_bwd_tail(gy, x, w, stats, dres, yb, gamma, rs, rps, want_param_grads=True, want_gamma=True,
-                             want_colsum=True):
+                             want_colsum=True, sample_scale=None, rows_per_sample=0):
     """dense_layernorm_bwd followed by scale_residual_bwd on its result, one row pass.
-    Returns (dx f32, dw, db, gyb bf16 = rs*gamma*dx, dgamma, gamma * colsum(rs*dx))."""
+    Returns (dx f32, dw, db, gyb bf16 = rs*gamma*dx, dgamma, gamma * colsum(rs*dx)).
+    sample_scale / rows_per_sample: the factor of the branch this norm opens, a promise that the rows of gy are zero where it
+    is 0 (octic_dense_layernorm_bwd_tail_skip: those rows of gy, x and stats stay unread, and yb's where rs is 0)."""
     d = x.shape[-1]
     rows = x.numel() // d
     dx = torch.empty_like(x)
@@ -1044,8 +1061,13 @@ def dense_layernorm_bwd_tail(gy, x, w, stats, dres, yb, gamma, rs, rps, want_par
     want2 = want_gamma or want_colsum
     p2 = torch.empty((nblk, 2, d), dtype=torch.float32, device=x.device) if want2 else None
     t = KERNEL_TIMER.start()
-    check(lib().octic_dense_layernorm_bwd_tail(_p(gy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(p1), _p(yb), _p(gamma),
-                                               _p(rs), int(rps), _p(gyb), _p(p2), rows, d, _stream(x)))
+    if sample_scale is not None:
+        check(lib().octic_dense_layernorm_bwd_tail_skip(_p(gy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(p1), _p(yb),
+                                                        _p(gamma), _p(rs), int(rps), _p(gyb), _p(p2), rows, d,
+                                                        _p(sample_scale), int(rows_per_sample), _stream(x)))
+    else:
+        check(lib().octic_dense_layernorm_bwd_tail(_p(gy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(p1), _p(yb),
+                                                   _p(gamma), _p(rs), int(rps), _p(gyb), _p(p2), rows, d, _stream(x)))
     KERNEL_TIMER.stop(t, "dense_ln_bwd_tail_kernel<bf16>", rows * d * (2 + 8 + (4 if dres is not None else 0) + 4))
     dw = db = dgamma = colsum = None
     if want_param_grads:
@@ -1194,8 +1216,9 @@ def _dense_ws(M, N, K, dev):
     return ws
 
 
-def dense_colsum(g):
-    """f32 column sums of a bf16 [rows, d] tensor (unit column stride): the bias gradient of a dense nn.Linear."""
+def dense_colsum(g, sample_scale=None, rows_per_sample=0):
+    """f32 column sums of a bf16 [rows, d] tensor (unit column stride): the bias gradient of a dense nn.Linear.
+    sample_scale / rows_per_sample: a promise that the rows of a sample are zero where its entry is 0 (they stay unread)."""
     _require_cuda(g)
     rows, d = g.shape
     if g.stride(1) != 1:
@@ -1203,7 +1226,11 @@ def dense_colsum(g):
     nblk = lib().octic_dense_gelu_blocks()
     partials = torch.empty((nblk, d), dtype=torch.float32, device=g.device)
     t = KERNEL_TIMER.start()
-    check(lib().octic_dense_colsum(_p(g), rows, d, g.stride(0), _p(partials), _stream(g)))
+    if sample_scale is not None:
+        check(lib().octic_dense_colsum_skip(_p(g), rows, d, g.stride(0), _p(partials), _p(sample_scale), int(rows_per_sample),
+                                            _stream(g)))
+    else:
+        check(lib().octic_dense_colsum(_p(g), rows, d, g.stride(0), _p(partials), _stream(g)))
     KERNEL_TIMER.stop(t, "dense_colsum_kernel", rows * d * 2)
     out = torch.empty(d, dtype=torch.float32, device=g.device)
     half = d // 2
