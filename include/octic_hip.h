@@ -873,6 +873,41 @@ int octic_seg_knn(const float* Q, int64_t ldq, int64_t n, const float* K, int64_
 int octic_seg_knn_vote(const int32_t* idx, int64_t ldi, int64_t n, const void* labels, int esize, int64_t R, int L, const int* ks,
                        int nk, uint8_t* out, void* stream);
 
+/* ---- the k-NN classification evaluation (KnnModule, dinov2/eval/knn.py:100-185) --------------------------------------------
+ * octic_knn_topk: for each of n query rows Q [n, D] (row stride ldq) the kmax key rows of K [M, D] (row stride ldk) with the
+ * LARGEST inner product (the reference's torch.mm + topk(max_k) on L2-normalised class tokens; nothing here normalises).  The
+ * similarity matrix never reaches memory.
+ * TOTAL ORDER: (similarity descending, key row index ascending): the larger similarity first, on equal similarity the lower
+ * index.  torch.topk leaves ties open; this rule is ours, the mirror of octic_seg_knn's.  A NaN similarity counts as -inf; a
+ * key at -inf is never listed, so a query with fewer than kmax listable keys ends on (-inf, -1).
+ * The similarity of a pair is a function of the two rows alone (one fmaf chain over D in a fixed order, the channel order of
+ * octic_seg_knn): idx and sim are bitwise equal for every split count and every query order or batching.  Exact f32 (f32-input
+ * MFMA), no floating-point atomics, 64-bit row offsets.  Limits: D % 64 == 0, 1 <= kmax <= OCTIC_KNN_KMAX, kmax <= M < 2^31,
+ * 0 <= splits <= 64 (anything else: OCTIC_ESHAPE before any launch).
+ * octic_knn_topk_plan: out[0] = key-axis splits of an automatic launch (1 once the query tiles fill the device), out[1] / out[2]
+ * = query rows / keys per tile, out[3] = workspace class (0: the workspace is not read, 1: it holds the splits' partial lists).
+ * octic_knn_topk_workspace_bytes: for `splits` as passed to octic_knn_topk (0 = the plan's); 256-byte aligned.
+ * idx int32 / sim f32 are [n, kmax] with row stride ldo >= kmax, sorted; columns kmax .. ldo-1 are not written.             */
+#define OCTIC_KNN_KMAX 256
+int octic_knn_topk_plan(int64_t n, int64_t M, int D, int kmax, int* out);
+int64_t octic_knn_topk_workspace_bytes(int64_t n, int64_t M, int D, int kmax, int splits);
+int octic_knn_topk(const float* Q, int64_t ldq, int64_t n, const float* K, int64_t ldk, int64_t M, int D, int kmax, int splits,
+                   int32_t* idx, float* sim, int64_t ldo, void* workspace, void* stream);
+/* The vote of KnnModule.forward (knn.py:179-184) on the lists above.  sim / idx are [n, kmax] (row stride ldi), labels DEVICE
+ * int64 [M] (the class of every key row), C >= 5 classes, inv_T = 1 / temperature (positive, finite), ks a HOST array of nk <= 8
+ * strictly ascending values in 1 .. kmax.  probas f32 [nk, n, C], every element written:
+ *   probas[i, r, c] = sum over j < ks[i] with labels[idx[r, j]] == c of w[r, j],   w[r, :] = softmax(sim[r, :kmax] * inv_T)
+ * The softmax runs over ALL kmax entries (max-subtracted, f32) and each k sums a prefix, so for k < kmax a row does not sum to 1.
+ * Every sum runs in rank order j = 0, 1, ...; no floating-point atomics.  An entry with index outside [0, M) or with a label
+ * outside [0, C) casts no vote (its weight is 0 in every sum over classes; its similarity still stands in the softmax's
+ * denominator, where an unlisted entry's -inf adds nothing).
+ * targets (nullable, DEVICE int64 [n]) with counters (DEVICE int64 [nk, 2]): the same launch ADDS, for each ks[i], the rows
+ * whose target class ranks first / among the first five to counters[i, 0] / counters[i, 1] (integer atomics).  The class
+ * ranking orders by proba descending, then class index ascending.  A target outside [0, C) counts no hit.                  */
+int octic_knn_vote(const float* sim, const int32_t* idx, int64_t ldi, int64_t n, int kmax, const int64_t* labels, int64_t M,
+                   int C, float inv_T, const int* ks, int nk, float* probas, const int64_t* targets, int64_t* counters,
+                   void* stream);
+
 /* ---- Mixup / CutMix and the BCE loss of the DeiT-III recipe (timm/data/mixup.py; deit/engine.py:47-59) -----------------
  * The host draws the per-sample parameters and uploads them as a DEVICE table of B rows; the kernels take everything about
  * the draw from it (never from arguments), so one captured launch serves every replay.  A row whose partner is outside

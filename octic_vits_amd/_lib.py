@@ -204,6 +204,12 @@ _PROTOS = {
                               c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     "octic_seg_knn_vote": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_int, c_i64, c_int, ctypes.POINTER(c_int), c_int, c_void_p,
                                    c_void_p]),
+    "octic_knn_topk_plan": (c_int, [c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_int)]),
+    "octic_knn_topk_workspace_bytes": (c_i64, [c_i64, c_i64, c_int, c_int, c_int]),
+    "octic_knn_topk": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_i64,
+                               c_void_p, c_void_p]),
+    "octic_knn_vote": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p, c_i64, c_int, c_float, ctypes.POINTER(c_int),
+                               c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "octic_mix_images": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "octic_mix_targets": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p]),
     "octic_mix_bce": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int,

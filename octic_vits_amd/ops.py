@@ -1576,6 +1576,88 @@ def seg_knn_vote(idx, labels, ks, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ classification k-NN (csrc/knn_cls.hip)
+KNN_CLS_KMAX = 256             # OCTIC_KNN_KMAX of include/octic_hip.h
+
+
+def knn_topk_plan(n, M, D, kmax):
+    """octic_knn_topk_plan: (key-axis splits, query rows per tile, keys per tile, workspace class)."""
+    answer = _lib.plan("octic_knn_topk_plan", int(n), int(M), int(D), int(kmax))
+    if answer is None:
+        check(-1)
+    return answer
+
+
+def knn_topk_workspace(n, M, D, kmax, splits, device):
+    """The workspace of knn_topk for this shape and split count (0 = the plan's): the partial lists of the splits."""
+    nbytes = lib().octic_knn_topk_workspace_bytes(n, M, D, kmax, splits)
+    check(min(nbytes, 0))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def knn_topk(Q, K, kmax, splits=0, out=None, workspace=None):
+    """The kmax rows of K with the largest inner product for every row of Q, ordered by (similarity descending, key row index
+    ascending).  Returns (idx int32, sim f32), both [n, kmax].  ``out`` may hold the two as 2-d tensors with a common row
+    stride >= kmax (columns past kmax are left alone)."""
+    n, D, ldq = _seg_rows(Q)
+    M, Dk, ldk = _seg_rows(K)
+    if Dk != D or K.device != Q.device:
+        raise ValueError("knn_topk: Q and K must have the same width and device")
+    if not 1 <= kmax <= KNN_CLS_KMAX:
+        raise ValueError(f"knn_topk: kmax must be in 1 .. {KNN_CLS_KMAX}")
+    if out is None:
+        out = (torch.empty(n, kmax, dtype=torch.int32, device=Q.device), torch.empty(n, kmax, dtype=torch.float32, device=Q.device))
+    idx, sim = out
+    ldo = idx.stride(0)
+    for o, dt in ((idx, torch.int32), (sim, torch.float32)):
+        if (o.dtype != dt or o.dim() != 2 or o.shape[0] != n or o.shape[1] < kmax or o.stride(1) != 1 or o.stride(0) != ldo
+                or o.device != Q.device):
+            raise ValueError("knn_topk: out must be (int32, f32) [n, >= kmax] rows with one common row stride")
+    if workspace is None:
+        workspace = knn_topk_workspace(n, M, D, kmax, splits, Q.device)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_knn_topk(_p(Q), ldq, n, _p(K), ldk, M, D, kmax, splits, _p(idx), _p(sim), ldo, _p(workspace), _stream(Q)))
+    # algorithmic bytes: every workgroup streams its share of the keys once per query tile, the queries once per key tile
+    qt, kt = 64, 128
+    KERNEL_TIMER.stop(t, "knn_topk_kernel", 4 * D * (M * ((n + qt - 1) // qt) + n * ((M + kt - 1) // kt)) + 8 * n * kmax,
+                      2.0 * n * M * D)
+    return idx, sim
+
+
+def knn_vote(sim, idx, labels, num_classes, inv_T, ks, out=None, targets=None, counters=None):
+    """f32 [len(ks), n, C]: probas[i, r, c] = the sum over j < ks[i] with labels[idx[r, j]] == c of softmax(sim[r] * inv_T)[j],
+    the softmax over all kmax = sim.shape[1] entries.  ks: 1 .. 8 strictly ascending values <= kmax.  With ``targets`` (int64 [n])
+    and ``counters`` (int64 [len(ks), 2]) the launch adds each k's top-1 / top-5 hits to the counters."""
+    _require_cuda(sim)
+    ks = [int(k) for k in ks]
+    C = int(num_classes)
+    if (sim.dtype != torch.float32 or idx.dtype != torch.int32 or sim.dim() != 2 or idx.shape != sim.shape or sim.stride(1) != 1
+            or idx.stride(1) != 1 or idx.stride(0) != sim.stride(0) or idx.device != sim.device):
+        raise ValueError("knn_vote: sim f32 / idx int32 must be [n, kmax] rows with one common row stride on one device")
+    n, kmax = sim.shape
+    if labels.dtype != torch.int64 or labels.dim() != 1 or not labels.is_contiguous() or labels.device != sim.device:
+        raise ValueError("knn_vote: labels must be a contiguous int64 [M] on the device of sim")
+    if not ks or len(ks) > 8 or not 1 <= kmax <= KNN_CLS_KMAX:
+        raise ValueError(f"knn_vote: 1 .. 8 values of k, kmax in 1 .. {KNN_CLS_KMAX}")
+    if (targets is None) != (counters is None):
+        raise ValueError("knn_vote: targets and counters go together")
+    if targets is not None and (targets.dtype != torch.int64 or targets.numel() != n or not targets.is_contiguous()
+                                or targets.device != sim.device or counters.dtype != torch.int64
+                                or tuple(counters.shape) != (len(ks), 2) or not counters.is_contiguous()
+                                or counters.device != sim.device):
+        raise ValueError("knn_vote: targets int64 [n] and counters int64 [len(ks), 2], contiguous, on the device of sim")
+    if out is None:
+        out = torch.empty(len(ks), n, C, dtype=torch.float32, device=sim.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (len(ks), n, C) or not out.is_contiguous() or out.device != sim.device:
+        raise ValueError("knn_vote: out must be a contiguous f32 [len(ks), n, C]")
+    if n:
+        t = KERNEL_TIMER.start()
+        check(lib().octic_knn_vote(_p(sim), _p(idx), sim.stride(0), n, kmax, _p(labels), labels.numel(), C, float(inv_T),
+                                   (ctypes.c_int * len(ks))(*ks), len(ks), _p(out), _p(targets), _p(counters), _stream(sim)))
+        KERNEL_TIMER.stop(t, "knn_vote_kernel", n * (16 * kmax + 4 * len(ks) * C))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ Mixup / CutMix + BCE (csrc/mixup.hip)
 def _mix_table(table, B):
     _require_cuda(table)
