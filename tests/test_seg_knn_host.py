@@ -48,7 +48,11 @@ def test_argument_refusals_return_their_codes_without_a_launch():
     # k out of range
     assert knn(L, kmax=0) == ESHAPE and knn(L, kmax=33, ldo=40) == ESHAPE
     # fewer keys than neighbours, no rows, too many keys, unknown metric or split count
-    assert knn(L, M=29) == ESHAPE and knn(L, M=30) != ESHAPE
+    # (M == kmax is served: asked of the queries that share octic_seg_knn's shape check and cannot launch - on a machine WITH a
+    # device the entry point itself would run the kernel on the placeholder pointers)
+    assert knn(L, M=29) == ESHAPE and L.octic_seg_knn_workspace_bytes(100, 29, 64, 30, 3, 1) == ESHAPE
+    assert L.octic_seg_knn_workspace_bytes(100, 30, 64, 30, 3, 1) == 256
+    assert L.octic_seg_knn_plan(100, 30, 64, 30, 3, (ctypes.c_int * 4)()) == OK
     assert knn(L, n=0) == ESHAPE and knn(L, M=2 ** 31) == ESHAPE and knn(L, metrics=0) == ESHAPE and knn(L, metrics=4) == ESHAPE
     assert knn(L, splits=-1) == ESHAPE and knn(L, splits=65) == ESHAPE
     # strides below the row width
