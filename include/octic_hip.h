@@ -979,6 +979,74 @@ int64_t octic_augment_workspace_bytes(int B, int H, int W);
 int octic_augment_u8(const uint8_t* src, void* dst, int dtype_out, const octic_aug_row* table, float mean0, float mean1,
                      float mean2, float std0, float std1, float std2, int B, int H, int W, void* workspace, void* stream);
 
+/* ---- DINOv2's multi-crop augmentation on ragged uint8 images (dinov2/data/augmentations.py: DataAugmentationDINO) ---------
+ * Bicubic RandomResizedCrop, RandomHorizontalFlip, RandomApply(ColorJitter with hue), RandomGrayscale, torchvision's
+ * GaussianBlur(9), RandomSolarize, ToTensor and Normalize.  The host draws everything and uploads one row per crop (all crops
+ * of one call have one output size) plus a pool of integer resampling coefficients; the kernels take everything about the
+ * draw from them.  Apart from the blur the arithmetic is Pillow's, rounding for rounding, with a uint8 image between all stages:
+ *   resize     img.crop(box).resize((S, S), BICUBIC), Pillow's 8-bit two-pass resample.  Per axis, crop length n: scale = n / S,
+ *              fs = max(scale, 1), support = 2 fs, taps = 2 ceil(support) + 1; for output x: center = (x + 0.5) scale,
+ *              xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), n),
+ *              w_j = bicubic((j + xmin - center + 0.5) / fs), a = -0.5: ((a+2)t - (a+3)) t t + 1 for t < 1,
+ *              (((t-5)t + 8)t - 4) a for t < 2; float64, normalised by their sum; k_j = (int)(w_j 2^22 +- 0.5), away from
+ *              zero.  out = clamp((sum_j k_j p[xmin + j] + 2^21) >> 22, 0, 255) in int32.  Horizontal pass first, to uint8, the
+ *              vertical pass on that.  A pass with n == S is the identity (the host gives it one tap of 2^22).  The HOST
+ *              computes xmin, the count and k; per crop and axis the pool holds int32 bounds[S][2] = (xmin, count) and then
+ *              k[S][taps] at the row's offset.  The kernels do integer sums only; bounds are clamped to the crop.
+ *   flip       x -> S-1-x (on the resized crop)
+ *   jitter     order[0..3] in turn; -1, an entry outside 0..3 or a repeated one is skipped.  0 brightness, 1 contrast,
+ *              2 saturation: v = trunc(clip(deg + f (v - deg), 0, 255)) in f32, product and sum rounded separately, deg = 0,
+ *              (2 S + N) / (2 N) in integers (S = the sum of L over the whole crop as it is at that point, N its pixels), the
+ *              pixel's L.  3 hue: Pillow's convert("HSV"), H = (H + hue_shift) & 255, convert("RGB"), with
+ *              RGB->HSV: V = max; max == min: H = S = 0; else in f32 cr = max - min, s = cr / max, rc, gc, bc = (max - c) / cr,
+ *                h = bc - gc (f32) if r == max, else (float)(2.0 + rc - bc) if g == max, else (float)(4.0 + gc - rc) (double),
+ *                h = (float)fmod(h / 6.0 + 1.0, 1.0) (double), H = clip8((int)(h 255.0)), S = clip8((int)(s 255.0)) (double)
+ *              HSV->RGB: S == 0: grey V; else hf = (float)H 6.0 / 255.0 (double), i = floor(hf), f = (float)(hf - i),
+ *                fs = (float)(S / 255.0), p = round(V (1 - fs)), q = round(V (1 - fs f)), t = round(V (1 - fs (1 - f))) in
+ *                double with C round(), clip8; i % 6 selects (V,t,p) (q,V,p) (p,V,t) (p,q,V) (t,p,V) (V,p,q)
+ *   grayscale  L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 in all three channels
+ *   blur       torchvision's gaussian_blur(9, sigma) of a uint8 image: f32, reflect padding 4, the host's nine f32 weights
+ *              blur_w (x = linspace(-4, 4, 9), pdf = exp(-0.5 (x / sigma)^2), pdf / pdf.sum(), all f32, computed as
+ *              torchvision does).  Separable: a = 0, then a = fmaf(blur_w[j], p[x - 4 + j], a) for j = 0..8 along x, the f32
+ *              results unrounded, the same along y over those, then rintf (half to even) and clip8.  (torchvision's own
+ *              summation order is its convolution library's; the results agree wherever the exact sum is not within the f32
+ *              accumulation error, about 1.2e-3, of a rounding tie.)
+ *   solarize   v < 128 ? v : 255 - v
+ *   output     (v / 255 - mean[c]) / std[c], two correctly rounded f32 divisions                                          */
+typedef struct {
+  int64_t src_offset;                      /* byte offset of the source image [src_h, src_w, 3] in `data`  */
+  int32_t src_h, src_w;
+  int32_t top, left, h, w;                 /* the crop box inside the source                               */
+  int32_t flip;                            /* != 0: mirrored along x                                       */
+  int32_t hcoef, htaps, vcoef, vtaps;      /* offsets (int32 words) of the two coefficient blocks in the pool, taps per output */
+  int32_t order[4];                        /* ColorJitter's ops in application order: 0 brightness, 1 contrast, 2 saturation, 3 hue, -1 skip */
+  float brightness, contrast, saturation;  /* the blend factors                                            */
+  int32_t hue_shift;                       /* (uint8)(int)(hue_factor 255)                                 */
+  int32_t gray, blur, solarize;            /* != 0: applied                                                */
+  float blur_w[9];                         /* the 1-D Gaussian weights (blur)                              */
+  int32_t pad[7];
+} octic_dino_row;                          /* 160 bytes */
+/* HOST code, no launch: the coefficient block of one axis as stated above, crop length n -> S: bounds[S][2] and k[S][taps]
+ * (unused taps 0).  taps must be 1 for n == S and 2 ceil(2 max(n / S, 1)) + 1 otherwise (at most 2048), else OCTIC_ESHAPE.   */
+int octic_dino_resize_coeffs(int n, int S, int taps, int32_t* bounds, int32_t* k);
+/* the most taps per output the resize kernel holds for output size S (its uint8 rows live in LDS); OCTIC_ESHAPE unless
+ * 5 <= S <= 4096.  The host refuses sources whose 2 ceil(2 max(n / S, 1)) + 1 exceeds it.                               */
+int octic_dino_resize_max_taps(int S);
+/* crops [N, S, S, 3] (uint8) = the resized, flipped crops of the rows.  data: the uint8 source images back to back
+ * (data_bytes in all), left untouched; coef: the pool (coef_len int32 words).  A row whose image, box or coefficient blocks do
+ * not lie inside data / the source / the pool gives an all-zero crop.  rows 8-byte aligned.  Bitwise reproducible.        */
+int octic_dino_resize_u8(const uint8_t* data, int64_t data_bytes, const octic_dino_row* rows, const int32_t* coef,
+                         int64_t coef_len, int N, int S, uint8_t* crops, void* stream);
+/* bytes of the workspace of octic_dino_color_u8 (per-tile sums of L, and the jittered uint8 crops); OCTIC_ESHAPE for N < 1,
+ * H or W < 5 (the blur's reflect padding) or H W 3 >= 2^31                                                                */
+int64_t octic_dino_color_workspace_bytes(int N, int H, int W);
+/* The chain behind the resize and flip on uint8 crops [N, H, W, 3], left untouched: jitter, grayscale, blur, solarize, output.
+ * The geometry fields of the rows are not read.  dst, by dtype_out: OCTIC_F32 - f32 [N, 3, H, W], normalised; OCTIC_U8 - uint8
+ * [N, H, W, 3], the pixels in front of ToTensor.  crops, dst and workspace must not overlap (OCTIC_ESHAPE).  Integer sums
+ * across pixels, no atomics: bitwise reproducible, and independent of a crop's place in the batch.                        */
+int octic_dino_color_u8(const uint8_t* crops, void* dst, int dtype_out, const octic_dino_row* rows, float mean0, float mean1,
+                        float mean2, float std0, float std1, float std2, int N, int H, int W, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,8 @@ contract is in include/octic_hip.h; tests/golden/augment_numpy.py restates it, t
 
 THE CROP STAYS ON THE HOST: decoding, ``RandomResizedCropAndInterpolation`` and the sampler (``RASampler``) work on the
 variable-size source image; what they yield - uint8 HWC crops of one size - is this module's input.  Not built: ``--src`` (the
-simple random crop), hue jitter, the DINOv2 augmentations.
+simple random crop) and hue jitter in this recipe.  The DINOv2 multi-crop augmentation, with the bicubic resized crop and hue
+on the device, is ``octic_vits_amd/dino_augment.py``.
 
 ``ThreeAugment.draw`` consumes the random streams exactly as the reference pipeline does for B samples in turn, per sample:
 

@@ -1763,3 +1763,89 @@ def augment_u8(src, table, mean, std, dst, workspace=None):
                                  _p(workspace), _stream(src)))
     KERNEL_TIMER.stop(t, "augment_kernel", 2 * src.numel() + dst.numel() * dst.element_size())
     return dst
+
+
+# ------------------------------------------------------------------------- DINOv2 multi-crop augmentation (csrc/dino_augment.hip)
+DINO_ROW_WORDS = 40          # sizeof(octic_dino_row) / 4
+
+
+def dino_resize_coeffs(n, S, taps):
+    """Host: Pillow's 8-bit bicubic coefficients of one axis, crop length n -> S, as numpy (bounds int32 [S, 2], k int32 [S, taps])."""
+    import numpy as np
+    bounds, k = np.empty((S, 2), np.int32), np.empty((S, taps), np.int32)
+    check(lib().octic_dino_resize_coeffs(int(n), int(S), int(taps), bounds.ctypes.data, k.ctypes.data))
+    return bounds, k
+
+
+def dino_resize_max_taps(S):
+    """The most taps per output pixel octic_dino_resize_u8 holds at output size S."""
+    n = lib().octic_dino_resize_max_taps(int(S))
+    if n < 0:
+        check(int(n))
+    return n
+
+
+def dino_color_workspace(N, H, W, device):
+    """The int32 workspace octic_dino_color_u8 needs for [N, H, W, 3] crops."""
+    n = lib().octic_dino_color_workspace_bytes(int(N), int(H), int(W))
+    if n < 0:
+        check(int(n))
+    return torch.empty((n + 3) // 4, dtype=torch.int32, device=device)
+
+
+def _dino_rows_ok(rows, N, what):
+    _require_cuda(rows)
+    if rows.dtype != torch.int32 or tuple(rows.shape) != (N, DINO_ROW_WORDS) or not rows.is_contiguous():
+        raise ValueError(f"{what}: the rows must be a contiguous int32 [{N}, {DINO_ROW_WORDS}] tensor (DinoAugParams.tables())")
+
+
+def dino_resize_u8(data, rows, coef, S, crops):
+    """crops [N, S, S, 3] (uint8) = the resized, flipped crops the device rows describe, cut from the packed uint8 images
+    `data` with the int32 coefficient pool `coef`."""
+    for t in (data, coef, crops):
+        _require_cuda(t)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise ValueError("dino_resize_u8: data must be a contiguous 1-D uint8 tensor (PackedImages.data)")
+    if coef.dtype != torch.int32 or coef.dim() != 1 or not coef.is_contiguous():
+        raise ValueError("dino_resize_u8: the coefficient pool must be a contiguous 1-D int32 tensor")
+    N = crops.shape[0]
+    if crops.dtype != torch.uint8 or tuple(crops.shape) != (N, S, S, 3) or not crops.is_contiguous():
+        raise ValueError(f"dino_resize_u8: the crops must be a contiguous uint8 [N, {S}, {S}, 3] tensor")
+    _dino_rows_ok(rows, N, "dino_resize_u8")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_dino_resize_u8(_p(data), data.numel(), _p(rows), _p(coef), coef.numel(), N, int(S), _p(crops), _stream(data)))
+    KERNEL_TIMER.stop(t, "dino_resize_kernel", data.numel() + crops.numel())
+    return crops
+
+
+def dino_color_u8(crops, rows, mean, std, dst, workspace=None):
+    """dst = the uint8 crops [N, H, W, 3] through ColorJitter, grayscale, blur and solarize as the device rows say; dst is f32
+    [N, 3, H, W] (normalised) or uint8 [N, H, W, 3] (the pixels in front of ToTensor)."""
+    _require_cuda(crops)
+    _require_cuda(dst)
+    if crops.dim() != 4 or crops.shape[3] != 3 or crops.dtype != torch.uint8 or not crops.is_contiguous():
+        raise ValueError("dino_color_u8: crops must be a contiguous uint8 [N, H, W, 3] tensor")
+    N, H, W, _ = crops.shape
+    _dino_rows_ok(rows, N, "dino_color_u8")
+    if dst.dtype == torch.float32:
+        want, code = (N, 3, H, W), _lib.F32
+    elif dst.dtype == torch.uint8:
+        want, code = (N, H, W, 3), _lib.U8
+    else:
+        raise TypeError(f"dino_color_u8: the output is float32 [N, 3, H, W] or uint8 [N, H, W, 3], got {dst.dtype}")
+    if tuple(dst.shape) != want or not dst.is_contiguous():
+        raise ValueError(f"dino_color_u8: the {dst.dtype} output must be a contiguous {want} tensor")
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("dino_color_u8: mean and std take three values each")
+    need = lib().octic_dino_color_workspace_bytes(N, H, W)
+    if need < 0:
+        check(int(need))
+    if workspace is None:
+        workspace = dino_color_workspace(N, H, W, crops.device)
+    elif workspace.dtype != torch.int32 or not workspace.is_cuda or workspace.numel() * 4 < need:
+        raise ValueError("dino_color_u8: the workspace must be an int32 GPU tensor of dino_color_workspace(N, H, W)'s size")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_dino_color_u8(_p(crops), _p(dst), code, _p(rows), *[float(v) for v in mean], *[float(v) for v in std],
+                                    N, H, W, _p(workspace), _stream(crops)))
+    KERNEL_TIMER.stop(t, "dino_color_kernels", 3 * crops.numel() + dst.numel() * dst.element_size())
+    return dst
