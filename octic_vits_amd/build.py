@@ -24,7 +24,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=False):
     os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
-    headers = [os.path.join(CSRC, "octic_common.hpp"), os.path.join(CSRC, "attn_common.hpp"), os.path.join(CSRC, "attn80_common.hpp"), os.path.join(CSRC, "gemm_args.hpp"),
+    headers = [os.path.join(CSRC, "octic_common.hpp"), os.path.join(CSRC, "attn_common.hpp"), os.path.join(CSRC, "attn80_common.hpp"), os.path.join(CSRC, "gemm_args.hpp"), os.path.join(CSRC, "knn_common.hpp"),
                os.path.join(HERE, "..", "include", "octic_hip.h")]
     objs, jobs = [], []
     for src in SOURCES:

@@ -1481,6 +1481,26 @@ def seg_confusion(labels, pred, ignore, counts):
     return counts
 
 
+# ------------------------------------------------------------------------------------------ the two k-NN searches (csrc/knn_common.hpp)
+def _knn_workspace(nbytes, device):
+    """The workspace of the byte count that a *_workspace_bytes query answered (a negative answer is its error code)."""
+    check(min(nbytes, 0))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _knn_out_ok(o, dtype, n, kmax, ldo, device):
+    """o is a ``dtype`` [n, >= kmax] tensor of rows with stride ldo on ``device``."""
+    return (o.dtype == dtype and o.dim() == 2 and o.shape[0] == n and o.shape[1] >= kmax and o.stride(1) == 1 and o.stride(0) == ldo
+            and o.device == device)
+
+
+def _knn_stream_bytes(plan, n, M, D):
+    """Algorithmic bytes of the plan's tiles: every workgroup streams its share of the keys once per query tile, the queries
+    once per key tile."""
+    _, qt, kt, _ = plan
+    return 4 * D * (M * ((n + qt - 1) // qt) + n * ((M + kt - 1) // kt))
+
+
 # ------------------------------------------------------------------------------------------ segmentation k-NN (csrc/segknn.hip)
 KNN_L2, KNN_COSINE, KNN_BOTH = 1, 2, 3
 KNN_KMAX = 32
@@ -1496,9 +1516,7 @@ def seg_knn_plan(n, M, D, kmax, metrics=KNN_BOTH):
 
 def seg_knn_workspace(n, M, D, kmax, metrics, splits, device):
     """The workspace of seg_knn for this shape and split count (0 = the plan's): the partial lists of the splits."""
-    nbytes = lib().octic_seg_knn_workspace_bytes(n, M, D, kmax, metrics, splits)
-    check(min(nbytes, 0))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _knn_workspace(lib().octic_seg_knn_workspace_bytes(n, M, D, kmax, metrics, splits), device)
 
 
 def seg_rownorms(X):
@@ -1539,8 +1557,7 @@ def seg_knn(Q, K, qnorm, knorm, skip, kmax, metrics=KNN_BOTH, splits=0, out=None
             if metrics & bit:
                 raise ValueError("seg_knn: out lacks a tensor of a metric that is asked for")
             continue
-        if (o.dtype != dt or o.dim() != 2 or o.shape[0] != n or o.shape[1] < kmax or o.stride(1) != 1 or o.stride(0) != ldo
-                or o.device != Q.device):
+        if not _knn_out_ok(o, dt, n, kmax, ldo, Q.device):
             raise ValueError("seg_knn: out tensors must be int32 / f32 [n, >= kmax] rows with one common row stride")
     if workspace is None:
         workspace = seg_knn_workspace(n, M, D, kmax, metrics, splits, Q.device)
@@ -1548,9 +1565,7 @@ def seg_knn(Q, K, qnorm, knorm, skip, kmax, metrics=KNN_BOTH, splits=0, out=None
     check(lib().octic_seg_knn(_p(Q), ldq, n, _p(K), ldk, M, D, _p(qnorm), _p(knorm), _p(skip), kmax, metrics, splits,
                               *[_p(o) for o in out], ldo, _p(workspace), _stream(Q)))
     nl = 2 if metrics == KNN_BOTH else 1
-    # algorithmic bytes: every workgroup streams its share of the keys once per query tile, the queries once per key tile
-    qt, kt = 128, 128
-    KERNEL_TIMER.stop(t, f"seg_knn_kernel<{metrics}>", 4 * D * (M * ((n + qt - 1) // qt) + n * ((M + kt - 1) // kt)) + 8 * nl * n * kmax,
+    KERNEL_TIMER.stop(t, f"seg_knn_kernel<{metrics}>", _knn_stream_bytes(seg_knn_plan(n, M, D, kmax, metrics), n, M, D) + 8 * nl * n * kmax,
                       2.0 * n * M * D)
     return tuple(out)
 
@@ -1590,9 +1605,7 @@ def knn_topk_plan(n, M, D, kmax):
 
 def knn_topk_workspace(n, M, D, kmax, splits, device):
     """The workspace of knn_topk for this shape and split count (0 = the plan's): the partial lists of the splits."""
-    nbytes = lib().octic_knn_topk_workspace_bytes(n, M, D, kmax, splits)
-    check(min(nbytes, 0))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _knn_workspace(lib().octic_knn_topk_workspace_bytes(n, M, D, kmax, splits), device)
 
 
 def knn_topk(Q, K, kmax, splits=0, out=None, workspace=None):
@@ -1610,17 +1623,13 @@ def knn_topk(Q, K, kmax, splits=0, out=None, workspace=None):
     idx, sim = out
     ldo = idx.stride(0)
     for o, dt in ((idx, torch.int32), (sim, torch.float32)):
-        if (o.dtype != dt or o.dim() != 2 or o.shape[0] != n or o.shape[1] < kmax or o.stride(1) != 1 or o.stride(0) != ldo
-                or o.device != Q.device):
+        if not _knn_out_ok(o, dt, n, kmax, ldo, Q.device):
             raise ValueError("knn_topk: out must be (int32, f32) [n, >= kmax] rows with one common row stride")
     if workspace is None:
         workspace = knn_topk_workspace(n, M, D, kmax, splits, Q.device)
     t = KERNEL_TIMER.start()
     check(lib().octic_knn_topk(_p(Q), ldq, n, _p(K), ldk, M, D, kmax, splits, _p(idx), _p(sim), ldo, _p(workspace), _stream(Q)))
-    # algorithmic bytes: every workgroup streams its share of the keys once per query tile, the queries once per key tile
-    qt, kt = 64, 128
-    KERNEL_TIMER.stop(t, "knn_topk_kernel", 4 * D * (M * ((n + qt - 1) // qt) + n * ((M + kt - 1) // kt)) + 8 * n * kmax,
-                      2.0 * n * M * D)
+    KERNEL_TIMER.stop(t, "knn_topk_kernel", _knn_stream_bytes(knn_topk_plan(n, M, D, kmax), n, M, D) + 8 * n * kmax, 2.0 * n * M * D)
     return idx, sim
 
 
