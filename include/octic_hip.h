@@ -596,6 +596,22 @@ int octic_dense_colsum(const void* g, int64_t rows, int d, int64_t ld, float* pa
  * read and zeros take their place in the same sums.                                                                  */
 int octic_dense_colsum_skip(const void* g, int64_t rows, int d, int64_t ld, float* partials, const float* sample_scale,
                             int64_t rows_per_sample, void* stream);
+/* The gate of DINOv2's SwiGLU FFN (dinov2/layers/swiglu_ffn.py:29-33: x1, x2 = w12(x).chunk(2, -1); silu(x1) * x2), bf16 with
+ * f32 arithmetic.  x12: [rows, 2H], row stride ld12 elements - columns [0, H) the gate x1, [H, 2H) the value x2.
+ * octic_swiglu_fwd: a[r, j] = bf16(silu(x12[r, j]) * x12[r, H + j]), j < H; a: [rows, H], row stride lda.
+ * octic_swiglu_bwd: with s = sigmoid(x1) and ga [rows, H] (row stride ldg) the cotangent of a,
+ *   dx12[r, j] = bf16(ga * x2 * s * (1 + x1 * (1 - s))),  dx12[r, H + j] = bf16(ga * x1 * s)   (dx12: row stride ldd)
+ *   and, when partials != NULL, octic_swiglu_blocks() slabs [2H] of f32 column sums of the STORED bf16 dx12 (what the GEMMs
+ *   downstream see), in a fixed order: reduce with octic_dense_finish(partials, blocks, H, db, db + H, NULL) - the bias
+ *   gradient of w12, in w12.bias order.
+ * Refused before any launch: H <= 0, H % 8 != 0 or a row stride shorter than its row (OCTIC_ESHAPE); a row stride that is
+ * no multiple of 8 or a base pointer off 16 bytes (OCTIC_EALIGN); a NULL operand (OCTIC_ENULL).  rows == 0: OCTIC_OK, no
+ * launch.  sigmoid is 1 / (1 + exp(-x)): finite inputs anywhere in bf16's range give finite or correctly infinite results,
+ * never NaN; for x1 >= 17 it is exactly 1, so a == bf16(x1 * x2), dx1 == bf16(ga * x2), dx2 == bf16(ga * x1) bit for bit. */
+int octic_swiglu_blocks(void);
+int octic_swiglu_fwd(const void* x12, int64_t ld12, void* a, int64_t lda, int64_t rows, int H, void* stream);
+int octic_swiglu_bwd(const void* x12, int64_t ld12, const void* ga, int64_t ldg, void* dx12, int64_t ldd, float* partials,
+                     int64_t rows, int H, void* stream);
 int octic_scale_residual_fwd(const float* x, const void* y, int y_dtype, const float* gamma, const float* rs,
                              int64_t rows_per_scale, float* out, int64_t rows, int d, void* stream);
 int octic_scale_residual_bwd(const float* gout, const void* y, int y_dtype, const float* gamma, const float* rs,

@@ -99,6 +99,9 @@ _PROTOS = {
     "octic_dense_finish_batch": (c_int, [c_void_p, c_int, c_void_p]),
     "octic_dense_gelu_blocks": (c_int, []),
     "octic_dense_gelu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p]),
+    "octic_swiglu_blocks": (c_int, []),
+    "octic_swiglu_fwd": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_void_p]),
+    "octic_swiglu_bwd": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_void_p]),
     "octic_dense_layernorm_fwd_rows": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float,
                                                c_void_p, c_void_p, c_void_p]),
     "octic_dense_layernorm_bwd_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,

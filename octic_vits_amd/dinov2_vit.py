@@ -1,7 +1,8 @@
 """The standard DINOv2 ViT (``DinoVisionTransformer``, dinov2/models/vision_transformer.py:43-339) on the HIP engine: the
 baseline of the octic DINOv2 models, ``vit_large`` / ``vit_huge`` (:342-367) next to ``hybrid_vit_large`` /
 ``hybrid_vit_huge`` (configs train/vitl16.yaml, train/vith16.yaml).  Same constructor keywords, methods, output
-dictionaries and ``state_dict`` keys as the reference for ``ffn_layer="mlp"`` and ``block_chunks=0``.
+dictionaries and ``state_dict`` keys as the reference for ``ffn_layer="mlp"`` / ``"swiglu"`` / ``"swiglufused"`` (the
+SwiGLU FFN of ViT-g/14: vit.SwiGLUFFNFused) and ``block_chunks=0``.
 
 Token assembly follows ``dinov2_models.OcticDinoVisionTransformer.prepare_tokens_with_masks``: without masks or register
 tokens everything (bias, positional rows, class row + class position) is fused into the lift GEMM's epilogue; otherwise the
@@ -46,8 +47,18 @@ class DinoVisionTransformer(nn.Module):
                  init_values=None, embed_layer=PatchEmbed, act_layer=nn.GELU, block_fn=Block, ffn_layer="mlp",
                  block_chunks=0, num_register_tokens=0, interpolate_antialias=False, interpolate_offset=0.1):
         super().__init__()
-        if ffn_layer != "mlp":
-            raise NotImplementedError(f"DinoVisionTransformer: ffn_layer={ffn_layer!r} (only 'mlp' runs on the engine)")
+        if ffn_layer in ("swiglu", "swiglufused"):          # vision_transformer.py:124-126: both names build the fused width
+            if embed_dim < 128:
+                # ops.dense_gemm_ok wants N >= 128 and K >= 128: below that width none of the FFN's four GEMMs (K = embed_dim
+                # forward of w12 and backward of w3, N = embed_dim the other way) can run on csrc/dense_gemm.hip in either
+                # direction, and no config is that narrow - such a model stays refused, as before the SwiGLU FFN existed
+                raise NotImplementedError(f"DinoVisionTransformer: ffn_layer={ffn_layer!r} needs embed_dim >= 128 (got "
+                                          f"{embed_dim}): narrower, no GEMM of the FFN fits the engine's dense kernels")
+            from .vit import SwiGLUFFNFused
+            block_fn = partial(block_fn, ffn_layer=SwiGLUFFNFused)
+        elif ffn_layer != "mlp":
+            raise NotImplementedError(f"DinoVisionTransformer: ffn_layer={ffn_layer!r} (only 'mlp', 'swiglu' and "
+                                      "'swiglufused' run on the engine)")
         if block_chunks > 0:
             raise NotImplementedError("DinoVisionTransformer: block_chunks > 0 (FSDP chunking) is not supported")
         norm_layer = partial(nn.LayerNorm, eps=1e-6)
@@ -184,7 +195,7 @@ class DinoVisionTransformer(nn.Module):
         bf = torch.bfloat16
         for b in self.blocks:
             if not isinstance(b, vit.NestedTensorBlock) or not isinstance(b.attn, vit.Attention) \
-                    or not isinstance(b.mlp, vit.Mlp) or not b.mlp.fusable():
+                    or not isinstance(b.mlp, (vit.Mlp, vit.SwiGLUFFN)) or not b.mlp.fusable():
                 return False
             if any(type(n) is not nn.LayerNorm or tuple(n.normalized_shape) != (d,) or d % 4 or d > 2048
                    for n in (b.norm1, b.norm2)):
@@ -284,6 +295,34 @@ class DinoVisionTransformer(nn.Module):
 def _refuse_pretrained(pretrained):
     if pretrained:
         raise RuntimeError("no pretrained weights are bundled (load a reference checkpoint with load_state_dict)")
+
+
+def _dino_vit(embed_dim, depth, num_heads, patch_size, num_register_tokens, pretrained, kwargs):
+    _refuse_pretrained(pretrained)
+    return DinoVisionTransformer(patch_size=patch_size, embed_dim=embed_dim, depth=depth, num_heads=num_heads, mlp_ratio=4,
+                                 block_fn=partial(Block, attn_class=MemEffAttention),
+                                 num_register_tokens=num_register_tokens, **kwargs)
+
+
+# The factories the reference's hub code asks for by name (hub/backbones.py:42: vits.__dict__[arch_name]) beside the two its
+# models file defines; the numbers are upstream DINOv2's (ViT-S/14, ViT-B/14, ViT-g/14 - the last with ffn_layer="swiglufused").
+@register_model
+def vit_small(patch_size=16, num_register_tokens=0, pretrained=False, **kwargs):
+    return _dino_vit(384, 12, 6, patch_size, num_register_tokens, pretrained, kwargs)
+
+
+@register_model
+def vit_base(patch_size=16, num_register_tokens=0, pretrained=False, **kwargs):
+    return _dino_vit(768, 12, 12, patch_size, num_register_tokens, pretrained, kwargs)
+
+
+@register_model
+def vit_giant2(patch_size=16, num_register_tokens=0, pretrained=False, **kwargs):
+    """ViT-g/14's backbone: embed_dim 1536, 40 blocks, 24 heads of 64; with ffn_layer="swiglufused" the FFN's hidden width is
+    4096 (w12 [8192, 1536], w3 [1536, 4096]).  That is the only FFN ViT-g/14 was published with, so it is this factory's default
+    (the hub code passes it explicitly); ffn_layer="mlp" still builds the plain MLP."""
+    kwargs.setdefault("ffn_layer", "swiglufused")
+    return _dino_vit(1536, 40, 24, patch_size, num_register_tokens, pretrained, kwargs)
 
 
 @register_model

@@ -20,6 +20,7 @@ Python, but opaque to Dynamo - every ctypes call is a graph break.  The ops belo
                  torch.ops.octic.dense_mlp / _bwd         timm Mlp: fc1 + GELU + fc2, gelu'(h) kept as a factor (round 6)   deit/vit.py:131-134
                  torch.ops.octic.attn_qkv / _bwd          SDPA on the fused [B,T,3,H,hd] projection   deit/vit.py:38-45
                  torch.ops.octic.scale_residual / _bwd    x + drop_path(gamma * y)      deit/vit.py:131-134
+                 torch.ops.octic.swiglu / _bwd            silu(x1) * x2 of the SwiGLU FFN    dinov2/layers/swiglu_ffn.py:32-33
 
 Weight preparation (bf16 casts, the transposed operand of the input gradient): a traced graph has no place for a cache keyed on
 parameter versions, so by default it happens inside the ops, per call.  Round 6: where ``train.FusedLamb`` owns the compute-dtype
@@ -703,5 +704,31 @@ def _sr_backward(ctx, gout):
 
 scale_residual.register_autograd(_sr_backward, setup_context=_sr_setup)
 
+@_lib.custom_op("octic::swiglu", mutates_args=())
+def swiglu(x12: Tensor) -> Tensor:
+    """silu(x1) * x2 with (x1, x2) = x12.chunk(2, -1), bf16 [..., 2H] -> [..., H] (dinov2/layers/swiglu_ffn.py:32-33) on
+    csrc/swiglu.hip."""
+    return ops.swiglu_fwd(_c(x12), x12.shape[-1] // 2)
+
+
+@swiglu.register_fake
+def _(x12):
+    return x12.new_empty(x12.shape[:-1] + (x12.shape[-1] // 2,))
+
+
+@_lib.custom_op("octic::swiglu_bwd", mutates_args=())
+def swiglu_bwd(ga: Tensor, x12: Tensor) -> Tensor:
+    """-> dx12 (the bias gradient of w12 is the column sum dense_linear_bwd takes of it)."""
+    return ops.swiglu_bwd(_c(x12), _c(ga.to(x12.dtype)), want_colsum=False)[0]
+
+
+@swiglu_bwd.register_fake
+def _(ga, x12):
+    return torch.empty_like(x12, memory_format=torch.contiguous_format)
+
+
+swiglu.register_autograd(lambda ctx, ga: (torch.ops.octic.swiglu_bwd(ga, *ctx.saved_tensors),),
+                         setup_context=lambda ctx, inputs, output: ctx.save_for_backward(inputs[0]))
+
 ALL_OPS = ("layernorm_d8", "linear_d8", "attn_packed", "lift", "handoff_cat", "power_spectrum", "dense_layernorm",
-           "dense_linear", "attn_qkv", "scale_residual")
+           "dense_linear", "attn_qkv", "scale_residual", "swiglu")

@@ -1389,6 +1389,59 @@ class DenseMlpFn(torch.autograd.Function):
         return gy, gx, gw1, db1, gw2, db2, dgamma, None, None, None, None, dnw, dnb, None, None, None
 
 
+class DenseSwigluFn(torch.autograd.Function):
+    """x + rs * gamma * w3(silu(x1) * x2) with (x1, x2) = w12(y).chunk(2, -1): DINOv2's SwiGLU FFN inside a standard block
+    (dinov2/layers/swiglu_ffn.py:30-34, block.py:94), the counterpart of DenseMlpFn.  w12 is a plain-epilogue GEMM on
+    csrc/dense_gemm.hip where "fc1" is routed (DENSE_HIP) and the kernel takes the shape, else the BLAS library; the gate and
+    its backward (with w12's bias gradient on the side) are the row kernels of csrc/swiglu.hip either way; w3 runs through the
+    shared residual tail as "fc2".  Weight gradients: csrc/dense_wgrad.hip (WGRAD_HIP)."""
+
+    @staticmethod
+    def forward(ctx, y, x, w12, b12, w3, b3, gamma, rs, rps, c1, c2, nw=None, nb=None, neps=None, rows_to=None, stream=None):
+        """The trailing arguments are DenseMlpFn's."""
+        ctx.wparams = (w12, w3)
+        x = _c(x)
+        yb = _c(y if y.dtype == torch.bfloat16 else y.to(torch.bfloat16))
+        H, D = w3.shape[1], w12.shape[1]
+        y2 = yb.reshape(-1, D)
+        M = y2.shape[0]
+        need_t = any(ctx.needs_input_grad[:2])            # (an inference pass - the DINOv2 teacher - never transposes)
+        # per GEMM: routed and a shape the hand-written kernel takes (others: the library, as vit.Mlp falls back)
+        hip12 = "fc1" in DENSE_HIP and ops.dense_gemm_ok(M, 2 * H, D)
+        hip3 = "fc2" in DENSE_HIP and ops.dense_gemm_ok(M, w3.shape[0], H)
+        w12b, w12t = c1.get_nt(w12, b12, need_t and "dfc1" in DENSE_HIP and ops.dense_gemm_ok(M, D, 2 * H))
+        w3b, w3t = c2.get_nt(w3, b3, need_t and "dfc2" in DENSE_HIP and ops.dense_gemm_ok(M, H, w3.shape[0]))
+        g32, rs32 = _f32(gamma), _f32(rs)
+        # x12 of a dropped sample is read by the gate alone, whose output meets rs = 0 behind w3 and zero dY rows in the gradients
+        ds = dense_skip_scale(rs32, rps, M, rows_to)
+        # w12's input gradient is dx12 W12 with dx12 = gate'(x12) * (gbr W3) and gbr = rs * gamma * gout: zero rows where rs is 0
+        row_skip_fill(y, row_skip_scale(rs32, rps, M, rows_to), rps, M)
+        x12 = _gemm_fwd("fc1" if hip12 else "fc1-library", y2, w12b, b12, c1, "plain", _tok(y.shape), ds, rps)
+        a = ops.swiglu_fwd(x12, H)
+        outs, tail = _resid_tail_fwd(ctx, x, "fc2" if hip3 else "fc2-library", a, w3b, b3, c2, _tok(y.shape), g32, rs32, rps,
+                                     nw, nb, neps, rows_to, stream)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(y2, x12, a, w12b, w12t, w3b, w3t, *tail)
+        ctx.meta = (b12 is not None, y.dtype, y.shape)
+        return outs
+
+    @staticmethod
+    def backward(ctx, gout, gyn=None):
+        y2, x12, a, w12b, w12t, w3b, w3t, *tail = ctx.saved_tensors
+        has_b12, y_dtype, y_shape = ctx.meta
+        gx, gbr, dgamma, db3, dnw, dnb = _resid_tail_bwd(ctx, tail, gout, gyn,
+                                                         ctx.needs_input_grad[11] or ctx.needs_input_grad[12])
+        rps = ctx.tail[1]
+        ds = dense_skip_scale(tail[2], rps, gbr.shape[0], ctx.rows_to)    # gbr = rs * gamma * gout: zero rows where rs is 0
+        ga = _gemm_dgrad(gbr, w3t, w3b, (*y_shape[:-1], a.shape[1]), a.dtype, ds, rps)
+        dx12, db12 = ops.swiglu_bwd(x12, ga, want_colsum=has_b12)
+        ss = wgrad_skip_scale(tail[2], rps, gbr.shape[0], ctx.rows_to)    # dx12 = gate' * (gbr W3): zero rows with gbr's
+        gw3 = _wgrad_lib(gbr, a, ctx.wparams[1], ss, rps)
+        gw12 = _wgrad_lib(dx12, y2, ctx.wparams[0], ss, rps)
+        gy = _gemm_dgrad(dx12, w12t, w12b, y_shape, y_dtype, ds, rps) if ctx.needs_input_grad[0] else None
+        return gy, gx, gw12, db12, gw3, db3, dgamma, None, None, None, None, dnw, dnb, None, None, None
+
+
 # -------------------------------------------------------------------------------------- hand-off
 class HandoffCatFn(torch.autograd.Function):
     @staticmethod

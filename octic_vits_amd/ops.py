@@ -1199,6 +1199,56 @@ def dense_gelu_bwd(h, g, want_colsum=True):
     return dh, out
 
 
+def _swiglu_rows(t, width, what):
+    """t as [rows, width] with unit column stride: a 2-D tensor as it is (its row stride travels to the kernel), anything else
+    contiguous and flattened."""
+    if t.dim() != 2:
+        t = t.reshape(-1, t.shape[-1]) if t.is_contiguous() else t.contiguous().view(-1, t.shape[-1])
+    if t.dtype != torch.bfloat16 or t.shape[1] != width or t.stride(1) != 1:
+        raise ValueError(f"swiglu: {what} must be bf16 [rows, {width}] with contiguous columns, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def swiglu_fwd(x12, H, out=None):
+    """a = silu(x1) * x2 for x12 = [x1 | x2] bf16 [..., 2H] (the gate of DINOv2's SwiGLU FFN) -> bf16 [..., H].
+    out: a 2-D [rows, H] destination (any row stride the library takes)."""
+    _require_cuda(x12)
+    lead = x12.shape[:-1]
+    x2d = _swiglu_rows(x12, 2 * H, "x12")
+    rows = x2d.shape[0]
+    a = torch.empty((rows, H), dtype=torch.bfloat16, device=x12.device) if out is None else _swiglu_rows(out, H, "out")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_swiglu_fwd(_p(x2d), x2d.stride(0), _p(a), a.stride(0), rows, H, _stream(x12)))
+    KERNEL_TIMER.stop(t, "swiglu_fwd_kernel", rows * H * 6)
+    return a.view(*lead, H) if out is None else out
+
+
+def swiglu_bwd(x12, ga, want_colsum=True, out=None):
+    """(dx12, db12): the cotangent of x12 = [x1 | x2] from ga, the cotangent of silu(x1) * x2, and - when asked - its f32
+    column sums [2H] (the bias gradient of w12, in w12.bias order).  out: a 2-D [rows, 2H] destination."""
+    _require_cuda(x12)
+    H = ga.shape[-1]
+    x2d, g2d = _swiglu_rows(x12, 2 * H, "x12"), _swiglu_rows(ga, H, "ga")
+    rows = x2d.shape[0]
+    if g2d.shape[0] != rows:
+        raise ValueError("swiglu_bwd: x12 and ga differ in rows")
+    d = torch.empty((rows, 2 * H), dtype=torch.bfloat16, device=x12.device) if out is None else _swiglu_rows(out, 2 * H, "out")
+    nblk = lib().octic_swiglu_blocks()
+    partials = torch.empty((nblk, 2 * H), dtype=torch.float32, device=x12.device) if want_colsum and rows else None
+    t = KERNEL_TIMER.start()
+    check(lib().octic_swiglu_bwd(_p(x2d), x2d.stride(0), _p(g2d), g2d.stride(0), _p(d), d.stride(0), _p(partials), rows, H,
+                                 _stream(x12)))
+    KERNEL_TIMER.stop(t, "swiglu_bwd_kernel", rows * H * 10)
+    dx = d.view(x12.shape) if out is None else out
+    if not want_colsum:
+        return dx, None
+    if partials is None:
+        return dx, torch.zeros(2 * H, dtype=torch.float32, device=x12.device)
+    db = torch.empty(2 * H, dtype=torch.float32, device=x12.device)
+    _finish(partials, nblk, H, db, None, None, _stream(x12), out1_ptr=db.data_ptr() + 4 * H)
+    return dx, db
+
+
 # ------------------------------------------------------------------------------------------ dense MFMA GEMMs
 _DG_WS = {}
 # octic_dense_gemm_workspace_bytes depends on the override table (OCTIC_ROUTE_DENSE_SPLIT makes a problem split that otherwise

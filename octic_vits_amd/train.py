@@ -515,7 +515,7 @@ def use_tuned_gemms(table=None):
 
 
 def library_gemm_layers(model):
-    """(nn.Linear, DenseWeightCache, role) of every projection of the standard half (vit.Attention / vit.Mlp)."""
+    """(nn.Linear, DenseWeightCache, role) of every projection of the standard half (vit.Attention / vit.Mlp / vit.SwiGLUFFN)."""
     from . import vit
     out = []
     for m in model.modules():
@@ -523,6 +523,8 @@ def library_gemm_layers(model):
             out += [(m.qkv, m._c1, "qkv"), (m.proj, m._c2, "proj")]
         elif isinstance(m, vit.Mlp):
             out += [(m.fc1, m._c1, "fc1"), (m.fc2, m._c2, "fc2")]
+        elif isinstance(m, vit.SwiGLUFFN):
+            out += [(m.w12, m._c1, "fc1"), (m.w3, m._c2, "fc2")]
     return out
 
 

@@ -91,6 +91,57 @@ class Mlp(nn.Module):
                                                self._c2)
 
 
+class SwiGLUFFN(nn.Module):
+    """dinov2.layers.SwiGLUFFN (dinov2/layers/swiglu_ffn.py:14-34): w3(silu(x1) * x2) with (x1, x2) = w12(x).chunk(2, -1).
+    Same constructor and state_dict keys (w12.weight/bias, w3.weight/bias).  ``forward`` is the reference's composition (CPU
+    and f32 runs); under bf16 autocast on the GPU a block calls ``forward_fused``: the two GEMMs on csrc/dense_gemm.hip where
+    it takes the shapes (the BLAS library otherwise) around the gate kernels of csrc/swiglu.hip."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=None, drop=0.0, bias=True):
+        super().__init__()
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        self.w12 = nn.Linear(in_features, 2 * hidden_features, bias=bias)
+        self.w3 = nn.Linear(hidden_features, out_features, bias=bias)
+        self._c1, self._c2 = _OF.DenseWeightCache(), _OF.DenseWeightCache()     # w12, w3
+
+    def forward(self, x):
+        x12 = self.w12(x)
+        x1, x2 = x12.chunk(2, dim=-1)
+        hidden = F.silu(x1) * x2
+        return self.w3(hidden)
+
+    def fusable(self):
+        return (type(self.w12) is nn.Linear and type(self.w3) is nn.Linear and self.w3.in_features % 8 == 0
+                and self.w12.out_features == 2 * self.w3.in_features)
+
+    def rows_ok(self, y):
+        """forward_fused takes `rows_to` for this input (both GEMMs run on the hand-written kernel)."""
+        return (_OF.dense_hip_ok(y, self.w12.weight) and _OF.dense_hip_ok(y, self.w3.weight)
+                and bool({"fc1", "fc2", "dfc1", "dfc2"} & _OF.DENSE_HIP))
+
+    def forward_fused(self, y, xres, gamma, rs, dtype, next_norm=None, rows_to=None):
+        """xres + rs*gamma*w3(silu(x1) * x2) with y already normalised and in the compute dtype; next_norm / rows_to as in
+        Mlp.forward_fused.  bf16 only: the gate kernels are bf16 (a block leaves f32 runs to ``forward``)."""
+        if dtype != torch.bfloat16 or not self.fusable():
+            raise RuntimeError("SwiGLUFFN.forward_fused: the engine path is bf16 with a hidden width that is a multiple of 8")
+        if rows_to is not None and (next_norm is not None or not self.rows_ok(y)):
+            raise RuntimeError("SwiGLUFFN.forward_fused: rows_to needs the hand-written bf16 path (check rows_ok first)")
+        norm, rows = _tail_args(next_norm, rows_to)
+        return _OF.DenseSwigluFn.apply(y, xres, self.w12.weight, self.w12.bias, self.w3.weight, self.w3.bias, gamma, rs,
+                                       _rows_per_scale(y, rs), self._c1, self._c2, *norm, *rows)
+
+
+class SwiGLUFFNFused(SwiGLUFFN):
+    """dinov2.layers.SwiGLUFFNFused (swiglu_ffn.py:54-72): hidden width int(hidden * 2 / 3) rounded up to a multiple of 8."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=None, drop=0.0, bias=True):
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        hidden_features = (int(hidden_features * 2 / 3) + 7) // 8 * 8
+        super().__init__(in_features=in_features, hidden_features=hidden_features, out_features=out_features, bias=bias)
+
+
 class Attention(nn.Module):
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., fused_attn=True,
                  proj_bias=True):
@@ -198,7 +249,7 @@ def _engine_regime(x, norm1, attn, norm2, mlp, scales, ntok=None):
     for n in (norm1, norm2):
         if type(n) is not nn.LayerNorm or tuple(n.normalized_shape) != (d,) or d % 4 or d > 2048:
             return None
-    if not (isinstance(attn, Attention) and isinstance(mlp, Mlp) and mlp.fusable()
+    if not (isinstance(attn, Attention) and isinstance(mlp, (Mlp, SwiGLUFFN)) and mlp.fusable()
             and attn.fusable(x.shape[1] if ntok is None else ntok, torch.bfloat16)):
         return None
     gammas = []
@@ -280,6 +331,10 @@ def _traced_block(x, norm1, attn, gamma1, dp1, norm2, mlp, gamma2, dp2):
     p = o.dense_linear(a, attn.proj.weight, attn.proj.bias, False, *attn._c2.static_nt())[0]
     x = o.scale_residual(x, p, gamma1, _drop_path_scale(dp1, x), N)
     y = o.dense_layernorm(x, norm2.weight, norm2.bias, norm2.eps, True)[0]
+    if isinstance(mlp, SwiGLUFFN):
+        x12 = o.dense_linear(y, mlp.w12.weight, mlp.w12.bias, False, *mlp._c1.static_nt())[0]
+        f = o.dense_linear(o.swiglu(x12), mlp.w3.weight, mlp.w3.bias, False, *mlp._c2.static_nt())[0]
+        return o.scale_residual(x, f, gamma2, _drop_path_scale(dp2, x), N)
     Hd = mlp.fc1.weight.shape[0]
     if _D._mlp_hip_ok(B * N, C, Hd):
         # fc1 + GELU + fc2 as one op: gelu'(h) is kept as a bf16 factor and applied inside fc2's input-gradient epilogue
@@ -390,11 +445,14 @@ class NestedTensorBlock(Block):
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=False, proj_bias=True, ffn_bias=True, drop=0.0,
                  attn_drop=0.0, init_values=None, drop_path=0.0, act_layer=nn.GELU, norm_layer=nn.LayerNorm,
                  attn_class=None, ffn_layer=None, **kwargs):
+        # ffn_layer (block.py:59, 77-83): None / Mlp = the timm MLP as before; anything else (SwiGLUFFNFused) builds self.mlp
+        other_ffn = ffn_layer is not None and ffn_layer is not Mlp
+        ffn = {"mlp_layer": lambda **kw: ffn_layer(bias=ffn_bias, **kw)} if other_ffn else {}
         super().__init__(dim, num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, proj_drop=drop, attn_drop=attn_drop,
-                         init_values=init_values, drop_path=drop_path, act_layer=act_layer, norm_layer=norm_layer)
+                         init_values=init_values, drop_path=drop_path, act_layer=act_layer, norm_layer=norm_layer, **ffn)
         if not proj_bias:
             self.attn.proj.bias = None
-        if not ffn_bias:
+        if not ffn_bias and not other_ffn:
             self.mlp.fc1.bias = None
             self.mlp.fc2.bias = None
         self.sample_drop_ratio = drop_path
