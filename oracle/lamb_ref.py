@@ -30,13 +30,21 @@ import numpy as np
 
 
 class LambRef:
-    def __init__(self, shapes, weight_decays, lr=3e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0):
-        self.lr, self.b1, self.b2, self.eps, self.max_grad_norm = float(lr), float(betas[0]), float(betas[1]), float(eps), max_grad_norm
+    """``lr``: one value, or one per tensor (the product's per-group learning rates, expanded).  ``trust_ratio=False``:
+    ratio = 1 for every tensor, i.e. AdamW with decoupled weight decay (what octic_adamw_step computes).  ``t`` is the number
+    of applied steps; a test may set it (with ``m`` / ``v``) before a step to stand in for a resumed run: the next
+    step's bias correction uses t + 1.  ``last_updates`` holds u of every tensor at the last applied step."""
+
+    def __init__(self, shapes, weight_decays, lr=3e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0, trust_ratio=True):
+        self.lr = float(lr) if np.ndim(lr) == 0 else [float(x) for x in lr]
+        self.b1, self.b2, self.eps, self.max_grad_norm = float(betas[0]), float(betas[1]), float(eps), max_grad_norm
+        self.trust_ratio = bool(trust_ratio)
         self.wd = [float(w) for w in weight_decays]
         self.m = [np.zeros(s, dtype=np.float64) for s in shapes]
         self.v = [np.zeros(s, dtype=np.float64) for s in shapes]
         self.t = 0
         self.last_grad_norm = None
+        self.last_updates = None      # u of every tensor at the last applied step (what the fused step leaves in the gradient)
 
     def step(self, params, grads):
         """params, grads: lists of float64 ndarrays; returns the updated parameter list (inputs are not modified)."""
@@ -47,19 +55,21 @@ class LambRef:
         clip = gn / self.max_grad_norm if (self.max_grad_norm and gn > self.max_grad_norm) else 1.0
         self.t += 1
         bc1, bc2 = 1.0 - self.b1 ** self.t, 1.0 - self.b2 ** self.t
-        out = []
+        out, self.last_updates = [], []
         for i, (p, g) in enumerate(zip(params, grads)):
             p = np.asarray(p, dtype=np.float64)
             gs = np.asarray(g, dtype=np.float64) / clip
             self.m[i] = self.b1 * self.m[i] + (1.0 - self.b1) * gs
             self.v[i] = self.b2 * self.v[i] + (1.0 - self.b2) * gs * gs
             u = (self.m[i] / bc1) / (np.sqrt(self.v[i] / bc2) + self.eps) + self.wd[i] * p
+            self.last_updates.append(u)
             ratio = 1.0
-            if self.wd[i] != 0.0:
+            if self.trust_ratio and self.wd[i] != 0.0:
                 pn, un = float(np.sqrt(np.sum(p * p))), float(np.sqrt(np.sum(u * u)))
                 if pn > 0.0 and un > 0.0:
                     ratio = pn / un
-            out.append(p - self.lr * ratio * u)
+            lr = self.lr[i] if isinstance(self.lr, list) else self.lr
+            out.append(p - lr * ratio * u)
         return out
 
 
