@@ -387,7 +387,7 @@ __global__ __launch_bounds__(256, 4) void ln_fwd_g8_kernel(const float* __restri
   }
   const float inv_n = lg.isE ? 1.0f / (float)(2 * c) : 1.0f / (float)c;
   const float wq = lg.isE ? 0.5f * inv_n : inv_n;      // weight of this lane's squares in S
-  const int stat_idx = (lg.acol0 == 0) ? lg.seg : (lane == 1 ? 6 : -1);
+  const int stat_idx = (lg.acol0 == 0) ? lg.seg : (lane == 1 ? 6 : (lane == 2 ? 7 : -1));   // slot 7 is the documented 0
   for (int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); m < M; m += nwaves) {
     const float* xr = x + m * ldx + lg.col0;
     f32x4 xv[NV];
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(256, 4) void ln_fwd_g8_kernel(const float* __restri
     TOUT* yr = y + m * ldy + lg.col0;
 #pragma unroll
     for (int i = 0; i < NV; ++i) store4<TOUT>(yr + i * lg.step4, xv[i] * rstd * av[i] + bv[i]);
-    if (stats && stat_idx >= 0) stats[m * 8 + stat_idx] = (stat_idx == 6) ? rstd : mean;
+    if (stats && stat_idx >= 0) stats[m * 8 + stat_idx] = (stat_idx == 6) ? rstd : (stat_idx == 7 ? 0.f : mean);
   }
 }
 

@@ -113,7 +113,7 @@ def _octic_operands(B, T, c):
 
 
 @pytest.mark.parametrize("B,T", [(6, 3), (7, 37), (5, 257)])
-@pytest.mark.parametrize("c", [32, 96, 160])
+@pytest.mark.parametrize("c", [32, 64, 96, 128, 160])          # every chunk count of the masked kernel
 def test_octic_layernorm_bwd_equals_the_unmasked_launch(c, B, T):
     from octic_vits_amd import ops
     x, alpha, stats, g, dres = _octic_operands(B, T, c)
