@@ -718,19 +718,22 @@ class AttentionD8(nn.Module):
         self.rope = rope
         self.att = F.scaled_dot_product_attention
 
+    def _plain_packed(self, xp, c, resid, rs, drop, rag):
+        """The plain packed attention path: forward() below hands rs to the packed attention node (OF.AttnPackedFn) between this
+        class's own qkv and proj, whose fused tail multiplies the branch by it - whatever the skip switches say."""
+        return (rs is not None and resid is not None and not COMPACT_DROP_PATH and not (rag is not None and rag.matches(xp))
+                and OF.ATTN_PACKED and drop == 0. and xp.is_cuda and not torch.compiler.is_compiling()
+                and not self.proj_drop.active and type(self.qkv) is LinearD8 and type(self.proj) is LinearD8
+                and OF.ops.attn_packed_ok(xp.shape[1], c, self.num_heads, compute_dtype(xp)))
+
     def _gemm_mask(self, xp, c, resid, rs, drop, rag):
         """rs as the sample mask of qkv's forward and of proj's input gradient, or None.  Their only readers are the attention
         forward and backward (qkv's own gradients read the input and dqkv, which a skipping backward zeroes), so the mask
         goes out exactly where the packed attention node below gets rs AND both launches it will run skip a dropped sample
         outright (ops.attn_skips_dropped, from the library's plan) - a kernel that computes the sample must find finite rows."""
-        if not (OF.LINEAR_SKIP_DROPPED and OF.ATTN_SKIP_DROPPED and rs is not None and resid is not None
-                and not COMPACT_DROP_PATH and not (rag is not None and rag.matches(xp)) and OF.ATTN_PACKED and drop == 0.
-                and xp.is_cuda and not torch.compiler.is_compiling() and not self.proj_drop.active
-                and type(self.qkv) is LinearD8 and type(self.proj) is LinearD8):
+        if not (OF.LINEAR_SKIP_DROPPED and OF.ATTN_SKIP_DROPPED and self._plain_packed(xp, c, resid, rs, drop, rag)):
             return None
         B, T, H = xp.shape[0], xp.shape[1], self.num_heads
-        if not OF.ops.attn_packed_ok(T, c, H, compute_dtype(xp)):
-            return None
         if OF.skip_scale(rs, B) is None or OF.linear_skip_scale(rs, T, B * T) is None:
             return None
         # the strides of ops.attn_fwd_packed / attn_bwd_packed: qkv and dqkv rows of 3 * 8c, o and dO rows of 8c
@@ -747,10 +750,7 @@ class AttentionD8(nn.Module):
         gemm_mask = self._gemm_mask(xp, c, resid, rs, drop, rag)
         # qkv's input gradient reads dqkv, the attention backward of dO = 0 for a dropped sample (proj's tail multiplies the branch
         # by rs): exact zeros wherever the packed attention node below gets rs, whether its kernels skip the sample or compute it
-        zero_dx = rs if (rs is not None and resid is not None and not COMPACT_DROP_PATH and not (rag is not None and rag.matches(xp))
-                         and OF.ATTN_PACKED and drop == 0. and xp.is_cuda and not torch.compiler.is_compiling()
-                         and not self.proj_drop.active and type(self.qkv) is LinearD8 and type(self.proj) is LinearD8
-                         and OF.ops.attn_packed_ok(xp.shape[1], c, self.num_heads, compute_dtype(xp))) else None
+        zero_dx = rs if self._plain_packed(xp, c, resid, rs, drop, rag) else None
         qkv = self.qkv(xs if isinstance(xs, Octic) else Octic(xp, c), skip_out=gemm_mask, zero_dx=zero_dx)
         if rag is not None and rag.matches(xp):
             # several crop sets in one row tensor: the softmax core walks the sets, everything around it ran once on all rows

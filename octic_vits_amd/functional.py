@@ -256,6 +256,51 @@ class PrepBatch:
             p.adopt(wb, wt, flat)
 
 
+def _linear_d8_fwd_prep(ctx, x, w5, cs5, bias, rs, cin, cout, rps, dtype, out_dtype, prep):
+    """What both LinearD8 nodes do in front of their forward launch: x in the compute dtype, the prepared weights, f32 copies of
+    bias / layer scale / row scale and the output to fill.  Leaves on ctx what _linear_d8_grads reads back (ctx.lin).
+    Returns (x, forward weights, M, y, b32, cs32, rs32)."""
+    ops._require_cuda(x)
+    x_in_dtype = x.dtype
+    if x.dtype != dtype:
+        x = ops.cast_rowscale(_c(x.float()), None, 1, dtype, cin)
+    x = _c(x)
+    wb, wt = prep.get(w5, cs5, dtype, cin, cout)
+    M = x.numel() // (8 * cin)
+    y = torch.empty(x.shape[:-1] + (8 * cout,), dtype=out_dtype, device=x.device)
+    b32 = None if bias is None else _c(bias.detach().float())
+    cs32 = None if cs5 is None else [_c(s.detach().float()) for s in cs5]
+    rs32 = None if rs is None else _c(rs.float())
+    ctx.lin = (cin, cout, rps, dtype, cs5 is not None, bias is not None, x_in_dtype, wt)
+    return x, wb, M, y, b32, cs32, rs32
+
+
+def _linear_d8_grads(ctx, x, g, w5, cs32, b32, ss_dx, z_dx=None):
+    """The gradient half of both LinearD8 nodes' backward, from g = the cotangent of the branch in the compute dtype: the
+    input-gradient launch under its masks (ss_dx / z_dx: LinearD8Fn.forward), the bias column sums and the weight gradients.
+    Returns (dx or None, dw5, dbias, dcs5)."""
+    cin, cout, rps, dtype, has_cs, has_bias, x_in_dtype, wt = ctx.lin
+    M = x.numel() // (8 * cin)
+    gv, xv = ops.pview(g, cout), ops.pview(x, cin)
+    dx = None
+    if ctx.needs_input_grad[0]:
+        dx = torch.empty(x.shape, dtype=dtype, device=x.device)
+        ops.linear_fwd(gv, wt, None, ops.pview(dx, cin), M, cout, cin, dtype, dtype, x, sample_scale=ss_dx, skip_rps=rps,
+                       dropped=z_dx, dropped_rps=rps)
+        if dx.dtype != x_in_dtype:
+            dx = dx.to(x_in_dtype)
+    # bias gradient = column sums of the invariant block of g: the bf16 wgrad kernel produces them on the side
+    # (one extra MFMA row); other paths run the column-sum kernel
+    dysum = ops.colsum_a1(gv, M, cout, dtype, x) if (has_bias and not ops.wgrad_has_colsum(cin, cout, dtype)) else None
+    w32 = [_c(w.detach().float()) for w in w5] if has_cs else None
+    f32_masters = all(w.dtype == torch.float32 for w in w5)      # else the casts below read dw at once: no deferral
+    dw, dcs, dbias = ops.linear_wgrad(xv, gv, M, cin, cout, dtype, x, w32=w32, cs5=cs32, bias=b32, dysum=dysum,
+                                      want_bias=has_bias, may_defer=f32_masters, wparams=w5 if f32_masters else None)
+    if not f32_masters:
+        dw = [d.to(w.dtype) for d, w in zip(dw, w5)]
+    return dx, dw, dbias, (dcs if has_cs else [None] * 5)
+
+
 class LinearD8Fn(torch.autograd.Function):
     """y = resid + rs*cs*(x W^T + b)   (resid / rs / cs optional).  See octic_hip.h for the math."""
 
@@ -270,21 +315,10 @@ class LinearD8Fn(torch.autograd.Function):
         forward hands its own rs to the launch as `dropped`: the tail multiplies those samples' rows by 0."""
         w5 = (wA1, wA2, wB1, wB2, wE)
         cs5 = None if sA1 is None else (sA1, sA2, sB1, sB2, sE)
-        ops._require_cuda(x)
         fused = resid is not None
         out_dtype = resid.dtype if fused else dtype
-        x_in_dtype = x.dtype
         handed = x
-        if x.dtype != dtype:
-            x = ops.cast_rowscale(_c(x.float()), None, 1, dtype, cin)
-        x = _c(x)
-        wb, wt = prep.get(w5, cs5, dtype, cin, cout)
-        lead = x.shape[:-1]
-        M = x.numel() // (8 * cin)
-        y = torch.empty(lead + (8 * cout,), dtype=out_dtype, device=x.device)
-        b32 = None if bias is None else _c(bias.detach().float())
-        cs32 = None if cs5 is None else [_c(s.detach().float()) for s in cs5]
-        rs32 = None if rs is None else _c(rs.float())
+        x, wb, M, y, b32, cs32, rs32 = _linear_d8_fwd_prep(ctx, x, w5, cs5, bias, rs, cin, cout, rps, dtype, out_dtype, prep)
         rv = ops.pview(_c(resid), cout) if fused else None
         plain = not fused and rs32 is None and cs32 is None
         ss_out = linear_skip_scale(skip_out, rps, M) if plain else None
@@ -296,39 +330,21 @@ class LinearD8Fn(torch.autograd.Function):
         # zero cotangent rows in, zero dx rows out (computed or stored, every row written): the norm in front may skip them
         row_skip_fill(handed, row_skip_scale(zero_dx, rps, M) if (plain and ss_dx is None) else None, rps, M)
         ctx.save_for_backward(x, rs32, b32, ss_dx, z_dx, *w5, *(cs32 or []))
-        ctx.meta = (cin, cout, rps, dtype, fused, cs5 is not None, bias is not None, x_in_dtype, wt)
+        ctx.fused = fused
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        cin, cout, rps, dtype, fused, has_cs, has_bias, x_in_dtype, wt = ctx.meta
+        cin, cout, rps, dtype, has_cs = ctx.lin[:5]
         x, rs32, b32, ss_dx, z_dx, *rest = ctx.saved_tensors
         w5, cs32 = rest[:5], (rest[5:] if has_cs else None)
-        M = x.numel() // (8 * cin)
         dy = _c(dy)
-        if fused or rs32 is not None or dy.dtype != dtype:
+        if ctx.fused or rs32 is not None or dy.dtype != dtype:
             g = ops.cast_rowscale(_c(dy.float()), rs32, rps, dtype, cout)  # cotangent of the branch
         else:
             g = dy
-        gv, xv = ops.pview(g, cout), ops.pview(x, cin)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(x.shape, dtype=dtype, device=x.device)
-            ops.linear_fwd(gv, wt, None, ops.pview(dx, cin), M, cout, cin, dtype, dtype, x, sample_scale=ss_dx, skip_rps=rps,
-                           dropped=z_dx, dropped_rps=rps)
-            if dx.dtype != x_in_dtype:
-                dx = dx.to(x_in_dtype)
-        # bias gradient = column sums of the invariant block of g: the bf16 wgrad kernel produces them on the side
-        # (one extra MFMA row); other paths run the column-sum kernel
-        dysum = ops.colsum_a1(gv, M, cout, dtype, x) if (has_bias and not ops.wgrad_has_colsum(cin, cout, dtype)) else None
-        w32 = [_c(w.detach().float()) for w in w5] if has_cs else None
-        f32_masters = all(w.dtype == torch.float32 for w in w5)      # else the casts below read dw at once: no deferral
-        dw, dcs, dbias = ops.linear_wgrad(xv, gv, M, cin, cout, dtype, x, w32=w32, cs5=cs32, bias=b32, dysum=dysum,
-                                          want_bias=has_bias, may_defer=f32_masters, wparams=w5 if f32_masters else None)
-        if not f32_masters:
-            dw = [d.to(w.dtype) for d, w in zip(dw, w5)]
-        dcs = dcs if has_cs else [None] * 5
-        return (dx, *dw, dbias, dy if fused else None, None, *dcs, None, None, None, None, None, None, None, None)
+        dx, dw, dbias, dcs = _linear_d8_grads(ctx, x, g, w5, cs32, b32, ss_dx, z_dx)
+        return (dx, *dw, dbias, dy if ctx.fused else None, None, *dcs, None, None, None, None, None, None, None, None)
 
 
 class LinearD8NormFn(torch.autograd.Function):
@@ -345,32 +361,22 @@ class LinearD8NormFn(torch.autograd.Function):
         its `dropped` mask (ring_skip_scale)."""
         w5 = (wA1, wA2, wB1, wB2, wE)
         cs5 = None if sA1 is None else (sA1, sA2, sB1, sB2, sE)
-        ops._require_cuda(x)
-        x_in_dtype = x.dtype
-        if x.dtype != dtype:
-            x = ops.cast_rowscale(_c(x.float()), None, 1, dtype, cin)
-        x = _c(x)
-        wb, wt = prep.get(w5, cs5, dtype, cin, cout)
-        M = x.numel() // (8 * cin)
-        y = torch.empty(x.shape[:-1] + (8 * cout,), dtype=resid.dtype, device=x.device)
-        b32 = None if bias is None else _c(bias.detach().float())
-        cs32 = None if cs5 is None else [_c(s.detach().float()) for s in cs5]
-        rs32 = None if rs is None else _c(rs.float())
+        x, wb, M, y, b32, cs32, rs32 = _linear_d8_fwd_prep(ctx, x, w5, cs5, bias, rs, cin, cout, rps, dtype, resid.dtype, prep)
         ops.linear_fwd(ops.pview(x, cin), wb, b32, ops.pview(y, cout), M, cin, cout, dtype, resid.dtype, x,
                        resid_v=ops.pview(_c(resid), cout), rs=rs32, rps=rps, cs5=cs32, dropped=ring_skip_scale(rs32, rps, M),
                        dropped_rps=rps)
         alpha = None if a1 is None else [_c(t.float()) for t in (a1, a2, b1, b2, ae)]
         yn, stats = ops.layernorm_fwd(y, alpha, None if beta is None else _c(beta.float()), eps, dtype, cout)
         ctx.save_for_backward(x, rs32, b32, y, stats, linear_skip_scale(skip_dx, rps, M), *w5, *(cs32 or []), *(alpha or []))
-        ctx.meta = (cin, cout, rps, dtype, cs5 is not None, bias is not None, x_in_dtype, wt, alpha is not None,
-                    beta is not None)
+        ctx.has_affine, ctx.has_beta = alpha is not None, beta is not None
         ctx.set_materialize_grads(False)
         row_skip_attach(ctx, yn)
         return y, yn
 
     @staticmethod
     def backward(ctx, dy, dyn):
-        cin, cout, rps, dtype, has_cs, has_bias, x_in_dtype, wt, has_affine, has_beta = ctx.meta
+        cin, cout, rps, dtype, has_cs = ctx.lin[:5]
+        has_affine = ctx.has_affine
         x, rs32, b32, y, stats, ss_dx, *rest = ctx.saved_tensors
         w5 = rest[:5]
         cs32 = rest[5:10] if has_cs else None
@@ -391,22 +397,8 @@ class LinearD8NormFn(torch.autograd.Function):
         dy = _c(dy)
         if g is None:
             g = ops.cast_rowscale(_c(dy.float()), rs32, rps, dtype, cout)  # cotangent of the branch
-        gv, xv = ops.pview(g, cout), ops.pview(x, cin)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(x.shape, dtype=dtype, device=x.device)
-            ops.linear_fwd(gv, wt, None, ops.pview(dx, cin), M, cout, cin, dtype, dtype, x, sample_scale=ss_dx, skip_rps=rps)
-            if dx.dtype != x_in_dtype:
-                dx = dx.to(x_in_dtype)
-        dysum = ops.colsum_a1(gv, M, cout, dtype, x) if (has_bias and not ops.wgrad_has_colsum(cin, cout, dtype)) else None
-        w32 = [_c(w.detach().float()) for w in w5] if has_cs else None
-        f32_masters = all(w.dtype == torch.float32 for w in w5)      # else the casts below read dw at once: no deferral
-        dw, dcs, dbias = ops.linear_wgrad(xv, gv, M, cin, cout, dtype, x, w32=w32, cs5=cs32, bias=b32, dysum=dysum,
-                                          want_bias=has_bias, may_defer=f32_masters, wparams=w5 if f32_masters else None)
-        if not f32_masters:
-            dw = [d.to(w.dtype) for d, w in zip(dw, w5)]
-        dcs = dcs if has_cs else [None] * 5
-        return (dx, *dw, dbias, dy, None, *dcs, None, None, None, None, None, *dal, dbeta if has_beta else None, None, None)
+        dx, dw, dbias, dcs = _linear_d8_grads(ctx, x, g, w5, cs32, b32, ss_dx)
+        return (dx, *dw, dbias, dy, None, *dcs, None, None, None, None, None, *dal, dbeta if ctx.has_beta else None, None, None)
 
 
 # --------------------------------------------------------------------------------- head packing
@@ -462,16 +454,17 @@ class AttnFn(torch.autograd.Function):
         return dq, dk, dv, None
 
 
+def _skip_from_env(name):
+    """One of the OCTIC_*_SKIP switches below: on unless the variable is set to 0."""
+    return os.environ.get(name, "1").strip() != "0"
+
+
 # Stochastic depth: a block draws its per-sample factor rs[b] (0 or 1 / keep) BEFORE the attention branch runs and the branch's
 # tail multiplies the branch output with it, so everything the softmax core computes for a dropped sample is discarded in the
 # forward and meets a zero cotangent in the backward.  With ATTN_SKIP_DROPPED the factor travels to the attention kernels, which
 # skip those samples where their work is dealt per (sample, head) - same launch shapes, so it lives inside a captured step
 # (include/octic_hip.h: octic_attn_*_skip; DESIGN.md section 3).  Read once at import from OCTIC_ATTN_SKIP (0 = off).
-def _attn_skip_from_env():
-    return os.environ.get("OCTIC_ATTN_SKIP", "1").strip() != "0"
-
-
-ATTN_SKIP_DROPPED = _attn_skip_from_env()
+ATTN_SKIP_DROPPED = _skip_from_env("OCTIC_ATTN_SKIP")
 
 
 def skip_scale(rs, B):
@@ -488,21 +481,23 @@ def skip_scale(rs, B):
 # reduces over multiplies zeros.  With WGRAD_SKIP_DROPPED the factor travels to the TN kernel, which leaves out the reduction
 # steps that only touch dropped samples - same launch shapes, same bits (include/octic_hip.h: octic_dense_wgrad_tn_skip).
 # Read once at import from OCTIC_WGRAD_SKIP (0 = off).
-def _wgrad_skip_from_env():
-    return os.environ.get("OCTIC_WGRAD_SKIP", "1").strip() != "0"
+WGRAD_SKIP_DROPPED = _skip_from_env("OCTIC_WGRAD_SKIP")
 
 
-WGRAD_SKIP_DROPPED = _wgrad_skip_from_env()
-
-
-def wgrad_skip_scale(rs, rps, M, rows_to=None):
-    """rs as the TN kernel's sample_scale for a weight gradient over M token rows: the branch's per-sample factor when the
-    switch is on and rs is one float32 entry per sample of rps rows on the GPU with rps * B == M; None for compact rows of a
-    stream (rows_to), the per-row factors of a ragged row tensor (rps 1), a traced value, eval and drop_path 0 (rs None)."""
-    if (not WGRAD_SKIP_DROPPED or rs is None or rows_to is not None or torch.compiler.is_compiling() or not rs.is_cuda
+def whole_sample_mask(rs, rps, M, rows_to=None):
+    """rs as the mask of whole samples over M token rows, whichever kernel family reads it: the branch's per-sample factor when
+    rs is one float32 entry per sample of rps rows on the GPU with rps * B == M; None for compact rows of a stream (rows_to),
+    the per-row factors of a ragged row tensor (rps 1), a traced value, eval and drop_path 0 (rs None).  The *_skip_scale
+    functions below are this behind their switches."""
+    if (rs is None or rows_to is not None or torch.compiler.is_compiling() or not rs.is_cuda
             or rs.dtype != torch.float32 or rs.dim() != 1 or not rs.is_contiguous() or rps < 2 or rs.numel() * rps != M):
         return None
     return rs.detach()
+
+
+def wgrad_skip_scale(rs, rps, M, rows_to=None):
+    """rs as the TN kernel's sample_scale for a weight gradient over M token rows: whole_sample_mask while the switch is on."""
+    return whole_sample_mask(rs, rps, M, rows_to) if WGRAD_SKIP_DROPPED else None
 
 
 # The eight dense_nt_kernel launches of a standard block (csrc/dense_gemm.hip) compute rows nobody needs for a dropped sample:
@@ -511,21 +506,12 @@ def wgrad_skip_scale(rs, rps, M, rows_to=None):
 # sample.  With DENSE_NT_SKIP_DROPPED the branch's factor travels to the kernel as its sample_scale: row panels whose samples
 # are all dropped store +0 instead of being computed, the kept rows keep their bits (include/octic_hip.h:
 # octic_dense_gemm_nt_tokens_skip).  Read once at import from OCTIC_DENSE_SKIP (0 = off).
-def _dense_skip_from_env():
-    return os.environ.get("OCTIC_DENSE_SKIP", "1").strip() != "0"
-
-
-DENSE_NT_SKIP_DROPPED = _dense_skip_from_env()
+DENSE_NT_SKIP_DROPPED = _skip_from_env("OCTIC_DENSE_SKIP")
 
 
 def dense_skip_scale(rs, rps, M, rows_to=None):
-    """rs as the sample_scale of a dense_nt_kernel launch over M token rows - under exactly wgrad_skip_scale's conditions: the
-    switch is on and rs is one float32 entry per sample of rps rows on the GPU with rps * B == M; None for compact rows
-    (rows_to), the per-row factors of a ragged row tensor (rps 1), a traced value, eval and drop_path 0 (rs None)."""
-    if (not DENSE_NT_SKIP_DROPPED or rs is None or rows_to is not None or torch.compiler.is_compiling() or not rs.is_cuda
-            or rs.dtype != torch.float32 or rs.dim() != 1 or not rs.is_contiguous() or rps < 2 or rs.numel() * rps != M):
-        return None
-    return rs.detach()
+    """rs as the sample_scale of a dense_nt_kernel launch over M token rows: whole_sample_mask while the switch is on."""
+    return whole_sample_mask(rs, rps, M, rows_to) if DENSE_NT_SKIP_DROPPED else None
 
 
 # In the octic MLP the same factor makes the D8-GELU's work on a dropped sample void in both directions: gelu(h) of such a
@@ -534,21 +520,12 @@ def dense_skip_scale(rs, rps, M, rows_to=None):
 # factor travels to the GELU kernels, which then move no input bytes for those rows and store zeros (zeros, not nothing: the
 # readers multiply by 0, which is harmless on finite values only) - same launch shapes, same results.
 # Read once at import from OCTIC_LINEAR_SKIP (0 = off).
-def _linear_skip_from_env():
-    return os.environ.get("OCTIC_LINEAR_SKIP", "1").strip() != "0"
-
-
-LINEAR_SKIP_DROPPED = _linear_skip_from_env()
+LINEAR_SKIP_DROPPED = _skip_from_env("OCTIC_LINEAR_SKIP")
 
 
 def linear_skip_scale(rs, rps, M, rows_to=None):
-    """rs as the sample_scale of the octic MLP's row kernels over M token rows - under the conditions of wgrad_skip_scale: the
-    switch is on and rs is one float32 entry per sample of rps rows on the GPU with rps * B == M; None for compact rows
-    (rows_to), the per-row factors of a ragged row tensor (rps 1), a traced value, eval and drop_path 0 (rs None)."""
-    if (not LINEAR_SKIP_DROPPED or rs is None or rows_to is not None or torch.compiler.is_compiling() or not rs.is_cuda
-            or rs.dtype != torch.float32 or rs.dim() != 1 or not rs.is_contiguous() or rps < 2 or rs.numel() * rps != M):
-        return None
-    return rs.detach()
+    """rs as the sample_scale of the octic MLP's row kernels over M token rows: whole_sample_mask while the switch is on."""
+    return whole_sample_mask(rs, rps, M, rows_to) if LINEAR_SKIP_DROPPED else None
 
 
 # The long-K GEMMs of an octic block (fc2 with its residual tail, the input gradients of fc1 and qkv) run the ring kernel, which
@@ -556,11 +533,7 @@ def linear_skip_scale(rs, rps, M, rows_to=None):
 # rows, or rs itself in a fused tail) instead of one about the output's readers.  The kernel then runs its live 128-row tiles
 # first, dealt evenly over the XCDs, and writes zeros / the residual for the dead ones without loading them.  A switch of its
 # own, effective only while LINEAR_SKIP_DROPPED is on: OCTIC_RING_SKIP (0 = off), read once at import.
-def _ring_skip_from_env():
-    return os.environ.get("OCTIC_RING_SKIP", "1").strip() != "0"
-
-
-RING_SKIP_DROPPED = _ring_skip_from_env()
+RING_SKIP_DROPPED = _skip_from_env("OCTIC_RING_SKIP")
 
 
 def ring_skip_scale(rs, rps, M):
@@ -575,21 +548,12 @@ def ring_skip_scale(rs, rps, M):
 # gradients.  The same zeros make up half of what the qkv bias gradient sums.  With ROW_SKIP_DROPPED the factor travels to
 # the backward row kernels (include/octic_hip.h: octic_dense_layernorm_bwd_tail_skip, octic_layernorm_d8_bwd*_skip,
 # octic_dense_colsum_skip) - same launch shapes, same values.  Read once at import from OCTIC_ROW_SKIP (0 = off).
-def _row_skip_from_env():
-    return os.environ.get("OCTIC_ROW_SKIP", "1").strip() != "0"
-
-
-ROW_SKIP_DROPPED = _row_skip_from_env()
+ROW_SKIP_DROPPED = _skip_from_env("OCTIC_ROW_SKIP")
 
 
 def row_skip_scale(rs, rps, M, rows_to=None):
-    """rs as the sample_scale of a backward row kernel over M token rows - under exactly wgrad_skip_scale's conditions: the
-    switch is on and rs is one float32 entry per sample of rps rows on the GPU with rps * B == M; None for compact rows
-    (rows_to), the per-row factors of a ragged row tensor (rps 1), a traced value, eval and drop_path 0 (rs None)."""
-    if (not ROW_SKIP_DROPPED or rs is None or rows_to is not None or torch.compiler.is_compiling() or not rs.is_cuda
-            or rs.dtype != torch.float32 or rs.dim() != 1 or not rs.is_contiguous() or rps < 2 or rs.numel() * rps != M):
-        return None
-    return rs.detach()
+    """rs as the sample_scale of a backward row kernel over M token rows: whole_sample_mask while the switch is on."""
+    return whole_sample_mask(rs, rps, M, rows_to) if ROW_SKIP_DROPPED else None
 
 
 class RowSkipSlot:
@@ -1051,7 +1015,7 @@ def _wgrad_lib(g2, x2, wparam=None, sample_scale=None, rps=0):
             and g2.stride(1) == 1 and x2.stride(1) == 1
             and ops.dense_wgrad_ok(M, N, K, max(g2.stride(0), x2.stride(0)))):
         dest = ops.grad_dest(wparam, (N, K))
-        dw = ops.dense_wgrad_tn(g2, x2, out=dest, sample_scale=sample_scale, rows_per_sample=rps if sample_scale is not None else 0)
+        dw = ops.dense_wgrad_tn(g2, x2, out=dest, sample_scale=sample_scale, rows_per_sample=rps)
         if dest is not None:
             ops.grad_written(wparam)
         return dw
@@ -1149,7 +1113,7 @@ def _gemm_fwd(tag, x2, wb, b, cache, name, tokens, ss=None, rps=0):
     for the hand-written kernel only."""
     if tag in DENSE_HIP:
         return ops.dense_gemm_nt(x2, wb, 0, bias=_f32(b), name=f"dense_nt_kernel<{name}>", tokens=tokens, sample_scale=ss,
-                                 rows_per_sample=rps if ss is not None else 0)
+                                 rows_per_sample=rps)
     return _linear_lib(x2, wb, None if b is None else cache.b)
 
 
@@ -1157,16 +1121,16 @@ def _gemm_dgrad(g2, wt, wb, shape, dtype, ss=None, rps=0):
     """Input gradient g2 W as `shape` in `dtype`: csrc/dense_gemm.hip on the transposed copy wt where the cache made one (the
     input gradient is routed to it), else the BLAS library on wb.  ss / rps: the mask under which g2's rows of a dropped sample
     are exactly zero (dense_skip_scale), for the hand-written kernel only."""
-    gx = (ops.dense_gemm_nt(g2, wt, 0, name="dense_nt_kernel<dgrad>", tokens=_tok(shape), sample_scale=ss,
-                            rows_per_sample=rps if ss is not None else 0) if wt is not None
-          else _mm_lib(g2, wb))
+    gx = (ops.dense_gemm_nt(g2, wt, 0, name="dense_nt_kernel<dgrad>", tokens=_tok(shape), sample_scale=ss, rows_per_sample=rps)
+          if wt is not None else _mm_lib(g2, wb))
     return gx.view(shape).to(dtype)
 
 
-def _resid_tail_fwd(ctx, x, tag, a2, wb, b, cache, tokens, g32, rs32, rps, nw, nb, neps, rows_to, stream):
+def _resid_tail_fwd(ctx, x, tag, a2, wb, b, cache, tokens, g32, rs32, rps, nw, nb, neps, rows_to, stream, ds):
     """out = x + rs * gamma * br with br = a2 wb^T + b, the GEMM `tag` (proj / fc2): the tail of both branches of a standard
     block.  neps is not None: the residual add and LayerNorm(out; nw, nb, neps) in bf16 as one row pass -> (out, yn).
     rows_to: x are compact rows of `stream`, the result goes back into it through the row map -> stream.
+    ds: rs32 as the sample mask of the GEMM (dense_skip_scale): br meets rs = 0 in every row of a dropped sample.
     Returns (the node's outputs, the tensors _resid_tail_bwd wants back from ctx.save_for_backward)."""
     ctx.rows_to, ctx.x_shape = rows_to, x.shape
     ctx.tail = (neps is not None, rps, b is not None, nw is not None, nb is not None)
@@ -1174,7 +1138,7 @@ def _resid_tail_fwd(ctx, x, tag, a2, wb, b, cache, tokens, g32, rs32, rps, nw, n
     if neps is None and rows_to is None and tag in DENSE_HIP and DENSE_RESID_FUSED:
         br, out = ops.dense_gemm_nt(a2, wb, 2, bias=_f32(b), gamma=g32, rs=rs32, rps=rps, x=x2, name="dense_nt_kernel<resid>")
         return out.view(x.shape), (br, g32, rs32)
-    br = _gemm_fwd(tag, a2, wb, b, cache, tag, tokens, dense_skip_scale(rs32, rps, a2.shape[0], rows_to), rps)   # br meets rs = 0
+    br = _gemm_fwd(tag, a2, wb, b, cache, tag, tokens, ds, rps)
     if neps is not None:
         nw32, nb32 = _f32(nw), _f32(nb)
         out, yn, stats = ops.dense_resid_layernorm_fwd(x2, br, g32, rs32, rps, nw32, nb32, neps, torch.bfloat16)
@@ -1238,12 +1202,13 @@ class DenseLinearNTFn(torch.autograd.Function):
         xb = _c(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16))
         wb, wt = cache.get_nt(w, b, ("d" + tag) in DENSE_HIP and ctx.needs_input_grad[0])
         x2 = xb.reshape(-1, wb.shape[1])
-        ds = dense_skip_scale(rs, rps, x2.shape[0])
+        mask = whole_sample_mask(rs, rps, x2.shape[0])
+        ds = mask if DENSE_NT_SKIP_DROPPED else None
         y = _gemm_fwd(tag, x2, wb, b, cache, "plain", _tok(x.shape), ds, rps)
-        ss = wgrad_skip_scale(rs, rps, x2.shape[0])
+        ss = mask if WGRAD_SKIP_DROPPED else None
         # zero cotangent rows in (the attention backward of dO = 0), zero input-gradient rows out: the bias column sums and the
         # backward of the norm that produced x may skip them
-        rk = row_skip_scale(rs, rps, x2.shape[0])
+        rk = mask if ROW_SKIP_DROPPED else None
         row_skip_fill(x, rk, rps, x2.shape[0])
         ctx.rps = rps
         ctx.save_for_backward(x2, wb, wt, ss, ds, rk)  # wt is None unless the input gradient is routed to the HIP kernel
@@ -1258,7 +1223,7 @@ class DenseLinearNTFn(torch.autograd.Function):
         gx = _gemm_dgrad(g2, wt, wb, x_shape, x_dtype, ds, ctx.rps) if ctx.needs_input_grad[0] else None
         gb = None
         if has_b:
-            gb = (ops.dense_colsum(g2, rk, ctx.rps if rk is not None else 0)
+            gb = (ops.dense_colsum(g2, rk, ctx.rps)
                   if g2.is_cuda and g2.dtype == torch.bfloat16 and g2.shape[1] % 8 == 0
                   else g2.sum(0, dtype=torch.float32))
         pair = ctx.pair
@@ -1271,8 +1236,7 @@ class DenseLinearNTFn(torch.autograd.Function):
                 # one mask for both problems: only where both halves carry the same factors
                 both = ss if (ss is not None and pss is not None and prps == ctx.rps and pss.data_ptr() == ss.data_ptr()
                               and pss.numel() == ss.numel()) else None
-                dw, _ = ops.dense_wgrad_tn_pair(g2, x2, pg, px, dw1=pdw, dw0=dest, sample_scale=both,
-                                                rows_per_sample=ctx.rps if both is not None else 0)
+                dw, _ = ops.dense_wgrad_tn_pair(g2, x2, pg, px, dw1=pdw, dw0=dest, sample_scale=both, rows_per_sample=ctx.rps)
                 ops.grad_written(landed, ctx.wparam if dest is not None else None)
                 return gx, dw, gb, None, None, None, None, None
             pair.flush()
@@ -1294,8 +1258,9 @@ class DenseProjResidFn(torch.autograd.Function):
         ab = _c(a if a.dtype == torch.bfloat16 else a.to(torch.bfloat16))
         wb, wt = cache.get_nt(w, b, "dproj" in DENSE_HIP and ctx.needs_input_grad[1])
         a2 = ab.reshape(-1, wb.shape[1])
-        outs, tail = _resid_tail_fwd(ctx, x, "proj", a2, wb, b, cache, _tok(a.shape), _f32(gamma), _f32(rs), rps,
-                                     nw, nb, neps, rows_to, stream)
+        rs32 = _f32(rs)
+        outs, tail = _resid_tail_fwd(ctx, x, "proj", a2, wb, b, cache, _tok(a.shape), _f32(gamma), rs32, rps,
+                                     nw, nb, neps, rows_to, stream, dense_skip_scale(rs32, rps, a2.shape[0], rows_to))
         ctx.save_for_backward(a2, wb, wt, *tail)
         ctx.meta = (a.dtype, a.shape)
         return outs
@@ -1307,9 +1272,10 @@ class DenseProjResidFn(torch.autograd.Function):
         gx, gy, dgamma, colsum, dnw, dnb = _resid_tail_bwd(ctx, tail, gout, gyn,
                                                            ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
         rps = ctx.tail[1]
-        ds = dense_skip_scale(tail[2], rps, gy.shape[0], ctx.rows_to)     # gy = rs * gamma * gout: zero rows where rs is 0
+        mask = whole_sample_mask(tail[2], rps, gy.shape[0], ctx.rows_to)  # gy = rs * gamma * gout: zero rows where rs is 0
+        ds = mask if DENSE_NT_SKIP_DROPPED else None
         ga = _gemm_dgrad(gy, wt, wb, a_shape, a_dtype, ds, rps) if ctx.needs_input_grad[1] else None
-        ss = wgrad_skip_scale(tail[2], rps, gy.shape[0], ctx.rows_to)
+        ss = mask if WGRAD_SKIP_DROPPED else None
         if _pair_ready(ctx.pair, gy, a2) and ops.dense_wgrad_ok(gy.shape[0], gy.shape[1], a2.shape[1]):
             dw = ctx.pair.park(gy, a2, ctx.wparam, ss, rps)   # written by the qkv weight gradient's launch (or at the end of the pass)
         else:
@@ -1341,24 +1307,24 @@ class DenseMlpFn(torch.autograd.Function):
         factor = GELU_FACTOR and "fc1" in DENSE_HIP and w2t is not None
         ctx.factor = factor
         # fc1's outputs of a dropped sample are read by fc2 (whose output meets rs = 0) and by gradients whose dY rows are zero
-        ds = dense_skip_scale(rs32, rps, y2.shape[0], rows_to)
-        drps = rps if ds is not None else 0
+        mask = whole_sample_mask(rs32, rps, y2.shape[0], rows_to)
+        ds = mask if DENSE_NT_SKIP_DROPPED else None
         # fc1's input gradient is dh W1 with dh = gelu' * (gbr W2) and gbr = rs * gamma * gout: zero rows where rs is 0, so
         # the backward of the norm that produced y may skip them
-        row_skip_fill(y, row_skip_scale(rs32, rps, y2.shape[0], rows_to), rps, y2.shape[0])
+        row_skip_fill(y, mask if ROW_SKIP_DROPPED else None, rps, y2.shape[0])
         if "fc1" in DENSE_HIP and not any(ctx.needs_input_grad):
             # no backward will come (inference, the DINOv2 teacher): gelu(h) only, nothing kept (mode 6)
             a = ops.dense_gemm_nt(y2, w1b, 6, bias=_f32(b1), name="dense_nt_kernel<gelu-only>", tokens=_tok(y.shape),
-                                  sample_scale=ds, rows_per_sample=drps)
+                                  sample_scale=ds, rows_per_sample=rps)
             h = a
         elif "fc1" in DENSE_HIP:
             h, a = ops.dense_gemm_nt(y2, w1b, 4 if factor else 1, bias=_f32(b1), name="dense_nt_kernel<gelu>",
-                                     tokens=_tok(y.shape), sample_scale=ds, rows_per_sample=drps)
+                                     tokens=_tok(y.shape), sample_scale=ds, rows_per_sample=rps)
         else:
             h = _linear_lib(y2, w1b, None if b1 is None else c1.b)
             a = torch.nn.functional.gelu(h)
         outs, tail = _resid_tail_fwd(ctx, x, "fc2", a, w2b, b2, c2, _tok(y.shape), g32, rs32, rps,
-                                     nw, nb, neps, rows_to, stream)
+                                     nw, nb, neps, rows_to, stream, ds)
         ctx.save_for_backward(y2, h, a, w1b, w1t, w2b, w2t, *tail)
         ctx.meta = (b1 is not None, y.dtype, y.shape)
         return outs
@@ -1370,19 +1336,19 @@ class DenseMlpFn(torch.autograd.Function):
         gx, gbr, dgamma, db2, dnw, dnb = _resid_tail_bwd(ctx, tail, gout, gyn,
                                                          ctx.needs_input_grad[11] or ctx.needs_input_grad[12])
         rps = ctx.tail[1]
-        ds = dense_skip_scale(tail[2], rps, gbr.shape[0], ctx.rows_to)    # gbr = rs * gamma * gout: zero rows where rs is 0
-        drps = rps if ds is not None else 0
+        mask = whole_sample_mask(tail[2], rps, gbr.shape[0], ctx.rows_to)  # gbr = rs * gamma * gout: zero rows where rs is 0
+        ds = mask if DENSE_NT_SKIP_DROPPED else None
         if w2t is not None:
             md = 5 if ctx.factor else 3
             if has_b1:                                                                  # gelu'(h) * (gbr W2), + db1
                 dh, db1 = ops.dense_gemm_nt(gbr, w2t, md, h=h, name="dense_nt_kernel<dgelu>", want_colsum=True,
-                                            tokens=_tok(y_shape), sample_scale=ds, rows_per_sample=drps)
+                                            tokens=_tok(y_shape), sample_scale=ds, rows_per_sample=rps)
             else:
                 dh, db1 = ops.dense_gemm_nt(gbr, w2t, md, h=h, name="dense_nt_kernel<dgelu>", tokens=_tok(y_shape),
-                                            sample_scale=ds, rows_per_sample=drps), None
+                                            sample_scale=ds, rows_per_sample=rps), None
         else:
             dh, db1 = ops.dense_gelu_bwd(h, _mm_lib(gbr, w2b), want_colsum=has_b1)
-        ss = wgrad_skip_scale(tail[2], rps, gbr.shape[0], ctx.rows_to)    # gbr = rs * gamma * gout, dh = gelu' * (gbr W2)
+        ss = mask if WGRAD_SKIP_DROPPED else None                         # gbr = rs * gamma * gout, dh = gelu' * (gbr W2)
         gw2 = _wgrad_lib(gbr, a, ctx.wparams[1], ss, rps)
         gw1 = _wgrad_lib(dh, y2, ctx.wparams[0], ss, rps)
         gy = _gemm_dgrad(dh, w1t, w1b, y_shape, y_dtype, ds, rps) if ctx.needs_input_grad[0] else None   # dh = gelu' * 0
@@ -1413,13 +1379,14 @@ class DenseSwigluFn(torch.autograd.Function):
         w3b, w3t = c2.get_nt(w3, b3, need_t and "dfc2" in DENSE_HIP and ops.dense_gemm_ok(M, H, w3.shape[0]))
         g32, rs32 = _f32(gamma), _f32(rs)
         # x12 of a dropped sample is read by the gate alone, whose output meets rs = 0 behind w3 and zero dY rows in the gradients
-        ds = dense_skip_scale(rs32, rps, M, rows_to)
+        mask = whole_sample_mask(rs32, rps, M, rows_to)
+        ds = mask if DENSE_NT_SKIP_DROPPED else None
         # w12's input gradient is dx12 W12 with dx12 = gate'(x12) * (gbr W3) and gbr = rs * gamma * gout: zero rows where rs is 0
-        row_skip_fill(y, row_skip_scale(rs32, rps, M, rows_to), rps, M)
+        row_skip_fill(y, mask if ROW_SKIP_DROPPED else None, rps, M)
         x12 = _gemm_fwd("fc1" if hip12 else "fc1-library", y2, w12b, b12, c1, "plain", _tok(y.shape), ds, rps)
         a = ops.swiglu_fwd(x12, H)
         outs, tail = _resid_tail_fwd(ctx, x, "fc2" if hip3 else "fc2-library", a, w3b, b3, c2, _tok(y.shape), g32, rs32, rps,
-                                     nw, nb, neps, rows_to, stream)
+                                     nw, nb, neps, rows_to, stream, ds)
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(y2, x12, a, w12b, w12t, w3b, w3t, *tail)
         ctx.meta = (b12 is not None, y.dtype, y.shape)
@@ -1432,10 +1399,11 @@ class DenseSwigluFn(torch.autograd.Function):
         gx, gbr, dgamma, db3, dnw, dnb = _resid_tail_bwd(ctx, tail, gout, gyn,
                                                          ctx.needs_input_grad[11] or ctx.needs_input_grad[12])
         rps = ctx.tail[1]
-        ds = dense_skip_scale(tail[2], rps, gbr.shape[0], ctx.rows_to)    # gbr = rs * gamma * gout: zero rows where rs is 0
+        mask = whole_sample_mask(tail[2], rps, gbr.shape[0], ctx.rows_to)  # gbr = rs * gamma * gout: zero rows where rs is 0
+        ds = mask if DENSE_NT_SKIP_DROPPED else None
         ga = _gemm_dgrad(gbr, w3t, w3b, (*y_shape[:-1], a.shape[1]), a.dtype, ds, rps)
         dx12, db12 = ops.swiglu_bwd(x12, ga, want_colsum=has_b12)
-        ss = wgrad_skip_scale(tail[2], rps, gbr.shape[0], ctx.rows_to)    # dx12 = gate' * (gbr W3): zero rows with gbr's
+        ss = mask if WGRAD_SKIP_DROPPED else None                         # dx12 = gate' * (gbr W3): zero rows with gbr's
         gw3 = _wgrad_lib(gbr, a, ctx.wparams[1], ss, rps)
         gw12 = _wgrad_lib(dx12, y2, ctx.wparams[0], ss, rps)
         gy = _gemm_dgrad(dx12, w12t, w12b, y_shape, y_dtype, ds, rps) if ctx.needs_input_grad[0] else None

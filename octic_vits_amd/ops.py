@@ -185,9 +185,11 @@ def split_packed(t, c):
 
 
 # ------------------------------------------------------------------------------------------ launches
-def _row_sample_scale(sample_scale, rows_per_sample, M, ref, what):
-    """(sample_scale, rows_per_sample) as a *_skip row kernel takes them: (None, 0) without a mask; a mask is one float32
-    factor per sample of rows_per_sample consecutive rows on the operands' device."""
+def _sample_scale(sample_scale, rows_per_sample, M, ref, what):
+    """(sample_scale, rows_per_sample) as every *_skip entry point takes them, for the launcher `what` over M rows of `ref`:
+    (None, 0) without a mask; a mask is one float32 factor per sample of rows_per_sample consecutive rows, contiguous, on the
+    operands' device (attention: M = B samples of one row).  Anything else is a ValueError here, before any launch; whether
+    rows_per_sample is positive and divides M is the library's check (OCTIC_ESHAPE)."""
     if sample_scale is None:
         return None, 0
     rps = int(rows_per_sample)
@@ -201,7 +203,7 @@ def _row_sample_scale(sample_scale, rows_per_sample, M, ref, what):
 def gelu_fwd(xv, yv, M, c, dtype, ref, sample_scale=None, rows_per_sample=0):
     """sample_scale / rows_per_sample: the stochastic-depth factor of the branch (octic_gelu_d8_fwd_skip) - input rows of a
     sample whose factor is 0 are not read, its output rows are +0."""
-    ss, rps = _row_sample_scale(sample_scale, rows_per_sample, M, ref, "gelu_fwd")
+    ss, rps = _sample_scale(sample_scale, rows_per_sample, M, ref, "gelu_fwd")
     t = KERNEL_TIMER.start()
     check(lib().octic_gelu_d8_fwd_skip(ctypes.byref(xv), ctypes.byref(yv), M, c, dt_code(dtype), _p(ss), rps, _stream(ref)))
     # (bytes stay the full batch's with a sample_scale: the host does not know the kept count without a sync)
@@ -210,7 +212,7 @@ def gelu_fwd(xv, yv, M, c, dtype, ref, sample_scale=None, rows_per_sample=0):
 
 def gelu_bwd(gv, xv, ov, M, c, dtype, ref, sample_scale=None, rows_per_sample=0):
     """sample_scale / rows_per_sample: as in gelu_fwd (octic_gelu_d8_bwd_skip: neither g nor x is read for a dropped sample)."""
-    ss, rps = _row_sample_scale(sample_scale, rows_per_sample, M, ref, "gelu_bwd")
+    ss, rps = _sample_scale(sample_scale, rows_per_sample, M, ref, "gelu_bwd")
     t = KERNEL_TIMER.start()
     check(lib().octic_gelu_d8_bwd_skip(ctypes.byref(gv), ctypes.byref(xv), ctypes.byref(ov), M, c, dt_code(dtype), _p(ss), rps,
                                        _stream(ref)))
@@ -233,22 +235,18 @@ def layernorm_fwd(x, alpha5, beta, eps, out_dtype, c, want_stats=True):
 def layernorm_bwd(g, x, stats, alpha5, dres, c, want_param_grads=True, sample_scale=None, rows_per_sample=0):
     """Returns (dx f32 packed, dalpha5 or None, dbeta or None).  dx = dres + LN'(g).
     sample_scale / rows_per_sample: the factor of the branch this norm opens, a promise that the rows of g are zero where it
-    is 0 (octic_layernorm_d8_bwd_skip: those rows of g, x and stats stay unread)."""
+    is 0 (octic_layernorm_d8_bwd_skip: those rows of g, x and stats stay unread); a malformed mask is a ValueError."""
     M = x.numel() // (8 * c)
+    ss, srps = _sample_scale(sample_scale, rows_per_sample, M, x, "layernorm_bwd")
     dx = torch.empty_like(x)
     nblk = lib().octic_layernorm_d8_bwd_blocks(M)
     partials = torch.empty((nblk, 2, 8 * c), dtype=torch.float32, device=x.device)
     gv, xv, dv = pview(g, c), pview(x, c), pview(dx, c)
     rv = pview(dres, c) if dres is not None else None
     t = KERNEL_TIMER.start()
-    if sample_scale is not None:
-        check(lib().octic_layernorm_d8_bwd_skip(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
-                                                ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
-                                                M, c, dt_code(g.dtype), _p(sample_scale), int(rows_per_sample), _stream(x)))
-    else:
-        check(lib().octic_layernorm_d8_bwd(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
-                                           ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
-                                           M, c, dt_code(g.dtype), _stream(x)))
+    check(lib().octic_layernorm_d8_bwd_skip(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
+                                            ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
+                                            M, c, dt_code(g.dtype), _p(ss), srps, _stream(x)))
     KERNEL_TIMER.stop(t, f"ln_bwd_kernel<{_DTN[g.dtype]}>", M * 8 * c * (g.element_size() + 8 + (4 if dres is not None else 0)))
     if not want_param_grads or alpha5 is None:
         return dx, None, None
@@ -297,6 +295,7 @@ def layernorm_bwd_cast(g, x, stats, alpha5, dres, c, rs, rps, want_param_grads=T
     """layernorm_bwd that also returns bf16(rs[row // rps] * dx): (dx, dalpha5, dbeta, gcast).  sample_scale / rows_per_sample:
     as in layernorm_bwd (the factor of the branch this norm opens; rs is that of the branch that ends in front of it)."""
     M = x.numel() // (8 * c)
+    ss, srps = _sample_scale(sample_scale, rows_per_sample, M, x, "layernorm_bwd_cast")
     dx = torch.empty_like(x)
     gc = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     nblk = lib().octic_layernorm_d8_bwd_blocks(M)
@@ -304,15 +303,9 @@ def layernorm_bwd_cast(g, x, stats, alpha5, dres, c, rs, rps, want_param_grads=T
     gv, xv, dv = pview(g, c), pview(x, c), pview(dx, c)
     rv = pview(dres, c) if dres is not None else None
     t = KERNEL_TIMER.start()
-    if sample_scale is not None:
-        check(lib().octic_layernorm_d8_bwd_cast_skip(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
-                                                     ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv),
-                                                     _p(partials), M, c, _p(rs), int(rps), _p(gc), _p(sample_scale),
-                                                     int(rows_per_sample), _stream(x)))
-    else:
-        check(lib().octic_layernorm_d8_bwd_cast(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
-                                                ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
-                                                M, c, _p(rs), int(rps), _p(gc), _stream(x)))
+    check(lib().octic_layernorm_d8_bwd_cast_skip(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
+                                                 ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
+                                                 M, c, _p(rs), int(rps), _p(gc), _p(ss), srps, _stream(x)))
     KERNEL_TIMER.stop(t, "ln_bwd_kernel<bf16>", M * 8 * c * (2 + 8 + (4 if dres is not None else 0) + 2))
     if not want_param_grads or alpha5 is None:
         return dx, None, None, gc
@@ -380,20 +373,6 @@ def grad_written(*params):
                 w(prm.data_ptr())
 
 
-def _wgrad_sample_scale(sample_scale, rows_per_sample, M, ref):
-    """The stochastic-depth mask of a TN launch as the kernel reads it (octic_dense_wgrad_tn_skip): (None, 0), or the
-    contiguous float32 factors - one per sample of rows_per_sample token rows - on the operands' device.  Whether
-    rows_per_sample divides M is the library's check (OCTIC_ESHAPE)."""
-    if sample_scale is None:
-        return None, 0
-    rps = int(rows_per_sample)
-    if (sample_scale.dtype != torch.float32 or sample_scale.device != ref.device or not sample_scale.is_contiguous()
-            or (rps > 0 and M % rps == 0 and sample_scale.numel() != M // rps)):
-        raise ValueError("dense_wgrad_tn: sample_scale must be a contiguous float32 tensor of M / rows_per_sample entries on "
-                         "the operands' device")
-    return sample_scale, rps
-
-
 def dense_wgrad_tn(dy, x, name=None, out=None, sample_scale=None, rows_per_sample=0):
     """dW[N,K] = dy[M,N]^T @ x[M,K] in f32 on csrc/dense_wgrad.hip (out: write it there).  sample_scale ([M / rows_per_sample]
     f32): the stochastic-depth factor of the branch dy belongs to - a 0 promises that the sample's dy rows are zero, and the
@@ -403,7 +382,7 @@ def dense_wgrad_tn(dy, x, name=None, out=None, sample_scale=None, rows_per_sampl
     K = x.shape[1]
     if dy.stride(1) != 1 or x.stride(1) != 1 or x.shape[0] != M:
         raise ValueError("dense_wgrad_tn: operands must be [M,N] / [M,K] row-major")
-    ss, rps = _wgrad_sample_scale(sample_scale, rows_per_sample, M, dy)
+    ss, rps = _sample_scale(sample_scale, rows_per_sample, M, dy, "dense_wgrad_tn")
     need = int(lib().octic_dense_wgrad_workspace_bytes(M, N, K))
     ws = _DW_WS.get(dy.device)
     if ws is None or ws.numel() < need:          # one workspace per device: launches on a stream are serial
@@ -432,7 +411,7 @@ def dense_wgrad_tn_pair(dy0, x0, dy1, x1, dw1=None, dw0=None, sample_scale=None,
     N1, K = dy1.shape[1], x0.shape[1]
     if not (dy1.shape[0] == M and x0.shape[0] == M and x1.shape == (M, K) and all(t.stride(1) == 1 for t in (dy0, x0, dy1, x1))):
         raise ValueError("dense_wgrad_tn_pair: operands must be [M,N0] / [M,K] / [M,N1] / [M,K] row-major")
-    ss, rps = _wgrad_sample_scale(sample_scale, rows_per_sample, M, dy0)
+    ss, rps = _sample_scale(sample_scale, rows_per_sample, M, dy0, "dense_wgrad_tn_pair")
     need = int(lib().octic_dense_wgrad_pair_workspace_bytes(M, N0, N1, K))
     ws = _DW_WS.get(dy0.device)
     if ws is None or ws.numel() < need:
@@ -455,8 +434,8 @@ def linear_fwd(xv, w5, bias, yv, M, cin, cout, dtype, out_dtype, ref, resid_v=No
     dropped sample may stay unwritten).  dropped / dropped_rps: the same factor under the other contract
     (octic_linear_d8_fwd_dropped): the input rows of a dropped sample are zero (plain launch, no bias) or rs is that mask (fused);
     every output row is written.  One mask per call.  Timer name, bytes and FLOP stay the full batch's."""
-    ss, srps = _row_sample_scale(sample_scale, skip_rps, M, ref, "linear_fwd")
-    dr, drps = _row_sample_scale(dropped, dropped_rps, M, ref, "linear_fwd")
+    ss, srps = _sample_scale(sample_scale, skip_rps, M, ref, "linear_fwd")
+    dr, drps = _sample_scale(dropped, dropped_rps, M, ref, "linear_fwd")
     if ss is not None and dr is not None:
         raise ValueError("linear_fwd: sample_scale and dropped are two contracts for one mask - pass one of them")
     t = KERNEL_TIMER.start()
@@ -593,16 +572,6 @@ def prep_views(flat, cin, cout, transposed):
     return out
 
 
-def _sample_scale(sample_scale, B, ref):
-    """The [B] float32 stochastic-depth factors of a launch as the kernels read them, or None (octic_attn_*_skip)."""
-    if sample_scale is None:
-        return None
-    if (sample_scale.dtype != torch.float32 or sample_scale.device != ref.device or sample_scale.numel() != B
-            or not sample_scale.is_contiguous()):
-        raise ValueError("attention: sample_scale must be a contiguous float32 tensor of B entries on the operands' device")
-    return sample_scale
-
-
 def attn_fwd(q, k, v, scale, out=None, sample_scale=None):
     """q,k,v: [B,H,T,hd] bf16 or float32 views with a common stride set (last dim contiguous) -> (o [B,H,T,hd],
     lse [B,H,T]); out: an optional [B,H,T,hd] view (last dim contiguous, 16-byte rows) that receives o.  float32
@@ -623,7 +592,7 @@ def attn_fwd(q, k, v, scale, out=None, sample_scale=None):
         check(lib().octic_attn_fwd_f32(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, T, hd, st[0], st[1], st[2],
                                        o.stride(0), o.stride(1), o.stride(2), float(scale), _stream(q)))
     else:
-        ss = _sample_scale(sample_scale, B, q)
+        ss, _ = _sample_scale(sample_scale, 1, B, q, "attn_fwd")
         check(lib().octic_attn_fwd_skip(_p(q), _p(k), _p(v), _p(o), _p(lse), B, H, T, hd, st[0], st[1], st[2],
                                         o.stride(0), o.stride(1), o.stride(2), float(scale), _p(ss), _stream(q)))
     # (bytes and FLOP stay the full batch's with a sample_scale: the host does not know the kept count without a sync)
@@ -705,7 +674,7 @@ def attn_bwd(q, k, v, o, dout, lse, scale, dq, dk, dv, sample_scale=None):
     delta = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
     f32 = q.dtype == torch.float32
     phases = _attn_bwd_phases(T, hd, dt_code(q.dtype), (st[2], so[2], sg[2]))
-    ss = None if f32 else _sample_scale(sample_scale, B, q)
+    ss = None if f32 else _sample_scale(sample_scale, 1, B, q, "attn_bwd")[0]
     for phase, name, nbytes, flops in phases:
         t = KERNEL_TIMER.start()
         args = (_p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, H,
@@ -728,9 +697,10 @@ def attn_fwd_packed(qkv, H, c, scale, out=None, sample_scale=None):
     B, T = qkv.shape[0], qkv.shape[1]
     o = out if out is not None else torch.empty((B, T, 8 * c), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
+    ss, _ = _sample_scale(sample_scale, 1, B, qkv, "attn_fwd_packed")
     t = KERNEL_TIMER.start()
     check(lib().octic_attn_fwd_packed_skip(_p(qkv), _p(o), _p(lse), B, H, T, c, qkv.stride(1), o.stride(1), float(scale),
-                                           _p(_sample_scale(sample_scale, B, qkv)), _stream(qkv)))
+                                           _p(ss), _stream(qkv)))
     KERNEL_TIMER.stop(t, _attn_fwd_name(T, 8 * (c // H), ld=(qkv.stride(1), o.stride(1), 0)), 4 * B * T * 8 * c * 2,
                       4.0 * B * T * T * 8 * c)
     return o, lse
@@ -741,7 +711,7 @@ def attn_bwd_packed(qkv, o, dout, lse, H, c, scale, out=None, sample_scale=None)
     B, T = qkv.shape[0], qkv.shape[1]
     dqkv = out if out is not None else torch.empty_like(qkv)
     delta = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
-    ss = _sample_scale(sample_scale, B, qkv)
+    ss, _ = _sample_scale(sample_scale, 1, B, qkv, "attn_bwd_packed")
     for phase, name, nbytes, flops in _attn_bwd_phases(T, 8 * (c // H), ld=(qkv.stride(1), o.stride(1), dqkv.stride(1))):
         t = KERNEL_TIMER.start()
         check(lib().octic_attn_bwd_packed_skip(_p(qkv), _p(o), _p(dout), _p(lse), _p(delta), _p(dqkv), B, H, T, c,
@@ -1051,9 +1021,11 @@ def dense_layernorm_bwd_tail(gy, x, w, stats, dres, yb, gamma, rs, rps, want_par
     """dense_layernorm_bwd followed by scale_residual_bwd on its result, one row pass.
     Returns (dx f32, dw, db, gyb bf16 = rs*gamma*dx, dgamma, gamma * colsum(rs*dx)).
     sample_scale / rows_per_sample: the factor of the branch this norm opens, a promise that the rows of gy are zero where it
-    is 0 (octic_dense_layernorm_bwd_tail_skip: those rows of gy, x and stats stay unread, and yb's where rs is 0)."""
+    is 0 (octic_dense_layernorm_bwd_tail_skip: those rows of gy, x and stats stay unread, and yb's where rs is 0); a malformed
+    mask is a ValueError."""
     d = x.shape[-1]
     rows = x.numel() // d
+    ss, srps = _sample_scale(sample_scale, rows_per_sample, rows, x, "dense_layernorm_bwd_tail")
     dx = torch.empty_like(x)
     gyb = torch.empty(x.shape, dtype=yb.dtype, device=x.device)
     nblk = lib().octic_dense_blocks(rows)
@@ -1061,13 +1033,8 @@ def dense_layernorm_bwd_tail(gy, x, w, stats, dres, yb, gamma, rs, rps, want_par
     want2 = want_gamma or want_colsum
     p2 = torch.empty((nblk, 2, d), dtype=torch.float32, device=x.device) if want2 else None
     t = KERNEL_TIMER.start()
-    if sample_scale is not None:
-        check(lib().octic_dense_layernorm_bwd_tail_skip(_p(gy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(p1), _p(yb),
-                                                        _p(gamma), _p(rs), int(rps), _p(gyb), _p(p2), rows, d,
-                                                        _p(sample_scale), int(rows_per_sample), _stream(x)))
-    else:
-        check(lib().octic_dense_layernorm_bwd_tail(_p(gy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(p1), _p(yb),
-                                                   _p(gamma), _p(rs), int(rps), _p(gyb), _p(p2), rows, d, _stream(x)))
+    check(lib().octic_dense_layernorm_bwd_tail_skip(_p(gy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(p1), _p(yb), _p(gamma),
+                                                    _p(rs), int(rps), _p(gyb), _p(p2), rows, d, _p(ss), srps, _stream(x)))
     KERNEL_TIMER.stop(t, "dense_ln_bwd_tail_kernel<bf16>", rows * d * (2 + 8 + (4 if dres is not None else 0) + 4))
     dw = db = dgamma = colsum = None
     if want_param_grads:
@@ -1268,19 +1235,17 @@ def _dense_ws(M, N, K, dev):
 
 def dense_colsum(g, sample_scale=None, rows_per_sample=0):
     """f32 column sums of a bf16 [rows, d] tensor (unit column stride): the bias gradient of a dense nn.Linear.
-    sample_scale / rows_per_sample: a promise that the rows of a sample are zero where its entry is 0 (they stay unread)."""
+    sample_scale / rows_per_sample: a promise that the rows of a sample are zero where its entry is 0 (they stay unread); a
+    malformed mask is a ValueError."""
     _require_cuda(g)
     rows, d = g.shape
     if g.stride(1) != 1:
         raise ValueError("dense_colsum: rows must be contiguous along d")
+    ss, srps = _sample_scale(sample_scale, rows_per_sample, rows, g, "dense_colsum")
     nblk = lib().octic_dense_gelu_blocks()
     partials = torch.empty((nblk, d), dtype=torch.float32, device=g.device)
     t = KERNEL_TIMER.start()
-    if sample_scale is not None:
-        check(lib().octic_dense_colsum_skip(_p(g), rows, d, g.stride(0), _p(partials), _p(sample_scale), int(rows_per_sample),
-                                            _stream(g)))
-    else:
-        check(lib().octic_dense_colsum(_p(g), rows, d, g.stride(0), _p(partials), _stream(g)))
+    check(lib().octic_dense_colsum_skip(_p(g), rows, d, g.stride(0), _p(partials), _p(ss), srps, _stream(g)))
     KERNEL_TIMER.stop(t, "dense_colsum_kernel", rows * d * 2)
     out = torch.empty(d, dtype=torch.float32, device=g.device)
     half = d // 2
@@ -1313,7 +1278,8 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
     a, b bf16 2-D, K contiguous.  tokens: the rows are whole images of that many tokens ([B, tokens, K] flattened) - 257 lets the
     launch use per-image row panels + the class-token kernel (octic_dense_gemm_nt_tokens); 0 = unknown.
     sample_scale / rows_per_sample: the stochastic-depth mask of octic_dense_gemm_nt_tokens_skip - f32 [M / rows_per_sample] on
-    the device, 0 = every reader of that sample's output rows accepts the computed result or +0 (never with mode 2)."""
+    the device, 0 = every reader of that sample's output rows accepts the computed result or +0 (never with mode 2); a
+    malformed mask is a ValueError."""
     _require_cuda(a)
     M, K = a.shape
     N = b.shape[0]
@@ -1326,26 +1292,20 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
     tokens = int(tokens) if (tokens and M % int(tokens) == 0) else 0
     if sample_scale is not None and mode == 2:
         raise ValueError("dense_gemm_nt: the fused residual tail (mode 2) takes no sample_scale")
-    # the plan in force: colsum rows, the timer name and (through the library's own sizing) the workspace belong to it
-    plan = ((lambda: dense_plan(M, N, K, mode, tokens)) if sample_scale is None else
-            (lambda: dense_plan_dropped(M, N, K, mode, tokens, rows_per_sample)))
-    cs_rows = plan()[1] if (mode in (3, 5) and want_colsum) else 0
+    ss, srps = _sample_scale(sample_scale, rows_per_sample, M, a, "dense_gemm_nt")
+    # the plan in force, with a mask or without: colsum rows, the timer name and (through the library's own sizing) the
+    # workspace belong to it
+    cs_rows = dense_plan(M, N, K, mode, tokens)[1] if (mode in (3, 5) and want_colsum) else 0
     cs = torch.empty((cs_rows, N), dtype=torch.float32, device=a.device) if cs_rows else None
     t = KERNEL_TIMER.start()
-    if sample_scale is None:
-        check(lib().octic_dense_gemm_nt_tokens(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias),
-                                               _p(gamma), _p(rs), int(rps), _p(x), _p(out), _p(h), _p(cs), _p(ws), tokens,
-                                               _stream(a)))
-    else:
-        check(lib().octic_dense_gemm_nt_tokens_skip(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N,
-                                                    _p(bias), _p(gamma), _p(rs), int(rps), _p(x), _p(out), _p(h), _p(cs),
-                                                    _p(sample_scale), int(rows_per_sample), _p(ws), tokens,
-                                                    _stream(a)))
+    check(lib().octic_dense_gemm_nt_tokens_skip(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias),
+                                                _p(gamma), _p(rs), int(rps), _p(x), _p(out), _p(h), _p(cs), _p(ss), srps,
+                                                _p(ws), tokens, _stream(a)))
     if t is not None:
         nb = 2 * (M * K + N * K + M * N * (2 if mode in (1, 3, 4, 5) else 1)) + (8 * M * N if mode == 2 else 0)
         # "@320": the launch ran the 256 x 320 tile (kernel symbol dense_nt_kernel<0, 5>), else <mode, 4>
         # (with per-image panels the timed interval also holds the class-token launch behind the panels')
-        wide = "@320" if plan()[0] == 320 else ""
+        wide = "@320" if dense_plan(M, N, K, mode, tokens)[0] == 320 else ""
         KERNEL_TIMER.stop(t, (name or f"dense_nt_kernel<{mode}>") + wide, nb, 2.0 * M * N * K)
     if mode in (1, 4):
         return c, c2

@@ -25,11 +25,11 @@ def test_skip_entry_points_are_declared_prototyped_and_exported():
 def test_switch_is_read_from_the_environment(monkeypatch):
     import octic_vits_amd.functional as OF
     monkeypatch.delenv("OCTIC_ATTN_SKIP", raising=False)
-    assert OF._attn_skip_from_env() is True                         # on by default
+    assert OF._skip_from_env("OCTIC_ATTN_SKIP") is True    # on by default
     monkeypatch.setenv("OCTIC_ATTN_SKIP", "0")
-    assert OF._attn_skip_from_env() is False
+    assert OF._skip_from_env("OCTIC_ATTN_SKIP") is False
     monkeypatch.setenv("OCTIC_ATTN_SKIP", "1")
-    assert OF._attn_skip_from_env() is True
+    assert OF._skip_from_env("OCTIC_ATTN_SKIP") is True
     assert isinstance(OF.ATTN_SKIP_DROPPED, bool)
 
 
@@ -42,11 +42,11 @@ def test_only_per_sample_gpu_factors_reach_the_kernels(monkeypatch):
     monkeypatch.setattr(OF, "ATTN_SKIP_DROPPED", False)
     assert OF.skip_scale(rs, 3) is None
     from octic_vits_amd import ops
-    assert ops._sample_scale(None, 3, rs) is None
-    assert ops._sample_scale(rs, 3, rs) is rs
+    assert ops._sample_scale(None, 1, 3, rs, "attn_fwd") == (None, 0)
+    assert ops._sample_scale(rs, 1, 3, rs, "attn_fwd")[0] is rs
     for bad in (rs.double(), rs[:2], torch.zeros(6)[::2]):
         with pytest.raises(ValueError, match="sample_scale"):
-            ops._sample_scale(bad, 3, rs)
+            ops._sample_scale(bad, 1, 3, rs, "attn_fwd")
 
 
 def test_rejections_come_back_before_any_launch():

@@ -229,11 +229,11 @@ def test_new_entry_points_are_declared_prototyped_and_exported():
 def test_switch_is_read_from_the_environment(monkeypatch):
     import octic_vits_amd.functional as OF
     monkeypatch.delenv("OCTIC_DENSE_SKIP", raising=False)
-    assert OF._dense_skip_from_env() is True                         # on by default
+    assert OF._skip_from_env("OCTIC_DENSE_SKIP") is True    # on by default
     monkeypatch.setenv("OCTIC_DENSE_SKIP", "0")
-    assert OF._dense_skip_from_env() is False
+    assert OF._skip_from_env("OCTIC_DENSE_SKIP") is False
     monkeypatch.setenv("OCTIC_DENSE_SKIP", "1")
-    assert OF._dense_skip_from_env() is True
+    assert OF._skip_from_env("OCTIC_DENSE_SKIP") is True
     assert isinstance(OF.DENSE_NT_SKIP_DROPPED, bool)
 
 

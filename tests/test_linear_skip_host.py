@@ -13,11 +13,11 @@ NEW = ("octic_linear_d8_fwd_skip", "octic_gelu_d8_fwd_skip", "octic_gelu_d8_bwd_
 def test_switch_reads_the_environment(monkeypatch):
     import octic_vits_amd.functional as OF
     monkeypatch.delenv("OCTIC_LINEAR_SKIP", raising=False)
-    assert OF._linear_skip_from_env() is True                       # on by default
+    assert OF._skip_from_env("OCTIC_LINEAR_SKIP") is True    # on by default
     monkeypatch.setenv("OCTIC_LINEAR_SKIP", "0")
-    assert OF._linear_skip_from_env() is False
+    assert OF._skip_from_env("OCTIC_LINEAR_SKIP") is False
     monkeypatch.setenv("OCTIC_LINEAR_SKIP", "1")
-    assert OF._linear_skip_from_env() is True
+    assert OF._skip_from_env("OCTIC_LINEAR_SKIP") is True
     assert isinstance(OF.LINEAR_SKIP_DROPPED, bool)
 
 

@@ -148,9 +148,9 @@ def test_entry_point_refusals():
 def test_switch_reads_the_environment(monkeypatch):
     import octic_vits_amd.functional as OF
     monkeypatch.delenv("OCTIC_RING_SKIP", raising=False)
-    assert OF._ring_skip_from_env() is True
+    assert OF._skip_from_env("OCTIC_RING_SKIP") is True
     monkeypatch.setenv("OCTIC_RING_SKIP", "0")
-    assert OF._ring_skip_from_env() is False
+    assert OF._skip_from_env("OCTIC_RING_SKIP") is False
     assert isinstance(OF.RING_SKIP_DROPPED, bool)
 
     class Factors:

@@ -61,11 +61,11 @@ def test_the_predicate_is_that_of_the_weight_gradient_skip(OF):
 def test_the_switch_reads_the_environment(monkeypatch):
     import octic_vits_amd.functional as OF
     monkeypatch.delenv("OCTIC_ROW_SKIP", raising=False)
-    assert OF._row_skip_from_env() is True
+    assert OF._skip_from_env("OCTIC_ROW_SKIP") is True
     monkeypatch.setenv("OCTIC_ROW_SKIP", "0")
-    assert OF._row_skip_from_env() is False
+    assert OF._skip_from_env("OCTIC_ROW_SKIP") is False
     monkeypatch.setenv("OCTIC_ROW_SKIP", " 1 ")
-    assert OF._row_skip_from_env() is True
+    assert OF._skip_from_env("OCTIC_ROW_SKIP") is True
 
 
 class _Ctx:

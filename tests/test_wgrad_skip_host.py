@@ -26,11 +26,11 @@ def test_skip_entry_points_are_declared_prototyped_and_exported():
 def test_switch_is_read_from_the_environment(monkeypatch):
     import octic_vits_amd.functional as OF
     monkeypatch.delenv("OCTIC_WGRAD_SKIP", raising=False)
-    assert OF._wgrad_skip_from_env() is True                        # on by default
+    assert OF._skip_from_env("OCTIC_WGRAD_SKIP") is True    # on by default
     monkeypatch.setenv("OCTIC_WGRAD_SKIP", "0")
-    assert OF._wgrad_skip_from_env() is False
+    assert OF._skip_from_env("OCTIC_WGRAD_SKIP") is False
     monkeypatch.setenv("OCTIC_WGRAD_SKIP", "1")
-    assert OF._wgrad_skip_from_env() is True
+    assert OF._skip_from_env("OCTIC_WGRAD_SKIP") is True
     assert isinstance(OF.WGRAD_SKIP_DROPPED, bool)
 
 
@@ -50,11 +50,11 @@ def test_only_per_sample_gpu_factors_reach_the_kernel(monkeypatch):
     assert OF.wgrad_skip_scale(meta.double(), 17, 51) is None
     monkeypatch.setattr(OF, "WGRAD_SKIP_DROPPED", False)
     assert OF.wgrad_skip_scale(meta, 17, 51) is None
-    assert ops._wgrad_sample_scale(None, 17, 51, rs) == (None, 0)
-    assert ops._wgrad_sample_scale(rs, 17, 51, rs) == (rs, 17)
+    assert ops._sample_scale(None, 17, 51, rs, "dense_wgrad_tn") == (None, 0)
+    assert ops._sample_scale(rs, 17, 51, rs, "dense_wgrad_tn") == (rs, 17)
     for bad in (rs.double(), rs[:2], torch.zeros(6)[::2]):
         with pytest.raises(ValueError, match="sample_scale"):
-            ops._wgrad_sample_scale(bad, 17, 51, rs)
+            ops._sample_scale(bad, 17, 51, rs, "dense_wgrad_tn")
 
 
 def test_rejections_come_back_before_any_launch():
