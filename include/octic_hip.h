@@ -68,7 +68,8 @@ const char* octic_strerror(int code);
  * It is the library's only process-global mutable state: not thread-safe against concurrent launches,
  * value 0 = automatic (the default), returns the previous value (OCTIC_ESHAPE for an unknown knob).              */
 enum {
-  OCTIC_ROUTE_DENSE_TILE = 0,      /* octic_dense_gemm_nt plain mode: 4 = 256 x 256 tile, 5 = 256 x 320 tile              */
+  OCTIC_ROUTE_DENSE_TILE = 0,      /* octic_dense_gemm_nt plain mode: 4 = 256 x 256 tile, 5 = 256 x 320 tile; + 16 / + 32 =
+                                      octic_dense_gemm_nt_tokens_adaptive always runs the 320- / the 256-wide tile          */
   OCTIC_ROUTE_DENSE_SPLIT = 1,     /* octic_dense_gemm_nt: n = K-split of the last partial round (1 = unsplit, in front)  */
   OCTIC_ROUTE_WGRAD_SLABS = 2,     /* octic_dense_wgrad_tn: number of row slabs                                           */
   OCTIC_ROUTE_WGRAD_TILE = 3,      /* octic_dense_wgrad_tn: 256 | 320 = tile width along K                                */
@@ -725,6 +726,29 @@ int octic_dense_gemm_plan_dropped(int M, int N, int K, int mode, int tokens, int
  * not take (mode 2, more than 1024 panels, bad rows_per_sample) or cap too small. */
 int octic_dense_gemm_order_dropped(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
                                    int cap, int* out_tm, int* out_tn, int* out_part, int* out_split, int* out_dead);
+/* octic_dense_gemm_nt_tokens_skip with the tile width of one kind of launch chosen on the device.  A masked plain-mode launch
+ * whose plan is per-image panels on the 320-wide tile, nothing split, ONE round of tiles (ViT-H: the N = 1280 launches at batch
+ * 64) lasts as long as one live tile however many panels the mask kills.  Cut 256 wide, its tiles are shorter and still one
+ * round while live panels * (N / 256) <= CUs; the kernel counts the live panels and takes the 256-wide tile body exactly then,
+ * the 320-wide one otherwise (grid = the larger tile count; the workgroups past the chosen width's tiles return).  Either
+ * width gives every output element the same MFMA sequence over K: the contract and the bits of kept rows are those of
+ * octic_dense_gemm_nt_tokens_skip.  Eligible: mask given, mode 0, that plan, N % 256 == 0, at most 1024 panels - anything else
+ * IS octic_dense_gemm_nt_tokens_skip.  OCTIC_ROUTE_DENSE_TILE + 16 / + 32 forces the wide / the narrow choice (tests, A/B). */
+int octic_dense_gemm_nt_tokens_adaptive(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode,
+                                        void* C, void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs,
+                                        int64_t rows_per_sample_rs, const float* X, float* OUT, const void* H, float* colsum,
+                                        const float* sample_scale, int rows_per_sample, void* workspace, int tokens,
+                                        void* stream);
+/* What it does with a masked launch of this problem: out[0] = 1 if the adaptive kernel takes it, out[1] = workgroups of the
+ * main launch, out[2] / out[3] = the two tile widths (320, 256), out[4] = the largest live-panel count that runs the 256-wide
+ * tile under the rule (-1 where 256 does not divide N).  OCTIC_ESHAPE for a bad rows_per_sample. */
+int octic_dense_gemm_plan_adaptive(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out5);
+/* Host query of the adaptive launch's item map (sample_scale is a HOST array), by the kernel's own functions.  Per workgroup
+ * in blockIdx order: out_tm / out_tn the tile at the chosen width (-1 = the workgroup returns), out_dead 1 for a dead tile
+ * (each nullable, `cap` entries); *out_width = 256 | 320.  Returns the number of workgroups, or OCTIC_ESHAPE for a launch the
+ * adaptive kernel does not take or cap too small. */
+int octic_dense_gemm_order_adaptive(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
+                                    int cap, int* out_tm, int* out_tn, int* out_dead, int* out_width);
 
 /* Weight gradient of an nn.Linear of the standard half (the autograd of deit/vit.py:33,46 and of timm Mlp.fc1 / fc2):
  *     dW[N,K] = dY[M,N]^T . X[M,K]     f32, nn.Linear layout

@@ -17,6 +17,9 @@ ABI_VERSION = 20
 (ROUTE_DENSE_TILE, ROUTE_DENSE_SPLIT, ROUTE_WGRAD_SLABS, ROUTE_WGRAD_TILE, ROUTE_LINEAR_RING, ROUTE_RING_EVEN,
  ROUTE_ATTN_LEGACY, ROUTE_ATTN_ONLINE, ROUTE_ATTN_BWD_PAIR, ROUTE_DENSE_IMAGE, ROUTE_DENSE_CLS2, ROUTE_ATTN_STREAM) = range(12)
 
+# ROUTE_DENSE_TILE, added to the width (0 | 4 | 5): what octic_dense_gemm_nt_tokens_adaptive chooses (0 = by its rule)
+DENSE_ADAPT_WIDE, DENSE_ADAPT_NARROW = 16, 32
+
 # kernel ids of octic_attn_plan (include/octic_hip.h)
 (ATTN_FWD_PERSIST, ATTN_FWD_A80_ONESHOT, ATTN_FWD_A80_ONLINE, ATTN_FWD_RESIDENT, ATTN_FWD_STREAM, ATTN_FWD_F32) = range(6)
 ATTN_BWD_SINGLE, ATTN_BWD_PAIR, ATTN_BWD_STREAM, ATTN_BWD_F32 = range(4)
@@ -168,6 +171,12 @@ _PROTOS = {
     "octic_dense_gemm_plan_dropped": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "octic_dense_gemm_order_dropped": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p]),
+    "octic_dense_gemm_nt_tokens_adaptive": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_i64, c_i64, c_int, c_void_p, c_void_p,
+                                                    c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "octic_dense_gemm_plan_adaptive": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    "octic_dense_gemm_order_adaptive": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                c_void_p, c_void_p]),
     "octic_dense_colsum": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p]),
     "octic_dense_colsum_skip": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
     "octic_dense_wgrad_workspace_bytes": (c_i64, [c_int, c_int, c_int]),

@@ -106,6 +106,10 @@ struct DgArgs {
   // stochastic-depth mask (SKIP kernels only; see dense_item_masked)
   const float* sample_scale;   // [M / rows_per_sample] f32: 0 = every reader of that sample's output rows accepts +0 for them
   int rows_per_sample;
+  // adaptive launches only (dense_nt_adaptive_kernel): the 256-wide alternative of a one-round 320-wide masked launch
+  int tiles_n_narrow;          // N / 256
+  int cus;                     // workgroup slots of one round
+  int narrow_force;            // 0 = dg_narrow_pays decides, 1 = always the 320-wide tile, 2 = always the 256-wide one
 };
 
 enum DgMode { DG_PLAIN = 0, DG_GELU = 1, DG_RESID = 2, DG_DGELU = 3,
@@ -220,6 +224,33 @@ __host__ __device__ inline void dense_item_masked(int tiles_m, int tiles_n, int 
   tile = dg_select_full(bm, tiles_m, tiles_n, full, rank, true);
 }
 
+// Adaptive width (dense_nt_adaptive_kernel).  A masked launch that is ONE round of 320-wide tiles lasts as long as one live tile
+// however many panels are dead.  Cut 256 wide, a panel is tiles_n_narrow shorter tiles (N = 1280: five of 0.8 the K-tile cost
+// instead of four): that launch is still one round - and a shorter one - exactly while the live tiles fit the workgroup slots.
+// Above that it would be two rounds, and the 320-wide launch stays.  The kept count is known on the device only.
+__host__ __device__ inline bool dg_narrow_pays(int live_panels, int tiles_n_narrow, int cus) {
+  return live_panels * tiles_n_narrow <= cus;              // (no live panel at all: narrow - every tile is a few stores)
+}
+__host__ __device__ inline bool dg_adaptive_narrow(int live_panels, int tiles_n_narrow, int cus, int force) {
+  return force == 2 || (force != 1 && dg_narrow_pays(live_panels, tiles_n_narrow, cus));
+}
+__host__ __device__ inline int dg_live_panels(const unsigned long long* bm, int tiles_m) {
+  int n = 0;
+  for (int w = 0; w < (tiles_m + 63) >> 6; ++w) n += __builtin_popcountll(bm[w]);
+  return n;
+}
+// blockIdx + bitmap -> the adaptive launch's item: the chosen width's own masked map (dense_item_masked over full tiles only);
+// tile < 0 for a workgroup past the chosen width's tile count.  tiles_n_wide / tiles_n_narrow = column tiles at 320 / 256.
+__host__ __device__ inline void dense_item_adaptive(int tiles_m, int tiles_n_wide, int tiles_n_narrow, int cus, int force, int bid,
+                                                    const unsigned long long* bm, bool& narrow, int& tile, bool& dead) {
+  narrow = dg_adaptive_narrow(dg_live_panels(bm, tiles_m), tiles_n_narrow, cus, force);
+  const int tiles_n = narrow ? tiles_n_narrow : tiles_n_wide, full = tiles_m * tiles_n;
+  tile = -1; dead = false;
+  if (bid >= full) return;
+  int rem_idx, part;
+  dense_item_masked(tiles_m, tiles_n, full, 1, 0, bid, bm, tile, rem_idx, part, dead);
+}
+
 __device__ inline void dg_wait_vmcnt(int n) {      // n even, wave-uniform; anything unexpected drains (always safe)
   switch (n) {
     case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
@@ -315,9 +346,15 @@ __device__ inline void dg_wait_imm() {
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int MODE, int NT, bool SKIP = false>
-__global__ __launch_bounds__(512, 1) void dense_nt_kernel(DgArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];   // two K-tiles of four units; re-used as 8 staged epilogue tiles
+// One tile of the launch, whichever way the workgroup came by it (the item selection of dense_nt_kernel or of
+// dense_nt_adaptive_kernel): the tile -> (tm, tn) map, the dead tile's stores, the DMA ring, the K loop, the epilogue and the
+// split-K publish.  Everything it is given is workgroup-uniform; it is entered before any ring barrier.
+// (The arguments come BY VALUE: through a reference the compiler rebuilt the epilogue's store addresses per row - two 64-bit adds
+// per store where the kernel-argument form has one - and the unchanged kernels came out 14 - 27 instructions longer than before
+// the body was a function; by value they have their former length and resources.)
+template <int MODE, int NT, bool SKIP>
+__device__ __forceinline__ void dense_nt_tile(const DgArgs a, char* lds, int tile, int kt_begin, int kt_end, int part, int rem_idx,
+                                              bool dead_item) {
   using GE = DgGeom<NT>;
   constexpr int NA = GE::NA, DG_BN = GE::BN;
   static_assert(NT == 4 || MODE == DG_PLAIN, "the fused tails exist for the 256-wide tile only");
@@ -330,65 +367,8 @@ __global__ __launch_bounds__(512, 1) void dense_nt_kernel(DgArgs a) {
   const int fr = lane & 15, kg = lane >> 4;
 #ifdef DG_TRACE
   int dgt_i = 0;
-  if (blockIdx.x == 0 && lane == 0) g_dg_trace[wid * 256 + 254] = __builtin_amdgcn_s_memrealtime();
 #endif
   DGT();
-  DGT2(0);
-#ifdef DG_TRACE2
-  if (wid == 0 && lane == 0 && blockIdx.x < 4096) {
-    unsigned xcc, hwid;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    g_dg_trace2[blockIdx.x * 8 + 7] = ((unsigned long long)hwid << 32) | xcc;
-  }
-#endif
-
-  // ---- work item -> (tile, k-range)
-  const int bid = blockIdx.x;
-  int tile, kt_begin, kt_end, part = 0, rem_idx = -1;
-  const int nkt_all = a.K / DG_BK;
-  bool dead_item = false;
-  if constexpr (SKIP) {
-    // live bitmap of the row panels, behind the ring: lane = panel, one ballot per 64 panels, before the first DMA (the
-    // factors are a cache line or two that every workgroup of the launch reads)
-    unsigned long long* const live_bm = (unsigned long long*)(lds + GE::LDS);
-    const int words = (a.tiles_m + 63) >> 6;
-    for (int w = wid; w < words; w += 8) {
-      const int p = w * 64 + lane;
-      const bool live = p < a.tiles_m && dg_panel_live(a.sample_scale, a.rows_per_sample, a.M, a.m_stride, a.m_base, p);
-      const unsigned long long m = __ballot(live);
-      if (lane == 0) live_bm[w] = m;
-    }
-    __syncthreads();
-    dense_item_masked(a.tiles_m, a.tiles_n, a.full_tiles, a.split, a.tail_pad, bid, live_bm, tile, rem_idx, part, dead_item);
-    tile = __builtin_amdgcn_readfirstlane(tile);
-    rem_idx = __builtin_amdgcn_readfirstlane(rem_idx);
-    part = __builtin_amdgcn_readfirstlane(part);
-    dead_item = __builtin_amdgcn_readfirstlane((int)dead_item) != 0;
-    if (tile < 0) return;                                                      // padding
-    kt_begin = rem_idx >= 0 ? (int)(((int64_t)nkt_all * part) / a.split) : 0;
-    kt_end = rem_idx >= 0 ? (int)(((int64_t)nkt_all * (part + 1)) / a.split) : nkt_all;
-  } else
-  if (bid >= a.tail_pad) {
-    // XCD-aware bijective remap over the full tiles (tail_pad is a multiple of 8: j & 7 is still the XCD of this workgroup)
-    const int j = bid - a.tail_pad;
-    const int nf = a.full_tiles;
-    const int xcd = j & 7, q8 = nf >> 3, r8 = nf & 7;
-    tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (j >> 3);
-    kt_begin = 0;
-    kt_end = nkt_all;
-  } else {
-    // The split parts of the last partial round go FIRST: the short items and their slab round trip (publish, last arriver
-    // re-reads `split` partial tiles) then run beside everybody's full tiles instead of forming the end of the launch
-    // (tools/dense_phases.py: N 5120 K 1280 203.5 -> 197.7 us; with K 5120 the reducers' CUs still end the launch).
-    const int r = bid;
-    if (r >= (a.tiles_m * a.tiles_n - a.full_tiles) * a.split) return;       // padding
-    rem_idx = r / a.split;
-    part = r - rem_idx * a.split;
-    tile = a.full_tiles + rem_idx;
-    kt_begin = (int)(((int64_t)nkt_all * part) / a.split);
-    kt_end = (int)(((int64_t)nkt_all * (part + 1)) / a.split);
-  }
   // tile -> (tm, tn): groups of 8 row panels, column-major inside a group
   int tm, tn;
   {
@@ -893,6 +873,114 @@ __global__ __launch_bounds__(512, 1) void dense_nt_kernel(DgArgs a) {
 #endif
 }
 
+// developer-only stamps of a workgroup's start (see DGT / DGT2)
+__device__ __forceinline__ void dg_trace_start() {
+#if defined(DG_TRACE) || defined(DG_TRACE2)
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+#endif
+#ifdef DG_TRACE
+  if (blockIdx.x == 0 && lane == 0) g_dg_trace[wid * 256 + 254] = __builtin_amdgcn_s_memrealtime();
+#endif
+  DGT2(0);
+#ifdef DG_TRACE2
+  if (wid == 0 && lane == 0 && blockIdx.x < 4096) {
+    unsigned xcc, hwid;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+    g_dg_trace2[blockIdx.x * 8 + 7] = ((unsigned long long)hwid << 32) | xcc;
+  }
+#endif
+}
+
+// live bitmap of the row panels at `live_bm` (LDS, behind the ring): lane = panel, one ballot per 64 panels, before the first DMA
+// (the factors are a cache line or two that every workgroup of the launch reads)
+__device__ __forceinline__ void dg_build_bitmap(const DgArgs& a, unsigned long long* live_bm) {
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int words = (a.tiles_m + 63) >> 6;
+  for (int w = wid; w < words; w += 8) {
+    const int p = w * 64 + lane;
+    const bool live = p < a.tiles_m && dg_panel_live(a.sample_scale, a.rows_per_sample, a.M, a.m_stride, a.m_base, p);
+    const unsigned long long m = __ballot(live);
+    if (lane == 0) live_bm[w] = m;
+  }
+  __syncthreads();
+}
+
+template <int MODE, int NT, bool SKIP = false>
+__global__ __launch_bounds__(512, 1) void dense_nt_kernel(DgArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];   // two K-tiles of four units; re-used as 8 staged epilogue tiles
+  using GE = DgGeom<NT>;
+  dg_trace_start();
+
+  // ---- work item -> (tile, k-range)
+  const int bid = blockIdx.x;
+  int tile, kt_begin, kt_end, part = 0, rem_idx = -1;
+  const int nkt_all = a.K / DG_BK;
+  bool dead_item = false;
+  if constexpr (SKIP) {
+    unsigned long long* const live_bm = (unsigned long long*)(lds + GE::LDS);
+    dg_build_bitmap(a, live_bm);
+    dense_item_masked(a.tiles_m, a.tiles_n, a.full_tiles, a.split, a.tail_pad, bid, live_bm, tile, rem_idx, part, dead_item);
+    tile = __builtin_amdgcn_readfirstlane(tile);
+    rem_idx = __builtin_amdgcn_readfirstlane(rem_idx);
+    part = __builtin_amdgcn_readfirstlane(part);
+    dead_item = __builtin_amdgcn_readfirstlane((int)dead_item) != 0;
+    if (tile < 0) return;                                                      // padding
+    kt_begin = rem_idx >= 0 ? (int)(((int64_t)nkt_all * part) / a.split) : 0;
+    kt_end = rem_idx >= 0 ? (int)(((int64_t)nkt_all * (part + 1)) / a.split) : nkt_all;
+  } else
+  if (bid >= a.tail_pad) {
+    // XCD-aware bijective remap over the full tiles (tail_pad is a multiple of 8: j & 7 is still the XCD of this workgroup)
+    const int j = bid - a.tail_pad;
+    const int nf = a.full_tiles;
+    const int xcd = j & 7, q8 = nf >> 3, r8 = nf & 7;
+    tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (j >> 3);
+    kt_begin = 0;
+    kt_end = nkt_all;
+  } else {
+    // The split parts of the last partial round go FIRST: the short items and their slab round trip (publish, last arriver
+    // re-reads `split` partial tiles) then run beside everybody's full tiles instead of forming the end of the launch
+    // (tools/dense_phases.py: N 5120 K 1280 203.5 -> 197.7 us; with K 5120 the reducers' CUs still end the launch).
+    const int r = bid;
+    if (r >= (a.tiles_m * a.tiles_n - a.full_tiles) * a.split) return;       // padding
+    rem_idx = r / a.split;
+    part = r - rem_idx * a.split;
+    tile = a.full_tiles + rem_idx;
+    kt_begin = (int)(((int64_t)nkt_all * part) / a.split);
+    kt_end = (int)(((int64_t)nkt_all * (part + 1)) / a.split);
+  }
+  dense_nt_tile<MODE, NT, SKIP>(a, lds, tile, kt_begin, kt_end, part, rem_idx, dead_item);
+}
+
+// The masked one-round launch of the 320-wide tile with its width chosen on the device (see dg_narrow_pays): the bitmap prologue of
+// the SKIP kernels, a popcount, and then one of the two tile bodies - the branch is workgroup-uniform and taken before any ring
+// barrier, nothing is added inside either K loop.  Full tiles only (no split front), plain epilogue.  Either width gives every
+// output element the same MFMA sequence over K, so the choice never shows in the bits of a kept row.
+__global__ __launch_bounds__(512, 1) void dense_nt_adaptive_kernel(DgArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];   // the ring of either width (both 144 KiB) + the bitmap
+  static_assert(DgGeom<4>::LDS <= DgGeom<5>::LDS, "the bitmap sits behind the wider tile's ring");
+  dg_trace_start();
+  unsigned long long* const live_bm = (unsigned long long*)(lds + DgGeom<5>::LDS);
+  dg_build_bitmap(a, live_bm);
+  bool narrow, dead_item;
+  int tile;
+  dense_item_adaptive(a.tiles_m, a.tiles_n, a.tiles_n_narrow, a.cus, a.narrow_force, blockIdx.x, live_bm, narrow, tile, dead_item);
+  narrow = __builtin_amdgcn_readfirstlane((int)narrow) != 0;
+  tile = __builtin_amdgcn_readfirstlane(tile);
+  dead_item = __builtin_amdgcn_readfirstlane((int)dead_item) != 0;
+  if (tile < 0) return;                                                        // past the chosen width's tiles
+  const int nkt_all = a.K / DG_BK;
+  if (narrow) {
+    DgArgs b = a;
+    b.tiles_n = a.tiles_n_narrow;
+    dense_nt_tile<DG_PLAIN, 4, true>(b, lds, tile, 0, nkt_all, 0, -1, dead_item);
+  } else {
+    dense_nt_tile<DG_PLAIN, 5, true>(a, lds, tile, 0, nkt_all, 0, -1, dead_item);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // The class-token rows of per-image launches: C[b * tokens][n] for b < nrows.  One workgroup = 16 rows x 16 columns; its
 // blockDim / 64 waves (1 .. 16, chosen by the host so that a wave contracts 320 of K where K allows: 4 / 12 / 16 waves for
@@ -1123,9 +1211,10 @@ inline DgPlan dense_plan_nt(int M, int N, int K, int cus, int nt, int force_spli
 // can land on another plan's tickets.
 constexpr int DG_TICKET_BYTES = 8192;
 
-// routing overrides (octic_route_override): OCTIC_ROUTE_DENSE_TILE 0 = choose by the cost model, 4 / 5 = force;
+// routing overrides (octic_route_override): OCTIC_ROUTE_DENSE_TILE low four bits 0 = choose by the cost model, 4 / 5 = force
+// (bits 4-5 belong to the adaptive launch: dense_plan_adaptive);
 // OCTIC_ROUTE_DENSE_SPLIT 0 = plan's choice, n = split of the remaining tiles (1 = unsplit, kept in front)
-static inline int dense_force_nt() { const int v = route(OCTIC_ROUTE_DENSE_TILE); return (v == 4 || v == 5) ? v : 0; }
+static inline int dense_force_nt() { const int v = route(OCTIC_ROUTE_DENSE_TILE) & 15; return (v == 4 || v == 5) ? v : 0; }
 static inline int dense_force_split() { const int v = route(OCTIC_ROUTE_DENSE_SPLIT); return v > 0 ? v : 0; }
 
 // The 320-wide tile serves plain-epilogue problems whose N is a multiple of 320 when the model says its launch is shorter
@@ -1191,6 +1280,25 @@ inline DgTokPlan dense_plan_tokens(int M, int N, int K, int cus, int mode, int t
   return t;
 }
 
+// The adaptive launch (dense_nt_adaptive_kernel) takes a masked plain-mode launch whose plan is per-image panels on the 320-wide
+// tile, nothing split, a single round - and whose N the 256-wide tile divides.  grid = the larger of the two widths' tile counts;
+// max_live = the largest live-panel count that runs narrow under the rule (-1 where 256 does not divide N).
+// OCTIC_ROUTE_DENSE_TILE bits 4-5 force the choice: 0 = by the rule, 1 = always wide, 2 = always narrow.
+struct DgAdaptive { bool eligible; int tiles_n_narrow, grid, max_live, force; };
+inline DgAdaptive dense_plan_adaptive(const DgTokPlan& tp, int N, int mode, int cus, bool masked) {
+  DgAdaptive d;
+  const DgPlan& p = tp.p;
+  d.tiles_n_narrow = (N % 256) == 0 ? N / 256 : 0;
+  d.max_live = d.tiles_n_narrow > 0 ? cus / d.tiles_n_narrow : -1;
+  const int f = (route(OCTIC_ROUTE_DENSE_TILE) >> 4) & 3;
+  d.force = f == 1 || f == 2 ? f : 0;
+  d.eligible = masked && mode == DG_PLAIN && tp.image && p.nt == 5 && p.rem == 0 && p.tail_pad == 0 && p.split == 1 &&
+               p.full <= cus && d.tiles_n_narrow > 0 && p.tiles_m <= kDgMaskCap;
+  const int narrow_tiles = p.tiles_m * d.tiles_n_narrow;
+  d.grid = d.eligible && narrow_tiles > p.grid ? narrow_tiles : p.grid;
+  return d;
+}
+
 }  // namespace octic
 
 using namespace octic;
@@ -1253,10 +1361,11 @@ int octic_dense_gemm_colsum_rows(int M, int N, int K) {
 // 4 GELUF (C = gelu'(pre-activation), C2 = gelu(pre-activation)), 5 DFACT (C = H * (A B^T), H = the factor of mode 4),
 // 6 GELUO (C = gelu(pre-activation) only: passes without a backward).
 // sample_scale / rows_per_sample: the stochastic-depth mask (see dense_item_masked); NULL = the unmasked launch.
-int octic_dense_gemm_nt_tokens_skip(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
-                                    void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
-                                    const float* X, float* OUT, const void* H, float* colsum, const float* sample_scale,
-                                    int rows_per_sample, void* workspace, int tokens, void* stream) {
+// adaptive: an eligible masked launch (dense_plan_adaptive) chooses its tile width on the device; anything else is untouched.
+static int dense_launch(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
+                        void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
+                        const float* X, float* OUT, const void* H, float* colsum, const float* sample_scale,
+                        int rows_per_sample, void* workspace, int tokens, void* stream, bool adaptive) {
   if (!A || !B || !C) return OCTIC_ENULL;
   if (sample_scale && (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0)) return OCTIC_ESHAPE;
   if (sample_scale && (((uintptr_t)sample_scale) & 3)) return OCTIC_EALIGN;
@@ -1307,8 +1416,17 @@ int octic_dense_gemm_nt_tokens_skip(const void* A, const void* B, int M, int N, 
     (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUF, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
     (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_DFACT, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
     (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUO, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_adaptive_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem5 + bmb);
     (void)hipGetLastError();
   }
+  const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), skip);
+  if (adaptive && ad.eligible) {
+    // same plan, same panels; the grid covers the tiles of either width and the workgroups past the chosen one return
+    a.tiles_n_narrow = ad.tiles_n_narrow;
+    a.cus = dense_cus();
+    a.narrow_force = ad.force;
+    dense_nt_adaptive_kernel<<<ad.grid, 512, smem5 + bmb, s>>>(a);
+  } else
   if (skip) {
     // same plan, same grid; the live bitmap sits behind the ring
     switch (mode) {
@@ -1364,6 +1482,23 @@ int octic_dense_gemm_nt_tokens_skip(const void* A, const void* B, int M, int N, 
   return launch_status();
 }
 
+int octic_dense_gemm_nt_tokens_skip(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
+                                    void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
+                                    const float* X, float* OUT, const void* H, float* colsum, const float* sample_scale,
+                                    int rows_per_sample, void* workspace, int tokens, void* stream) {
+  return dense_launch(A, B, M, N, K, lda, ldb, mode, C, C2, ldc, bias, gamma, rs, rps, X, OUT, H, colsum, sample_scale,
+                      rows_per_sample, workspace, tokens, stream, false);
+}
+
+// octic_dense_gemm_nt_tokens_skip with the tile width of an eligible launch chosen on the device (dense_nt_adaptive_kernel)
+int octic_dense_gemm_nt_tokens_adaptive(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode,
+                                        void* C, void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs,
+                                        int64_t rps, const float* X, float* OUT, const void* H, float* colsum,
+                                        const float* sample_scale, int rows_per_sample, void* workspace, int tokens, void* stream) {
+  return dense_launch(A, B, M, N, K, lda, ldb, mode, C, C2, ldc, bias, gamma, rs, rps, X, OUT, H, colsum, sample_scale,
+                      rows_per_sample, workspace, tokens, stream, true);
+}
+
 int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
                                void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
                                const float* X, float* OUT, const void* H, float* colsum, void* workspace, int tokens,
@@ -1405,6 +1540,51 @@ int octic_dense_gemm_order_dropped(int M, int N, int K, int mode, int tokens, co
     if (out_dead) out_dead[bid] = dead ? 1 : 0;
   }
   return p.grid;
+}
+
+// What octic_dense_gemm_nt_tokens_adaptive does with a masked launch of this problem: out[0] = 1 if the adaptive kernel takes it
+// (else it is octic_dense_gemm_nt_tokens_skip), out[1] = workgroups of the main launch, out[2] / out[3] = the two tile widths
+// (320, 256), out[4] = the largest live-panel count that still runs the 256-wide tile under the rule (-1: 256 does not divide N).
+int octic_dense_gemm_plan_adaptive(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out) {
+  if (!out) return OCTIC_ENULL;
+  if (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0 || N <= 0 || K < 2 * DG_BK) return OCTIC_ESHAPE;
+  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
+  const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), mode != DG_RESID);
+  out[0] = ad.eligible ? 1 : 0;
+  out[1] = ad.grid;
+  out[2] = 320;
+  out[3] = 256;
+  out[4] = ad.max_live;
+  return OCTIC_OK;
+}
+
+// What the adaptive launch gives each workgroup, in blockIdx order, by the kernel's own functions (dense_item_adaptive):
+// sample_scale is a HOST array.  out_tm / out_tn = the tile at the chosen width (-1 = the workgroup returns), out_dead = 1 for a
+// dead tile (each may be NULL, `cap` entries), *out_width = 256 | 320.  Returns the number of workgroups; OCTIC_ESHAPE for a
+// launch the adaptive kernel does not take or cap < that.
+int octic_dense_gemm_order_adaptive(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
+                                    int cap, int* out_tm, int* out_tn, int* out_dead, int* out_width) {
+  if (!sample_scale) return OCTIC_ENULL;
+  if (M <= 0 || N <= 0 || K < 2 * DG_BK || rows_per_sample <= 0 || (M % rows_per_sample) != 0) return OCTIC_ESHAPE;
+  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
+  const DgPlan p = tp.p;
+  const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), true);
+  if (!ad.eligible || cap < ad.grid) return OCTIC_ESHAPE;
+  unsigned long long bm[kDgMaskWords] = {};
+  for (int tm = 0; tm < p.tiles_m; ++tm)
+    if (dg_panel_live(sample_scale, rows_per_sample, M, tokens, 1, tm)) bm[tm >> 6] |= 1ull << (tm & 63);
+  bool narrow = false;
+  for (int bid = 0; bid < ad.grid; ++bid) {
+    int tile, tm = -1, tn = -1;
+    bool dead;
+    dense_item_adaptive(p.tiles_m, p.tiles_n, ad.tiles_n_narrow, dense_cus(), ad.force, bid, bm, narrow, tile, dead);
+    if (tile >= 0) dg_tile_panel(p.tiles_m, narrow ? ad.tiles_n_narrow : p.tiles_n, tile, tm, tn);
+    if (out_tm) out_tm[bid] = tm;
+    if (out_tn) out_tn[bid] = tn;
+    if (out_dead) out_dead[bid] = dead ? 1 : 0;
+  }
+  if (out_width) *out_width = narrow ? 256 : 320;
+  return ad.grid;
 }
 
 int octic_dense_gemm_nt(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,

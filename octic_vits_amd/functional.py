@@ -509,6 +509,14 @@ def wgrad_skip_scale(rs, rps, M, rows_to=None):
 DENSE_NT_SKIP_DROPPED = _skip_from_env("OCTIC_DENSE_SKIP")
 
 
+# A masked N = 1280 launch (proj, fc2, the input gradients of qkv / proj / fc1) is one round of 256 x 320 tiles, so it lasts as
+# long as one live tile whatever the mask drops.  With DENSE_NARROW_DROPPED such a launch counts its live panels on the device
+# and runs 256-wide tiles - shorter, and still one round - while they fit the CUs (include/octic_hip.h:
+# octic_dense_gemm_nt_tokens_adaptive); same bits.  Effective only while DENSE_NT_SKIP_DROPPED is on (no mask, no choice).  Read
+# once at import from OCTIC_DENSE_NARROW (0 = off).
+DENSE_NARROW_DROPPED = _skip_from_env("OCTIC_DENSE_NARROW")
+
+
 def dense_skip_scale(rs, rps, M, rows_to=None):
     """rs as the sample_scale of a dense_nt_kernel launch over M token rows: whole_sample_mask while the switch is on."""
     return whole_sample_mask(rs, rps, M, rows_to) if DENSE_NT_SKIP_DROPPED else None

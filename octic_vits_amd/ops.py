@@ -1269,6 +1269,19 @@ def dense_plan_dropped(M, N, K, mode, tokens, rows_per_sample):
     return out[0], out[1], bool(out[2]), out[3]
 
 
+def dense_plan_adaptive(M, N, K, mode, tokens, rows_per_sample):
+    """(adaptive kernel takes it?, main-launch workgroups, wide width, narrow width, most live panels that run narrow) of a masked
+    octic_dense_gemm_nt_tokens_adaptive launch."""
+    out = (ctypes.c_int * 5)()
+    check(lib().octic_dense_gemm_plan_adaptive(M, N, K, mode, int(tokens), int(rows_per_sample), out))
+    return bool(out[0]), out[1], out[2], out[3], out[4]
+
+
+def _dense_narrow():
+    from . import functional          # (functional imports this module)
+    return functional.DENSE_NARROW_DROPPED
+
+
 def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h=None, name=None, want_colsum=False,
                   tokens=0, sample_scale=None, rows_per_sample=0):
     """C[M,N] = a[M,K] @ b[N,K]^T on the hand-written MFMA kernel (csrc/dense_gemm.hip) with a fused tail:
@@ -1297,10 +1310,11 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
     # workspace belong to it
     cs_rows = dense_plan(M, N, K, mode, tokens)[1] if (mode in (3, 5) and want_colsum) else 0
     cs = torch.empty((cs_rows, N), dtype=torch.float32, device=a.device) if cs_rows else None
+    # a masked launch may choose its tile width on the device (functional.DENSE_NARROW_DROPPED; the library decides which launches)
+    entry = lib().octic_dense_gemm_nt_tokens_adaptive if (ss is not None and _dense_narrow()) else lib().octic_dense_gemm_nt_tokens_skip
     t = KERNEL_TIMER.start()
-    check(lib().octic_dense_gemm_nt_tokens_skip(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias),
-                                                _p(gamma), _p(rs), int(rps), _p(x), _p(out), _p(h), _p(cs), _p(ss), srps,
-                                                _p(ws), tokens, _stream(a)))
+    check(entry(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias), _p(gamma), _p(rs), int(rps),
+                _p(x), _p(out), _p(h), _p(cs), _p(ss), srps, _p(ws), tokens, _stream(a)))
     if t is not None:
         nb = 2 * (M * K + N * K + M * N * (2 if mode in (1, 3, 4, 5) else 1)) + (8 * M * N if mode == 2 else 0)
         # "@320": the launch ran the 256 x 320 tile (kernel symbol dense_nt_kernel<0, 5>), else <mode, 4>

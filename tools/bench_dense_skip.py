@@ -5,7 +5,8 @@ stochastic-depth mask.
 
 Four cases per shape: unmasked (sample_scale None), all kept (prices the bitmap prologue: same tiles, same order), a fixed
 Bernoulli(0.5) mask (seed 0), all dropped (prices the dead tile).  Each case is timed as `iters` launches between two events
-after a warm-up, microseconds per launch."""
+after a warm-up, microseconds per launch.  The shapes run with functional.DENSE_NARROW_DROPPED off (the masked launch at the
+plan's width); the launches octic_dense_gemm_nt_tokens_adaptive takes get a second row with it on ("... adaptive")."""
 import argparse
 import json
 import os
@@ -14,7 +15,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from octic_vits_amd import ops  # noqa: E402
+from octic_vits_amd import functional, ops  # noqa: E402
 
 B, T = 64, 257
 SHAPES = [("qkv forward", 3840, 1280, 0), ("proj", 1280, 1280, 0), ("fc1 + factor", 5120, 1280, 4), ("fc2", 1280, 5120, 0),
@@ -47,18 +48,23 @@ def main():
              "all dropped": torch.zeros(B, device=dev)}
     rows = []
     print(f"kept samples of the Bernoulli mask: {int((bern != 0).sum())} of {B}")
-    print(f"{'launch':22s} " + " ".join(f"{k:>12s}" for k in masks))
+    print(f"{'launch':30s} " + " ".join(f"{k:>12s}" for k in masks))
     for name, N, K, mode in SHAPES:
         a = torch.randn(B * T, K, device=dev).to(torch.bfloat16)
         w = (torch.randn(N, K, device=dev) * K ** -0.5).to(torch.bfloat16)
         h = torch.rand(B * T, N, device=dev).to(torch.bfloat16) if mode == 5 else None
-        res = {}
-        for label, ss in masks.items():
-            fn = lambda: ops.dense_gemm_nt(a, w, mode, h=h, want_colsum=mode == 5, tokens=T, sample_scale=ss,
-                                           rows_per_sample=T if ss is not None else 0)
-            res[label] = timed(fn, args.iters)
-        rows.append(dict(launch=name, N=N, K=K, mode=mode, us=res))
-        print(f"{name:22s} " + " ".join(f"{res[k]:12.1f}" for k in masks))
+        for adaptive in (False, True):
+            if adaptive and not ops.dense_plan_adaptive(B * T, N, K, mode, T, T)[0]:
+                continue
+            functional.DENSE_NARROW_DROPPED = adaptive
+            res = {}
+            for label, ss in masks.items():
+                fn = lambda: ops.dense_gemm_nt(a, w, mode, h=h, want_colsum=mode == 5, tokens=T, sample_scale=ss,
+                                               rows_per_sample=T if ss is not None else 0)
+                res[label] = timed(fn, args.iters)
+            label = name + (" adaptive" if adaptive else "")
+            rows.append(dict(launch=label, N=N, K=K, mode=mode, us=res))
+            print(f"{label:30s} " + " ".join(f"{res[k]:12.1f}" for k in masks))
     if args.json:
         with open(args.json, "w") as f:
             json.dump(dict(batch=B, tokens=T, kept=int((bern != 0).sum()), iters=args.iters, rows=rows), f, indent=1)
