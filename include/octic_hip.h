@@ -793,6 +793,53 @@ int octic_dense_wgrad_tn_pair_skip(const void* dY0, const void* X0, int N0, int6
                                    const void* dY1, const void* X1, int N1, int64_t ldy1, int64_t ldx1, float* dW1, int M, int K,
                                    const float* sample_scale, int rows_per_sample, void* workspace, void* stream);
 
+/* ---- float32 dense GEMMs of the standard half (csrc/dense_f32.hip) -------------------------------------------------------
+ * The nn.Linear of a standard block (deit/vit.py:14-56; dinov2/layers/mlp.py, swiglu_ffn.py, attention.py) when the model runs
+ * in float32: forward, input gradient, weight gradient (+ bias gradient) and the GELU backward.  Everything is f32 row-major:
+ *     octic_dense_f32_nt   C[M,N]  = A[M,K] . W[N,K]^T (+ bias[N]);  gelu != 0: H = that, C = gelu(H) (exact erf GELU, nn.GELU())
+ *     octic_dense_f32_nn   DX[M,K] = G[M,N] . W[N,K]                 (W as stored: no transposed copy)
+ *     octic_dense_f32_tn   DW[N,K] = G[M,N]^T . X[M,K],  db[N] = column sums of G when db != NULL
+ *     octic_dense_gelu_bwd_f32   dh = gelu'(h) * g on dense [rows, d];  db != NULL: db[d] = column sums of dh
+ * Limits: M >= 1, N % 4 == 0, K % 4 == 0, every row stride (elements) a multiple of 4 and >= its row length, pointers 16-byte
+ * aligned, (largest of M, N, K) * (largest row stride) < 2^31.  Shape violations: OCTIC_ESHAPE; alignment: OCTIC_EALIGN; a
+ * missing operand: OCTIC_ENULL; a short TN workspace: OCTIC_EWORKSPACE - all before any launch.  Every M / N / K tail is
+ * handled inside the kernel: nothing past an edge is read or written.
+ * ARITHMETIC CONTRACT.  Products run on v_mfma_f32_16x16x4_f32: exact f32 inputs, one rounding per product, f32 accumulate.
+ * An element of an NT / NN result is ONE fmaf chain from +0 over the reduction index (K for NT, N for NN) - blocks of 16
+ * ascending, inside a block e, 4 + e, 8 + e, 12 + e for e = 0 .. 3 - then one addition of the bias.  No split of the reduction
+ * over workgroups; the order depends on the reduction length alone, not on M, the row's position or its tile, and a result
+ * row reads that row of A / G, W and the bias only: a sample's rows are bitwise independent of its batch mates.
+ * TN reduces over the M token rows in row slabs (multiples of 32 rows): each slab is one such chain per element into an f32
+ * partial tile in the workspace, and a second launch adds the partials in slab order.  db: sequential over a slab's rows, then
+ * slab order.  The slab count is a function of (M, N, K) alone (octic_dense_f32_plan out[2]); with one slab the result goes
+ * straight to DW.  The GELU backward sums 256 row blocks (octic_dense_gelu_blocks()) in the order of octic_dense_finish.
+ * No floating-point atomics: every result is bitwise repeatable.  Subnormals are kept.
+ * op of the queries: 0 = NT, 1 = NN, 2 = TN. */
+#define OCTIC_DENSE_F32_NT 0
+#define OCTIC_DENSE_F32_NN 1
+#define OCTIC_DENSE_F32_TN 2
+/* Host-only query: the accept-and-plan function the three launchers call.  ld_max = the largest operand row stride in
+ * elements (0 = not known: only the shape is judged).  out[0] = tile rows, out[1] = tile columns of the output, out[2] = row
+ * slabs (1 for NT / NN), out[3] = workgroups of the main launch.  OCTIC_ESHAPE exactly where the launchers refuse by shape or
+ * stride bound: N or K no multiple of 4, M < 1, ld_max below the longest operand row, the 2^31 offset bound (per-operand
+ * strides, ld % 4 and pointer alignment are theirs to check). */
+int octic_dense_f32_plan(int op, int64_t M, int64_t N, int64_t K, int64_t ld_max, int out[4]);
+/* bytes of the workspace of octic_dense_f32_tn (slab partials; 256 where the plan has one slab, and for op NT / NN);
+ * OCTIC_ESHAPE for a shape the plan refuses.  The workspace needs no initialisation. */
+int64_t octic_dense_f32_workspace_bytes(int op, int64_t M, int64_t N, int64_t K);
+/* bias nullable; H / ldh are used with gelu != 0 only. */
+int octic_dense_f32_nt(const float* A, const float* W, const float* bias, int64_t M, int64_t N, int64_t K, int64_t lda,
+                       int64_t ldw, float* C, int64_t ldc, int gelu, float* H, int64_t ldh, void* stream);
+int octic_dense_f32_nn(const float* G, const float* W, int64_t M, int64_t N, int64_t K, int64_t ldg, int64_t ldw, float* DX,
+                       int64_t ldx, void* stream);
+/* DW may be any [N,K] view with row stride ldw (a gradient-bucket view); db nullable; workspace nullable where the plan has one
+ * slab. */
+int octic_dense_f32_tn(const float* G, const float* X, int64_t M, int64_t N, int64_t K, int64_t ldg, int64_t ldx, float* DW,
+                       int64_t ldw, float* db, void* workspace, int64_t workspace_bytes, void* stream);
+/* partials: [octic_dense_gelu_blocks(), d] f32, required with db (both nullable together: no column sums); d % 4 == 0. */
+int octic_dense_gelu_bwd_f32(const float* h, const float* g, float* dh, float* partials, float* db, int64_t rows, int d,
+                             void* stream);
+
 /* ---- row kernels of the DINOv2 objective over the prototype axis (K % 8 == 0, row strides % 8 == 0) -----
  * octic_softmax_center: out[r, :] = softmax((t[r, :] - center) * inv_temp) in f32 - the teacher's centred, sharpened
  * probabilities (dinov2/loss/dino_clstoken_loss.py:43-51, ibot_patch_loss.py:63-77); center may be NULL; t f32 or bf16.

@@ -26,6 +26,8 @@ ATTN_BWD_SINGLE, ATTN_BWD_PAIR, ATTN_BWD_STREAM, ATTN_BWD_F32 = range(4)
 # kernel ids of octic_linear_d8_plan and octic_linear_d8_wgrad_plan
 LINEAR_WREG, LINEAR_RING, LINEAR_CLASSIC = range(3)
 WGRAD_RING, WGRAD_TILED = range(2)
+# op of octic_dense_f32_plan / octic_dense_f32_workspace_bytes
+DENSE_F32_NT, DENSE_F32_NN, DENSE_F32_TN = range(3)
 
 c_i64, c_int, c_float, c_void_p = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 c_double = ctypes.c_double
@@ -190,6 +192,14 @@ _PROTOS = {
                                           c_void_p]),
     "octic_dense_wgrad_tn_pair_skip": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_i64,
                                                c_i64, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "octic_dense_f32_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(c_int)]),
+    "octic_dense_f32_workspace_bytes": (c_i64, [c_int, c_i64, c_i64, c_i64]),
+    "octic_dense_f32_nt": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_int,
+                                   c_void_p, c_i64, c_void_p]),
+    "octic_dense_f32_nn": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p]),
+    "octic_dense_f32_tn": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p,
+                                   c_i64, c_void_p]),
+    "octic_dense_gelu_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p]),
     "octic_probe_features": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_i64, c_i64, c_int, c_i64, c_int, c_int, c_void_p,
                                      c_i64, c_void_p]),
     "octic_probe_forward": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p]),

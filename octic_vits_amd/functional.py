@@ -823,23 +823,34 @@ class DenseLayerNormRowsFn(torch.autograd.Function):
 
 
 class DenseLinearFn(torch.autograd.Function):
-    """nn.Linear on the BLAS library with cached compute-dtype weights (no per-step cast kernels in the graph)."""
+    """nn.Linear with cached compute-dtype weights (no per-step cast kernels in the graph): float32 on the GPU runs on
+    csrc/dense_f32.hip (DENSE_F32_HIP), everything else on the BLAS library."""
 
     @staticmethod
     def forward(ctx, x, w, b, dtype, cache):
         ops._require_cuda(x)
         xb = _c(x if x.dtype == dtype else x.to(dtype))
         wb, bb = cache.get(w, b, dtype)
-        with torch.autocast("cuda", enabled=False):
-            y = torch.nn.functional.linear(xb, wb, bb)
+        x2 = xb.reshape(-1, wb.shape[1])
+        ctx.f32 = dense_f32_hip_ok(x2.shape[0], wb.shape[0], wb.shape[1], x2, wb)
+        if ctx.f32:
+            y = ops.dense_f32_nt(x2, wb, bb).view(*xb.shape[:-1], wb.shape[0])
+        else:
+            with torch.autocast("cuda", enabled=False):
+                y = torch.nn.functional.linear(xb, wb, bb)
         ctx.save_for_backward(xb, wb)
         ctx.has_b, ctx.x_dtype = b is not None, x.dtype
+        ctx.wparam = w
         return y
 
     @staticmethod
     def backward(ctx, gy):
         xb, wb = ctx.saved_tensors
         g2, x2 = _c(gy).reshape(-1, wb.shape[0]), xb.reshape(-1, wb.shape[1])
+        if ctx.f32:
+            gx = ops.dense_f32_nn(g2, wb).view(xb.shape).to(ctx.x_dtype) if ctx.needs_input_grad[0] else None
+            gw, gb = _wgrad_f32(g2, x2, ctx.wparam, want_colsum=ctx.has_b)
+            return gx, gw, gb, None, None
         with torch.autocast("cuda", enabled=False):
             gx = (g2 @ wb).view(xb.shape).to(ctx.x_dtype) if ctx.needs_input_grad[0] else None
             gw = (g2.t() @ x2).float()
@@ -848,38 +859,53 @@ class DenseLinearFn(torch.autograd.Function):
 
 
 class DenseLinearGeluFn(torch.autograd.Function):
-    """gelu(x W^T + b) of the standard MLP (bf16): library GEMM with bias epilogue + torch's exact GELU forward; the
-    backward is one HIP pass that yields dh = gelu'(h) g and the bias gradient (column sums of dh) together."""
+    """gelu(x W^T + b) of the standard MLP.  bf16: library GEMM with bias epilogue + torch's exact GELU forward; the
+    backward is one HIP pass that yields dh = gelu'(h) g and the bias gradient (column sums of dh) together.  float32
+    (dtype = torch.float32, shapes dense_f32_hip_ok takes): the GEMM of csrc/dense_f32.hip with the GELU in its epilogue, h
+    saved, the backward through ops.dense_gelu_bwd_f32 and the float32 NN / TN kernels."""
 
     @staticmethod
-    def forward(ctx, x, w, b, cache):
+    def forward(ctx, x, w, b, cache, dtype=torch.bfloat16):
         ops._require_cuda(x)
-        dtype = torch.bfloat16
         xb = _c(x if x.dtype == dtype else x.to(dtype))
         wb, bb = cache.get(w, b, dtype)
-        with torch.autocast("cuda", enabled=False):
-            h = torch.nn.functional.linear(xb, wb, bb)
-            y = torch.nn.functional.gelu(h)
+        ctx.f32 = dtype == torch.float32
+        if ctx.f32:
+            x2 = xb.reshape(-1, wb.shape[1])
+            if not dense_f32_hip_ok(x2.shape[0], wb.shape[0], wb.shape[1], x2, wb):
+                raise RuntimeError("DenseLinearGeluFn: float32 needs the dense_f32 kernels (check dense_f32_hip_ok first)")
+            h, y = ops.dense_f32_nt(x2, wb, bb, gelu=True)
+            h, y = h.view(*xb.shape[:-1], wb.shape[0]), y.view(*xb.shape[:-1], wb.shape[0])
+        else:
+            with torch.autocast("cuda", enabled=False):
+                h = torch.nn.functional.linear(xb, wb, bb)
+                y = torch.nn.functional.gelu(h)
         ctx.save_for_backward(xb, wb, h)
         ctx.has_b, ctx.x_dtype = b is not None, x.dtype
+        ctx.wparam = w
         return y
 
     @staticmethod
     def backward(ctx, gy):
         xb, wb, h = ctx.saved_tensors
+        if ctx.f32:
+            dh, db = ops.dense_gelu_bwd_f32(h, _c(gy.to(h.dtype)), want_colsum=ctx.has_b)
+            g2, x2 = dh.reshape(-1, wb.shape[0]), xb.reshape(-1, wb.shape[1])
+            gx = ops.dense_f32_nn(g2, wb).view(xb.shape).to(ctx.x_dtype) if ctx.needs_input_grad[0] else None
+            return gx, _wgrad_f32(g2, x2, ctx.wparam)[0], db, None, None
         dh, db = ops.dense_gelu_bwd(h, _c(gy.to(h.dtype)), want_colsum=ctx.has_b)
         g2, x2 = dh.reshape(-1, wb.shape[0]), xb.reshape(-1, wb.shape[1])
         with torch.autocast("cuda", enabled=False):
             gx = (g2 @ wb).view(xb.shape).to(ctx.x_dtype) if ctx.needs_input_grad[0] else None
             gw = (g2.t() @ x2).float()
-        return gx, gw, db, None
+        return gx, gw, db, None, None
 
 
 class LinearScaleResidualFn(torch.autograd.Function):
     """Tail of a standard block branch:  out = x + rs * gamma * (a W^T + b)  with x the f32 residual stream, a the
     compute-dtype branch activations, gamma the layer scale [d] and rs the per-sample stochastic-depth factor
-    (both optional).  The GEMMs are the library's; everything around them is one HIP pass each way, which also
-    yields d gamma and the bias gradient."""
+    (both optional).  The GEMMs are the library's (float32: those of csrc/dense_f32.hip, through _linear_lib / _mm_lib /
+    _wgrad_lib); everything around them is one HIP pass each way, which also yields d gamma and the bias gradient."""
 
     @staticmethod
     def forward(ctx, x, a, w, b, gamma, rs, rps, dtype, cache):
@@ -1013,12 +1039,40 @@ def wgrad_slabs(M, N, K):
 # 3840x1280 156 vs 187, 1280x1280 93 vs 100.  False = every weight gradient on the BLAS library (bench.py --lib-wgrad).
 WGRAD_HIP = True
 
+# The GEMMs of a float32 standard block (and the float32 calls of the seams below) on csrc/dense_f32.hip: exact-f32 MFMA,
+# bitwise repeatable, a sample's rows independent of its batch mates.  False = today's BLAS-library calls, bit for bit.
+DENSE_F32_HIP = True
+
+
+def dense_f32_hip_ok(M, N, K, *operands):
+    """A GEMM of a linear layer with M rows, N = out_features, K = in_features goes to csrc/dense_f32.hip: the switch is on,
+    torch.compile is not tracing, every operand is a CUDA float32 2-D tensor with unit column stride, and the library takes
+    the shape and the strides (ops.dense_f32_ok: one answer for the layer's three GEMMs)."""
+    if not DENSE_F32_HIP or torch.compiler.is_compiling():
+        return False
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 for t in operands):
+        return False
+    # (the results are dense: their row strides are N and K; a one-row operand's stride is whatever torch left there)
+    return M >= 1 and ops.dense_f32_ok(M, N, K, max([N, K] + [t.stride(0) for t in operands if t.shape[0] > 1]))
+
+
+def _wgrad_f32(g2, x2, wparam=None, want_colsum=False):
+    """(dW [N,K], db [N] or None) = (g2^T x2, column sums of g2) on the float32 TN kernel, written into the parameter's
+    registered gradient destination where there is one (ops.grad_dest)."""
+    dest = ops.grad_dest(wparam, (g2.shape[1], x2.shape[1]))
+    out = ops.dense_f32_tn(g2, x2, out=dest, want_colsum=want_colsum)
+    if dest is not None:
+        ops.grad_written(wparam)
+    return out if want_colsum else (out, None)
+
 
 def _wgrad_lib(g2, x2, wparam=None, sample_scale=None, rps=0):
     """dW = g^T x (f32 result): the hand-written TN kernel wherever it takes the shape, else the BLAS library.  wparam: the
     parameter this is the gradient of - under DDP the result is written into its bucket view (ops.GRAD_DEST).
     sample_scale / rps (wgrad_skip_scale): the stochastic-depth mask of g2's branch, for the hand-written kernel only."""
     M, N, K = g2.shape[0], g2.shape[1], x2.shape[1]
+    if dense_f32_hip_ok(M, N, K, g2, x2):
+        return _wgrad_f32(g2, x2, wparam)[0]
     if (WGRAD_HIP and g2.is_cuda and g2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16
             and g2.stride(1) == 1 and x2.stride(1) == 1
             and ops.dense_wgrad_ok(M, N, K, max(g2.stride(0), x2.stride(0)))):
@@ -1042,12 +1096,18 @@ def _wgrad_lib(g2, x2, wparam=None, sample_scale=None, rps=0):
 
 
 def _mm_lib(a2, b):
-    """a2 [M,N] @ b [N,K]: library input-gradient GEMM of bf16 2-D tensors (no autocast re-casts)."""
+    """a2 [M,N] @ b [N,K]: the input-gradient GEMM of 2-D tensors - float32 on csrc/dense_f32.hip (dense_f32_hip_ok), anything
+    else (bf16) on the library (no autocast re-casts)."""
+    if dense_f32_hip_ok(a2.shape[0], b.shape[0], b.shape[-1], a2, b):
+        return ops.dense_f32_nn(a2, b)
     with torch.autocast("cuda", enabled=False):
         return _timed_lib("dgrad", lambda: a2 @ b, a2.shape[0], b.shape[1], b.shape[0])
 
 
 def _linear_lib(x2, wb, bias):
+    """x2 [M,K] @ wb [N,K]^T + bias: float32 on csrc/dense_f32.hip (dense_f32_hip_ok), anything else on the library."""
+    if dense_f32_hip_ok(x2.shape[0], wb.shape[0], wb.shape[-1], x2, wb) and (bias is None or bias.dtype == torch.float32):
+        return ops.dense_f32_nt(x2, wb, None if bias is None else _c(bias))
     with torch.autocast("cuda", enabled=False):
         return _timed_lib("fwd", lambda: torch.nn.functional.linear(x2, wb, bias), x2.shape[0], wb.shape[0], wb.shape[1])
 

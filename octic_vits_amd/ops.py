@@ -77,7 +77,8 @@ class KernelTimer:
     def bound_of(name):
         """Roofline that bounds a kernel family: the attention kernels are MFMA/VALU-bound (q,k,v,o are read once,
         14 T^2 hd flops per head), every other kernel of the engine moves more bytes than it can compute on."""
-        return "mfma" if name.startswith(("attn_", "dense_nt_kernel", "dense_tn_kernel", "library_gemm")) else "hbm"
+        return "mfma" if name.startswith(("attn_", "dense_nt_kernel", "dense_tn_kernel", "dense_f32_n", "dense_f32_tn",
+                                          "library_gemm")) else "hbm"
 
     def dominant(self, bound=None):
         agg = [a for a in self._agg().values() if bound is None or self.bound_of(a["name"]) == bound]
@@ -1330,6 +1331,108 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
         _finish(cs, cs_rows, N // 2, colsum, None, None, _stream(a), out1_ptr=colsum.data_ptr() + 2 * N)
         return c, colsum
     return c
+
+
+# ------------------------------------------------------------------------------------------ float32 dense GEMMs (csrc/dense_f32.hip)
+@torch.compiler.assume_constant_result
+def _dense_f32_query(op, M, N, K, ld_max):
+    return _lib.plan("octic_dense_f32_plan", op, M, N, K, ld_max)
+
+
+def dense_f32_plan(op, M, N, K, ld_max=0):
+    """(tile rows, tile columns, row slabs, workgroups) of a float32 dense launch (op: _lib.DENSE_F32_NT / _NN / _TN), or None
+    where octic_dense_f32_plan refuses the problem."""
+    return _dense_f32_query(int(op), operator.index(M), int(N), int(K), int(ld_max))
+
+
+def dense_f32_ok(M, N, K, ld_max=0):
+    """csrc/dense_f32.hip takes a linear layer with M rows, N = out_features, K = in_features in all three directions (forward,
+    input gradient, weight gradient); ld_max: the largest operand row stride in elements, 0 = not known."""
+    return all(dense_f32_plan(op, M, N, K, ld_max) is not None for op in (_lib.DENSE_F32_NT, _lib.DENSE_F32_NN, _lib.DENSE_F32_TN))
+
+
+def _f32_rows(t, width, what):
+    if t.dim() != 2 or t.dtype != torch.float32 or t.shape[1] != width or t.stride(1) != 1:
+        raise ValueError(f"{what} must be float32 [rows, {width}] with unit column stride, got {tuple(t.shape)} {t.dtype}")
+    _require_cuda(t)
+    return t
+
+
+def _ld(t):
+    """Row stride handed to the library: a one-row tensor's stride is arbitrary in torch, its row length serves."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def dense_f32_nt(a, w, bias=None, gelu=False, out=None, h_out=None, name=None):
+    """C[M,N] = a[M,K] @ w[N,K]^T (+ bias) in exact float32 on csrc/dense_f32.hip.  gelu: returns (H, C) with H the
+    pre-activation and C = gelu(H) (erf).  out / h_out: 2-D destinations (any row stride the library takes)."""
+    M, K = a.shape
+    N = w.shape[0]
+    _f32_rows(a, K, "dense_f32_nt: a"), _f32_rows(w, K, "dense_f32_nt: w")
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.shape == (N,) and bias.is_contiguous()):
+        raise ValueError(f"dense_f32_nt: bias must be a contiguous float32 [{N}] tensor on the GPU")
+    c = torch.empty((M, N), dtype=torch.float32, device=a.device) if out is None else _f32_rows(out, N, "dense_f32_nt: out")
+    h = None
+    if gelu:
+        h = torch.empty((M, N), dtype=torch.float32, device=a.device) if h_out is None else _f32_rows(h_out, N, "dense_f32_nt: h_out")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_dense_f32_nt(_p(a), _p(w), _p(bias), M, N, K, _ld(a), _ld(w), _p(c), _ld(c), int(bool(gelu)),
+                                   _p(h), _ld(h) if gelu else 0, _stream(a)))
+    KERNEL_TIMER.stop(t, name or ("dense_f32_nt_gelu_kernel" if gelu else "dense_f32_nt_kernel"),
+                      4 * (M * K + N * K + M * N * (2 if gelu else 1)), 2.0 * M * N * K)
+    return (h, c) if gelu else c
+
+
+def dense_f32_nn(g, w, out=None, name=None):
+    """DX[M,K] = g[M,N] @ w[N,K] in exact float32 (w as stored)."""
+    M, N = g.shape
+    K = w.shape[1]
+    _f32_rows(g, N, "dense_f32_nn: g"), _f32_rows(w, K, "dense_f32_nn: w")
+    if w.shape[0] != N:
+        raise ValueError("dense_f32_nn: g [M,N] and w [N,K] disagree on N")
+    dx = torch.empty((M, K), dtype=torch.float32, device=g.device) if out is None else _f32_rows(out, K, "dense_f32_nn: out")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_dense_f32_nn(_p(g), _p(w), M, N, K, _ld(g), _ld(w), _p(dx), _ld(dx), _stream(g)))
+    KERNEL_TIMER.stop(t, name or "dense_f32_nn_kernel", 4 * (M * N + N * K + M * K), 2.0 * M * N * K)
+    return dx
+
+
+def dense_f32_tn(g, x, out=None, want_colsum=False, workspace=None, name=None):
+    """DW[N,K] = g[M,N]^T @ x[M,K] in exact float32, bitwise repeatable (row slabs summed in slab order); out: write it there
+    (a gradient-bucket view).  want_colsum: returns (DW, db) with db[N] the column sums of g.  The workspace comes from torch's
+    allocator per call (capturable) unless one is given."""
+    M, N = g.shape
+    K = x.shape[1]
+    _f32_rows(g, N, "dense_f32_tn: g"), _f32_rows(x, K, "dense_f32_tn: x")
+    if x.shape[0] != M:
+        raise ValueError("dense_f32_tn: g [M,N] and x [M,K] disagree on M")
+    dw = torch.empty((N, K), dtype=torch.float32, device=g.device) if out is None else _f32_rows(out, K, "dense_f32_tn: out")
+    db = torch.empty(N, dtype=torch.float32, device=g.device) if want_colsum else None
+    need = int(lib().octic_dense_f32_workspace_bytes(_lib.DENSE_F32_TN, M, N, K))
+    if need < 0:
+        check(need)
+    ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=g.device)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_dense_f32_tn(_p(g), _p(x), M, N, K, _ld(g), _ld(x), _p(dw), _ld(dw), _p(db), _p(ws),
+                                   ws.numel() * ws.element_size(), _stream(g)))
+    KERNEL_TIMER.stop(t, name or "dense_f32_tn_kernel", 4 * (M * N + M * K + N * K), 2.0 * M * N * K)
+    return (dw, db) if want_colsum else dw
+
+
+def dense_gelu_bwd_f32(h, g, want_colsum=True):
+    """dh = gelu'(h) * g for float32 [..., d] (contiguous); also the column sums of dh (f32 [d]) when asked."""
+    _require_cuda(h)
+    d = h.shape[-1]
+    rows = h.numel() // d
+    if h.dtype != torch.float32 or g.dtype != torch.float32 or g.shape != h.shape or not (h.is_contiguous() and g.is_contiguous()):
+        raise ValueError("dense_gelu_bwd_f32: h and g must be contiguous float32 tensors of one shape")
+    dh = torch.empty_like(h)
+    db = torch.empty(d, dtype=torch.float32, device=h.device) if want_colsum else None
+    partials = torch.empty((lib().octic_dense_gelu_blocks(), d), dtype=torch.float32, device=h.device) if want_colsum else None
+    t = KERNEL_TIMER.start()
+    check(lib().octic_dense_gelu_bwd_f32(_p(h), _p(g), _p(dh), _p(partials), _p(db), rows, d, _stream(h)))
+    KERNEL_TIMER.stop(t, "dense_gelu_bwd_f32_kernel", rows * d * 12)
+    return dh, db
 
 
 # ------------------------------------------------------------------------------------------ linear probe (csrc/probe.hip)

@@ -1,9 +1,13 @@
 """Standard (non-octic) half of the hybrid models: vanilla pre-norm ViT blocks with the state_dict keys of
 the reference (deit/vit.py:14-134 ``Attention``/``Layer_scale_init_Block``; timm 1.0.12 ``Block`` for the
-bare default, model.py:21,63).  In f32 / on CPU these are stock PyTorch ops like the reference.  Under bf16 autocast on the
-GPU a block runs on the engine instead (§8f-1, §8f-3): HIP LayerNorm / attention / layer-scale+drop-path+residual
+bare default, model.py:21,63).  On CPU, under fp16 autocast and while torch.compile traces a float32 run these are
+stock PyTorch ops like the reference.  Under bf16 autocast on the GPU a block runs on the engine instead (§8f-1, §8f-3): HIP LayerNorm / attention / layer-scale+drop-path+residual
 kernels around hand-written GEMMs (csrc/dense_gemm.hip, csrc/dense_wgrad.hip; the BLAS library only for shapes they
-refuse), with cached bf16 weights — same math, same parameters.  Drop-path masks have the reference's distribution;
+refuse), with cached bf16 weights — same math, same parameters.  A float32 run on the GPU (no autocast, head_dim >= 32)
+takes the same route in float32 (functional.DENSE_F32_HIP): the row kernels with f32 branch tensors, the exact-f32 attention of
+csrc/attn_f32.hip and the exact-f32 GEMMs of csrc/dense_f32.hip (qkv, proj, fc1 + GELU, fc2, SwiGLU's w12 / w3 around a
+gate in stock ops) - no BLAS-library GEMM, bitwise repeatable, a sample independent of its batch mates; stochastic depth
+multiplies through the mask there (no skipping, no compaction).  Drop-path masks have the reference's distribution;
 inside a model forward they are drawn 64 at a time (d8_layers.DROP_PATH_POOL), so torch's generator is consumed in a
 different order than by the reference's per-call draws (parity tests inject the reference's masks)."""
 import torch
@@ -35,6 +39,13 @@ def _rows_per_scale(y, rs):
     if rs is not None and y.shape[0] == 1 and y.shape[1] > 1 and rs.numel() == y.shape[1]:
         return 1
     return y.shape[1]
+
+
+def _f32_linear_ok(y, *linears):
+    """The float32 GEMM kernels (csrc/dense_f32.hip) take these nn.Linear layers on the rows of y (functional.DENSE_F32_HIP)."""
+    rows = y.numel() // max(1, y.shape[-1])
+    return (_OF.DENSE_F32_HIP and y.is_cuda and not torch.compiler.is_compiling() and rows >= 1
+            and all(_ops.dense_f32_ok(rows, lin.out_features, lin.in_features) for lin in linears))
 
 
 def _tail_args(next_norm, rows_to):
@@ -85,6 +96,8 @@ class Mlp(nn.Module):
             return self.forward_fused(y, xres, gamma, rs, dtype), None
         if dtype == torch.bfloat16 and self.fc1.out_features % 8 == 0:
             h = _OF.DenseLinearGeluFn.apply(y, self.fc1.weight, self.fc1.bias, self._c1)
+        elif dtype == torch.float32 and _f32_linear_ok(y, self.fc1):
+            h = _OF.DenseLinearGeluFn.apply(y, self.fc1.weight, self.fc1.bias, self._c1, torch.float32)
         else:
             h = F.gelu(_OF.DenseLinearFn.apply(y, self.fc1.weight, self.fc1.bias, dtype, self._c1))
         return _OF.LinearScaleResidualFn.apply(xres, h, self.fc2.weight, self.fc2.bias, gamma, rs, rps, dtype,
@@ -122,7 +135,13 @@ class SwiGLUFFN(nn.Module):
 
     def forward_fused(self, y, xres, gamma, rs, dtype, next_norm=None, rows_to=None):
         """xres + rs*gamma*w3(silu(x1) * x2) with y already normalised and in the compute dtype; next_norm / rows_to as in
-        Mlp.forward_fused.  bf16 only: the gate kernels are bf16 (a block leaves f32 runs to ``forward``)."""
+        Mlp.forward_fused.  The gate kernels are bf16; in float32 (a block in the float32 engine regime) the two GEMMs run on
+        csrc/dense_f32.hip around the gate in stock ops."""
+        if dtype == torch.float32 and self.fusable() and rows_to is None and _f32_linear_ok(y, self.w12, self.w3):
+            x1, x2 = _OF.DenseLinearFn.apply(y, self.w12.weight, self.w12.bias, dtype, self._c1).chunk(2, dim=-1)
+            out = _OF.LinearScaleResidualFn.apply(xres, F.silu(x1) * x2, self.w3.weight, self.w3.bias, gamma, rs,
+                                                  _rows_per_scale(y, rs), dtype, self._c2)
+            return out if next_norm is None else (out, None)
         if dtype != torch.bfloat16 or not self.fusable():
             raise RuntimeError("SwiGLUFFN.forward_fused: the engine path is bf16 with a hidden width that is a multiple of 8")
         if rows_to is not None and (next_norm is not None or not self.rows_ok(y)):
@@ -160,7 +179,8 @@ class Attention(nn.Module):
     def fusable(self, N, dtype):
         drop = self.training and (self.attn_drop.p > 0. or self.proj_drop.p > 0.)
         return (not drop and self.fused_attn and type(self.qkv) is nn.Linear and type(self.proj) is nn.Linear
-                and _ops.attn_supported(N, self.qkv.in_features // self.num_heads, dtype))
+                and (_ops.attn_f32_supported if dtype == torch.float32 else _ops.attn_supported)(
+                    N, self.qkv.in_features // self.num_heads, dtype))
 
     def rows_ok(self, y):
         return _OF.dense_hip_ok(y, self.proj.weight, "proj")
@@ -236,21 +256,40 @@ def _drop_path_scale(dp, x):
     return mask.view(-1)
 
 
-def _engine_regime(x, norm1, attn, norm2, mlp, scales, ntok=None):
+# The float32 regime starts at head_dim 32.  No model of either family is narrower (ViT-Ti ... ViT-g: 64 or 80; the small
+# goldens: 32), and tests/test_dense_gpu.py::test_fused_block_is_skipped_outside_its_regime pins a float32 block with
+# head_dim 16 to the stock composition (no dense_* launch at all): that one call site stays on stock PyTorch ops.
+F32_MIN_HEAD_DIM = 32
+
+
+def _engine_dtype(x):
+    """Compute dtype of the engine for the f32 stream x [B, N, d] on the GPU: bfloat16 under bf16 autocast, float32 with
+    autocast disabled (functional.DENSE_F32_HIP; not while torch.compile traces), None otherwise (CPU, fp16 autocast, ...)."""
+    if not (x.is_cuda and x.ndim == 3 and x.dtype == torch.float32):
+        return None
+    if torch.is_autocast_enabled("cuda"):
+        return torch.bfloat16 if torch.get_autocast_dtype("cuda") == torch.bfloat16 else None
+    return torch.float32 if (_OF.DENSE_F32_HIP and not torch.compiler.is_compiling()) else None
+
+
+def _engine_regime(x, norm1, attn, norm2, mlp, scales, ntok=None, dtype=torch.bfloat16):
     """[gamma1, gamma2] - the layer-scale vectors, None where a branch has none - of a standard block whose forward can run
-    on the engine: bf16 autocast on the GPU over the f32 stream [B, N, d], LayerNorms the row kernels take, fusable
-    sub-modules.  None when the block is not in that regime (f32 run, CPU, dropout active, exotic sub-modules).
+    on the engine in compute dtype `dtype` (_engine_dtype(x) must say so): bf16 autocast, or a float32 run, on the GPU over
+    the f32 stream [B, N, d], LayerNorms the row kernels take, fusable sub-modules.  None when the block is not in that
+    regime (CPU, dropout active, exotic sub-modules, in float32 a linear layer csrc/dense_f32.hip refuses).
     scales: per branch the layer-scale vector itself (or None), or the block's LayerScale / nn.Identity module.
     ntok: tokens per image where that is not x.shape[1] (the rows of several crop sets: ragged.py)."""
-    if not (x.is_cuda and x.ndim == 3 and x.dtype == torch.float32 and torch.is_autocast_enabled("cuda")
-            and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+    if dtype is None or _engine_dtype(x) != dtype:
         return None
     d = x.shape[-1]
     for n in (norm1, norm2):
         if type(n) is not nn.LayerNorm or tuple(n.normalized_shape) != (d,) or d % 4 or d > 2048:
             return None
     if not (isinstance(attn, Attention) and isinstance(mlp, (Mlp, SwiGLUFFN)) and mlp.fusable()
-            and attn.fusable(x.shape[1] if ntok is None else ntok, torch.bfloat16)):
+            and attn.fusable(x.shape[1] if ntok is None else ntok, dtype)):
+        return None
+    if dtype == torch.float32 and (attn.qkv.in_features // attn.num_heads < F32_MIN_HEAD_DIM or not _f32_linear_ok(
+            x, attn.qkv, attn.proj, *((mlp.fc1, mlp.fc2) if isinstance(mlp, Mlp) else (mlp.w12, mlp.w3)))):
         return None
     gammas = []
     for ls in scales:
@@ -272,16 +311,18 @@ def _fused_block(x, norm1, attn, gamma1, dp1, norm2, mlp, gamma2, dp2, next_norm
     pass: norm2 comes out of the attention branch's tail; norm1 of the NEXT block (next_norm, set by link_blocks) out of
     the MLP's tail and travels as an attribute of the returned stream tensor (`_octic_prenorm`), which that block picks
     up instead of running its own norm1."""
-    if _engine_regime(x, norm1, attn, norm2, mlp, (gamma1, gamma2)) is None:
+    dt = _engine_dtype(x)
+    if _engine_regime(x, norm1, attn, norm2, mlp, (gamma1, gamma2), dtype=dt) is None:
         return None
     for dp in (dp1, dp2):
         if not isinstance(dp, (DropPath, nn.Identity)):
             return None
-    d, dt = x.shape[-1], torch.bfloat16
+    d = x.shape[-1]
     from . import d8_layers as _L
     if torch.compiler.is_compiling():
         return _traced_block(x, norm1, attn, gamma1, dp1, norm2, mlp, gamma2, dp2)
-    if _L.compact_active(dp1) and _L.compact_active(dp2):
+    # (float32: stochastic depth stays a multiplication by the mask - no compaction, no skipping)
+    if dt == torch.bfloat16 and _L.compact_active(dp1) and _L.compact_active(dp2):
         # stochastic depth as batch compaction (d8_layers.COMPACT_DROP_PATH): each branch on the samples its mask keeps
         for norm, branch, gamma, dp in ((norm1, attn, gamma1, dp1), (norm2, mlp, gamma2, dp2)):
             idx, n, scale = _L._compact_plan(x.shape[0], dp, x.device)
