@@ -1134,6 +1134,52 @@ int64_t octic_dino_color_workspace_bytes(int N, int H, int W);
 int octic_dino_color_u8(const uint8_t* crops, void* dst, int dtype_out, const octic_dino_row* rows, float mean0, float mean1,
                         float mean2, float std0, float std1, float std2, int N, int H, int W, void* workspace, void* stream);
 
+/* ---- the DeiT-III crops and evaluation resize on ragged uint8 images (deit/augment.py:90-108, deit/datasets.py:91-132) -------
+ * timm's RandomResizedCropAndInterpolation(bicubic), the --src crop (Resize + RandomCrop(padding, reflect)), the evaluation
+ * transform (Resize(bicubic) + CenterCrop) and the quarter turns / mirror of --rot-eval / --flop-eval, as ONE windowed resample:
+ * an OH x OW window of the reflect-padded, resized box of a source, turned and mirrored.  The host draws everything and uploads
+ * one row per output image plus the coefficient pool of octic_dino_resize_coeffs (a block per image and axis, w -> rw and
+ * h -> rh, layout as above).  Output pixel (y, x) of image n:
+ *   orientation  undo the mirror (flip != 0: x -> OW-1-x), then the rot quarter turns COUNTER-CLOCKWISE, to get the position
+ *                (wy, wx) in the window: rot 0 (y, x); 1 (x, OH-1-y); 2 (OH-1-y, OW-1-x); 3 (OW-1-x, y).  This is
+ *                ImageOps.mirror(img.rotate(90 rot)) of Pillow (rotate turns counter-clockwise and takes its exact transpose
+ *                path for quarter turns of a square image; checked against Pillow 12), numpy.rot90(window, rot)[:, ::-1].
+ *                rot 1 and 3 need OH == OW.
+ *   window       (ry, rx) = (win_top + wy - pad, win_left + wx - pad), reflected into [0, rh) x [0, rw) as
+ *                numpy.pad(mode="reflect") does: i < 0 -> -i, i >= n -> 2 (n - 1) - i (no edge repeat; pad < min(rh, rw)).
+ *   resize       pixel (ry, rx) of img.crop(box).resize((rw, rh), BICUBIC): Pillow's 8-bit two-pass resample exactly as stated
+ *                for octic_dino_resize_u8 - horizontal pass to uint8, the vertical pass on that, a pass of equal lengths the
+ *                identity.  Only the resized rows and columns the window touches are computed.  The products k_j p run on
+ *                the 24-bit multiplier: exact for |k_j| < 2^23, which Pillow's coefficients (at most 2^22 (1 + the side lobes))
+ *                are; the host checks it.
+ *   output       OCTIC_U8: the pixel; OCTIC_F32: (v / 255 - mean[c]) / std[c], two correctly rounded f32 divisions          */
+typedef struct {                           /* one output image; 8-byte aligned, 80 bytes                   */
+  int64_t src_offset;                      /* byte offset of the source image [src_h, src_w, 3] in `data`  */
+  int32_t src_h, src_w;
+  int32_t top, left, h, w;                 /* the box that is resampled                                    */
+  int32_t rh, rw;                          /* the size the box is resampled to                             */
+  int32_t pad;                             /* reflect padding round the resized image                      */
+  int32_t win_top, win_left;               /* the OH x OW window in the padded resized image               */
+  int32_t rot, flip;                       /* rot in 0..3: quarter turns counter-clockwise, then (flip != 0) mirrored along x */
+  int32_t hcoef, htaps, vcoef, vtaps;      /* offsets (int32 words) of the two coefficient blocks in the pool (w -> rw: bounds[rw][2],
+                                              k[rw][htaps]; h -> rh likewise), taps per output               */
+  int32_t reserved;
+} octic_crop_row;
+/* the most taps per output of the VERTICAL pass the kernel holds for windows OW wide (its uint8 rows live in LDS);
+ * OCTIC_ESHAPE unless 5 <= OW <= 4096.  The host refuses boxes whose 2 ceil(2 max(h / rh, 1)) + 1 exceeds it.             */
+int octic_crop_resize_max_taps(int OW);
+/* window rows per workgroup of octic_crop_resize_u8 (what its tests put their output heights around)                        */
+int octic_crop_resize_rows(void);
+/* dst, by dtype_out: OCTIC_U8 - uint8 [N, OH, OW, 3]; OCTIC_F32 - f32 [N, 3, OH, OW], normalised.  data: the uint8 source
+ * images back to back (data_bytes in all), left untouched; coef: the pool (coef_len int32 words).  5 <= OH, OW <= 4096.  A row
+ * whose source, box, coefficient blocks or window do not lie inside data / the source / the pool / the padded resized image,
+ * whose rot is outside 0..3 (or odd with OH != OW) or whose pad is negative or >= min(rh, rw) gives an all-zero image (f32: 0.0),
+ * never a stray access; every bound read from the pool is clamped.  rows 8-byte aligned; data and dst must not overlap
+ * (OCTIC_ESHAPE).  Integer sums only, no atomics: bitwise reproducible, and independent of an image's place in the batch.  */
+int octic_crop_resize_u8(const uint8_t* data, int64_t data_bytes, const octic_crop_row* rows, const int32_t* coef,
+                         int64_t coef_len, int N, int OH, int OW, void* dst, int dtype_out, float mean0, float mean1,
+                         float mean2, float std0, float std1, float std2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

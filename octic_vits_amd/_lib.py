@@ -243,6 +243,9 @@ _PROTOS = {
     "octic_dino_resize_u8": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p]),
     "octic_dino_color_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
     "octic_dino_color_u8": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_float] * 6 + [c_int, c_int, c_int, c_void_p, c_void_p]),
+    "octic_crop_resize_max_taps": (c_int, [c_int]),
+    "octic_crop_resize_rows": (c_int, []),
+    "octic_crop_resize_u8": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_int] + [c_float] * 6 + [c_void_p]),
 }
 
 

@@ -7,13 +7,16 @@ runs as HIP kernels (csrc/augment.hip) on the decoded, cropped uint8 batch [B, H
 batch on their way to the device, and no PIL chain on the host.  The kernels reproduce PIL's arithmetic bit for bit (the
 contract is in include/octic_hip.h; tests/golden/augment_numpy.py restates it, tests/golden/augment.npz holds PIL's results).
 
-THE CROP STAYS ON THE HOST: decoding, ``RandomResizedCropAndInterpolation`` and the sampler (``RASampler``) work on the
-variable-size source image; what they yield - uint8 HWC crops of one size - is this module's input.  Not built: ``--src`` (the
-simple random crop) and hue jitter in this recipe.  The DINOv2 multi-crop augmentation, with the bicubic resized crop and hue
-on the device, is ``octic_vits_amd/dino_augment.py``.
+THE CROP IN FRONT is ``octic_vits_amd/crop.py`` (csrc/crop.hip): ``ThreeAugment(crop=RandomResizedCrop())`` or, for ``--src``,
+``crop=SrcCrop()`` takes the decoded sources of any sizes as a ``dino_augment.PackedImages``; ``apply_sources`` runs the crop launch
+(uint8 crops of one size) and then the kernels of this module, and ``draw_sources`` draws, per sample, the crop's variates and
+then the ones listed below - the reference pipeline's order on the shared ``random`` stream.  Without ``crop`` the input is the
+uint8 HWC crops of one size that a host-side crop yields.  Decoding and the sampler (``RASampler``) stay on the host; hue jitter is
+not part of this recipe.  The DINOv2 multi-crop augmentation is ``octic_vits_amd/dino_augment.py``.
 
 ``ThreeAugment.draw`` consumes the random streams exactly as the reference pipeline does for B samples in turn, per sample:
 
+0. with ``crop`` (``draw_sources`` only): the crop's own draws, see ``octic_vits_amd/crop.py``;
 1. flip: ``torch.rand(1) < hflip``;
 2. ``RandomChoice``: one ``random.random()`` (``random.choices`` without weights: ``floor(random() * 3)``);
 3. the chosen op's own ``random.random()`` test - at p = 1 always true, but consumed;
@@ -134,7 +137,8 @@ class ThreeAugment:
     """The reference's 3-Augment behind the crop on the HIP kernels of csrc/augment.hip (see the module docstring for the
     draw order).  ``apply`` maps a uint8 [B, H, W, 3] batch on the GPU to the normalised f32 [B, 3, H, W] batch."""
 
-    def __init__(self, color_jitter=0.3, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, hflip=0.5, rng=None, generator=None):
+    def __init__(self, color_jitter=0.3, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, hflip=0.5, rng=None, generator=None,
+                 crop=None):
         if color_jitter is not None and color_jitter < 0:
             raise ValueError("ThreeAugment: color_jitter must be non-negative")
         if len(mean) != 3 or len(std) != 3:
@@ -146,31 +150,54 @@ class ThreeAugment:
         self.hflip = hflip
         self.rng = random if rng is None else rng
         self.generator = generator
+        if crop is not None and not (hasattr(crop, "draw_one") and hasattr(crop, "launch")):
+            raise TypeError(f"ThreeAugment: `crop` must be a transform of octic_vits_amd.crop, got {type(crop).__name__}")
+        self.crop = crop
         self._workspaces = {}
 
     # ---- the host side -------------------------------------------------------------------------------------------------
     def draw(self, B):
         """One draw for B samples, sample by sample in the reference pipeline's order."""
         p = AugParams.identity(int(B))
-        r, g = self.rng, self.generator
-        jitter = self.color_jitter is not None and not self.color_jitter == 0
         for i in range(len(p)):
-            p.flip[i] = bool(torch.rand(1, generator=g) < self.hflip)
-            choice = int(r.random() * 3)
-            if choice == 2:
-                if r.random() <= 1.0:
-                    p.op[i] = OP_BLUR
-                    p.radius[i] = r.uniform(0.1, 2.0)
-            elif r.random() < 1.0:
-                p.op[i] = OP_GRAY if choice == 0 else OP_SOLARIZE
-            if jitter:
-                lo, hi = max(0.0, 1.0 - self.color_jitter), 1.0 + self.color_jitter
-                perm = torch.randperm(4, generator=g).numpy()
-                p.order[i] = np.where(perm < 3, perm, -1)
-                p.brightness[i] = float(torch.empty(1).uniform_(lo, hi, generator=g))
-                p.contrast[i] = float(torch.empty(1).uniform_(lo, hi, generator=g))
-                p.saturation[i] = float(torch.empty(1).uniform_(lo, hi, generator=g))
+            self._draw_sample(p, i)
         return p
+
+    def _draw_sample(self, p, i):
+        r, g = self.rng, self.generator
+        p.flip[i] = bool(torch.rand(1, generator=g) < self.hflip)
+        choice = int(r.random() * 3)
+        if choice == 2:
+            if r.random() <= 1.0:
+                p.op[i] = OP_BLUR
+                p.radius[i] = r.uniform(0.1, 2.0)
+        elif r.random() < 1.0:
+            p.op[i] = OP_GRAY if choice == 0 else OP_SOLARIZE
+        if self.color_jitter is not None and not self.color_jitter == 0:
+            lo, hi = max(0.0, 1.0 - self.color_jitter), 1.0 + self.color_jitter
+            perm = torch.randperm(4, generator=g).numpy()
+            p.order[i] = np.where(perm < 3, perm, -1)
+            p.brightness[i] = float(torch.empty(1).uniform_(lo, hi, generator=g))
+            p.contrast[i] = float(torch.empty(1).uniform_(lo, hi, generator=g))
+            p.saturation[i] = float(torch.empty(1).uniform_(lo, hi, generator=g))
+
+    def _need_crop(self, what):
+        if self.crop is None:
+            raise RuntimeError(f"ThreeAugment.{what}: built without `crop` (octic_vits_amd.crop.RandomResizedCrop or SrcCrop)")
+
+    def draw_sources(self, heights, widths):
+        """One draw for B decoded sources of the given sizes -> (``CropParams``, ``AugParams``): per sample, in turn, the crop's
+        draws and then what ``draw`` consumes for that sample - the reference pipeline's stream order."""
+        self._need_crop("draw_sources")
+        heights = np.ascontiguousarray(heights, dtype=np.int64).reshape(-1)
+        widths = np.ascontiguousarray(widths, dtype=np.int64).reshape(-1)
+        if heights.shape != widths.shape or len(heights) == 0 or min(heights.min(), widths.min()) < 1:
+            raise ValueError("ThreeAugment.draw_sources: heights and widths must be [B] each, B >= 1, all sides >= 1")
+        p, drawn = AugParams.identity(len(heights)), []
+        for i in range(len(p)):
+            drawn.append(self.crop.draw_one(int(heights[i]), int(widths[i])))
+            self._draw_sample(p, i)
+        return self.crop.params(heights, widths, drawn), p
 
     # ---- the device side -----------------------------------------------------------------------------------------------
     @staticmethod
@@ -210,6 +237,18 @@ class ThreeAugment:
             raise ValueError("ThreeAugment.apply: the parameters were drawn for another batch size")
         table = torch.from_numpy(params.table()).to(images_u8.device)
         return self.launch(images_u8, table, out=out, uint8_out=uint8_out)
+
+    def apply_sources(self, packed, params=None, out=None, uint8_out=False):
+        """``apply`` for a ``dino_augment.PackedImages`` of decoded sources: the crop launch (uint8 crops), then the launches of
+        ``apply``.  params: the pair ``draw_sources`` returns (default: a fresh one)."""
+        self._need_crop("apply_sources")
+        from .dino_augment import PackedImages
+        if not isinstance(packed, PackedImages):
+            raise TypeError(f"ThreeAugment.apply_sources: `packed` must be a PackedImages (pack_images), got {type(packed).__name__}")
+        if params is None:
+            params = self.draw_sources(*packed.host_sizes())
+        crop_params, aug_params = params
+        return self.apply(self.crop.apply(packed, crop_params, uint8_out=True), aug_params, out=out, uint8_out=uint8_out)
 
     def to_tensor(self, images_u8, out=None):
         """``ToTensor`` + ``Normalize`` only (the identity row): the evaluation loader's transform behind its crop."""

@@ -39,7 +39,7 @@ from . import ssl as _ssl
 from .augment import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD
 
 __all__ = ["PackedImages", "pack_images", "DinoAugParams", "DinoAugment", "resize_coeffs", "blur_weights", "hue_shift",
-           "ROW_WORDS"]
+           "upload_tables", "ROW_WORDS"]
 
 ROW_WORDS = ops.DINO_ROW_WORDS
 _f32 = np.float32
@@ -270,6 +270,25 @@ class DinoAugParams:
 
 
 # ------------------------------------------------------------------------------------------------ the transform
+def upload_tables(dev, tables, uploaded, device):
+    """Host tables (numpy, by name) -> the device tables ``dev`` = {name: (device tensor, pinned staging)} through their staging
+    buffers; only the used part of each travels.  ``uploaded`` keeps the event of the last upload per table set: the staging
+    buffers are reused only when it has passed."""
+    done = uploaded.get(id(dev))
+    if done is not None:
+        done.synchronize()                                  # the staging buffers are free again
+    out = {}
+    for k, (d, pinned) in dev.items():
+        src = torch.from_numpy(tables[k])
+        n = src.shape[0]
+        pinned[:n].copy_(src)
+        d[:n].copy_(pinned[:n], non_blocking=True)
+        out[k] = d
+    done = uploaded[id(dev)] = torch.cuda.Event()
+    done.record(torch.cuda.current_stream(device))
+    return out
+
+
 class DinoAugment:
     """``DataAugmentationDINO`` on the HIP kernels of csrc/dino_augment.hip; the defaults are ``ssl_default_config.yaml``'s.
     ``max_side`` bounds the sources' sides (the loader's job): it fixes the capacity of the device tables."""
@@ -367,19 +386,7 @@ class DinoAugment:
         dev = self.device_tables(B, device)
         if tables["coef"].size > dev["coef"][0].numel():
             raise ValueError("DinoAugment: the coefficient pool exceeds the capacity `max_side` fixes")
-        done = self._uploaded.get(id(dev))
-        if done is not None:
-            done.synchronize()                              # the staging buffers are free again
-        out = {}
-        for k, (d, pinned) in dev.items():
-            src = torch.from_numpy(tables[k])
-            n = src.shape[0]
-            pinned[:n].copy_(src)
-            d[:n].copy_(pinned[:n], non_blocking=True)
-            out[k] = d
-        done = self._uploaded[id(dev)] = torch.cuda.Event()
-        done.record(torch.cuda.current_stream(device))
-        return out
+        return upload_tables(dev, tables, self._uploaded, device)
 
     def _workspace(self, N, H, W, device, crops=True):
         """(workspace, uint8 crops buffer) of one launch, kept per shape AND stream: calls on different streams get buffers of

@@ -1985,3 +1985,48 @@ def dino_color_u8(crops, rows, mean, std, dst, workspace=None):
                                     N, H, W, _p(workspace), _stream(crops)))
     KERNEL_TIMER.stop(t, "dino_color_kernels", 3 * crops.numel() + dst.numel() * dst.element_size())
     return dst
+
+
+# ------------------------------------------------------------------------- DeiT crops and evaluation resize (csrc/crop.hip)
+CROP_ROW_WORDS = 20          # sizeof(octic_crop_row) / 4
+
+
+def crop_resize_max_taps(OW):
+    """The most taps per output pixel octic_crop_resize_u8 holds for windows OW wide."""
+    n = lib().octic_crop_resize_max_taps(int(OW))
+    if n < 0:
+        check(int(n))
+    return n
+
+
+def crop_resize_rows():
+    """Window rows per workgroup of octic_crop_resize_u8."""
+    return int(lib().octic_crop_resize_rows())
+
+
+def crop_resize_u8(data, rows, coef, mean, std, dst):
+    """dst = the windows the device rows (octic_crop_row) describe, cut from the packed uint8 images `data` with the int32
+    coefficient pool `coef`: uint8 [N, OH, OW, 3], or f32 [N, 3, OH, OW] normalised with mean / std (three floats each)."""
+    for t in (data, rows, coef, dst):
+        _require_cuda(t)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise ValueError("crop_resize_u8: data must be a contiguous 1-D uint8 tensor (PackedImages.data)")
+    if coef.dtype != torch.int32 or coef.dim() != 1 or not coef.is_contiguous():
+        raise ValueError("crop_resize_u8: the coefficient pool must be a contiguous 1-D int32 tensor")
+    if dst.dim() != 4 or not dst.is_contiguous():
+        raise ValueError("crop_resize_u8: the output must be a contiguous uint8 [N, OH, OW, 3] or float32 [N, 3, OH, OW] tensor")
+    if dst.dtype == torch.float32 and dst.shape[1] == 3:
+        (N, _, OH, OW), code = dst.shape, _lib.F32
+    elif dst.dtype == torch.uint8 and dst.shape[3] == 3:
+        (N, OH, OW, _), code = dst.shape, _lib.U8
+    else:
+        raise TypeError(f"crop_resize_u8: the output is float32 [N, 3, OH, OW] or uint8 [N, OH, OW, 3], got {tuple(dst.shape)} {dst.dtype}")
+    if rows.dtype != torch.int32 or tuple(rows.shape) != (N, CROP_ROW_WORDS) or not rows.is_contiguous():
+        raise ValueError(f"crop_resize_u8: the rows must be a contiguous int32 [{N}, {CROP_ROW_WORDS}] tensor (CropParams.tables())")
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("crop_resize_u8: mean and std take three values each")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_crop_resize_u8(_p(data), data.numel(), _p(rows), _p(coef), coef.numel(), N, OH, OW, _p(dst), code,
+                                     *[float(v) for v in mean], *[float(v) for v in std], _stream(data)))
+    KERNEL_TIMER.stop(t, "crop_resize_kernel", data.numel() + dst.numel() * dst.element_size())
+    return dst

@@ -1043,7 +1043,10 @@ class Trainer:
         cropped batch as uint8 [B, H, W, 3]: every step draws the flip / op / jitter parameters on the host, uploads them as a second
         small device table and runs the kernels of csrc/augment.hip on the WHOLE batch in front of the mix; their normalised f32
         [B, 3, H, W] output is what the mix (or, without ``mixup``, the model) reads, and a captured step's input buffer is the uint8
-        batch.  None: ``step`` takes normalised f32 images as before.
+        batch.  With ``ThreeAugment(crop=...)`` (``octic_vits_amd.crop``: ``RandomResizedCrop`` or ``SrcCrop``) they also take the
+        decoded SOURCES of any sizes as a ``dino_augment.PackedImages``: the crop launch (csrc/crop.hip) runs eagerly in front - for a
+        captured step outside the graph, writing into the graph's uint8 staging batch - and the rest is the same path; a uint8
+        batch is still accepted and skips the crop.  None: ``step`` takes normalised f32 images as before.
         segment_graphs = n > 0 (GPU only): forward and backward run as 2 n hipGraph replays (``SegmentedModel``), the
         loss, the gradient all-reduce hooks and the optimizer stay eager - the cheap-on-the-host step for gradient
         accumulation, where the whole-step graph of ``capture`` does not apply.
@@ -1218,6 +1221,24 @@ class Trainer:
         """A fresh 3-Augment draw for this uint8 batch, on its way to the device table (as ``_mix_draw``)."""
         return self._aug_table(samples.shape[0], samples.device).upload(self.augment.draw(samples.shape[0]))
 
+    def _is_packed(self, samples):
+        """A batch of decoded sources in front of the crop (``Trainer(augment=ThreeAugment(crop=...))``)."""
+        from .dino_augment import PackedImages
+        if not isinstance(samples, PackedImages):
+            return False
+        if self.augment is None or self.augment.crop is None:
+            raise TypeError("Trainer: a PackedImages batch needs Trainer(augment=ThreeAugment(crop=...)) (octic_vits_amd.crop)")
+        return True
+
+    def _crop_sources(self, packed, out=None):
+        """This step's crop and 3-Augment draws for a batch of decoded sources (per sample the crop's, then the augmentation's: the
+        reference's stream order), the augmentation table on its way to the device, and the crop launch: the uint8 [B, S, S, 3]
+        crops, written into ``out`` (a captured step's staging batch) if given."""
+        crop_params, aug_params = self.augment.draw_sources(*packed.host_sizes())
+        crops = self.augment.crop.apply(packed, crop_params, out=out, uint8_out=True)
+        self._aug_table(crops.shape[0], crops.device).upload(aug_params)
+        return crops
+
     def _aug_batch(self, samples):
         """The launches of the augmentation (also what ``capture`` records): uint8 [B, H, W, 3] -> normalised f32 [B, 3, H, W]."""
         return self.augment.launch(samples, self._aug_table(samples.shape[0], samples.device).table)
@@ -1294,17 +1315,21 @@ class Trainer:
         if self._ddp_args is not None and self.model is self.segmented:
             raise RuntimeError("Trainer(distributed=True, segment_graphs=n): call capture_segments(micro_batch) before the "
                                "first step (the slices are captured, then wrapped in DistributedDataParallel)")
-        if self.augment is not None:
+        packed = self._is_packed(samples)
+        if self.augment is not None and not packed:
             self.augment.check_batch(samples, "Trainer(augment=...)")
         if self.mixup is not None:
-            self._mix_check(samples, targets)
+            self._mix_check(samples.offsets if packed else samples, targets)
         self.model.train()
         # engine.py:67-71 two steps late on a pinned host copy (_LossWatch): no stream drain per step
         self._steps += 1
         if self._steps % self.check_every == 0:
             self._watch.check()
         if self.augment is not None:
-            self._aug_draw(samples)
+            if packed:
+                samples = self._crop_sources(samples)
+            else:
+                self._aug_draw(samples)
             samples = self._aug_batch(samples)
         if self.mixup is not None:
             self._mix_draw(samples)
@@ -1383,12 +1408,19 @@ class Trainer:
         if self.mixup is not None:
             # sx / sy are the staging images and labels; the parameter table is the third static input (``_mix_table``):
             # ``GraphedStep.replay`` refills all three in front of the replay, the mix kernels and the loss are in the graph
-            self._mix_check(samples, targets)
-        if self.augment is not None:                    # sx is the uint8 staging batch; the augmentation table a static input
-            self.augment.check_batch(samples, "Trainer(augment=...)")
-        sx, sy = samples.clone(), targets.clone()
-        for _ in range(max(1, warmup)):
-            self.step(sx, sy)
+            self._mix_check(samples.offsets if self._is_packed(samples) else samples, targets)
+        sy = targets.clone()
+        if self._is_packed(samples):                    # decoded sources: the warm-up steps crop them as eager steps do (the same
+            for _ in range(max(1, warmup)):             # draws); the graph's input is the uint8 staging batch the crop launch of
+                self.step(samples, sy)                  # every ``replay`` fills from outside the graph
+            S = self.augment.crop.size
+            sx = torch.zeros(len(samples), S, S, 3, dtype=torch.uint8, device=sy.device)
+        else:
+            if self.augment is not None:                # sx is the uint8 staging batch; the augmentation table a static input
+                self.augment.check_batch(samples, "Trainer(augment=...)")
+            sx = samples.clone()
+            for _ in range(max(1, warmup)):
+                self.step(sx, sy)
         torch.cuda.synchronize()
         self.model.train()
         graph = torch.cuda.CUDAGraph()
@@ -1487,7 +1519,10 @@ class GraphedStep:
         # keeps a pinned host copy per step, taken by a stream-ordered copy behind the replay)
         if t._steps % t.check_every == 0:
             t._watch.check()
-        if samples is not None and samples.data_ptr() != self.samples.data_ptr():
+        packed = samples is not None and t._is_packed(samples)
+        if packed:                                      # decoded sources: cropped into the staging batch, outside the graph
+            t._crop_sources(samples, out=self.samples)
+        elif samples is not None and samples.data_ptr() != self.samples.data_ptr():
             if t.augment is not None:
                 t.augment.check_batch(samples, "Trainer(augment=...)")
             self.samples.copy_(samples, non_blocking=True)
@@ -1495,7 +1530,7 @@ class GraphedStep:
             if t.mixup is not None:
                 t._mix_check(self.samples, targets)
             self.targets.copy_(targets, non_blocking=True)
-        if t.augment is not None:                       # this step's 3-Augment draw, likewise
+        if t.augment is not None and not packed:        # this step's 3-Augment draw, likewise (drawn with the crop's if packed)
             t._aug_draw(self.samples)
         if t.mixup is not None:                         # this step's Mixup / CutMix draw: the captured kernels read the table
             t._mix_draw(self.samples)
@@ -1516,19 +1551,27 @@ class _null:
 
 
 @torch.no_grad()
-def evaluate(model, batches, graphed=True):
+def evaluate(model, batches, graphed=True, transform=None):
     """deit/engine.py:98-128 on one GPU: eval mode, bf16 autocast, ``batches`` yields (images, int64 labels).  Per batch the
     cross-entropy sum and the top-1 / top-5 counts accumulate ON THE DEVICE (``ops.probe_ce`` with one head); the host reads
     them once at the end.  Returns {"loss": mean over the images, "acc1", "acc5": percentages} as the reference's
     ``global_avg`` meters (weighted by batch size).  graphed: batches of the first batch's shape run through
     ``serve.GraphedForward``, a ragged last batch eagerly.  Images may also come as uint8 [B, H, W, 3] (decoded, cropped): they
-    go through ``augment.to_tensor`` (ToTensor + Normalize on the device, ImageNet's mean / std as in deit/datasets.py:134-135)."""
+    go through ``augment.to_tensor`` (ToTensor + Normalize on the device, ImageNet's mean / std as in deit/datasets.py:134-135), or
+    as ``dino_augment.PackedImages`` (decoded sources of any sizes): those go through ``transform``, a ``crop.EvalTransform``
+    (default ``EvalTransform()``: Resize(256, bicubic) + CenterCrop(224) + ToTensor + Normalize in one launch of csrc/crop.hip)."""
+    from .dino_augment import PackedImages
     from . import ops
     model.eval()
     gf = None
     loss_sum = topk = None
     n = 0
     for images, labels in batches:
+        if isinstance(images, PackedImages):
+            if transform is None:
+                from .crop import EvalTransform
+                transform = EvalTransform()
+            images = transform(images)
         ops._require_cuda(images)
         ops._require_cuda(labels)
         if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] != images.shape[0]:
