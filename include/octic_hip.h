@@ -954,6 +954,21 @@ int octic_seg_rownorms(const float* X, int64_t ldx, int64_t N, int D, float* nor
 int octic_seg_knn(const float* Q, int64_t ldq, int64_t n, const float* K, int64_t ldk, int64_t M, int D, const float* qnorm,
                   const float* knorm, const uint8_t* skip, int kmax, int metrics, int splits, int32_t* idx_l2, float* dist_l2,
                   int32_t* idx_cos, float* dist_cos, int64_t ldo, void* workspace, void* stream);
+/* The same search on rows of bf16 (the reference's `classifiers_kwargs: {knn: {dtype: bfloat16}}`, eval_config.yaml; the casts
+ * of KNNClassifier._fit / _predict_batch, eval_segmentation.py:207, :248).  X, Q and K hold bf16 values the caller rounded ONCE
+ * (round to nearest even, torch's cast); strides are in elements and rows are 16-byte aligned (ldx, ldq, ldk % 8 == 0).
+ * Everything after that cast is f32: octic_seg_rownorms_bf16 sums the squares of the rounded values in f32 in a fixed order;
+ * octic_seg_knn_bf16 forms the dot products on the bf16 MFMA (16x16x32) with f32 accumulation - one accumulator chain over D in
+ * ascending channel order per pair - and then the SAME ordering keys, TOTAL ORDER, NaN and skip rules as octic_seg_knn; dist_*
+ * are those f32 values.  Both distances come from the one pass: no second, normalised-then-rounded copy of the keys exists.
+ * The list ordered by the f32 distance of the rounded operands is one valid answer to the reference's bf16 problem (whose
+ * 8-bit distances tie in bulk, and torch.topk leaves ties open), and a reproducible one: bitwise equal for every split count
+ * and every query order or batching.  Same limits, error codes, tiles, plan and workspace as octic_seg_knn:
+ * octic_seg_knn_plan and octic_seg_knn_workspace_bytes answer for both element types.                                        */
+int octic_seg_rownorms_bf16(const void* X, int64_t ldx, int64_t N, int D, float* norms, void* stream);
+int octic_seg_knn_bf16(const void* Q, int64_t ldq, int64_t n, const void* K, int64_t ldk, int64_t M, int D, const float* qnorm,
+                       const float* knorm, const uint8_t* skip, int kmax, int metrics, int splits, int32_t* idx_l2,
+                       float* dist_l2, int32_t* idx_cos, float* dist_cos, int64_t ldo, void* workspace, void* stream);
 /* out [nk, n, L] (uint8): out[i, r, l] = the most frequent of labels[idx[r, 0 .. ks[i]-1], l], the smallest value on a tie
  * (torch.mode), over the raw label values (an ignored value can win).  idx has row stride ldi; labels is [R, L] of esize-byte
  * integers (values 0 .. 255) and an index outside [0, R) casts no vote.  ks: HOST array of nk <= 8 ascending values 1 .. 32.  */

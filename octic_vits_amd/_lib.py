@@ -224,6 +224,9 @@ _PROTOS = {
     "octic_seg_rownorms": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p]),
     "octic_seg_knn": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                               c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
+    "octic_seg_rownorms_bf16": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p]),
+    "octic_seg_knn_bf16": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     "octic_seg_knn_vote": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_int, c_i64, c_int, ctypes.POINTER(c_int), c_int, c_void_p,
                                    c_void_p]),
     "octic_knn_topk_plan": (c_int, [c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_int)]),

@@ -19,6 +19,11 @@
 // for the distances, the two row norms).  It does not depend on the pair's place in a tile, on the split or on the batch, so the
 // merged lists are the global answer and results are bitwise equal for every split count, every query order and every
 // batching.  No floating-point atomics.  Every row and element offset is 64-bit.
+// BF16 OPERANDS (knn_stream_bf16, seg_knn_kernel only): rows already rounded to bf16 go through LDS in chunks of 64 channels
+// (the same 128 bytes a row as 32 f32 channels, so the same image and the same row stride) and the dot products run on
+// mfma_f32_16x16x32_bf16 with f32 accumulation: per pair ONE accumulator chain over the D / 32 k-steps in ascending channel
+// order, step s holding channels 32 s .. 32 s + 31.  What the instruction does inside a step is a function of its 32 operand
+// pairs alone, so the contract above holds for this stream as it stands: a dot depends on the two rows and on D only.
 #pragma once
 #include "octic_common.hpp"
 
@@ -26,6 +31,7 @@ namespace octic {
 
 constexpr int KNN_KT = 128;     // keys per tile
 constexpr int KNN_LD = 36;      // 32 k + 4: as SEG_FW_LD of segeval.hip
+constexpr int KNN_LD16 = 72;    // the same 144-byte row as bf16: 64 k + 8
 constexpr int KNN_MAX_SPLITS = 64;
 
 __device__ __forceinline__ f32x4 knn_mfma16(float a, float b, f32x4 c) {
@@ -114,6 +120,79 @@ __device__ __forceinline__ void knn_stream(const float* __restrict__ Q, int64_t 
             for (int bt = 0; bt < BT; ++bt)
 #pragma unroll
               for (int ct = 0; ct < 4; ++ct) acc[bt][ct + 4 * h] = knn_mfma16(a4[bt][e], b4[ct][e], acc[bt][ct + 4 * h]);
+        }
+      }
+    }
+    epilogue(t, acc);
+  }
+}
+
+// knn_stream on rows of bf16: the same ownership, prefetch, barriers and accumulator meaning, 64 channels a chunk.  A fragment
+// is one 16-byte LDS read per lane: lane (r, q) holds channels 8 q .. 8 q + 7 of row r of the 32-channel k-step, for the query
+// tile (the A operand) and for the key tile (B) alike; the C / D mapping of the 16x16x32 form is that of the 16x16x4 form.
+// The row stride of 144 bytes puts the 16 rows of a read on 16 different 4-bank groups, as in the f32 stream.
+template <int BT, typename Meta, typename Epilogue>
+__device__ __forceinline__ void knn_stream_bf16(const bf16* __restrict__ Q, int64_t ldq, int64_t n, const bf16* __restrict__ K,
+                                                int64_t ldk, int M, int D, int tiles_per_split, bf16* Qs, bf16* Ks, Meta& meta,
+                                                Epilogue&& epilogue) {
+  constexpr int QP = 2 * BT;                        // staging: 32 rows x 8 x 16 bytes per pass, QP passes for Q, 4 for K
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, q = lane >> 4;
+  const int srow = tid >> 3, sc8 = (tid & 7) * 8;
+  const int64_t q0 = (int64_t)blockIdx.x * (64 * BT);
+  const int ktiles = (int)(((int64_t)M + KNN_KT - 1) / KNN_KT);
+  const int t0 = blockIdx.y * tiles_per_split;
+  const int t1 = t0 + tiles_per_split < ktiles ? t0 + tiles_per_split : ktiles;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const u32x4 zero16 = {0u, 0u, 0u, 0u};
+
+  u32x4 qr[QP], kr[4];
+  auto fetch = [&](int t, int k0) {
+    const int kb = t * KNN_KT;
+#pragma unroll
+    for (int i = 0; i < QP; ++i) {
+      const int64_t qrow = q0 + srow + 32 * i;
+      qr[i] = qrow < n ? *(const u32x4*)(Q + qrow * ldq + k0 + sc8) : zero16;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned krow = (unsigned)kb + srow + 32 * i;     // a 32-bit bound test, as in knn_stream
+      kr[i] = krow < (unsigned)M ? *(const u32x4*)(K + (int64_t)krow * ldk + k0 + sc8) : zero16;
+    }
+    if (k0 == 0) meta.load(kb);
+  };
+
+  if (t0 < t1) fetch(t0, 0);
+  for (int t = t0; t < t1; ++t) {
+    f32x4 acc[BT][8];
+#pragma unroll
+    for (int i = 0; i < BT; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[i][j] = zero;
+    for (int k0 = 0; k0 < D; k0 += 64) {
+      __syncthreads();                       // the previous chunk's reads (and the previous tile's epilogue) are done
+#pragma unroll
+      for (int i = 0; i < QP; ++i) *(u32x4*)(Qs + (srow + 32 * i) * KNN_LD16 + sc8) = qr[i];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) *(u32x4*)(Ks + (srow + 32 * i) * KNN_LD16 + sc8) = kr[i];
+      if (k0 == 0) meta.store();
+      __syncthreads();
+      if (k0 + 64 < D) fetch(t, k0 + 64);    // in flight under the products
+      else if (t + 1 < t1) fetch(t + 1, 0);  // ... and under the epilogue
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {          // the two k-steps of the chunk, in channel order
+        bf16x8 a8[BT];
+#pragma unroll
+        for (int bt = 0; bt < BT; ++bt) a8[bt] = *(const bf16x8*)(Qs + (16 * BT * w + 16 * bt + r) * KNN_LD16 + 32 * j + 8 * q);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          bf16x8 b8[4];
+#pragma unroll
+          for (int ct = 0; ct < 4; ++ct) b8[ct] = *(const bf16x8*)(Ks + (16 * (ct + 4 * h) + r) * KNN_LD16 + 32 * j + 8 * q);
+#pragma unroll
+          for (int bt = 0; bt < BT; ++bt)
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct)
+              acc[bt][ct + 4 * h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a8[bt], b8[ct], acc[bt][ct + 4 * h], 0, 0, 0);
         }
       }
     }

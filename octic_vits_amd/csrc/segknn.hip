@@ -19,6 +19,11 @@
 // knn_common.hpp, which this kernel shares with knn_topk_kernel (knn_cls.hip).  Here a distance that is NaN (a zero row under
 // cosine) counts as +inf and a skipped key is at +inf, so neither is ever listed.  The distance is a contraction-free expression
 // of the pair's dot product and the two row norms.  Limits: D % 64 == 0, 1 <= kmax <= 32, kmax <= M < 2^31.
+// BF16 ROWS (the reference's `dtype: bfloat16`): seg_rownorms_kernel<bf16> and seg_knn_kernel<bf16, MET> take rows the caller
+// has rounded to bf16 ONCE.  Everything after that cast is f32 and is the code above: the norms are f32 sums of the rounded
+// values in a fixed order, the dots come from knn_stream_bf16 (bf16 MFMA, f32 accumulation), the ordering keys, the total
+// order, the NaN and skip rules, the lists, the merge and the vote are shared with the f32 rows, not copied.  Both distances
+// still come from one pass: there is no second, normalised-then-rounded copy of the keys.
 #include "knn_common.hpp"
 
 namespace octic {
@@ -46,18 +51,24 @@ __device__ __forceinline__ float knn_cos(float qs, float ks, float dot) {   // q
   return d == d ? d : KnnAsc::worst();
 }
 
-// one wave per row
-__global__ __launch_bounds__(256) void seg_rownorms_kernel(const float* __restrict__ X, int64_t ldx, int64_t N, int D,
+// one wave per row; T = float or bf16, 16 bytes per lane and step
+template <typename T>
+__global__ __launch_bounds__(256) void seg_rownorms_kernel(const T* __restrict__ X, int64_t ldx, int64_t N, int D,
                                                            float* __restrict__ norms) {
+  constexpr int W = 16 / (int)sizeof(T);
+  typedef __attribute__((ext_vector_type(W))) T vec;
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
-  const float* x = X + row * ldx;
+  const T* x = X + row * ldx;
   float s = 0.f;
-  for (int c = 4 * lane; c < D; c += 256) {
-    const f32x4 v = *(const f32x4*)(x + c);
+  for (int c = W * lane; c < D; c += 64 * W) {
+    const vec v = *(const vec*)(x + c);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) s = fmaf(v[j], v[j], s);
+    for (int j = 0; j < W; ++j) {
+      const float f = (float)v[j];
+      s = fmaf(f, f, s);
+    }
   }
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o);
@@ -104,10 +115,21 @@ struct SegKeyNorms {
   }
 };
 
+// The stream of the operand type: knn_stream for f32 rows, knn_stream_bf16 for bf16 rows, on LDS images of the same bytes.
+template <typename T> struct KnnOperand;
+template <> struct KnnOperand<float> {
+  static constexpr int LD = KNN_LD;
+  template <typename... A> static __device__ __forceinline__ void stream(A&&... a) { knn_stream<KNN_BT>(static_cast<A&&>(a)...); }
+};
+template <> struct KnnOperand<bf16> {
+  static constexpr int LD = KNN_LD16;
+  template <typename... A> static __device__ __forceinline__ void stream(A&&... a) { knn_stream_bf16<KNN_BT>(static_cast<A&&>(a)...); }
+};
+
 // wave w owns query rows 32 w .. 32 w + 31 of the tile (knn_stream<2>) and therefore their lists
-template <int MET>
-__global__ __launch_bounds__(256) void seg_knn_kernel(const float* __restrict__ Q, int64_t ldq, int64_t n,
-                                                      const float* __restrict__ K, int64_t ldk, int M, int D,
+template <typename T, int MET>
+__global__ __launch_bounds__(256) void seg_knn_kernel(const T* __restrict__ Q, int64_t ldq, int64_t n,
+                                                      const T* __restrict__ K, int64_t ldk, int M, int D,
                                                       const float* __restrict__ qnorm, const float* __restrict__ knorm,
                                                       const uint8_t* __restrict__ skip, int kmax, int tiles_per_split,
                                                       int* __restrict__ idx0, float* __restrict__ dist0, int* __restrict__ idx1,
@@ -115,8 +137,8 @@ __global__ __launch_bounds__(256) void seg_knn_kernel(const float* __restrict__ 
   constexpr int NL = MET == 3 ? 2 : 1;
   constexpr bool L2 = (MET & 1) != 0, COS = (MET & 2) != 0;
   constexpr int CS = NL - 1;                      // the list slot of cosine (L2, when asked for, is slot 0)
-  __shared__ __attribute__((aligned(16))) float Qs[KNN_QT * KNN_LD];
-  __shared__ __attribute__((aligned(16))) float Ks[KNN_KT * KNN_LD];
+  __shared__ __attribute__((aligned(16))) T Qs[KNN_QT * KnnOperand<T>::LD];
+  __shared__ __attribute__((aligned(16))) T Ks[KNN_KT * KnnOperand<T>::LD];
   __shared__ float Kn[KNN_KT];
   __shared__ float Qn[KNN_QT];
   __shared__ float Ld[NL][KNN_QT][KNN_KMAX];
@@ -139,7 +161,7 @@ __global__ __launch_bounds__(256) void seg_knn_kernel(const float* __restrict__ 
 
   SegKeyNorms meta = {knorm, skip, M, Kn, -1.f};
   // ---- per key tile: ordering keys, the filter, the rare insert
-  knn_stream<KNN_BT>(Q, ldq, n, K, ldk, M, D, tiles_per_split, Qs, Ks, meta, [&](int t, const f32x4 (&acc)[KNN_BT][8]) {
+  KnnOperand<T>::stream(Q, ldq, n, K, ldk, M, D, tiles_per_split, Qs, Ks, meta, [&](int t, const f32x4 (&acc)[KNN_BT][8]) {
     const int kb = t * KNN_KT;
     float kn[8], ks[8];
 #pragma unroll
@@ -239,6 +261,37 @@ inline int knn_shape_check(int64_t n, int64_t M, int D, int kmax, int metrics) {
   return (metrics < 1 || metrics > 3) ? OCTIC_ESHAPE : KnnPlan::shape_check(n, M, D, kmax);
 }
 
+// the two entry points of each element type: every refusal comes before any launch; strides are in elements, rows 16-byte aligned
+template <typename T>
+int seg_rownorms(const T* X, int64_t ldx, int64_t N, int D, float* norms, void* stream) {
+  if (!X || !norms) return OCTIC_ENULL;
+  if (N < 1 || D < 64 || D % 64 || ldx < D || (N + 3) / 4 > 0x7FFFFFFFll) return OCTIC_ESHAPE;
+  if ((((uintptr_t)X) & 15) || (ldx * sizeof(T) & 15)) return OCTIC_EALIGN;
+  seg_rownorms_kernel<T><<<dim3((unsigned)((N + 3) / 4)), 256, 0, (hipStream_t)stream>>>(X, ldx, N, D, norms);
+  return launch_status();
+}
+
+template <typename T>
+int seg_knn(const T* Q, int64_t ldq, int64_t n, const T* K, int64_t ldk, int64_t M, int D, const float* qnorm,
+            const float* knorm, const uint8_t* skip, int kmax, int metrics, int splits, int32_t* idx_l2, float* dist_l2,
+            int32_t* idx_cos, float* dist_cos, int64_t ldo, void* workspace, void* stream) {
+  if (!Q || !K || !qnorm || !knorm) return OCTIC_ENULL;
+  if (int e = knn_shape_check(n, M, D, kmax, metrics)) return e;
+  if (((metrics & 1) && (!idx_l2 || !dist_l2)) || ((metrics & 2) && (!idx_cos || !dist_cos))) return OCTIC_ENULL;
+  if (splits < 0 || splits > KNN_MAX_SPLITS || ldq < D || ldk < D || ldo < kmax) return OCTIC_ESHAPE;
+  if ((((uintptr_t)Q) & 15) || (((uintptr_t)K) & 15) || (ldq * sizeof(T) & 15) || (ldk * sizeof(T) & 15)) return OCTIC_EALIGN;
+  int* const out_i[2] = {(metrics & 1) ? idx_l2 : idx_cos, idx_cos};
+  float* const out_d[2] = {(metrics & 1) ? dist_l2 : dist_cos, dist_cos};
+  const hipStream_t st = (hipStream_t)stream;
+  return KnnPlan::run<KnnAsc>(n, M, kmax, splits, metrics == 3 ? 2 : 1, out_i, out_d, ldo, workspace, st,
+                              [&](dim3 grid, int tps, int* const* ki, float* const* kd, int64_t kld, int64_t stride) {
+#define KNN_CALL(MET_) seg_knn_kernel<T, MET_><<<grid, 256, 0, st>>>(Q, ldq, n, K, ldk, (int)M, D, qnorm, knorm, skip, kmax, tps, \
+                                                                    ki[0], kd[0], ki[1], kd[1], kld, stride)
+    if (metrics == 1) KNN_CALL(1); else if (metrics == 2) KNN_CALL(2); else KNN_CALL(3);
+#undef KNN_CALL
+  });
+}
+
 }  // namespace
 }  // namespace octic
 
@@ -259,31 +312,23 @@ int64_t octic_seg_knn_workspace_bytes(int64_t n, int64_t M, int D, int kmax, int
 }
 
 int octic_seg_rownorms(const float* X, int64_t ldx, int64_t N, int D, float* norms, void* stream) {
-  if (!X || !norms) return OCTIC_ENULL;
-  if (N < 1 || D < 64 || D % 64 || ldx < D || (N + 3) / 4 > 0x7FFFFFFFll) return OCTIC_ESHAPE;
-  if ((((uintptr_t)X) & 15) || (ldx & 3)) return OCTIC_EALIGN;
-  seg_rownorms_kernel<<<dim3((unsigned)((N + 3) / 4)), 256, 0, (hipStream_t)stream>>>(X, ldx, N, D, norms);
-  return launch_status();
+  return seg_rownorms(X, ldx, N, D, norms, stream);
+}
+int octic_seg_rownorms_bf16(const void* X, int64_t ldx, int64_t N, int D, float* norms, void* stream) {
+  return seg_rownorms((const bf16*)X, ldx, N, D, norms, stream);
 }
 
 int octic_seg_knn(const float* Q, int64_t ldq, int64_t n, const float* K, int64_t ldk, int64_t M, int D, const float* qnorm,
                   const float* knorm, const uint8_t* skip, int kmax, int metrics, int splits, int32_t* idx_l2, float* dist_l2,
                   int32_t* idx_cos, float* dist_cos, int64_t ldo, void* workspace, void* stream) {
-  if (!Q || !K || !qnorm || !knorm) return OCTIC_ENULL;
-  if (int e = knn_shape_check(n, M, D, kmax, metrics)) return e;
-  if (((metrics & 1) && (!idx_l2 || !dist_l2)) || ((metrics & 2) && (!idx_cos || !dist_cos))) return OCTIC_ENULL;
-  if (splits < 0 || splits > KNN_MAX_SPLITS || ldq < D || ldk < D || ldo < kmax) return OCTIC_ESHAPE;
-  if ((((uintptr_t)Q) & 15) || (((uintptr_t)K) & 15) || (ldq & 3) || (ldk & 3)) return OCTIC_EALIGN;
-  int* const out_i[2] = {(metrics & 1) ? idx_l2 : idx_cos, idx_cos};
-  float* const out_d[2] = {(metrics & 1) ? dist_l2 : dist_cos, dist_cos};
-  const hipStream_t st = (hipStream_t)stream;
-  return KnnPlan::run<KnnAsc>(n, M, kmax, splits, metrics == 3 ? 2 : 1, out_i, out_d, ldo, workspace, st,
-                              [&](dim3 grid, int tps, int* const* ki, float* const* kd, int64_t kld, int64_t stride) {
-#define KNN_CALL(MET_) seg_knn_kernel<MET_><<<grid, 256, 0, st>>>(Q, ldq, n, K, ldk, (int)M, D, qnorm, knorm, skip, kmax, tps, \
-                                                                 ki[0], kd[0], ki[1], kd[1], kld, stride)
-    if (metrics == 1) KNN_CALL(1); else if (metrics == 2) KNN_CALL(2); else KNN_CALL(3);
-#undef KNN_CALL
-  });
+  return seg_knn(Q, ldq, n, K, ldk, M, D, qnorm, knorm, skip, kmax, metrics, splits, idx_l2, dist_l2, idx_cos, dist_cos, ldo,
+                 workspace, stream);
+}
+int octic_seg_knn_bf16(const void* Q, int64_t ldq, int64_t n, const void* K, int64_t ldk, int64_t M, int D, const float* qnorm,
+                       const float* knorm, const uint8_t* skip, int kmax, int metrics, int splits, int32_t* idx_l2, float* dist_l2,
+                       int32_t* idx_cos, float* dist_cos, int64_t ldo, void* workspace, void* stream) {
+  return seg_knn((const bf16*)Q, ldq, n, (const bf16*)K, ldk, M, D, qnorm, knorm, skip, kmax, metrics, splits, idx_l2, dist_l2,
+                 idx_cos, dist_cos, ldo, workspace, stream);
 }
 
 int octic_seg_knn_vote(const int32_t* idx, int64_t ldi, int64_t n, const void* labels, int esize, int64_t R, int L, const int* ks,

@@ -1646,23 +1646,38 @@ def seg_knn_workspace(n, M, D, kmax, metrics, splits, device):
     return _knn_workspace(lib().octic_seg_knn_workspace_bytes(n, M, D, kmax, metrics, splits), device)
 
 
+_KNN_ROW_DTYPES = {torch.float32: ("", "f32"), torch.bfloat16: ("_bf16", "bf16")}   # entry-point suffix, KERNEL_TIMER tag
+
+
+def _seg_knn_rows(X):
+    """X as the rows of the k-NN search: f32 or bf16 [N, D] with contiguous channels -> (N, D, row stride, suffix, tag)."""
+    _require_cuda(X)
+    if X.dim() != 2 or X.dtype not in _KNN_ROW_DTYPES or X.stride(1) != 1:
+        raise ValueError("the segmentation k-NN ops take an f32 or bf16 [N, D] matrix with contiguous channels")
+    return (X.shape[0], X.shape[1], X.stride(0)) + _KNN_ROW_DTYPES[X.dtype]
+
+
 def seg_rownorms(X):
-    """f32 [N]: the squared norm of every row of the f32 rows X [N, D], summed in a fixed order."""
-    N, D, ldx = _seg_rows(X)
+    """f32 [N]: the squared norm of every row of the f32 or bf16 rows X [N, D], summed in f32 in a fixed order."""
+    N, D, ldx, suffix, tag = _seg_knn_rows(X)
     norms = torch.empty(N, dtype=torch.float32, device=X.device)
     t = KERNEL_TIMER.start()
-    check(lib().octic_seg_rownorms(_p(X), ldx, N, D, _p(norms), _stream(X)))
-    KERNEL_TIMER.stop(t, "seg_rownorms_kernel", 4 * N * (D + 1), 2.0 * N * D)
+    check(getattr(lib(), "octic_seg_rownorms" + suffix)(_p(X), ldx, N, D, _p(norms), _stream(X)))
+    KERNEL_TIMER.stop(t, f"seg_rownorms_kernel<{tag}>", X.element_size() * N * D + 4 * N, 2.0 * N * D)
     return norms
 
 
 def seg_knn(Q, K, qnorm, knorm, skip, kmax, metrics=KNN_BOTH, splits=0, out=None, workspace=None):
     """The kmax nearest rows of K for every row of Q under the squared L2 distance (metrics & 1), the cosine distance
     (metrics & 2) or both, ordered by (distance, key row index).  skip: None or uint8 [M], non-zero = the key is never listed.
+    Q and K are both f32 or both bf16 rows (bf16: values rounded once by the caller; everything after is f32, see
+    include/octic_hip.h); a mixed pair is a ValueError.
     Returns (idx_l2, dist_l2, idx_cos, dist_cos): int32 / f32 [n, kmax], None for a metric not asked for.  ``out`` may hold
     those four as 2-d tensors with a common row stride >= kmax (columns past kmax are left alone)."""
-    n, D, ldq = _seg_rows(Q)
-    M, Dk, ldk = _seg_rows(K)
+    if K.dtype != Q.dtype:
+        raise ValueError(f"seg_knn: Q ({Q.dtype}) and K ({K.dtype}) must share one dtype")
+    n, D, ldq, suffix, tag = _seg_knn_rows(Q)
+    M, Dk, ldk, _, _ = _seg_knn_rows(K)
     if Dk != D or K.device != Q.device:
         raise ValueError("seg_knn: Q and K must have the same width and device")
     for v, rows in ((qnorm, n), (knorm, M)):
@@ -1689,11 +1704,11 @@ def seg_knn(Q, K, qnorm, knorm, skip, kmax, metrics=KNN_BOTH, splits=0, out=None
     if workspace is None:
         workspace = seg_knn_workspace(n, M, D, kmax, metrics, splits, Q.device)
     t = KERNEL_TIMER.start()
-    check(lib().octic_seg_knn(_p(Q), ldq, n, _p(K), ldk, M, D, _p(qnorm), _p(knorm), _p(skip), kmax, metrics, splits,
-                              *[_p(o) for o in out], ldo, _p(workspace), _stream(Q)))
+    check(getattr(lib(), "octic_seg_knn" + suffix)(_p(Q), ldq, n, _p(K), ldk, M, D, _p(qnorm), _p(knorm), _p(skip), kmax, metrics,
+                                                   splits, *[_p(o) for o in out], ldo, _p(workspace), _stream(Q)))
     nl = 2 if metrics == KNN_BOTH else 1
-    KERNEL_TIMER.stop(t, f"seg_knn_kernel<{metrics}>", _knn_stream_bytes(seg_knn_plan(n, M, D, kmax, metrics), n, M, D) + 8 * nl * n * kmax,
-                      2.0 * n * M * D)
+    stream_bytes = _knn_stream_bytes(seg_knn_plan(n, M, D, kmax, metrics), n, M, D) * Q.element_size() // 4
+    KERNEL_TIMER.stop(t, f"seg_knn_kernel<{tag}, {metrics}>", stream_bytes + 8 * nl * n * kmax, 2.0 * n * M * D)
     return tuple(out)
 
 

@@ -24,6 +24,9 @@ matrix.  Neighbours are ordered by (distance, row index) - ``torch.topk`` leaves
 "knn" (its refusal is pinned by earlier tests); the reference's default ``("logreg", "knn")`` runs through ``extract_splits`` +
 ``eval_features``, which share one backbone pass.  The final refit is on train + val with the validation rows FIRST in the
 resident matrix (the reference concatenates train then val): row order matters to k-NN only through exact distance ties.
+``KNNClassifier(dtype="bfloat16")`` - what the reference's eval_config.yaml sets - rounds keys and queries to bf16 ONCE and
+computes everything after that cast in float32 (norms, bf16-MFMA dots with f32 accumulation, ordering keys, the same total
+order): one deterministic member of the reference's set of valid bf16 answers; the class docstring has the rule.
 
 Not here: the L1 / Linf / inner_product distances and more than 32 neighbours, RobustScaler / PCA standardisation, datasets
 and transforms, multi-rank grid splitting.
@@ -454,9 +457,23 @@ class KNNClassifier:
     ``train_set_chunk_size`` and ``device`` are kept for the signature and not used: the keys are the resident matrix, streamed
     by one kernel.  ``fit`` keeps views (sub-sampling is a row stride), marks the patches whose mode label is ignored as skipped
     keys (``Classifier.fit``, :83) and computes the key norms.  The vote is over the neighbours' raw pixel labels, so an ignored
-    value can win a pixel, as in the reference.  Distances "cosine" and "L2"; at most 32 neighbours."""
+    value can win a pixel, as in the reference.  Distances "cosine" and "L2"; at most 32 neighbours.
+
+    ``dtype="bfloat16"`` is the reference's shipped configuration (``classifiers_kwargs: {knn: {dtype: bfloat16}}``,
+    eval_config.yaml).  The reference casts keys and queries to bf16, forms bf16 distances and calls ``torch.topk`` on them;
+    those carry 8 significant bits and tie in bulk, ``topk`` leaves ties open, so its lists are not reproducible.  Here:
+    1. operands are rounded ONCE, with ``tensor.to(torch.bfloat16)`` (the reference's own cast): the keys in ``fit`` after
+       sub-sampling, each query batch in ``predict_grid``.  The bf16 copy of the keys is what stays resident; the caller's f32
+       matrix is not kept.
+    2. everything after the cast is float32: the row norms of the rounded rows (a fixed-order f32 sum), the dot products (bf16
+       MFMA, f32 accumulation), the ordering keys, the total order (distance, key row index), the NaN and skip rules.
+    3. both distances come from one pass; there is no second, normalised-then-rounded copy of the keys for the cosine distance.
+    Rounding is monotone, so the list ordered by the f32 distance of the rounded operands is one valid top-k of the
+    reference's bf16 distances (for cosine: within one bf16 ulp, the price of rounding once instead of normalising in bf16),
+    and a deterministic one.  Any other ``dtype`` than "float32" / "bfloat16" is a ValueError."""
 
     DISTANCES = {"L2": ops.KNN_L2, "cosine": ops.KNN_COSINE}
+    DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16}
     # Queries go through the kernels in batches of at most this many rows: the neighbour lists and votes of a batch are a few
     # hundred bytes per row, and the workspace the library asks for (octic_seg_knn_workspace_bytes) holds partial lists only
     # while splits x query tiles stays near the CU count, so memory is bounded whatever the number of rows.
@@ -465,9 +482,9 @@ class KNNClassifier:
     def __init__(self, ignore_labels: Sequence[int], inference_bs: int = 1024, train_set_chunk_size: Optional[int] = 262144,
                  train_set_subsampling: int = 1, device: str = "cuda", dtype: str = "float32",
                  num_neighbors: Sequence[int] = (1, 3, 10, 30), distance: Sequence[str] = ("cosine", "L2")):
-        if dtype != "float32":
-            raise ValueError("KNNClassifier: the HIP engine computes k-NN distances in float32 only")
-        self.device, self.dtype = device, torch.float32
+        if dtype not in self.DTYPES:
+            raise ValueError(f"KNNClassifier: the HIP engine computes k-NN distances from float32 or bfloat16 operands, not {dtype!r}")
+        self.device, self.dtype = device, self.DTYPES[dtype]
         self.inference_bs, self.train_set_chunk_size = inference_bs, train_set_chunk_size
         self.train_set_subsampling = train_set_subsampling
         self.ignore_labels = ignore_labels
@@ -519,6 +536,8 @@ class KNNClassifier:
             ignore[int(v) & 255] = True
         self.skip_ = ignore[modes.long()].to(torch.uint8)
         self.n_keys_ = int(features.shape[0]) - int(self.skip_.sum())
+        if self.dtype != torch.float32:
+            features = features.to(self.dtype)       # rounded once; this copy, not the caller's matrix, stays resident
         self.train_X, self.train_y = features, labels
         self.key_norms_ = ops.seg_rownorms(features)
 
@@ -544,6 +563,8 @@ class KNNClassifier:
         ws = ops.seg_knn_workspace(bs, M, D, kmax, metrics, 0, dev) if n else None
         for i in range(0, n, bs):
             q = features[i:i + bs]
+            if self.dtype != torch.float32:
+                q = q.to(self.dtype)
             if q.shape[0] != bs:                     # the last batch: its own plan and workspace
                 ws = ops.seg_knn_workspace(q.shape[0], M, D, kmax, metrics, 0, dev)
             idx_l2, _, idx_cos, _ = ops.seg_knn(q, self.train_X, ops.seg_rownorms(q), self.key_norms_, self.skip_, kmax, metrics,

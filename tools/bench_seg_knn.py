@@ -10,7 +10,14 @@ engine: keys once per query tile, queries once per key tile, lists, neighbour la
 re-reads every distance matrix).  The engine's TFLOP/s stand next to the 122 TFLOP/s of an untuned f32-MFMA GEMM as a yardstick,
 not a threshold.  The one condition: the engine's full grid must not take longer than the composition's.
 
-    python tools/bench_seg_knn.py [--queries 8192] [--keys 262144] [--iters 20] [--out profiles/bench_seg_knn.txt]
+``--dtype bfloat16`` is the reference's shipped configuration (``classifiers_kwargs: {knn: {dtype: bfloat16}}``): the engine arm
+casts the query batch to bf16 inside the timed region (as ``KNNClassifier.predict_grid`` does; the keys are cast once, as in
+``fit``) and runs the bf16-MFMA pass, the composition runs the reference's own arithmetic on bf16 tensors, and a third arm,
+``engine_float32``, runs the float32 pass on the same data in the same alternation - so the bf16 time, the f32 time and the
+composition's time come from ONE run.  Two conditions then: the bf16 grid must take no longer than the f32 grid, and no longer
+than the bf16 composition.  The engine's TFLOP/s stand next to the bf16 MFMA peak (2.5 PFLOP/s dense).
+
+    python tools/bench_seg_knn.py [--dtype float32|bfloat16] [--queries 8192] [--keys 262144] [--iters 20] [--out FILE]
 Prints one JSON document.  Needs a GPU: there is no CPU path."""
 import argparse
 import json
@@ -23,6 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from octic_vits_amd import ops  # noqa: E402
 
 F32_MFMA_GEMM_TFLOPS = 122.0   # an untuned LDS-tiled f32-MFMA GEMM at 4096^3: the yardstick
+BF16_MFMA_PEAK_TFLOPS = 2500.0  # the dense bf16 MFMA peak of one MI355X
 KS = (1, 3, 10, 30)
 DISTANCES = ("cosine", "L2")
 QUERY_CHUNK = 1024             # the reference's inference_bs
@@ -41,6 +49,7 @@ def main():
     ap.add_argument("--pixels", type=int, default=256)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dtype", choices=("float32", "bfloat16"), default="float32")
     ap.add_argument("--engine-only", action="store_true", help="a few engine passes only (a kernel-trace run)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -56,15 +65,24 @@ def main():
     labels = (kcls[:, None] + 1).to(torch.uint8).repeat(1, L)
     labels[torch.rand(M, L, generator=g, device=dev) < 0.1] = 0
     kmax = KS[-1]
-    knorm = ops.seg_rownorms(K)
+    dtype = getattr(torch, args.dtype)
+    bf16 = dtype == torch.bfloat16
+    Kd = K.to(dtype)                                   # the resident keys of the arm's dtype: cast once, as in fit
+    knorm = {torch.float32: ops.seg_rownorms(K)}
+    knorm[dtype] = ops.seg_rownorms(Kd)
     ws = ops.seg_knn_workspace(n, M, D, kmax, ops.KNN_BOTH, 0, dev)
     out4 = [torch.empty(n, kmax, dtype=dt, device=dev) for dt in (torch.int32, torch.float32, torch.int32, torch.float32)]
     votes = torch.empty(2, len(KS), n, L, dtype=torch.uint8, device=dev)
 
-    def engine():
-        ops.seg_knn(Q, K, ops.seg_rownorms(Q), knorm, None, kmax, ops.KNN_BOTH, 0, out=out4, workspace=ws)
-        ops.seg_knn_vote(out4[0], labels, KS, out=votes[0])
-        ops.seg_knn_vote(out4[2], labels, KS, out=votes[1])
+    def engine_of(keys):
+        def run():
+            q = Q.to(keys.dtype)                       # a copy only at bf16: the cast of the query batch
+            ops.seg_knn(q, keys, ops.seg_rownorms(q), knorm[keys.dtype], None, kmax, ops.KNN_BOTH, 0, out=out4, workspace=ws)
+            ops.seg_knn_vote(out4[0], labels, KS, out=votes[0])
+            ops.seg_knn_vote(out4[2], labels, KS, out=votes[1])
+        return run
+
+    engine = engine_of(Kd)
 
     def stock():
         res = {}
@@ -72,11 +90,11 @@ def main():
             for dist in DISTANCES:
                 pred = torch.empty(n, L, dtype=torch.uint8, device=dev)
                 for i in range(0, n, QUERY_CHUNK):
-                    q = Q[i:i + QUERY_CHUNK]
+                    q = Q[i:i + QUERY_CHUNK].to(dtype)
                     if dist == "L2":
-                        d = torch.cdist(q, K, p=2)
+                        d = torch.cdist(q, Kd, p=2)
                     else:
-                        d = 1 - (q / torch.norm(q, dim=-1)[:, None]) @ (K / torch.norm(K, dim=-1)[:, None]).T
+                        d = 1 - (q / torch.norm(q, dim=-1)[:, None]) @ (Kd / torch.norm(Kd, dim=-1)[:, None]).T
                     idx = torch.topk(d, k, dim=-1, largest=False).indices
                     pred[i:i + QUERY_CHUNK] = labels[idx].mode(dim=1).values
                 res[(k, dist)] = pred
@@ -89,11 +107,15 @@ def main():
         print(json.dumps({"engine_only_passes": 5}))
         return
     arms = {"engine": engine, "stock_torch": stock}
+    if bf16:
+        arms["engine_float32"] = engine_of(K)
     for _ in range(args.warmup):
         for fn in arms.values():
             fn()
     torch.cuda.synchronize()
-    # same inputs: how many pixel predictions of the two arms agree (f32 rounding may swap near-tied neighbours)
+    # same inputs: how many pixel predictions of the two arms agree (f32 rounding may swap near-tied neighbours; at bf16 the
+    # composition ranks 8-bit distances, which tie in bulk, so its neighbour sets are one arbitrary choice among many)
+    engine()
     res = stock()
     agree = {f"{k}_{d}": round(float((votes[1 - DISTANCES.index(d), KS.index(k)] == res[(k, d)]).float().mean()), 6)
              for k in KS for d in DISTANCES}
@@ -110,25 +132,36 @@ def main():
     product = 2.0 * n * M * D
     splits, qt, kt, _ = ops.seg_knn_plan(n, M, D, kmax, ops.KNN_BOTH)
     grid = len(KS) * len(DISTANCES)
+    es = float(Kd.element_size())
+
+    def engine_bytes(esize):
+        return (esize * D * (M * -(-n // qt) + n * -(-M // kt)) + 2 * 8.0 * n * kmax * (1 + (splits if splits > 1 else 0))
+                + 2.0 * n * L * (kmax + len(KS)))
+
     work = {
-        "engine": {"products": 1, "flops": product,
-                   "hbm_bytes": 4.0 * D * (M * -(-n // qt) + n * -(-M // kt)) + 2 * 8.0 * n * kmax * (1 + (splits if splits > 1 else 0))
-                   + 2.0 * n * L * (kmax + len(KS))},
+        "engine": {"products": 1, "flops": product, "hbm_bytes": engine_bytes(es)},
+        "engine_float32": {"products": 1, "flops": product, "hbm_bytes": engine_bytes(4.0)},
         # per grid point: queries and keys once per query chunk, the distance matrix written and read by topk, labels gathered
         "stock_torch": {"products": grid, "flops": grid * product,
-                        "hbm_bytes": grid * (4.0 * D * (n + M * -(-n // QUERY_CHUNK)) + 2 * 4.0 * n * M) + sum(2.0 * n * L * (k + 1) for k in KS)}}
-    out = {"device": torch.cuda.get_device_name(0), "queries": n, "keys": M, "dim": D, "pixels": L, "kmax": kmax, "ks": KS,
+                        "hbm_bytes": grid * (es * D * (n + M * -(-n // QUERY_CHUNK)) + 2 * es * n * M) + sum(2.0 * n * L * (k + 1) for k in KS)}}
+    out = {"device": torch.cuda.get_device_name(0), "dtype": args.dtype, "queries": n, "keys": M, "dim": D, "pixels": L, "kmax": kmax, "ks": KS,
            "distances": DISTANCES, "key_splits": splits, "pixel_agreement": agree, "arms": {}}
     for name, v in ms.items():
         med = sorted(v)[len(v) // 2] * 1e-3
         out["arms"][name] = dict(_stats(v), products=work[name]["products"], TFLOP=round(work[name]["flops"] / 1e12, 3),
-                                 f32_TFLOPs=round(work[name]["flops"] / med / 1e12, 1),
+                                 TFLOPs=round(work[name]["flops"] / med / 1e12, 1),
                                  alg_hbm_GB=round(work[name]["hbm_bytes"] / 1e9, 2),
                                  alg_hbm_TBps=round(work[name]["hbm_bytes"] / med / 1e12, 3))
     eng, stk = out["arms"]["engine"]["median_ms"], out["arms"]["stock_torch"]["median_ms"]
     out["engine_vs_stock"] = {"stock_over_engine": round(stk / eng, 3), "engine_not_slower": eng <= stk,
-                              "engine_f32_TFLOPs": out["arms"]["engine"]["f32_TFLOPs"],
-                              "yardstick_untuned_f32_mfma_gemm_TFLOPs": F32_MFMA_GEMM_TFLOPS}
+                              "engine_TFLOPs": out["arms"]["engine"]["TFLOPs"]}
+    if bf16:
+        f32 = out["arms"]["engine_float32"]["median_ms"]
+        out["engine_vs_stock"].update(bf16_mfma_peak_TFLOPs=BF16_MFMA_PEAK_TFLOPS,
+                                      fraction_of_bf16_mfma_peak=round(out["arms"]["engine"]["TFLOPs"] / BF16_MFMA_PEAK_TFLOPS, 4))
+        out["bfloat16_vs_float32"] = {"float32_over_bfloat16": round(f32 / eng, 3), "bfloat16_not_slower": eng <= f32}
+    else:
+        out["engine_vs_stock"]["yardstick_untuned_f32_mfma_gemm_TFLOPs"] = F32_MFMA_GEMM_TFLOPS
     ops.KERNEL_TIMER.enable()
     for _ in range(5):
         engine()
@@ -141,6 +174,8 @@ def main():
             f.write(text + "\n")
     if not out["engine_vs_stock"]["engine_not_slower"]:
         raise SystemExit("bench_seg_knn: the engine's full grid takes LONGER than the stock composition's")
+    if bf16 and not out["bfloat16_vs_float32"]["bfloat16_not_slower"]:
+        raise SystemExit("bench_seg_knn: the bfloat16 grid takes LONGER than the float32 grid")
 
 
 if __name__ == "__main__":
