@@ -855,6 +855,27 @@ int octic_soft_ce_bwd(const void* s, int s_dtype, int64_t lds, const float* tpro
                       const float* g, const float* lse, const float* tsum, void* ds, int64_t ldd, int64_t rows, int K,
                       void* stream);
 
+/* ---- Sinkhorn-Knopp teacher targets of the DINO / iBOT terms (dinov2/loss/dino_clstoken_loss.py:53-76,
+ * ibot_patch_loss.py:79-116) without the K x B matrix Q: with E[b, k] = exp((x[b, k] - rowmax[b]) * inv_temp), rowmax[b] the
+ * largest logit of row b, every state of Q is E[b, k] u[k] v[b].  One round is  r = protos(shift = rowmax, weight = v);
+ * [all-reduce r over ranks];  u = 1 / r;  c = rows(u);  v = 1 / c;  the first round's weight is exp((rowmax[b] - m) *
+ * inv_temp) with m the maximum of rowmax over all ranks (rowmax from octic_sinkhorn_rows with u = NULL), the last round ends
+ * in octic_sinkhorn_final, which sums its own c.  The reference's total sum and its constants K and B cancel in the result
+ * and are not applied; the result is finite where the reference's exp(x / temp) overflows.  x is f32 or bf16 [rows, K] with
+ * row stride ldx >= K, 16-byte aligned rows; K % 8 == 0; inv_temp > 0; rows >= 1 (rows == 0 is OCTIC_ESHAPE: there is no
+ * round to run); u, r, partials, out 16-byte aligned f32.  No atomics and fixed summation orders: bitwise reproducible.
+ * octic_sinkhorn_slabs: the row slabs of the prototype-sum pass for this row count (OCTIC_ESHAPE for rows < 1).
+ * octic_sinkhorn_protos: r[k] = sum_b weight[b] exp((x[b, k] - shift[b]) inv_temp); partials is a [slabs, K] f32 workspace,
+ *   nullable where slabs == 1.  octic_sinkhorn_rows: rowmax[b] = max_k x[b, k], c[b] = sum_k u[k] E[b, k] (u nullable: 1).
+ *   octic_sinkhorn_final: out[b, k] = u[k] E[b, k] / sum_k' u[k'] E[b, k'], contiguous [rows, K] f32 (u nullable: 1). */
+int octic_sinkhorn_slabs(int64_t rows);
+int octic_sinkhorn_protos(const void* x, int x_dtype, int64_t ldx, float inv_temp, const float* shift, const float* weight,
+                          float* partials, float* r, int64_t rows, int K, void* stream);
+int octic_sinkhorn_rows(const void* x, int x_dtype, int64_t ldx, float inv_temp, const float* u, float* rowmax, float* c,
+                        int64_t rows, int K, void* stream);
+int octic_sinkhorn_final(const void* x, int x_dtype, int64_t ldx, float inv_temp, const float* u, float* out, int64_t rows,
+                         int K, void* stream);
+
 /* ---- linear-probe evaluation of a frozen backbone (dinov2/eval/linear.py) ----------------------------------------------
  * The grid of nn.Linear(K_h, C) classifiers of setup_linear_classifiers (linear.py:237-258) as one launch per stage over
  * all classifiers.  Every classifier reads a column range [col0, col0 + K) of one f32 feature row

@@ -120,6 +120,11 @@ _PROTOS = {
                                   c_void_p]),
     "octic_soft_ce_bwd": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_i64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
                                   c_i64, c_int, c_void_p]),
+    "octic_sinkhorn_slabs": (c_int, [c_i64]),
+    "octic_sinkhorn_protos": (c_int, [c_void_p, c_int, c_i64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int,
+                                      c_void_p]),
+    "octic_sinkhorn_rows": (c_int, [c_void_p, c_int, c_i64, c_float, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p]),
+    "octic_sinkhorn_final": (c_int, [c_void_p, c_int, c_i64, c_float, c_void_p, c_void_p, c_i64, c_int, c_void_p]),
     "octic_scale_residual_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int,
                                          c_void_p]),
     "octic_scale_residual_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_void_p,

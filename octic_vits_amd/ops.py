@@ -1099,6 +1099,54 @@ def soft_ce_bwd(s, tprob, inv_temp, g, lse, tsum):
     return ds.view(s.shape)
 
 
+def _sinkhorn_rows2d(x):
+    """The logits of a Sinkhorn pass: a 2-D f32 / bf16 tensor as (view with 16-byte aligned rows, rows, K, row stride)."""
+    _require_cuda(x)
+    if x.dim() != 2:
+        raise ValueError("sinkhorn passes take 2-D logits [rows, K]")
+    if x.data_ptr() % 16:
+        x = x.clone(memory_format=torch.contiguous_format)
+    return _rows2d(x)
+
+
+def sinkhorn_rows(x, inv_temp, u=None):
+    """Sample-sum pass of csrc/ssl_loss.hip: (rowmax [rows], c [rows]) f32, rowmax[b] = max_k x[b, k] and
+    c[b] = sum_k u[k] exp((x[b, k] - rowmax[b]) * inv_temp) (u f32 [K] contiguous, or None: 1)."""
+    x2, rows, K, ld = _sinkhorn_rows2d(x)
+    rowmax, c = (torch.empty(rows, dtype=torch.float32, device=x.device) for _ in range(2))
+    tk = KERNEL_TIMER.start()
+    check(lib().octic_sinkhorn_rows(_p(x2), dt_code(x2.dtype), ld, float(inv_temp), _p(u), _p(rowmax), _p(c), rows, K,
+                                    _stream(x)))
+    KERNEL_TIMER.stop(tk, f"sinkhorn_rows_kernel<{_DTN[x2.dtype]}>", rows * K * x2.element_size())
+    return rowmax, c
+
+
+def sinkhorn_protos(x, inv_temp, shift, weight):
+    """Prototype-sum pass: r [K] f32, r[k] = sum_b weight[b] exp((x[b, k] - shift[b]) * inv_temp) (shift, weight f32 [rows]);
+    per-slab partial sums in a fixed order, no atomics."""
+    x2, rows, K, ld = _sinkhorn_rows2d(x)
+    slabs = lib().octic_sinkhorn_slabs(rows)
+    if slabs < 0:
+        check(slabs)
+    r = torch.empty(K, dtype=torch.float32, device=x.device)
+    part = torch.empty((slabs, K), dtype=torch.float32, device=x.device) if slabs > 1 else None
+    tk = KERNEL_TIMER.start()
+    check(lib().octic_sinkhorn_protos(_p(x2), dt_code(x2.dtype), ld, float(inv_temp), _p(shift), _p(weight), _p(part), _p(r),
+                                      rows, K, _stream(x)))
+    KERNEL_TIMER.stop(tk, f"sinkhorn_protos_kernel<{_DTN[x2.dtype]}>", rows * K * x2.element_size() + (slabs > 1) * slabs * K * 8)
+    return r
+
+
+def sinkhorn_final(x, inv_temp, u):
+    """Final pass: out [rows, K] contiguous f32, out[b, :] = u E[b, :] / sum_k u[k] E[b, k], E[b, k] = exp((x[b, k] - rowmax[b]) * inv_temp)."""
+    x2, rows, K, ld = _sinkhorn_rows2d(x)
+    out = torch.empty((rows, K), dtype=torch.float32, device=x.device)
+    tk = KERNEL_TIMER.start()
+    check(lib().octic_sinkhorn_final(_p(x2), dt_code(x2.dtype), ld, float(inv_temp), _p(u), _p(out), rows, K, _stream(x)))
+    KERNEL_TIMER.stop(tk, f"sinkhorn_final_kernel<{_DTN[x2.dtype]}>", rows * K * (2 * x2.element_size() + 4))
+    return out
+
+
 def scale_residual_fwd(x, y, gamma, rs, rps):
     """out = x + rs[row // rps] * gamma * y   (x f32, y f32/bf16, same shape [..., d])."""
     _require_cuda(x)

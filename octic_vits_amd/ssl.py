@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from . import functional as _OF
 
-FUSED_LOSS_ROWS = True      # GPU: the prototype-axis passes of the DINO / iBOT terms on csrc/ssl_loss.hip (False: the eager composition)
+FUSED_LOSS_ROWS = True      # GPU: the prototype-axis passes of the DINO / iBOT terms, both centerings, on csrc/ssl_loss.hip (False: the eager composition)
 
 
 def _world():
@@ -99,7 +99,44 @@ class _Centered(nn.Module):
             self.updated = True
 
 
+def sinkhorn_fused_ok(teacher_output, n_iterations):
+    """These logits take the Sinkhorn-Knopp row kernels of csrc/ssl_loss.hip; everything else runs the eager composition.
+    (In a process group a rank whose batch has no rows takes the same path as the others: its collectives must match theirs.)"""
+    return bool(FUSED_LOSS_ROWS and _OF.loss_rows_ok(teacher_output) and teacher_output.dim() == 2 and n_iterations >= 1
+                and (teacher_output.shape[0] >= 1 or _world() > 1))
+
+
+def _sinkhorn_fused(x, teacher_temp, n_iterations):
+    """Sinkhorn-Knopp without the matrix Q: with E[b, k] = exp((x[b, k] - rowmax[b]) / temp) every state of the reference's Q is
+    E[b, k] u[k] v[b]; the total sum and the constants K and B cancel in the result.  r[k] = sum_b E[b, k] v[b] is summed over
+    ranks, u = 1 / r, c[b] = sum_k E[b, k] u[k], v = 1 / c, and the result is E u / c as contiguous f32 [rows, K].  The first
+    round's v[b] = exp((rowmax[b] - m) / temp), m the largest logit of all ranks: the reference's exp(x / temp) up to the
+    constant exp(-m / temp), so the result is the reference's wherever that is finite, and finite where its exp overflows.  A
+    rank without rows only joins the collectives."""
+    ops, world, rows = _OF.ops, _world(), x.shape[0]
+    inv_temp = float(np.float32(1.0) / np.float32(teacher_temp))    # the f32 reciprocal torch multiplies by in x / temp
+    if rows:
+        rowmax, _ = ops.sinkhorn_rows(x, inv_temp)
+        m = rowmax.max()
+    else:
+        m = torch.full((), -math.inf, dtype=torch.float32, device=x.device)
+    if world > 1:
+        dist.all_reduce(m, op=dist.ReduceOp.MAX)
+    weight = torch.exp((rowmax - m) * inv_temp) if rows else None
+    for it in range(n_iterations):
+        r = (ops.sinkhorn_protos(x, inv_temp, rowmax, weight) if rows
+             else torch.zeros(x.shape[1], dtype=torch.float32, device=x.device))
+        if world > 1:
+            dist.all_reduce(r)
+        u = r.reciprocal_()
+        if rows and it + 1 < n_iterations:
+            weight = ops.sinkhorn_rows(x, inv_temp, u)[1].reciprocal_()
+    return ops.sinkhorn_final(x, inv_temp, u) if rows else torch.empty(x.shape, dtype=torch.float32, device=x.device)
+
+
 def _sinkhorn(teacher_output, teacher_temp, B_total, n_iterations):
+    if sinkhorn_fused_ok(teacher_output, n_iterations):
+        return _sinkhorn_fused(teacher_output, teacher_temp, n_iterations)
     Q = torch.exp(teacher_output.float() / teacher_temp).t()       # K x B
     K = Q.shape[0]
     s = torch.sum(Q)
