@@ -749,6 +749,33 @@ int octic_dense_gemm_plan_adaptive(int M, int N, int K, int mode, int tokens, in
  * adaptive kernel does not take or cap too small. */
 int octic_dense_gemm_order_adaptive(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
                                     int cap, int* out_tm, int* out_tn, int* out_dead, int* out_width);
+/* octic_dense_gemm_nt_tokens_adaptive with the launch's class-token rows inside the main launch.  The adaptive launch leaves the
+ * CUs of its dead tiles idle for most of its length while the class-token rows wait behind it for one or two latency-bound
+ * launches of their own.  With fold_cls != 0, a launch the adaptive kernel takes whose K is at most 16 slices of 320 becomes ONE
+ * launch: the adaptive launch's workgroups, workgroup for workgroup, followed at the END of the grid by class-token workgroups
+ * (512 threads; an item = 16 class-token rows x 16 columns, computed inside one workgroup: a slice of 320 per wave as ten MFMAs
+ * from a zero accumulator, f32 partial tiles summed in slice order from slice 0, bias in f32, one rounding - the arithmetic
+ * and the bits of the stand-alone class-token kernels).  Every class-token row is written; the mask does not apply to them.
+ * fold_cls == 0, or any other launch: exactly octic_dense_gemm_nt_tokens_adaptive.  When few CUs are free the class-token
+ * workgroups run behind the live tiles, so callers fold where the mask is expected to drop enough samples
+ * (functional.DENSE_CLS_FOLD_MIN_DROP). */
+int octic_dense_gemm_nt_tokens_adaptive_cls(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode,
+                                            void* C, void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs,
+                                            int64_t rows_per_sample_rs, const float* X, float* OUT, const void* H, float* colsum,
+                                            const float* sample_scale, int rows_per_sample, void* workspace, int tokens,
+                                            int fold_cls, void* stream);
+/* What it does (fold_cls != 0) with a masked launch of this problem: out[0] = 1 if the folded kernel takes it, out[1] = workgroups
+ * of the launch, out[2] = class-token workgroups among them (the last ones), out[3] = class-token items of the busiest of those,
+ * out[4] = tile workgroups in front (= out[1] of octic_dense_gemm_plan_adaptive).  OCTIC_ESHAPE for a bad rows_per_sample. */
+int octic_dense_gemm_plan_adaptive_cls(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out5);
+/* Host query of the folded launch's item map (sample_scale is a HOST array), by the kernel's own functions.  out_tm / out_tn /
+ * out_dead / out_width: as octic_dense_gemm_order_adaptive, one entry per workgroup of the launch (-1 / -1 / 0 for a class-token
+ * workgroup).  out_cls_rt / out_cls_ct: row tile and column tile (of 16) of the class-token items, out[3] entries per
+ * class-token workgroup in the order it takes them, -1 = none (each nullable, `cls_cap` entries).  Returns the number of
+ * workgroups, or OCTIC_ESHAPE for a launch the folded kernel does not take or a cap too small. */
+int octic_dense_gemm_order_adaptive_cls(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
+                                        int cap, int* out_tm, int* out_tn, int* out_dead, int* out_width, int cls_cap,
+                                        int* out_cls_rt, int* out_cls_ct);
 
 /* Weight gradient of an nn.Linear of the standard half (the autograd of deit/vit.py:33,46 and of timm Mlp.fc1 / fc2):
  *     dW[N,K] = dY[M,N]^T . X[M,K]     f32, nn.Linear layout

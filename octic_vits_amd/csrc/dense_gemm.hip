@@ -1142,6 +1142,131 @@ __global__ __launch_bounds__(256) void dense_cls_sum_kernel(DgArgs a, int tokens
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The class-token rows INSIDE the adaptive launch (dense_nt_adaptive_cls_kernel).  At drop_path 0.5 the adaptive launch keeps
+// ~160 of 256 CUs busy with live tiles; the dead tiles in front of the grid leave theirs after a few stores.  The class-token
+// work of the launch - so far one or two latency-bound launches serially behind it - is appended to the grid as `wgs`
+// workgroups BEHIND the tiles, where it is dispatched onto the CUs the dead tiles free.  An item is one 16-row x 16-column
+// class-token tile and lives in one workgroup: K is cut into slices of CLS_KSLICE = 320, a wave contracts a slice as ten MFMAs
+// from a zero accumulator (weights first), the f32 partial tiles meet in LDS and are summed in slice order from slice 0, the
+// bias is added in f32, one rounding, plain store: the arithmetic of dense_cls_kernel<0> with K / 320 waves and of
+// dense_cls_part_kernel + dense_cls_sum_kernel, bit for bit.  Eight waves: K / 320 <= 8 slices -> 8 / slices items share a
+// pass of the workgroup (four at K = 640, two at K = 1280); more slices -> wave w takes slices w and w + 8 into separate
+// partials (two batches of loads, both requested before the first MFMA).  Passes are dealt grid-stride over the workgroups.
+// Nothing waits on another workgroup; the dispatch order decides the timing only.
+constexpr int kDgFoldWgs = 80;                   // class-token workgroups at most: 320 items = 1 / 2 / 4 / 4 passes each at K = 640 / 1280 / 3840 / 5120
+__host__ __device__ inline bool dg_fold_k(int K) { return K > 0 && (K % CLS_KSLICE) == 0 && K / CLS_KSLICE <= 16; }
+__host__ __device__ inline int dg_fold_ipp(int nks) { return nks <= 8 ? 8 / nks : 1; }      // items per pass of a workgroup
+__host__ __device__ inline int dg_fold_items(int N, int nrows) { return (N >> 4) * ((nrows + 15) >> 4); }
+__host__ __device__ inline int dg_fold_passes(int N, int K, int nrows) {
+  const int ipp = dg_fold_ipp(K / CLS_KSLICE);
+  return (dg_fold_items(N, nrows) + ipp - 1) / ipp;
+}
+// blockIdx -> class-token workgroup of the folded launch (-1: a tile workgroup, whose item is dense_item_adaptive's)
+__host__ __device__ inline int dg_fold_wg(int bid, int tile_wgs) { return bid < tile_wgs ? -1 : bid - tile_wgs; }
+// the item (column tile item % (N / 16), row tile item / (N / 16)) of slot `slot` in pass `it` of class-token workgroup cw of
+// `wgs`; -1 = none
+__host__ __device__ inline int dg_fold_item(int items, int ipp, int wgs, int cw, int it, int slot) {
+  if (slot >= ipp) return -1;
+  const int64_t item = ((int64_t)it * wgs + cw) * ipp + slot;
+  return item < items ? (int)item : -1;
+}
+
+__device__ __forceinline__ void dense_cls_fold_wg(const DgArgs& a, char* lds, int tokens, int nrows, int cw, int wgs) {
+  f32x4* const part = (f32x4*)lds;                          // [2 (pass parity)][16 partial tiles][64 lanes]: the head of the ring
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int fr = lane & 15, kg = lane >> 4;
+  const int nks = a.K / CLS_KSLICE, ipp = dg_fold_ipp(nks);
+  const int ntn = a.N >> 4, items = dg_fold_items(a.N, nrows);
+  const int passes = (items + ipp - 1) / ipp;
+  const int slot = nks <= 8 ? wid / nks : 0;                // (>= ipp: an idle wave, nks = 3, 5, 6, 7)
+  const int ks0 = nks <= 8 ? wid - slot * nks : wid;        // first slice of this wave; partial tile index = slot * nks + ks0 = wid
+  const bool two = nks > 8 && wid + 8 < nks;                // ... and slice wid + 8
+  constexpr int U = CLS_KSLICE / 32;                        // static register indices only, one batch of loads per slice
+#pragma unroll 1
+  for (int it = 0; it * wgs + cw < passes; ++it) {
+    const int item = __builtin_amdgcn_readfirstlane(dg_fold_item(items, ipp, wgs, cw, it, slot));
+    f32x4* const buf = part + (it & 1) * 16 * 64;
+    const int tn = item % ntn, tb = item / ntn;
+    const int n0 = tn * 16, b0 = tb * 16;
+    const bool lead = item >= 0 && ks0 == 0;
+    f32x4 bv = {0, 0, 0, 0};
+    if (item >= 0) {
+      int brow = b0 + fr;
+      brow = brow < nrows ? brow : nrows - 1;               // rows past the batch read a valid row and are dropped at the end
+      const bf16* wp = a.B + (int64_t)(n0 + fr) * a.ldb + ks0 * CLS_KSLICE + kg * 8;
+      const bf16* xp = a.A + (int64_t)brow * tokens * a.lda + ks0 * CLS_KSLICE + kg * 8;
+      if (lead && a.bias) bv = *(const f32x4*)(a.bias + n0 + 4 * kg);
+      bf16x8 wf[U], xf[U], wg[U], xg[U];
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        wf[j] = *(const bf16x8*)(wp + j * 32);
+        xf[j] = *(const bf16x8*)(xp + j * 32);
+      }
+      if (two) {
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+          wg[j] = *(const bf16x8*)(wp + 8 * CLS_KSLICE + j * 32);
+          xg[j] = *(const bf16x8*)(xp + 8 * CLS_KSLICE + j * 32);
+        }
+      }
+      f32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < U; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[j], acc, 0, 0, 0);
+      buf[wid * 64 + lane] = acc;
+      if (two) {
+        f32x4 acc2 = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < U; ++j) acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wg[j], xg[j], acc2, 0, 0, 0);
+        buf[(wid + 8) * 64 + lane] = acc2;
+      }
+    }
+    // one barrier per pass: the partial tiles of pass `it` are read while pass it + 1 fills the other half, and pass it + 2
+    // writes this half only behind the barrier of pass it + 1, which the reader reaches after its sums
+    __syncthreads();
+    if (lead) {
+      const f32x4* src = buf + (slot * nks) * 64 + lane;
+      f32x4 v = src[0];
+      for (int s = 1; s < nks; ++s) v = v + src[s * 64];
+      if (a.bias) v = v + bv;
+      // lane (fr, kg) = token row b0 + fr, output columns n0 + 4 kg .. + 3
+      if (b0 + fr < nrows)
+        *(bf16x4*)(a.C + (int64_t)(b0 + fr) * tokens * a.ldc + n0 + 4 * kg) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+    }
+  }
+}
+
+// dense_nt_adaptive_kernel with the launch's class-token rows: workgroups [0, tile_wgs) are the adaptive launch's, workgroup
+// for workgroup; [tile_wgs, tile_wgs + cls_wgs) are class-token workgroups - at the END of the grid, so that none of them
+// holds a CU before every live tile has one.
+__global__ __launch_bounds__(512, 1) void dense_nt_adaptive_cls_kernel(DgArgs a, int tokens, int nrows, int tile_wgs, int cls_wgs) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];   // the ring of either width + the bitmap; class-token partial tiles
+  dg_trace_start();
+  const int cw = __builtin_amdgcn_readfirstlane(dg_fold_wg(blockIdx.x, tile_wgs));
+  if (cw >= 0) {
+    dense_cls_fold_wg(a, lds, tokens, nrows, cw, cls_wgs);
+    return;
+  }
+  unsigned long long* const live_bm = (unsigned long long*)(lds + DgGeom<5>::LDS);
+  dg_build_bitmap(a, live_bm);
+  bool narrow, dead_item;
+  int tile;
+  dense_item_adaptive(a.tiles_m, a.tiles_n, a.tiles_n_narrow, a.cus, a.narrow_force, blockIdx.x, live_bm, narrow, tile, dead_item);
+  narrow = __builtin_amdgcn_readfirstlane((int)narrow) != 0;
+  tile = __builtin_amdgcn_readfirstlane(tile);
+  dead_item = __builtin_amdgcn_readfirstlane((int)dead_item) != 0;
+  if (tile < 0) return;                                                        // past the chosen width's tiles
+  const int nkt_all = a.K / DG_BK;
+  if (narrow) {
+    DgArgs b = a;
+    b.tiles_n = a.tiles_n_narrow;
+    dense_nt_tile<DG_PLAIN, 4, true>(b, lds, tile, 0, nkt_all, 0, -1, dead_item);
+  } else {
+    dense_nt_tile<DG_PLAIN, 5, true>(a, lds, tile, 0, nkt_all, 0, -1, dead_item);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Schedule: `full` tiles get one workgroup each; the remaining r = tiles - full tiles (the partial last round on the
 // `cus` workgroup slots) are split along K over `split` workgroups each, so the last round also fills the chip.
 struct DgPlan { int nt, tiles_m, tiles_n, full, rem, split, tail_pad, grid; double cost; };
@@ -1299,6 +1424,21 @@ inline DgAdaptive dense_plan_adaptive(const DgTokPlan& tp, int N, int mode, int 
   return d;
 }
 
+// The folded launch (dense_nt_adaptive_cls_kernel) takes an eligible adaptive launch whose K the class-token workgroup cuts into
+// at most 16 slices of 320.  tile_wgs = the adaptive launch's grid, wgs = class-token workgroups behind it, per_wg = class-token
+// items of the busiest of them.
+struct DgFold { bool taken; int tile_wgs, wgs, per_wg, grid; };
+inline DgFold dense_plan_fold(const DgAdaptive& ad, int images, int N, int K) {
+  DgFold f = {false, ad.grid, 0, 0, ad.grid};
+  if (!ad.eligible || !dg_fold_k(K) || images <= 0) return f;
+  const int passes = dg_fold_passes(N, K, images);
+  f.taken = true;
+  f.wgs = passes < kDgFoldWgs ? passes : kDgFoldWgs;
+  f.per_wg = (passes + f.wgs - 1) / f.wgs * dg_fold_ipp(K / CLS_KSLICE);
+  f.grid = f.tile_wgs + f.wgs;
+  return f;
+}
+
 }  // namespace octic
 
 using namespace octic;
@@ -1365,7 +1505,7 @@ int octic_dense_gemm_colsum_rows(int M, int N, int K) {
 static int dense_launch(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
                         void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
                         const float* X, float* OUT, const void* H, float* colsum, const float* sample_scale,
-                        int rows_per_sample, void* workspace, int tokens, void* stream, bool adaptive) {
+                        int rows_per_sample, void* workspace, int tokens, void* stream, bool adaptive, bool fold_cls = false) {
   if (!A || !B || !C) return OCTIC_ENULL;
   if (sample_scale && (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0)) return OCTIC_ESHAPE;
   if (sample_scale && (((uintptr_t)sample_scale) & 3)) return OCTIC_EALIGN;
@@ -1417,9 +1557,19 @@ static int dense_launch(const void* A, const void* B, int M, int N, int K, int64
     (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_DFACT, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
     (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUO, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
     (void)hipFuncSetAttribute((const void*)dense_nt_adaptive_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem5 + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_adaptive_cls_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem5 + bmb);
     (void)hipGetLastError();
   }
   const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), skip);
+  const DgFold fold = dense_plan_fold(ad, tp.images, N, K);
+  if (adaptive && fold_cls && fold.taken) {
+    // the adaptive launch below with the class-token workgroups behind its tiles: ONE launch, no dense_cls_* launch
+    a.tiles_n_narrow = ad.tiles_n_narrow;
+    a.cus = dense_cus();
+    a.narrow_force = ad.force;
+    dense_nt_adaptive_cls_kernel<<<fold.grid, 512, smem5 + bmb, s>>>(a, tokens, tp.images, fold.tile_wgs, fold.wgs);
+    return launch_status();
+  }
   if (adaptive && ad.eligible) {
     // same plan, same panels; the grid covers the tiles of either width and the workgroups past the chosen one return
     a.tiles_n_narrow = ad.tiles_n_narrow;
@@ -1497,6 +1647,17 @@ int octic_dense_gemm_nt_tokens_adaptive(const void* A, const void* B, int M, int
                                         const float* sample_scale, int rows_per_sample, void* workspace, int tokens, void* stream) {
   return dense_launch(A, B, M, N, K, lda, ldb, mode, C, C2, ldc, bias, gamma, rs, rps, X, OUT, H, colsum, sample_scale,
                       rows_per_sample, workspace, tokens, stream, true);
+}
+
+// octic_dense_gemm_nt_tokens_adaptive with the class-token rows of an eligible launch of foldable K computed by workgroups at the
+// end of the main launch's grid (dense_nt_adaptive_cls_kernel) where fold_cls != 0; any other launch IS the adaptive call
+int octic_dense_gemm_nt_tokens_adaptive_cls(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode,
+                                            void* C, void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs,
+                                            int64_t rps, const float* X, float* OUT, const void* H, float* colsum,
+                                            const float* sample_scale, int rows_per_sample, void* workspace, int tokens,
+                                            int fold_cls, void* stream) {
+  return dense_launch(A, B, M, N, K, lda, ldb, mode, C, C2, ldc, bias, gamma, rs, rps, X, OUT, H, colsum, sample_scale,
+                      rows_per_sample, workspace, tokens, stream, true, fold_cls != 0);
 }
 
 int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
@@ -1585,6 +1746,66 @@ int octic_dense_gemm_order_adaptive(int M, int N, int K, int mode, int tokens, c
   }
   if (out_width) *out_width = narrow ? 256 : 320;
   return ad.grid;
+}
+
+// What octic_dense_gemm_nt_tokens_adaptive_cls (fold_cls != 0) does with a masked launch of this problem: out[0] = 1 if the folded
+// kernel takes it (else it is the adaptive call), out[1] = workgroups of the launch, out[2] = class-token workgroups among them
+// (the last ones), out[3] = class-token items (16 rows x 16 columns) of the busiest of those, out[4] = tile workgroups in front.
+int octic_dense_gemm_plan_adaptive_cls(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out) {
+  if (!out) return OCTIC_ENULL;
+  if (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0 || N <= 0 || K < 2 * DG_BK) return OCTIC_ESHAPE;
+  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
+  const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), mode != DG_RESID);
+  const DgFold f = dense_plan_fold(ad, tp.images, N, K);
+  out[0] = f.taken ? 1 : 0;
+  out[1] = f.grid;
+  out[2] = f.wgs;
+  out[3] = f.per_wg;
+  out[4] = f.tile_wgs;
+  return OCTIC_OK;
+}
+
+// What the folded launch gives each workgroup, in blockIdx order, by the kernel's own functions (dg_fold_wg, dense_item_adaptive,
+// dg_fold_item): sample_scale is a HOST array.  out_tm / out_tn / out_dead / out_width: as octic_dense_gemm_order_adaptive, one
+// entry per workgroup (`cap` entries; -1 / 0 for a class-token workgroup).  out_cls_rt / out_cls_ct: row tile and column tile of
+// the class-token items, per_wg (out[3] of the plan) entries per class-token workgroup in the order it takes them, -1 = none
+// (`cls_cap` entries each; each may be NULL).  Returns the number of workgroups; OCTIC_ESHAPE for a launch the folded kernel does
+// not take or a cap too small.
+int octic_dense_gemm_order_adaptive_cls(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
+                                        int cap, int* out_tm, int* out_tn, int* out_dead, int* out_width, int cls_cap,
+                                        int* out_cls_rt, int* out_cls_ct) {
+  if (!sample_scale) return OCTIC_ENULL;
+  if (M <= 0 || N <= 0 || K < 2 * DG_BK || rows_per_sample <= 0 || (M % rows_per_sample) != 0) return OCTIC_ESHAPE;
+  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
+  const DgPlan p = tp.p;
+  const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), true);
+  const DgFold f = dense_plan_fold(ad, tp.images, N, K);
+  if (!f.taken || cap < f.grid || ((out_cls_rt || out_cls_ct) && cls_cap < f.wgs * f.per_wg)) return OCTIC_ESHAPE;
+  unsigned long long bm[kDgMaskWords] = {};
+  for (int tm = 0; tm < p.tiles_m; ++tm)
+    if (dg_panel_live(sample_scale, rows_per_sample, M, tokens, 1, tm)) bm[tm >> 6] |= 1ull << (tm & 63);
+  const int nks = K / CLS_KSLICE, ipp = dg_fold_ipp(nks), ntn = N >> 4, items = dg_fold_items(N, tp.images);
+  bool narrow = dg_adaptive_narrow(dg_live_panels(bm, p.tiles_m), ad.tiles_n_narrow, dense_cus(), ad.force);
+  for (int bid = 0; bid < f.grid; ++bid) {
+    int tile = -1, tm = -1, tn = -1;
+    bool dead = false;
+    const int cw = dg_fold_wg(bid, f.tile_wgs);
+    if (cw < 0) {
+      dense_item_adaptive(p.tiles_m, p.tiles_n, ad.tiles_n_narrow, dense_cus(), ad.force, bid, bm, narrow, tile, dead);
+      if (tile >= 0) dg_tile_panel(p.tiles_m, narrow ? ad.tiles_n_narrow : p.tiles_n, tile, tm, tn);
+    } else {
+      for (int e = 0; e < f.per_wg; ++e) {
+        const int item = dg_fold_item(items, ipp, f.wgs, cw, e / ipp, e % ipp);
+        if (out_cls_rt) out_cls_rt[cw * f.per_wg + e] = item >= 0 ? item / ntn : -1;
+        if (out_cls_ct) out_cls_ct[cw * f.per_wg + e] = item >= 0 ? item % ntn : -1;
+      }
+    }
+    if (out_tm) out_tm[bid] = tm;
+    if (out_tn) out_tn[bid] = tn;
+    if (out_dead) out_dead[bid] = dead ? 1 : 0;
+  }
+  if (out_width) *out_width = narrow ? 256 : 320;
+  return f.grid;
 }
 
 int octic_dense_gemm_nt(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,

@@ -517,6 +517,27 @@ DENSE_NT_SKIP_DROPPED = _skip_from_env("OCTIC_DENSE_SKIP")
 DENSE_NARROW_DROPPED = _skip_from_env("OCTIC_DENSE_NARROW")
 
 
+# Such a launch leaves the CUs of its dead tiles idle for most of its length, and its class-token rows wait behind it for one or
+# two latency-bound launches of their own (dense_cls_kernel, or dense_cls_part_kernel + dense_cls_sum_kernel).  With DENSE_CLS_FOLD
+# they are computed by workgroups at the end of the main launch's grid, on the CUs the dead tiles free (include/octic_hip.h:
+# octic_dense_gemm_nt_tokens_adaptive_cls); same bits.  Effective only while DENSE_NARROW_DROPPED is on.  Read once at import from
+# OCTIC_DENSE_CLS_FOLD (0 = off).
+DENSE_CLS_FOLD = _skip_from_env("OCTIC_DENSE_CLS_FOLD")
+# Smallest drop probability of the branch at which a launch asks for the fold.  The host cannot know the kept count without a
+# sync, only its distribution: with 64 samples, 64 or more CUs are free while at most 38 are kept (5 x 38 = 190 narrow tiles), and
+# when fewer are free the class-token workgroups run BEHIND the live tiles, where a K = 5120 item in one workgroup is slower
+# than the two stand-alone launches.  The standalone table (NOTES.md, "class-token rows ride in the main launch") has the five
+# launches of a block 61 / 54 us ahead with the fold at 32 / 38 kept, 37 us behind at 45 (31 CUs free for 80 workgroups), 42 ahead at
+# 52 (the wide tile: 48 CUs free) and 60 behind at 64.  Kept is Binomial(64, 1 - drop): at drop 0.5, 0.95 of the draws are at most
+# 38; at 0.4 half of them are and 0.06 are 45 or more; at 0.3 the mean is 45.
+DENSE_CLS_FOLD_MIN_DROP = 0.4
+
+
+def dense_cls_fold(drop_prob):
+    """fold_cls of ops.dense_gemm_nt for a launch under the mask of a branch with this drop probability (None / 0: no draw)."""
+    return bool(DENSE_CLS_FOLD and DENSE_NARROW_DROPPED and drop_prob is not None and float(drop_prob) >= DENSE_CLS_FOLD_MIN_DROP)
+
+
 def dense_skip_scale(rs, rps, M, rows_to=None):
     """rs as the sample_scale of a dense_nt_kernel launch over M token rows: whole_sample_mask while the switch is on."""
     return whole_sample_mask(rs, rps, M, rows_to) if DENSE_NT_SKIP_DROPPED else None
@@ -1175,30 +1196,32 @@ def _tok(shape):
     return int(shape[-2]) if len(shape) >= 3 else 0
 
 
-def _gemm_fwd(tag, x2, wb, b, cache, name, tokens, ss=None, rps=0):
+def _gemm_fwd(tag, x2, wb, b, cache, name, tokens, ss=None, rps=0, drop=None):
     """x2 wb^T + b (bf16): csrc/dense_gemm.hip with a plain epilogue (f32 bias b) where `tag` is routed to it (DENSE_HIP),
     else the BLAS library with the cache's compute-dtype bias.  ss / rps: the branch's stochastic-depth mask (dense_skip_scale),
-    for the hand-written kernel only."""
+    for the hand-written kernel only; drop: the probability it was drawn with (dense_cls_fold)."""
     if tag in DENSE_HIP:
         return ops.dense_gemm_nt(x2, wb, 0, bias=_f32(b), name=f"dense_nt_kernel<{name}>", tokens=tokens, sample_scale=ss,
-                                 rows_per_sample=rps)
+                                 rows_per_sample=rps, fold_cls=ss is not None and dense_cls_fold(drop))
     return _linear_lib(x2, wb, None if b is None else cache.b)
 
 
-def _gemm_dgrad(g2, wt, wb, shape, dtype, ss=None, rps=0):
+def _gemm_dgrad(g2, wt, wb, shape, dtype, ss=None, rps=0, drop=None):
     """Input gradient g2 W as `shape` in `dtype`: csrc/dense_gemm.hip on the transposed copy wt where the cache made one (the
     input gradient is routed to it), else the BLAS library on wb.  ss / rps: the mask under which g2's rows of a dropped sample
-    are exactly zero (dense_skip_scale), for the hand-written kernel only."""
-    gx = (ops.dense_gemm_nt(g2, wt, 0, name="dense_nt_kernel<dgrad>", tokens=_tok(shape), sample_scale=ss, rows_per_sample=rps)
+    are exactly zero (dense_skip_scale), for the hand-written kernel only; drop: the probability it was drawn with."""
+    gx = (ops.dense_gemm_nt(g2, wt, 0, name="dense_nt_kernel<dgrad>", tokens=_tok(shape), sample_scale=ss, rows_per_sample=rps,
+                            fold_cls=ss is not None and dense_cls_fold(drop))
           if wt is not None else _mm_lib(g2, wb))
     return gx.view(shape).to(dtype)
 
 
-def _resid_tail_fwd(ctx, x, tag, a2, wb, b, cache, tokens, g32, rs32, rps, nw, nb, neps, rows_to, stream, ds):
+def _resid_tail_fwd(ctx, x, tag, a2, wb, b, cache, tokens, g32, rs32, rps, nw, nb, neps, rows_to, stream, ds, drop=None):
     """out = x + rs * gamma * br with br = a2 wb^T + b, the GEMM `tag` (proj / fc2): the tail of both branches of a standard
     block.  neps is not None: the residual add and LayerNorm(out; nw, nb, neps) in bf16 as one row pass -> (out, yn).
     rows_to: x are compact rows of `stream`, the result goes back into it through the row map -> stream.
     ds: rs32 as the sample mask of the GEMM (dense_skip_scale): br meets rs = 0 in every row of a dropped sample.
+    drop: the probability rs was drawn with, where the caller knows it (dense_cls_fold).
     Returns (the node's outputs, the tensors _resid_tail_bwd wants back from ctx.save_for_backward)."""
     ctx.rows_to, ctx.x_shape = rows_to, x.shape
     ctx.tail = (neps is not None, rps, b is not None, nw is not None, nb is not None)
@@ -1206,7 +1229,7 @@ def _resid_tail_fwd(ctx, x, tag, a2, wb, b, cache, tokens, g32, rs32, rps, nw, n
     if neps is None and rows_to is None and tag in DENSE_HIP and DENSE_RESID_FUSED:
         br, out = ops.dense_gemm_nt(a2, wb, 2, bias=_f32(b), gamma=g32, rs=rs32, rps=rps, x=x2, name="dense_nt_kernel<resid>")
         return out.view(x.shape), (br, g32, rs32)
-    br = _gemm_fwd(tag, a2, wb, b, cache, tag, tokens, ds, rps)
+    br = _gemm_fwd(tag, a2, wb, b, cache, tag, tokens, ds, rps, drop)
     if neps is not None:
         nw32, nb32 = _f32(nw), _f32(nb)
         out, yn, stats = ops.dense_resid_layernorm_fwd(x2, br, g32, rs32, rps, nw32, nb32, neps, torch.bfloat16)
@@ -1261,18 +1284,20 @@ class DenseLinearNTFn(torch.autograd.Function):
     gradient on csrc/dense_gemm.hip.  deit/vit.py:33 (``self.qkv(x)``)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, cache, tag, pair=None, rs=None, rps=0):
+    def forward(ctx, x, w, b, cache, tag, pair=None, rs=None, rps=0, drop=None):
         """rs / rps: the stochastic-depth factor of the branch this projection opens and the rows per entry, where EVERYTHING
         computed from the output is multiplied by it (the qkv projection of vit.Attention.forward_fused) - the cotangent rows
-        of a dropped sample are then zero and the weight gradient may skip them (wgrad_skip_scale)."""
+        of a dropped sample are then zero and the weight gradient may skip them (wgrad_skip_scale).  drop: the probability rs
+        was drawn with (dense_cls_fold)."""
         ctx.pair = pair
+        ctx.drop = drop
         ctx.wparam = w
         xb = _c(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16))
         wb, wt = cache.get_nt(w, b, ("d" + tag) in DENSE_HIP and ctx.needs_input_grad[0])
         x2 = xb.reshape(-1, wb.shape[1])
         mask = whole_sample_mask(rs, rps, x2.shape[0])
         ds = mask if DENSE_NT_SKIP_DROPPED else None
-        y = _gemm_fwd(tag, x2, wb, b, cache, "plain", _tok(x.shape), ds, rps)
+        y = _gemm_fwd(tag, x2, wb, b, cache, "plain", _tok(x.shape), ds, rps, drop)
         ss = mask if WGRAD_SKIP_DROPPED else None
         # zero cotangent rows in (the attention backward of dO = 0), zero input-gradient rows out: the bias column sums and the
         # backward of the norm that produced x may skip them
@@ -1288,7 +1313,7 @@ class DenseLinearNTFn(torch.autograd.Function):
         x2, wb, wt, ss, ds, rk = ctx.saved_tensors
         has_b, x_dtype, x_shape, tag = ctx.meta
         g2 = _c(gy).reshape(-1, wb.shape[0])
-        gx = _gemm_dgrad(g2, wt, wb, x_shape, x_dtype, ds, ctx.rps) if ctx.needs_input_grad[0] else None
+        gx = _gemm_dgrad(g2, wt, wb, x_shape, x_dtype, ds, ctx.rps, ctx.drop) if ctx.needs_input_grad[0] else None
         gb = None
         if has_b:
             gb = (ops.dense_colsum(g2, rk, ctx.rps)
@@ -1306,9 +1331,9 @@ class DenseLinearNTFn(torch.autograd.Function):
                               and pss.numel() == ss.numel()) else None
                 dw, _ = ops.dense_wgrad_tn_pair(g2, x2, pg, px, dw1=pdw, dw0=dest, sample_scale=both, rows_per_sample=ctx.rps)
                 ops.grad_written(landed, ctx.wparam if dest is not None else None)
-                return gx, dw, gb, None, None, None, None, None
+                return gx, dw, gb, None, None, None, None, None, None
             pair.flush()
-        return gx, _wgrad_lib(g2, x2, ctx.wparam, ss, ctx.rps), gb, None, None, None, None, None
+        return gx, _wgrad_lib(g2, x2, ctx.wparam, ss, ctx.rps), gb, None, None, None, None, None, None
 
 
 class DenseProjResidFn(torch.autograd.Function):
@@ -1316,11 +1341,14 @@ class DenseProjResidFn(torch.autograd.Function):
     fused epilogue; backward = one HIP row pass (gy, d gamma, bias gradient) + the input-gradient GEMM."""
 
     @staticmethod
-    def forward(ctx, x, a, w, b, gamma, rs, rps, cache, nw=None, nb=None, neps=None, pair=None, rows_to=None, stream=None):
+    def forward(ctx, x, a, w, b, gamma, rs, rps, cache, nw=None, nb=None, neps=None, pair=None, rows_to=None, stream=None,
+                drop=None):
         """neps is not None: also return LayerNorm(out; nw, nb, neps) in bf16 - the norm that opens the next branch - from
         the same row pass that adds the residual (NEXT_NORM_FUSED).  rows_to (RowsTo; stream = rows_to.stream, passed as a
-        tensor so that autograd sees the in-place edit): x are compact rows of the stream, the result goes back into it."""
+        tensor so that autograd sees the in-place edit): x are compact rows of the stream, the result goes back into it.
+        drop: the probability rs was drawn with (dense_cls_fold)."""
         ctx.pair = pair
+        ctx.drop = drop
         ctx.wparam = w
         x = _c(x)
         ab = _c(a if a.dtype == torch.bfloat16 else a.to(torch.bfloat16))
@@ -1328,7 +1356,7 @@ class DenseProjResidFn(torch.autograd.Function):
         a2 = ab.reshape(-1, wb.shape[1])
         rs32 = _f32(rs)
         outs, tail = _resid_tail_fwd(ctx, x, "proj", a2, wb, b, cache, _tok(a.shape), _f32(gamma), rs32, rps,
-                                     nw, nb, neps, rows_to, stream, dense_skip_scale(rs32, rps, a2.shape[0], rows_to))
+                                     nw, nb, neps, rows_to, stream, dense_skip_scale(rs32, rps, a2.shape[0], rows_to), drop)
         ctx.save_for_backward(a2, wb, wt, *tail)
         ctx.meta = (a.dtype, a.shape)
         return outs
@@ -1342,13 +1370,13 @@ class DenseProjResidFn(torch.autograd.Function):
         rps = ctx.tail[1]
         mask = whole_sample_mask(tail[2], rps, gy.shape[0], ctx.rows_to)  # gy = rs * gamma * gout: zero rows where rs is 0
         ds = mask if DENSE_NT_SKIP_DROPPED else None
-        ga = _gemm_dgrad(gy, wt, wb, a_shape, a_dtype, ds, rps) if ctx.needs_input_grad[1] else None
+        ga = _gemm_dgrad(gy, wt, wb, a_shape, a_dtype, ds, rps, ctx.drop) if ctx.needs_input_grad[1] else None
         ss = mask if WGRAD_SKIP_DROPPED else None
         if _pair_ready(ctx.pair, gy, a2) and ops.dense_wgrad_ok(gy.shape[0], gy.shape[1], a2.shape[1]):
             dw = ctx.pair.park(gy, a2, ctx.wparam, ss, rps)   # written by the qkv weight gradient's launch (or at the end of the pass)
         else:
             dw = _wgrad_lib(gy, a2, ctx.wparam, ss, rps)
-        return gx, ga, dw, colsum, dgamma, None, None, None, dnw, dnb, None, None, None, None
+        return gx, ga, dw, colsum, dgamma, None, None, None, dnw, dnb, None, None, None, None, None
 
 
 class DenseMlpFn(torch.autograd.Function):
@@ -1359,10 +1387,12 @@ class DenseMlpFn(torch.autograd.Function):
     csrc/dense_wgrad.hip (WGRAD_HIP)."""
 
     @staticmethod
-    def forward(ctx, y, x, w1, b1, w2, b2, gamma, rs, rps, c1, c2, nw=None, nb=None, neps=None, rows_to=None, stream=None):
+    def forward(ctx, y, x, w1, b1, w2, b2, gamma, rs, rps, c1, c2, nw=None, nb=None, neps=None, rows_to=None, stream=None,
+                drop=None):
         """neps is not None: also return LayerNorm(out; nw, nb, neps) in bf16 (the NEXT block's norm1) from the row pass
-        that adds the residual.  rows_to / stream: as in DenseProjResidFn."""
+        that adds the residual.  rows_to / stream / drop: as in DenseProjResidFn."""
         ctx.wparams = (w1, w2)
+        ctx.drop = drop
         x = _c(x)
         yb = _c(y if y.dtype == torch.bfloat16 else y.to(torch.bfloat16))
         need_t = any(ctx.needs_input_grad[:2])            # (an inference pass - the DINOv2 teacher - never transposes)
@@ -1392,7 +1422,7 @@ class DenseMlpFn(torch.autograd.Function):
             h = _linear_lib(y2, w1b, None if b1 is None else c1.b)
             a = torch.nn.functional.gelu(h)
         outs, tail = _resid_tail_fwd(ctx, x, "fc2", a, w2b, b2, c2, _tok(y.shape), g32, rs32, rps,
-                                     nw, nb, neps, rows_to, stream, ds)
+                                     nw, nb, neps, rows_to, stream, ds, drop)
         ctx.save_for_backward(y2, h, a, w1b, w1t, w2b, w2t, *tail)
         ctx.meta = (b1 is not None, y.dtype, y.shape)
         return outs
@@ -1419,8 +1449,8 @@ class DenseMlpFn(torch.autograd.Function):
         ss = mask if WGRAD_SKIP_DROPPED else None                         # gbr = rs * gamma * gout, dh = gelu' * (gbr W2)
         gw2 = _wgrad_lib(gbr, a, ctx.wparams[1], ss, rps)
         gw1 = _wgrad_lib(dh, y2, ctx.wparams[0], ss, rps)
-        gy = _gemm_dgrad(dh, w1t, w1b, y_shape, y_dtype, ds, rps) if ctx.needs_input_grad[0] else None   # dh = gelu' * 0
-        return gy, gx, gw1, db1, gw2, db2, dgamma, None, None, None, None, dnw, dnb, None, None, None
+        gy = _gemm_dgrad(dh, w1t, w1b, y_shape, y_dtype, ds, rps, ctx.drop) if ctx.needs_input_grad[0] else None   # dh = gelu' * 0
+        return gy, gx, gw1, db1, gw2, db2, dgamma, None, None, None, None, dnw, dnb, None, None, None, None
 
 
 class DenseSwigluFn(torch.autograd.Function):

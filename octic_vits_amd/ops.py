@@ -1331,8 +1331,21 @@ def _dense_narrow():
     return functional.DENSE_NARROW_DROPPED
 
 
+def dense_plan_adaptive_cls(M, N, K, mode, tokens, rows_per_sample):
+    """(folded kernel takes it?, workgroups of the launch, class-token workgroups at its end, class-token items of the busiest
+    one, tile workgroups in front) of a masked octic_dense_gemm_nt_tokens_adaptive_cls launch with fold_cls on."""
+    out = (ctypes.c_int * 5)()
+    check(lib().octic_dense_gemm_plan_adaptive_cls(M, N, K, mode, int(tokens), int(rows_per_sample), out))
+    return bool(out[0]), out[1], out[2], out[3], out[4]
+
+
+def _dense_cls_fold():
+    from . import functional          # (functional imports this module)
+    return functional.DENSE_NARROW_DROPPED and functional.DENSE_CLS_FOLD
+
+
 def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h=None, name=None, want_colsum=False,
-                  tokens=0, sample_scale=None, rows_per_sample=0):
+                  tokens=0, sample_scale=None, rows_per_sample=0, fold_cls=False):
     """C[M,N] = a[M,K] @ b[N,K]^T on the hand-written MFMA kernel (csrc/dense_gemm.hip) with a fused tail:
     mode 0 -> c ; 1 -> (c, gelu(c)) ; 2 -> (c, x + rs*gamma*c) ; 3 -> gelu'(h) * c (want_colsum: also the f32 column
     sums of that result) ; 4 -> (gelu'(c), gelu(c)) ; 5 -> h * c with h = the factor of mode 4 (want_colsum as 3) ;
@@ -1341,7 +1354,9 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
     launch use per-image row panels + the class-token kernel (octic_dense_gemm_nt_tokens); 0 = unknown.
     sample_scale / rows_per_sample: the stochastic-depth mask of octic_dense_gemm_nt_tokens_skip - f32 [M / rows_per_sample] on
     the device, 0 = every reader of that sample's output rows accepts the computed result or +0 (never with mode 2); a
-    malformed mask is a ValueError."""
+    malformed mask is a ValueError.
+    fold_cls: the caller expects the mask to drop enough samples for the class-token rows to ride in the main launch
+    (functional.dense_cls_fold; octic_dense_gemm_nt_tokens_adaptive_cls decides which launches can) - same bits either way."""
     _require_cuda(a)
     M, K = a.shape
     N = b.shape[0]
@@ -1362,8 +1377,13 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
     # a masked launch may choose its tile width on the device (functional.DENSE_NARROW_DROPPED; the library decides which launches)
     entry = lib().octic_dense_gemm_nt_tokens_adaptive if (ss is not None and _dense_narrow()) else lib().octic_dense_gemm_nt_tokens_skip
     t = KERNEL_TIMER.start()
-    check(entry(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias), _p(gamma), _p(rs), int(rps),
-                _p(x), _p(out), _p(h), _p(cs), _p(ss), srps, _p(ws), tokens, _stream(a)))
+    if fold_cls and ss is not None and _dense_cls_fold():
+        check(lib().octic_dense_gemm_nt_tokens_adaptive_cls(
+            _p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias), _p(gamma), _p(rs), int(rps),
+            _p(x), _p(out), _p(h), _p(cs), _p(ss), srps, _p(ws), tokens, 1, _stream(a)))
+    else:
+        check(entry(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias), _p(gamma), _p(rs), int(rps),
+                    _p(x), _p(out), _p(h), _p(cs), _p(ss), srps, _p(ws), tokens, _stream(a)))
     if t is not None:
         nb = 2 * (M * K + N * K + M * N * (2 if mode in (1, 3, 4, 5) else 1)) + (8 * M * N if mode == 2 else 0)
         # "@320": the launch ran the 256 x 320 tile (kernel symbol dense_nt_kernel<0, 5>), else <mode, 4>

@@ -80,10 +80,11 @@ class Mlp(nn.Module):
         return (_OF.dense_hip_ok(y, self.fc1.weight) and _OF.dense_hip_ok(y, self.fc2.weight)
                 and bool({"fc1", "fc2", "dfc1", "dfc2"} & _OF.DENSE_HIP))
 
-    def forward_fused(self, y, xres, gamma, rs, dtype, next_norm=None, rows_to=None):
+    def forward_fused(self, y, xres, gamma, rs, dtype, next_norm=None, rows_to=None, drop=None):
         """xres + rs*gamma*fc2(gelu(fc1(y))) with y already normalised and in the compute dtype.  next_norm (an
         nn.LayerNorm): the hand-written path also returns next_norm(result) from the residual row pass -> (x, y_next).
-        rows_to (functional.RowsTo): y / xres are compact rows of a stream; the result is written back into it."""
+        rows_to (functional.RowsTo): y / xres are compact rows of a stream; the result is written back into it.
+        drop: the probability rs was drawn with, where the caller knows it (functional.dense_cls_fold)."""
         rps = _rows_per_scale(y, rs)
         hip = dtype == torch.bfloat16 and self.rows_ok(y)
         if rows_to is not None and (not hip or next_norm is not None):
@@ -91,7 +92,7 @@ class Mlp(nn.Module):
         if hip:
             norm, rows = _tail_args(next_norm, rows_to)
             return _OF.DenseMlpFn.apply(y, xres, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, gamma,
-                                        rs, rps, self._c1, self._c2, *norm, *rows)
+                                        rs, rps, self._c1, self._c2, *norm, *rows, drop)
         if next_norm is not None:
             return self.forward_fused(y, xres, gamma, rs, dtype), None
         if dtype == torch.bfloat16 and self.fc1.out_features % 8 == 0:
@@ -133,9 +134,9 @@ class SwiGLUFFN(nn.Module):
         return (_OF.dense_hip_ok(y, self.w12.weight) and _OF.dense_hip_ok(y, self.w3.weight)
                 and bool({"fc1", "fc2", "dfc1", "dfc2"} & _OF.DENSE_HIP))
 
-    def forward_fused(self, y, xres, gamma, rs, dtype, next_norm=None, rows_to=None):
+    def forward_fused(self, y, xres, gamma, rs, dtype, next_norm=None, rows_to=None, drop=None):
         """xres + rs*gamma*w3(silu(x1) * x2) with y already normalised and in the compute dtype; next_norm / rows_to as in
-        Mlp.forward_fused.  The gate kernels are bf16; in float32 (a block in the float32 engine regime) the two GEMMs run on
+        Mlp.forward_fused (drop is accepted and unused: this FFN's launches keep their class-token kernels).  The gate kernels are bf16; in float32 (a block in the float32 engine regime) the two GEMMs run on
         csrc/dense_f32.hip around the gate in stock ops."""
         if dtype == torch.float32 and self.fusable() and rows_to is None and _f32_linear_ok(y, self.w12, self.w3):
             x1, x2 = _OF.DenseLinearFn.apply(y, self.w12.weight, self.w12.bias, dtype, self._c1).chunk(2, dim=-1)
@@ -185,10 +186,11 @@ class Attention(nn.Module):
     def rows_ok(self, y):
         return _OF.dense_hip_ok(y, self.proj.weight, "proj")
 
-    def forward_fused(self, y, xres, gamma, rs, dtype, next_norm=None, rows_to=None):
+    def forward_fused(self, y, xres, gamma, rs, dtype, next_norm=None, rows_to=None, drop=None):
         """xres + rs*gamma*proj(attention(qkv(y))) with y already normalised and in the compute dtype.  next_norm (an
         nn.LayerNorm): the hand-written path also returns next_norm(result) from the residual row pass -> (x, y_next).
-        rows_to (functional.RowsTo): y / xres are compact rows of a stream; the result is written back into it."""
+        rows_to (functional.RowsTo): y / xres are compact rows of a stream; the result is written back into it.
+        drop: the probability rs was drawn with, where the caller knows it (functional.dense_cls_fold)."""
         B, N, C = y.shape
         hd = C // self.num_heads
         bf = dtype == torch.bfloat16
@@ -197,7 +199,7 @@ class Attention(nn.Module):
             # drops and the weight gradient may skip them - whole samples of a plain batch only (functional.wgrad_skip_scale)
             plain = rows_to is None and not (_OF.RAGGED is not None and _OF.RAGGED.matches(y))
             qkv = _OF.DenseLinearNTFn.apply(y, self.qkv.weight, self.qkv.bias, self._c1, "qkv", self._wgpair,
-                                            rs if plain else None, _rows_per_scale(y, rs) if plain else 0)
+                                            rs if plain else None, _rows_per_scale(y, rs) if plain else 0, drop)
         else:
             qkv = _OF.DenseLinearFn.apply(y, self.qkv.weight, self.qkv.bias, dtype, self._c1)
         rag = _OF.RAGGED
@@ -217,7 +219,7 @@ class Attention(nn.Module):
         if hip:
             norm, rows = _tail_args(next_norm, rows_to)
             return _OF.DenseProjResidFn.apply(xres, a, self.proj.weight, self.proj.bias, gamma, rs, rps, self._c2,
-                                              *norm, self._wgpair, *rows)
+                                              *norm, self._wgpair, *rows, drop)
         out = _OF.LinearScaleResidualFn.apply(xres, a, self.proj.weight, self.proj.bias, gamma, rs, rps, dtype, self._c2)
         return out if next_norm is None else (out, None)
 
@@ -240,6 +242,11 @@ class Attention(nn.Module):
             attn = self.attn_drop(((q * self.scale) @ k.transpose(-2, -1)).softmax(dim=-1))
             x = attn @ v
         return self.proj_drop(self.proj(x.transpose(1, 2).reshape(B, N, C)))
+
+
+def _drop_prob(dp):
+    """The probability _drop_path_scale draws dp's factor with, or None where it draws none."""
+    return dp.drop_prob if (isinstance(dp, DropPath) and dp.drop_prob > 0. and dp.training) else None
 
 
 def _drop_path_scale(dp, x):
@@ -342,19 +349,19 @@ def _fused_block(x, norm1, attn, gamma1, dp1, norm2, mlp, gamma2, dp2, next_norm
         y, xres = _OF.DenseLayerNormFn.apply(x, norm1.weight, norm1.bias, norm1.eps, dt)
     y2 = None
     if fuse:
-        x, y2 = attn.forward_fused(y, xres, gamma1, _drop_path_scale(dp1, x), dt, next_norm=norm2)
+        x, y2 = attn.forward_fused(y, xres, gamma1, _drop_path_scale(dp1, x), dt, next_norm=norm2, drop=_drop_prob(dp1))
     else:
-        x = attn.forward_fused(y, xres, gamma1, _drop_path_scale(dp1, x), dt)
+        x = attn.forward_fused(y, xres, gamma1, _drop_path_scale(dp1, x), dt, drop=_drop_prob(dp1))
     if y2 is not None:
         y, xres = y2, x
     else:
         y, xres = _OF.DenseLayerNormFn.apply(x, norm2.weight, norm2.bias, norm2.eps, dt)
     if fuse and type(next_norm) is nn.LayerNorm and tuple(next_norm.normalized_shape) == (d,):
-        out, yn = mlp.forward_fused(y, xres, gamma2, _drop_path_scale(dp2, x), dt, next_norm=next_norm)
+        out, yn = mlp.forward_fused(y, xres, gamma2, _drop_path_scale(dp2, x), dt, next_norm=next_norm, drop=_drop_prob(dp2))
         if yn is not None:
             out._octic_prenorm = (next_norm, yn, out._version)
         return out
-    return mlp.forward_fused(y, xres, gamma2, _drop_path_scale(dp2, x), dt)
+    return mlp.forward_fused(y, xres, gamma2, _drop_path_scale(dp2, x), dt, drop=_drop_prob(dp2))
 
 
 def _traced_block(x, norm1, attn, gamma1, dp1, norm2, mlp, gamma2, dp2):
