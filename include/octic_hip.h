@@ -944,6 +944,58 @@ int octic_probe_ce(const float* logits, const int64_t* labels, int nheads, int B
 int octic_probe_sgd(const octic_probe_head* heads, int nheads, int total_ktiles, const float* F, int64_t ldf,
                     const float* dlogits, int B, int C, const float* lr, float momentum, void* stream);
 
+/* ---- attentive-probe evaluation of a frozen backbone (dinov2/eval/segmentation/eval_classification.py; csrc/attnpool.hip) ----
+ * The grid of G AttnPoolClassifier heads (one query token, kv = nn.Linear(D, 2D), SDPA with H = D / 64 heads of 64,
+ * nn.Linear(D, C)) on f32 patch tokens X [B, N, D] (row stride ldx), without keys or values: with Wk = kv.weight[:D],
+ * Wv = kv.weight[D:], scale = 1/8, GH = G H and c = g H + h,
+ *     U[c, :] = scale sum_j q_g[64h+j] Wk_g[64h+j, :];   S = X U^T (octic_dense_f32_nt);   P[b, :, c] = softmax_n S[b, :, c];
+ *     Z[b, c, :] = sum_n P[b, n, c] X[b, n, :];          pooled[b, g D + 64h+j] = Wv_g[64h+j, :] . Z[b, c, :] + bv_g[64h+j]
+ * (the key bias adds a constant over n and cancels in the softmax; sum_n P = 1 carries the value bias through).  The linear
+ * layer and the loss are octic_probe_forward / octic_probe_ce on pooled as [B, G D] with col0 = g D.
+ * Arguments of type `const float* const*` / `float* const*` are DEVICE arrays of G pointers, one per classifier; the host
+ * cannot see them, so 16-byte alignment of the pointers in them is the caller's to keep (the array itself is checked).
+ * Limits: D % 64 == 0, 64 <= D <= 16384, 1 <= B <= 65535, 1 <= G <= 1024, N, C >= 1, row strides multiples of 4 and no
+ * shorter than their rows: OCTIC_ESHAPE / OCTIC_EALIGN, OCTIC_ENULL for a missing operand, all before any launch.  Every
+ * token, column and batch tail is handled inside the kernels.
+ * ARITHMETIC CONTRACT.  The products (pool, value, dinput, dweight, dz, dwv and the first pass of dscores) run on
+ * v_mfma_f32_16x16x4_f32: an element is ONE chain from +0 over its reduction index in chunks of 16 ascending, step e of a
+ * chunk adding indices e, 4 + e, 8 + e, 12 + e; then one multiplication by alpha and one addition of the bias where there
+ * is one.  The order depends on the reduction length alone, and everything that belongs to image b reads image b only: a
+ * sample's rows are bitwise independent of its batch mates.  Token reductions of the softmax and its backward: token lanes
+ * y = n mod 4 sequentially, then lanes 0 .. 3.  No floating-point atomics: every result is bitwise repeatable. */
+/* U [rows, D] dense, rows in GH .. GH + 3: rows >= GH are written as zero (the padding octic_dense_f32_nt's N % 4 needs). */
+int octic_attnpool_fold(const float* const* q, const float* const* wk, int G, int D, float* U, int64_t rows, void* stream);
+/* In place on S [B N, lds]: columns < GH become the softmax over the N rows of each image (exp2 domain, maximum subtracted:
+ * finite for finite scores, exactly 1 for N = 1), columns GH .. lds-1 become zero. */
+int octic_attnpool_softmax(float* S, int64_t lds, int64_t B, int N, int GH, void* stream);
+/* Z [B, GH, D] dense from P [B N, ldp] and X [B N, ldx]. */
+int octic_attnpool_pool(const float* P, int64_t ldp, const float* X, int64_t ldx, int64_t B, int N, int D, int GH, float* Z,
+                        void* stream);
+/* pooled [B, ldo >= G D] from Z; wv[g] = Wv_g [D, D] row-major, bv[g] = its bias [D]. */
+int octic_attnpool_value(const float* Z, const float* const* wv, const float* const* bv, int B, int G, int D, float* pooled,
+                         int64_t ldo, void* stream);
+/* The backward of G nn.Linear(K, C) layers whose logit gradients are dlogits [G, B, C] dense (octic_probe_ce's):
+ * dinput:  dF[b, g D + d] = alpha sum_c dlogits[g, b, c] w[g][c, d]                     (w[g] [C, D] row-major);
+ * dweight: dw[g][c, k] = alpha sum_b dlogits[g, b, c] F[b, col0 + g col_stride + k]     (dw[g] [C, K] dense; K any);
+ * colsum:  dst[g][c] = alpha sum_r src[g group_stride + r ld + c], r ascending          (bias gradients). */
+int octic_attnpool_dinput(const float* dlogits, const float* const* w, int G, int B, int C, int D, float alpha, float* dF,
+                          int64_t ldd, void* stream);
+int octic_attnpool_dweight(const float* dlogits, const float* F, int64_t ldf, int64_t col0, int64_t col_stride, int G, int B,
+                           int C, int K, float alpha, float* const* dw, void* stream);
+int octic_attnpool_colsum(const float* src, int64_t group_stride, int64_t ld, int G, int rows, int cols, float alpha,
+                          float* const* dst, void* stream);
+/* dZ[b, c, :] = sum_j dpooled[b, g D + 64h+j] Wv_g[64h+j, :];   dwv[g][64h+j, :] = sum_b dpooled[b, g D + 64h+j] Z[b, c, :]. */
+int octic_attnpool_dz(const float* dpooled, int64_t ldd, const float* const* wv, int B, int G, int D, float* dZ, void* stream);
+int octic_attnpool_dwv(const float* dpooled, int64_t ldd, const float* Z, int B, int G, int D, float* const* dwv, void* stream);
+/* dS [B N, ldp] = P (dP - sum_n P dP) with dP[b, n, c] = X[b, n, :] . dZ[b, c, :]: two launches, dP lives in dS between them
+ * (dS must not be P); columns GH .. ldp-1 of dS become zero.  dU = dS^T X is octic_dense_f32_tn. */
+int octic_attnpool_dscores(const float* X, int64_t ldx, const float* dZ, const float* P, int64_t ldp, int64_t B, int N, int D,
+                           int GH, float* dS, void* stream);
+/* dq[g][64h+j] = scale Wk_g[64h+j, :] . dU[c, :];  dwk[g][64h+j, :] = scale q_g[64h+j] dU[c, :];  dbk[g][:] = 0 exactly (the
+ * key bias cannot change any output).  dU [GH (+ padding), D] dense. */
+int octic_attnpool_unfold(const float* const* q, const float* const* wk, const float* dU, int G, int D, float* const* dq,
+                          float* const* dwk, float* const* dbk, void* stream);
+
 /* ---- linear segmentation evaluation of a frozen backbone (dinov2/eval/segmentation/eval_segmentation.py) --------------
  * Multinomial logistic regression (LogregClassifier, :281-337) on standardised f32 patch features X [N, D] (row stride ldx
  * elements, 16-byte aligned rows) resident in device memory; W is [C, D] row-major, contiguous.  Supported: 2 <= C <= 256,

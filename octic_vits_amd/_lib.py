@@ -217,6 +217,18 @@ _PROTOS = {
     "octic_probe_ce": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
     "octic_probe_sgd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p]),
+    "octic_attnpool_fold": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p]),
+    "octic_attnpool_softmax": (c_int, [c_void_p, c_i64, c_i64, c_int, c_int, c_void_p]),
+    "octic_attnpool_pool": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "octic_attnpool_value": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
+    "octic_attnpool_dinput": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_i64, c_void_p]),
+    "octic_attnpool_dweight": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                       c_void_p]),
+    "octic_attnpool_colsum": (c_int, [c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "octic_attnpool_dz": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "octic_attnpool_dwv": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "octic_attnpool_dscores": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "octic_attnpool_unfold": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "octic_seg_ldd": (c_int, [c_int]),
     "octic_seg_slabs": (c_int, [c_i64, c_int, c_int]),
     "octic_seg_workspace_bytes": (c_i64, [c_i64, c_int, c_int]),

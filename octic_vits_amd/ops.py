@@ -1548,6 +1548,93 @@ def probe_sgd(table, nheads, total_ktiles, F, dlogits, B, C, lr, momentum, sumK)
     KERNEL_TIMER.stop(t, "probe_sgd_kernel", 16 * C * sumK, 2.0 * B * C * sumK)
 
 
+# ------------------------------------------------------------------------------------------ attentive probe (csrc/attnpool.hip)
+# Thin launches: tensors are f32 on the GPU, `*_ptrs` are int64 device tensors of G per-classifier addresses (ptr_table below);
+# the library refuses bad shapes and alignments.  Names ending in _mfma are GEMM-shaped (bench_attnpool bounds them by the f32
+# MFMA rate, the others by HBM).
+def ptr_table(tensors, device):
+    """Device array of the tensors' addresses (int64), the `const float* const*` of the attnpool entry points."""
+    return torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64, device=device)
+
+
+def attnpool_fold(q_ptrs, wk_ptrs, G, D, U):
+    _require_cuda(U)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_fold(_p(q_ptrs), _p(wk_ptrs), G, D, _p(U), U.shape[0], _stream(U)))
+    KERNEL_TIMER.stop(t, "attnpool_fold_kernel", 4 * (G * D * D + G * D + U.numel()))
+
+
+def attnpool_softmax(S, B, N, GH):
+    _require_cuda(S)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_softmax(_p(S), S.stride(0), B, N, GH, _stream(S)))
+    KERNEL_TIMER.stop(t, "attnpool_softmax_kernel", 4 * 4 * S.numel())
+
+
+def attnpool_pool(P, X, ldx, B, N, D, GH, Z):
+    _require_cuda(X)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_pool(_p(P), P.stride(0), _p(X), ldx, B, N, D, GH, _p(Z), _stream(X)))
+    KERNEL_TIMER.stop(t, "attnpool_pool_mfma", 4 * B * (N * GH + N * D + GH * D), 2.0 * B * N * GH * D)
+
+
+def attnpool_value(Z, wv_ptrs, bv_ptrs, B, G, D, pooled):
+    _require_cuda(Z)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_value(_p(Z), _p(wv_ptrs), _p(bv_ptrs), B, G, D, _p(pooled), pooled.stride(0), _stream(Z)))
+    KERNEL_TIMER.stop(t, "attnpool_value_mfma", 4 * (B * G * D * (D // 64 + 1) + G * D * D), 2.0 * B * G * D * D)
+
+
+def attnpool_dinput(dlogits, w_ptrs, G, B, C, D, alpha, dF):
+    _require_cuda(dlogits)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_dinput(_p(dlogits), _p(w_ptrs), G, B, C, D, float(alpha), _p(dF), dF.stride(0), _stream(dF)))
+    KERNEL_TIMER.stop(t, "attnpool_dinput_mfma", 4 * G * (B * C + C * D + B * D), 2.0 * G * B * C * D)
+
+
+def attnpool_dweight(dlogits, F, col0, col_stride, G, B, C, K, alpha, dw_ptrs):
+    _require_cuda(dlogits)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_dweight(_p(dlogits), _p(F), F.stride(0), col0, col_stride, G, B, C, K, float(alpha), _p(dw_ptrs),
+                                       _stream(F)))
+    KERNEL_TIMER.stop(t, "attnpool_dweight_mfma", 4 * G * (B * C + B * K + C * K), 2.0 * G * B * C * K)
+
+
+def attnpool_colsum(src, group_stride, ld, G, rows, cols, alpha, dst_ptrs):
+    _require_cuda(src)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_colsum(_p(src), group_stride, ld, G, rows, cols, float(alpha), _p(dst_ptrs), _stream(src)))
+    KERNEL_TIMER.stop(t, "attnpool_colsum_kernel", 4 * G * cols * (rows + 1))
+
+
+def attnpool_dz(dpooled, wv_ptrs, B, G, D, dZ):
+    _require_cuda(dpooled)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_dz(_p(dpooled), dpooled.stride(0), _p(wv_ptrs), B, G, D, _p(dZ), _stream(dZ)))
+    KERNEL_TIMER.stop(t, "attnpool_dz_mfma", 4 * (B * G * D * (D // 64 + 1) + G * D * D), 2.0 * B * G * D * D)
+
+
+def attnpool_dwv(dpooled, Z, B, G, D, dwv_ptrs):
+    _require_cuda(dpooled)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_dwv(_p(dpooled), dpooled.stride(0), _p(Z), B, G, D, _p(dwv_ptrs), _stream(Z)))
+    KERNEL_TIMER.stop(t, "attnpool_dwv_mfma", 4 * (B * G * D * (D // 64 + 1) + G * D * D), 2.0 * B * G * D * D)
+
+
+def attnpool_dscores(X, ldx, dZ, P, B, N, D, GH, dS):
+    _require_cuda(X)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_dscores(_p(X), ldx, _p(dZ), _p(P), P.stride(0), B, N, D, GH, _p(dS), _stream(X)))
+    KERNEL_TIMER.stop(t, "attnpool_dscores_mfma", 4 * B * (N * D + GH * D + 4 * N * GH), 2.0 * B * N * GH * D)
+
+
+def attnpool_unfold(q_ptrs, wk_ptrs, dU, G, D, dq_ptrs, dwk_ptrs, dbk_ptrs):
+    _require_cuda(dU)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_attnpool_unfold(_p(q_ptrs), _p(wk_ptrs), _p(dU), G, D, _p(dq_ptrs), _p(dwk_ptrs), _p(dbk_ptrs), _stream(dU)))
+    KERNEL_TIMER.stop(t, "attnpool_unfold_kernel", 4 * (2 * G * D * D + G * D * (D // 64) + 3 * G * D))
+
+
 # ------------------------------------------------------------------------------------------ segmentation logreg (csrc/segeval.hip)
 def _seg_rows(X):
     """X as f32 rows: [N, D] with contiguous channels and a 16-byte aligned row stride."""
