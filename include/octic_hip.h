@@ -78,7 +78,9 @@ enum {
   OCTIC_ROUTE_ATTN_LEGACY = 6,     /* octic_attn_*: 1 = the two-kernel online-softmax family for every shape              */
   OCTIC_ROUTE_ATTN_ONLINE = 7,     /* octic_attn_fwd*: 1 = persistent online-softmax forward instead of the one-shot one  */
   OCTIC_ROUTE_ATTN_BWD_PAIR = 8,   /* octic_attn_bwd*: 1 = the dq + dkv kernel pair instead of the single-pass backward   */
-  OCTIC_ROUTE_DENSE_IMAGE = 9,     /* octic_dense_gemm_nt_tokens: 1 = per-image panels wherever legal, 2 = never, 3 = plain only */
+  OCTIC_ROUTE_DENSE_IMAGE = 9,     /* octic_dense_gemm_nt_tokens: 1 = per-image panels wherever legal, 2 = never, 3 = plain only;
+                                      octic_dense_gemm_nt_tokens_image: + 4 = per-image panels wherever it can take the launch,
+                                      + 8 = class-token rows in a launch of their own, + 16 = never (the former call)           */
   OCTIC_ROUTE_DENSE_CLS2 = 10,     /* class-token rows of per-image launches as two launches (K split): 1 = never, 2 = wherever legal */
   OCTIC_ROUTE_ATTN_STREAM = 11,    /* octic_attn_*: 1 = the streaming (K / V through LDS in blocks) kernels for every T too   */
   OCTIC_ROUTE_COUNT = 12
@@ -776,6 +778,37 @@ int octic_dense_gemm_plan_adaptive_cls(int M, int N, int K, int mode, int tokens
 int octic_dense_gemm_order_adaptive_cls(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
                                         int cap, int* out_tm, int* out_tn, int* out_dead, int* out_width, int cls_cap,
                                         int* out_cls_rt, int* out_cls_ct);
+
+/* octic_dense_gemm_nt_tokens_adaptive_cls for a launch under the stochastic-depth mask of a branch that drops each sample with
+ * probability `drop`.  With 257 tokens a classic panel of 256 consecutive rows straddles two images and is dead only when both are
+ * dropped (live share 1 - drop^2); a per-image panel dies with its image (1 - drop).  A masked launch of mode 0 / 5 (mode 4 too
+ * under OCTIC_ROUTE_DENSE_IMAGE + 4; by itself it stays classic, see csrc/dense_gemm.hip kDgImageKeep) that the
+ * former call keeps on classic panels (sample_scale per image: rows_per_sample == tokens == 257, K % 128 == 0, N % 16 == 0) runs
+ * on per-image panels of the 256-wide tile - full tiles only, nothing split along K - where the modelled expected launch is a
+ * tenth shorter (the model: csrc/dense_gemm.hip dense_plan_image).  Its class-token rows are computed by workgroups at the END of
+ * the grid (K at most 16 slices of 320; the arithmetic and bits of dense_cls_kernel: a slice per wave, partial tiles summed in
+ * slice order, the mode's epilogue; mode 5 leaves their column sums in slab rows 2 * images onward), else by the class-token
+ * launch behind the main one.  The grid depends on the problem and `drop` only, never on the mask's values.  Kept rows: the bits
+ * of the unmasked per-image launch with nothing split; rows of a dropped sample: those or +0, tile by tile; every class-token row
+ * is computed.  drop <= 0, sample_scale NULL, or any launch it does not take (the N = 1280 launches among them): exactly
+ * octic_dense_gemm_nt_tokens_adaptive_cls. */
+int octic_dense_gemm_nt_tokens_image(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode,
+                                     void* C, void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs,
+                                     int64_t rows_per_sample_rs, const float* X, float* OUT, const void* H, float* colsum,
+                                     const float* sample_scale, int rows_per_sample, void* workspace, int tokens,
+                                     int fold_cls, double drop, void* stream);
+/* What it does with a launch of this problem (masked != 0: with a sample_scale): out[0] = 1 if it leaves the former call's plan
+ * for per-image panels, out[1] = workgroups of the main launch, out[2] = class-token workgroups among them (the last ones; 0 = a
+ * launch of their own, or not taken), out[3] = class-token items (16 rows x 16 columns) of the busiest of those, out[4] = tile
+ * workgroups in front, out[5] = tile width of the plan in force (256 | 320), out[6] = colsum slab rows of modes 3 / 5 under the
+ * plan in force, out[7] = 1 if the plan in force is per-image panels.  OCTIC_ESHAPE for a bad shape or rows_per_sample. */
+int octic_dense_gemm_plan_image(int M, int N, int K, int mode, int tokens, int rows_per_sample, int masked, double drop, int* out8);
+/* Host query of a taken launch's item map (sample_scale is a HOST array), by the kernel's own functions.  Per workgroup in blockIdx
+ * order: out_tm / out_tn the tile (-1 for a class-token workgroup), out_dead 1 for a dead tile (each nullable, `cap` entries);
+ * out_cls_rt / out_cls_ct as octic_dense_gemm_order_adaptive_cls.  Returns the number of workgroups, or OCTIC_ESHAPE for a launch
+ * not taken or a cap too small. */
+int octic_dense_gemm_order_image(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample, double drop,
+                                 int cap, int* out_tm, int* out_tn, int* out_dead, int cls_cap, int* out_cls_rt, int* out_cls_ct);
 
 /* Weight gradient of an nn.Linear of the standard half (the autograd of deit/vit.py:33,46 and of timm Mlp.fc1 / fc2):
  *     dW[N,K] = dY[M,N]^T . X[M,K]     f32, nn.Linear layout

@@ -19,6 +19,8 @@ ABI_VERSION = 20
 
 # ROUTE_DENSE_TILE, added to the width (0 | 4 | 5): what octic_dense_gemm_nt_tokens_adaptive chooses (0 = by its rule)
 DENSE_ADAPT_WIDE, DENSE_ADAPT_NARROW = 16, 32
+# ROUTE_DENSE_IMAGE, added to its value (0 .. 3): what octic_dense_gemm_nt_tokens_image does (0 = by its model)
+DENSE_IMAGE_ALWAYS, DENSE_IMAGE_CLS_APART, DENSE_IMAGE_NEVER = 4, 8, 16
 
 # kernel ids of octic_attn_plan (include/octic_hip.h)
 (ATTN_FWD_PERSIST, ATTN_FWD_A80_ONESHOT, ATTN_FWD_A80_ONLINE, ATTN_FWD_RESIDENT, ATTN_FWD_STREAM, ATTN_FWD_F32) = range(6)
@@ -190,6 +192,12 @@ _PROTOS = {
     "octic_dense_gemm_plan_adaptive_cls": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "octic_dense_gemm_order_adaptive_cls": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                     c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "octic_dense_gemm_nt_tokens_image": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_i64, c_i64, c_int, c_void_p,
+                                                 c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_void_p]),
+    "octic_dense_gemm_plan_image": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, ctypes.POINTER(c_int)]),
+    "octic_dense_gemm_order_image": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_double, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_int, c_void_p, c_void_p]),
     "octic_dense_colsum": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p]),
     "octic_dense_colsum_skip": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
     "octic_dense_wgrad_workspace_bytes": (c_i64, [c_int, c_int, c_int]),

@@ -1171,7 +1171,11 @@ __host__ __device__ inline int dg_fold_item(int items, int ipp, int wgs, int cw,
   return item < items ? (int)item : -1;
 }
 
-__device__ __forceinline__ void dense_cls_fold_wg(const DgArgs& a, char* lds, int tokens, int nrows, int cw, int wgs) {
+// MODE: DG_PLAIN as above; DG_GELUF / DG_DFACT (dense_nt_image_cls_kernel) end an item with dense_cls_kernel<MODE>'s epilogue, statement
+// for statement, and DG_DFACT leaves its column sums in slab row colsum_row0 + row tile as that kernel does.
+template <int MODE = DG_PLAIN>
+__device__ __forceinline__ void dense_cls_fold_wg(const DgArgs& a, char* lds, int tokens, int nrows, int cw, int wgs, int colsum_row0 = 0) {
+  static_assert(MODE == DG_PLAIN || MODE == DG_GELUF || MODE == DG_DFACT, "class-token epilogues of the folded launches");
   f32x4* const part = (f32x4*)lds;                          // [2 (pass parity)][16 partial tiles][64 lanes]: the head of the ring
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1191,12 +1195,14 @@ __device__ __forceinline__ void dense_cls_fold_wg(const DgArgs& a, char* lds, in
     const int n0 = tn * 16, b0 = tb * 16;
     const bool lead = item >= 0 && ks0 == 0;
     f32x4 bv = {0, 0, 0, 0};
+    bf16x4 hv = {0, 0, 0, 0};
     if (item >= 0) {
       int brow = b0 + fr;
       brow = brow < nrows ? brow : nrows - 1;               // rows past the batch read a valid row and are dropped at the end
       const bf16* wp = a.B + (int64_t)(n0 + fr) * a.ldb + ks0 * CLS_KSLICE + kg * 8;
       const bf16* xp = a.A + (int64_t)brow * tokens * a.lda + ks0 * CLS_KSLICE + kg * 8;
       if (lead && a.bias) bv = *(const f32x4*)(a.bias + n0 + 4 * kg);
+      if (MODE == DG_DFACT && lead && b0 + fr < nrows) hv = *(const bf16x4*)(a.H + (int64_t)(b0 + fr) * tokens * a.ldc + n0 + 4 * kg);
       bf16x8 wf[U], xf[U], wg[U], xg[U];
 #pragma unroll
       for (int j = 0; j < U; ++j) {
@@ -1228,10 +1234,54 @@ __device__ __forceinline__ void dense_cls_fold_wg(const DgArgs& a, char* lds, in
       const f32x4* src = buf + (slot * nks) * 64 + lane;
       f32x4 v = src[0];
       for (int s = 1; s < nks; ++s) v = v + src[s * 64];
-      if (a.bias) v = v + bv;
       // lane (fr, kg) = token row b0 + fr, output columns n0 + 4 kg .. + 3
-      if (b0 + fr < nrows)
-        *(bf16x4*)(a.C + (int64_t)(b0 + fr) * tokens * a.ldc + n0 + 4 * kg) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+      if constexpr (MODE == DG_PLAIN) {
+        if (a.bias) v = v + bv;
+        if (b0 + fr < nrows)
+          *(bf16x4*)(a.C + (int64_t)(b0 + fr) * tokens * a.ldc + n0 + 4 * kg) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+      } else {
+        v = v + bv;
+        const bf16x4 cb = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+        const bool rok = b0 + fr < nrows;
+        const int64_t m = (int64_t)(b0 + fr) * tokens;
+        const int n = n0 + 4 * kg;
+        bf16* cp = a.C + m * a.ldc + n;
+        float cs[4] = {0, 0, 0, 0};
+        if (rok) {
+          if (MODE == DG_GELUF) {
+            bf16x4 y, f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              float gv, dv;
+              dg_gelu_both((float)cb[e], gv, dv);
+              y[e] = (bf16)gv;
+              f[e] = (bf16)dv;
+            }
+            *(bf16x4*)cp = f;
+            *(bf16x4*)(a.C2 + m * a.ldc + n) = y;
+          } else {
+            bf16x4 d;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              d[e] = (bf16)((float)hv[e] * (float)cb[e]);
+              cs[e] = (float)d[e];
+            }
+            *(bf16x4*)cp = d;
+          }
+        }
+        if (MODE == DG_DFACT && a.colsum != nullptr) {      // (wave-uniform: `lead` is)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float t = cs[e];
+            t += __shfl_xor(t, 1, 64);
+            t += __shfl_xor(t, 2, 64);
+            t += __shfl_xor(t, 4, 64);
+            t += __shfl_xor(t, 8, 64);
+            cs[e] = t;
+          }
+          if (fr == 0) *(f32x4*)(a.colsum + (int64_t)(colsum_row0 + tb) * a.N + n) = f32x4{cs[0], cs[1], cs[2], cs[3]};
+        }
+      }
     }
   }
 }
@@ -1264,6 +1314,29 @@ __global__ __launch_bounds__(512, 1) void dense_nt_adaptive_cls_kernel(DgArgs a,
   } else {
     dense_nt_tile<DG_PLAIN, 5, true>(a, lds, tile, 0, nkt_all, 0, -1, dead_item);
   }
+}
+
+// The masked multi-round launch on per-image panels with its class-token rows (octic_dense_gemm_nt_tokens_image): workgroups
+// [0, tile_wgs) are dense_nt_kernel<MODE, 4, true>'s on a plan of full tiles only (dead tiles first, live tiles dealt over the eight
+// chunks), [tile_wgs, tile_wgs + cls_wgs) are class-token workgroups - dispatched last, into the partial last round of the live tiles.
+template <int MODE>
+__global__ __launch_bounds__(512, 1) void dense_nt_image_cls_kernel(DgArgs a, int tokens, int nrows, int tile_wgs, int cls_wgs, int colsum_row0) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];   // the ring + the bitmap; class-token partial tiles
+  dg_trace_start();
+  const int cw = __builtin_amdgcn_readfirstlane(dg_fold_wg(blockIdx.x, tile_wgs));
+  if (cw >= 0) {
+    dense_cls_fold_wg<MODE>(a, lds, tokens, nrows, cw, cls_wgs, colsum_row0);
+    return;
+  }
+  unsigned long long* const live_bm = (unsigned long long*)(lds + DgGeom<4>::LDS);
+  dg_build_bitmap(a, live_bm);
+  int tile, rem_idx, part;
+  bool dead_item;
+  dense_item_masked(a.tiles_m, a.tiles_n, a.full_tiles, 1, 0, blockIdx.x, live_bm, tile, rem_idx, part, dead_item);
+  tile = __builtin_amdgcn_readfirstlane(tile);
+  dead_item = __builtin_amdgcn_readfirstlane((int)dead_item) != 0;
+  if (tile < 0) return;
+  dense_nt_tile<MODE, 4, true>(a, lds, tile, 0, a.K / DG_BK, 0, -1, dead_item);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1387,7 +1460,7 @@ inline DgTokPlan dense_plan_tokens(int M, int N, int K, int cus, int mode, int t
   t.p = dense_plan(M, N, K, cus, mode);
   t.image = false;
   t.images = 0;
-  const int force = route(OCTIC_ROUTE_DENSE_IMAGE);
+  const int force = route(OCTIC_ROUTE_DENSE_IMAGE) & 3;     // (bits 2-4 belong to dense_plan_image)
   if (tokens != 257 || M % tokens != 0 || mode == DG_RESID || (K % 128) != 0 || (N % 16) != 0 || force == 2) return t;
   const int B = M / tokens;
   const DgPlan pi = dense_plan(B * DG_BM, N, K, cus, mode);
@@ -1437,6 +1510,80 @@ inline DgFold dense_plan_fold(const DgAdaptive& ad, int images, int N, int K) {
   f.per_wg = (passes + f.wgs - 1) / f.wgs * dg_fold_ipp(K / CLS_KSLICE);
   f.grid = f.tile_wgs + f.wgs;
   return f;
+}
+
+// Per-image panels for a MASKED launch that dense_plan_tokens keeps on classic panels (octic_dense_gemm_nt_tokens_image).  With 257
+// tokens a classic panel of 256 consecutive rows straddles two images and dies only when both are dropped, a per-image panel dies
+// with its own image: at drop probability p the live shares are 1 - p^2 against 1 - p.  The host knows p, not the mask, so it compares
+// EXPECTED launch lengths in the unit of dense_plan_nt's cost (one K-tile of the 256-wide tile): list scheduling of
+// tiles x (live x (K / 64 + 3) + (1 - live) x 1) over `cus` slots, never shorter than one live tile;
+//   classic:   live = mean over the panels of 1 - p^(samples the panel touches), on the plan in force today;
+//   per-image: live = 1 - p on images x ceil(N / 256) full tiles of the 256-wide tile, nothing split (an unsplit partial last round
+//              is where the class-token workgroups land), plus the class-token rows: folded, passes x DG_FOLD_PASS units of work on
+//              the same slots; in a launch of their own, dense_cls_cost.
+// The model has no rounds and no L2 in it and the unmasked pair measured level (see dense_plan_tokens), so per-image panels are
+// taken only where it promises a tenth: at ViT-H / B = 64 that is p >= 0.2 for fc1, and at p = 0.5 65 against 88 units.
+// Legal for modes 0 / 4 / 5 only (the class-token epilogues of the folded launch), with the mask given per image.
+// OCTIC_ROUTE_DENSE_IMAGE bits: + 4 = always where legal, + 8 = the class-token rows in a launch of their own, + 16 = never.
+// kDgImageKeep[m]: 1 = the model may move mode m (the per-launch keep rule, decided in the step - NOTES.md "Masked wide dense GEMMs"):
+// qkv (0) and the fc2 input gradient (5) are kept.  fc1 + factor (4) measured 38 us per launch shorter too, but with it the state the
+// headline step leaves moved further from the parent's than the accepted distance (first moments: 4.3e-6 against 2 x 1.05e-6, the
+// distance the N = 1280 launches' own layout knob gives), so it stays on classic panels; + 4 still forces it (tests, A/B).
+#define DG_FOLD_PASS 2.0     // one pass of a class-token workgroup: a memory round trip + 10 - 20 MFMAs per wave, ~3 us
+constexpr int kDgImageKeep[7] = {1, 0, 0, 0, 0, 1, 0};
+__host__ inline bool dg_image_mode(int mode) { return mode == DG_PLAIN || mode == DG_GELUF || mode == DG_DFACT; }
+struct DgImage { bool taken, fold; DgPlan p; int images, tile_wgs, wgs, per_wg, grid; double cost_classic, cost_image; };
+inline double dense_masked_cost(double tiles, int nkt, double wf, double live, int cus) {
+  const double tile_cost = nkt * wf + 3.0, load = tiles * (live * tile_cost + (1.0 - live)) / cus;
+  const double floor = live > 0.0 ? tile_cost : 1.0;
+  return load > floor ? load : floor;
+}
+inline DgImage dense_plan_image(const DgTokPlan& tp, int M, int N, int K, int cus, int mode, int tokens, bool masked,
+                                int rows_per_sample, double drop) {
+  DgImage d = {};
+  d.p = tp.p;
+  d.grid = tp.p.grid;
+  const int r = route(OCTIC_ROUTE_DENSE_IMAGE);
+  if (!masked || !(drop > 0.0) || tp.image || (r & 16) || (r & 3) == 2) return d;
+  if (!dg_image_mode(mode)) return d;
+  if (tokens != 257 || M % tokens != 0 || rows_per_sample != tokens || (K % 128) != 0 || (N % 16) != 0) return d;
+  const int B = M / tokens;
+  if (B > kDgMaskCap) return d;
+  const double p = drop < 1.0 ? drop : 1.0;
+  const int nkt = K / DG_BK;
+  // classic: the samples each panel of the plan in force touches
+  double live_c = 0.0;
+  for (int tm = 0; tm < tp.p.tiles_m; ++tm) {
+    const int m0 = tm * DG_BM, m1 = (m0 + DG_BM < M ? m0 + DG_BM : M) - 1;
+    live_c += 1.0 - pow(p, (double)(m1 / tokens - m0 / tokens + 1));
+  }
+  live_c /= tp.p.tiles_m;
+  d.cost_classic = dense_masked_cost((double)tp.p.tiles_m * tp.p.tiles_n, nkt, tp.p.nt / 4.0, live_c, cus);
+  DgPlan pi = {};
+  pi.nt = 4;
+  pi.tiles_m = B;
+  pi.tiles_n = (N + 255) / 256;
+  pi.full = pi.tiles_m * pi.tiles_n;
+  pi.split = 1;
+  pi.grid = pi.full;
+  const bool fold = !(r & 8) && dg_fold_k(K);
+  const int passes = fold ? dg_fold_passes(N, K, B) : 0;
+  d.cost_image = dense_masked_cost((double)pi.full, nkt, 1.0, 1.0 - p, cus) +
+                 (fold ? passes * DG_FOLD_PASS * (K > 8 * CLS_KSLICE ? 1.5 : 1.0) / cus : dense_cls_cost(B, N, K, mode));
+  pi.cost = d.cost_image;
+  if (!(r & 4) && !(kDgImageKeep[mode] && d.cost_image * 1.1 < d.cost_classic)) return d;
+  d.taken = true;
+  d.fold = fold;
+  d.p = pi;
+  d.images = B;
+  d.tile_wgs = pi.grid;
+  if (fold) {
+    const int cap = cus / 2 > 1 ? cus / 2 : 1;               // half a round: what the partial last round of the live tiles leaves on average
+    d.wgs = passes < cap ? passes : cap;
+    d.per_wg = (passes + d.wgs - 1) / d.wgs * dg_fold_ipp(K / CLS_KSLICE);
+  }
+  d.grid = d.tile_wgs + d.wgs;
+  return d;
 }
 
 }  // namespace octic
@@ -1505,7 +1652,8 @@ int octic_dense_gemm_colsum_rows(int M, int N, int K) {
 static int dense_launch(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
                         void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
                         const float* X, float* OUT, const void* H, float* colsum, const float* sample_scale,
-                        int rows_per_sample, void* workspace, int tokens, void* stream, bool adaptive, bool fold_cls = false) {
+                        int rows_per_sample, void* workspace, int tokens, void* stream, bool adaptive, bool fold_cls = false,
+                        double image_drop = 0.0) {
   if (!A || !B || !C) return OCTIC_ENULL;
   if (sample_scale && (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0)) return OCTIC_ESHAPE;
   if (sample_scale && (((uintptr_t)sample_scale) & 3)) return OCTIC_EALIGN;
@@ -1522,7 +1670,15 @@ static int dense_launch(const void* A, const void* B, int M, int N, int K, int64
   a.A = (const bf16*)A; a.B = (const bf16*)B; a.lda = lda; a.ldb = ldb; a.M = M; a.N = N; a.K = K;
   a.C = (bf16*)C; a.C2 = (bf16*)C2; a.ldc = ldc; a.bias = bias; a.gamma = gamma; a.rs = rs; a.rps = rs ? rps : 1;
   a.X = X; a.OUT = OUT; a.H = (const bf16*)H; a.colsum = (mode == DG_DGELU || mode == DG_DFACT) ? colsum : nullptr;
-  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
+  DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
+  // image_drop > 0 (octic_dense_gemm_nt_tokens_image): a masked launch may leave classic panels for per-image ones
+  const DgImage img = dense_plan_image(tp, M, N, K, dense_cus(), mode, tokens, sample_scale != nullptr && mode != DG_RESID && image_drop > 0.0,
+                                       rows_per_sample, image_drop);
+  if (img.taken) {
+    tp.p = img.p;
+    tp.image = true;
+    tp.images = img.images;
+  }
   const DgPlan p = tp.p;
   a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.full_tiles = p.full; a.split = p.split; a.tail_pad = p.tail_pad;
   a.m_stride = tp.image ? tokens : DG_BM;
@@ -1558,7 +1714,21 @@ static int dense_launch(const void* A, const void* B, int M, int N, int K, int64
     (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUO, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
     (void)hipFuncSetAttribute((const void*)dense_nt_adaptive_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem5 + bmb);
     (void)hipFuncSetAttribute((const void*)dense_nt_adaptive_cls_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem5 + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_image_cls_kernel<DG_PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_image_cls_kernel<DG_GELUF>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
+    (void)hipFuncSetAttribute((const void*)dense_nt_image_cls_kernel<DG_DFACT>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
     (void)hipGetLastError();
+  }
+  if (img.taken && img.fold) {
+    // the masked launch on per-image panels with the class-token workgroups behind its tiles: ONE launch, no dense_cls_* launch
+    const int cr0 = 2 * img.images;
+    switch (mode) {
+      case DG_PLAIN: dense_nt_image_cls_kernel<DG_PLAIN><<<img.grid, 512, smem + bmb, s>>>(a, tokens, img.images, img.tile_wgs, img.wgs, cr0); break;
+      case DG_GELUF: dense_nt_image_cls_kernel<DG_GELUF><<<img.grid, 512, smem + bmb, s>>>(a, tokens, img.images, img.tile_wgs, img.wgs, cr0); break;
+      case DG_DFACT: dense_nt_image_cls_kernel<DG_DFACT><<<img.grid, 512, smem + bmb, s>>>(a, tokens, img.images, img.tile_wgs, img.wgs, cr0); break;
+      default: return OCTIC_ESHAPE;
+    }
+    return launch_status();
   }
   const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), skip);
   const DgFold fold = dense_plan_fold(ad, tp.images, N, K);
@@ -1806,6 +1976,79 @@ int octic_dense_gemm_order_adaptive_cls(int M, int N, int K, int mode, int token
   }
   if (out_width) *out_width = narrow ? 256 : 320;
   return f.grid;
+}
+
+// octic_dense_gemm_nt_tokens_adaptive_cls for a launch under the mask of a branch that drops a sample with probability `drop`:
+// a launch that call keeps on classic panels may run on per-image panels with its class-token rows folded (dense_plan_image,
+// dense_nt_image_cls_kernel); drop <= 0, no mask, or any launch dense_plan_image does not take: exactly that call
+int octic_dense_gemm_nt_tokens_image(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode,
+                                     void* C, void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs,
+                                     int64_t rps, const float* X, float* OUT, const void* H, float* colsum,
+                                     const float* sample_scale, int rows_per_sample, void* workspace, int tokens,
+                                     int fold_cls, double drop, void* stream) {
+  return dense_launch(A, B, M, N, K, lda, ldb, mode, C, C2, ldc, bias, gamma, rs, rps, X, OUT, H, colsum, sample_scale,
+                      rows_per_sample, workspace, tokens, stream, true, fold_cls != 0, drop > 0.0 ? drop : 0.0);
+}
+
+// What octic_dense_gemm_nt_tokens_image does with a launch of this problem (masked != 0: a sample_scale is given): out[0] = 1 if it
+// leaves the former call's plan for per-image panels, out[1] = workgroups of the main launch, out[2] = class-token workgroups among
+// them (the last ones; 0 = the class-token rows have a launch of their own, or the plan is the former call's), out[3] = class-token
+// items of the busiest of those, out[4] = tile workgroups in front, out[5] = tile width of the plan in force (256 | 320), out[6] =
+// colsum slab rows of modes 3 / 5 under the plan in force, out[7] = 1 if the plan in force is per-image panels (either call's).
+int octic_dense_gemm_plan_image(int M, int N, int K, int mode, int tokens, int rows_per_sample, int masked, double drop, int* out) {
+  if (!out) return OCTIC_ENULL;
+  if (M <= 0 || N <= 0 || K < 2 * DG_BK) return OCTIC_ESHAPE;
+  if (masked && (rows_per_sample <= 0 || (M % rows_per_sample) != 0)) return OCTIC_ESHAPE;
+  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
+  const DgImage d = dense_plan_image(tp, M, N, K, dense_cus(), mode, tokens, masked != 0 && mode != DG_RESID && drop > 0.0, rows_per_sample, drop);
+  const bool image = d.taken || tp.image;
+  const int images = d.taken ? d.images : tp.images;
+  out[0] = d.taken ? 1 : 0;
+  out[1] = d.grid;
+  out[2] = d.wgs;
+  out[3] = d.per_wg;
+  out[4] = d.taken ? d.tile_wgs : tp.p.grid;
+  out[5] = d.p.nt == 5 ? 320 : 256;
+  out[6] = image ? 2 * images + (images + 15) / 16 : 2 * ((M + DG_BM - 1) / DG_BM);
+  out[7] = image ? 1 : 0;
+  return OCTIC_OK;
+}
+
+// What a launch that octic_dense_gemm_plan_image reports taken gives each workgroup, in blockIdx order, by the kernel's own functions
+// (dg_fold_wg, dense_item_masked, dg_fold_item): sample_scale is a HOST array.  out_tm / out_tn / out_dead: one entry per workgroup
+// (`cap` entries; -1 / -1 / 0 for a class-token workgroup); out_cls_rt / out_cls_ct: as octic_dense_gemm_order_adaptive_cls.  Returns
+// the number of workgroups; OCTIC_ESHAPE for a launch not taken or a cap too small.
+int octic_dense_gemm_order_image(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample, double drop,
+                                 int cap, int* out_tm, int* out_tn, int* out_dead, int cls_cap, int* out_cls_rt, int* out_cls_ct) {
+  if (!sample_scale) return OCTIC_ENULL;
+  if (M <= 0 || N <= 0 || K < 2 * DG_BK || rows_per_sample <= 0 || (M % rows_per_sample) != 0) return OCTIC_ESHAPE;
+  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
+  const DgImage d = dense_plan_image(tp, M, N, K, dense_cus(), mode, tokens, mode != DG_RESID && drop > 0.0, rows_per_sample, drop);
+  if (!d.taken || cap < d.grid || ((out_cls_rt || out_cls_ct) && cls_cap < d.wgs * d.per_wg)) return OCTIC_ESHAPE;
+  const DgPlan& p = d.p;
+  unsigned long long bm[kDgMaskWords] = {};
+  for (int tm = 0; tm < p.tiles_m; ++tm)
+    if (dg_panel_live(sample_scale, rows_per_sample, M, tokens, 1, tm)) bm[tm >> 6] |= 1ull << (tm & 63);
+  const int nks = K / CLS_KSLICE, ipp = d.wgs > 0 ? dg_fold_ipp(nks) : 1, ntn = N >> 4, items = dg_fold_items(N, d.images);
+  for (int bid = 0; bid < d.grid; ++bid) {
+    int tile = -1, tm = -1, tn = -1, rem_idx, part;
+    bool dead = false;
+    const int cw = dg_fold_wg(bid, d.tile_wgs);
+    if (cw < 0) {
+      dense_item_masked(p.tiles_m, p.tiles_n, p.full, 1, 0, bid, bm, tile, rem_idx, part, dead);
+      if (tile >= 0) dg_tile_panel(p.tiles_m, p.tiles_n, tile, tm, tn);
+    } else {
+      for (int e = 0; e < d.per_wg; ++e) {
+        const int item = dg_fold_item(items, ipp, d.wgs, cw, e / ipp, e % ipp);
+        if (out_cls_rt) out_cls_rt[cw * d.per_wg + e] = item >= 0 ? item / ntn : -1;
+        if (out_cls_ct) out_cls_ct[cw * d.per_wg + e] = item >= 0 ? item % ntn : -1;
+      }
+    }
+    if (out_tm) out_tm[bid] = tm;
+    if (out_tn) out_tn[bid] = tn;
+    if (out_dead) out_dead[bid] = dead ? 1 : 0;
+  }
+  return d.grid;
 }
 
 int octic_dense_gemm_nt(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,

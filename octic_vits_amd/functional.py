@@ -538,6 +538,16 @@ def dense_cls_fold(drop_prob):
     return bool(DENSE_CLS_FOLD and DENSE_NARROW_DROPPED and drop_prob is not None and float(drop_prob) >= DENSE_CLS_FOLD_MIN_DROP)
 
 
+# The three multi-round launches of a block (qkv, fc1 + factor, fc2's input gradient) run on classic panels of 256 consecutive
+# rows, which straddle two 257-token images and die only when both are dropped.  With DENSE_IMAGE_DROPPED a launch whose caller
+# knows the branch's drop probability asks the library whether per-image panels - dead with their own image, class-token rows
+# computed at the end of the same launch - are expected to be shorter (include/octic_hip.h: octic_dense_gemm_nt_tokens_image).
+# Kept rows have the bits of the unmasked per-image launch.  The library moves qkv and fc2's input gradient; fc1 stays classic by
+# its keep table (NOTES.md "Masked wide dense GEMMs").  Effective only while DENSE_NT_SKIP_DROPPED is on.  Read once at
+# import from OCTIC_DENSE_IMAGE_SKIP (0 = off: the calls are exactly the former ones).
+DENSE_IMAGE_DROPPED = _skip_from_env("OCTIC_DENSE_IMAGE_SKIP")
+
+
 def dense_skip_scale(rs, rps, M, rows_to=None):
     """rs as the sample_scale of a dense_nt_kernel launch over M token rows: whole_sample_mask while the switch is on."""
     return whole_sample_mask(rs, rps, M, rows_to) if DENSE_NT_SKIP_DROPPED else None
@@ -1202,7 +1212,7 @@ def _gemm_fwd(tag, x2, wb, b, cache, name, tokens, ss=None, rps=0, drop=None):
     for the hand-written kernel only; drop: the probability it was drawn with (dense_cls_fold)."""
     if tag in DENSE_HIP:
         return ops.dense_gemm_nt(x2, wb, 0, bias=_f32(b), name=f"dense_nt_kernel<{name}>", tokens=tokens, sample_scale=ss,
-                                 rows_per_sample=rps, fold_cls=ss is not None and dense_cls_fold(drop))
+                                 rows_per_sample=rps, fold_cls=ss is not None and dense_cls_fold(drop), drop=drop)
     return _linear_lib(x2, wb, None if b is None else cache.b)
 
 
@@ -1417,7 +1427,7 @@ class DenseMlpFn(torch.autograd.Function):
             h = a
         elif "fc1" in DENSE_HIP:
             h, a = ops.dense_gemm_nt(y2, w1b, 4 if factor else 1, bias=_f32(b1), name="dense_nt_kernel<gelu>",
-                                     tokens=_tok(y.shape), sample_scale=ds, rows_per_sample=rps)
+                                     tokens=_tok(y.shape), sample_scale=ds, rows_per_sample=rps, drop=drop)
         else:
             h = _linear_lib(y2, w1b, None if b1 is None else c1.b)
             a = torch.nn.functional.gelu(h)
@@ -1440,10 +1450,10 @@ class DenseMlpFn(torch.autograd.Function):
             md = 5 if ctx.factor else 3
             if has_b1:                                                                  # gelu'(h) * (gbr W2), + db1
                 dh, db1 = ops.dense_gemm_nt(gbr, w2t, md, h=h, name="dense_nt_kernel<dgelu>", want_colsum=True,
-                                            tokens=_tok(y_shape), sample_scale=ds, rows_per_sample=rps)
+                                            tokens=_tok(y_shape), sample_scale=ds, rows_per_sample=rps, drop=ctx.drop)
             else:
                 dh, db1 = ops.dense_gemm_nt(gbr, w2t, md, h=h, name="dense_nt_kernel<dgelu>", tokens=_tok(y_shape),
-                                            sample_scale=ds, rows_per_sample=rps), None
+                                            sample_scale=ds, rows_per_sample=rps, drop=ctx.drop), None
         else:
             dh, db1 = ops.dense_gelu_bwd(h, _mm_lib(gbr, w2b), want_colsum=has_b1)
         ss = mask if WGRAD_SKIP_DROPPED else None                         # gbr = rs * gamma * gout, dh = gelu' * (gbr W2)

@@ -1344,8 +1344,30 @@ def _dense_cls_fold():
     return functional.DENSE_NARROW_DROPPED and functional.DENSE_CLS_FOLD
 
 
+_DG_IMAGE_PLANS = {}
+_lib.on_route_override(_DG_IMAGE_PLANS.clear)
+
+
+def dense_plan_image(M, N, K, mode, tokens, rows_per_sample, drop, masked=True):
+    """(leaves the former call's plan for per-image panels?, workgroups of the main launch, class-token workgroups at its end,
+    class-token items of the busiest one, tile workgroups in front, tile width, colsum slab rows, per-image panels in force?) of
+    an octic_dense_gemm_nt_tokens_image launch under the mask of a branch with drop probability `drop`."""
+    key = (M, N, K, mode, int(tokens), int(rows_per_sample), bool(masked), float(drop or 0.0))
+    ans = _DG_IMAGE_PLANS.get(key)
+    if ans is None:
+        out = (ctypes.c_int * 8)()
+        check(lib().octic_dense_gemm_plan_image(M, N, K, mode, key[4], key[5], int(key[6]), key[7], out))
+        ans = _DG_IMAGE_PLANS[key] = (bool(out[0]), out[1], out[2], out[3], out[4], out[5], out[6], bool(out[7]))
+    return ans
+
+
+def _dense_image():
+    from . import functional          # (functional imports this module)
+    return functional.DENSE_NT_SKIP_DROPPED and functional.DENSE_IMAGE_DROPPED
+
+
 def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h=None, name=None, want_colsum=False,
-                  tokens=0, sample_scale=None, rows_per_sample=0, fold_cls=False):
+                  tokens=0, sample_scale=None, rows_per_sample=0, fold_cls=False, drop=None):
     """C[M,N] = a[M,K] @ b[N,K]^T on the hand-written MFMA kernel (csrc/dense_gemm.hip) with a fused tail:
     mode 0 -> c ; 1 -> (c, gelu(c)) ; 2 -> (c, x + rs*gamma*c) ; 3 -> gelu'(h) * c (want_colsum: also the f32 column
     sums of that result) ; 4 -> (gelu'(c), gelu(c)) ; 5 -> h * c with h = the factor of mode 4 (want_colsum as 3) ;
@@ -1356,7 +1378,9 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
     the device, 0 = every reader of that sample's output rows accepts the computed result or +0 (never with mode 2); a
     malformed mask is a ValueError.
     fold_cls: the caller expects the mask to drop enough samples for the class-token rows to ride in the main launch
-    (functional.dense_cls_fold; octic_dense_gemm_nt_tokens_adaptive_cls decides which launches can) - same bits either way."""
+    (functional.dense_cls_fold; octic_dense_gemm_nt_tokens_adaptive_cls decides which launches can) - same bits either way.
+    drop: the probability the mask was drawn with, where the caller knows it: a masked launch may then leave classic row panels
+    for per-image ones (functional.DENSE_IMAGE_DROPPED; octic_dense_gemm_nt_tokens_image decides which launches do)."""
     _require_cuda(a)
     M, K = a.shape
     N = b.shape[0]
@@ -1372,12 +1396,21 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
     ss, srps = _sample_scale(sample_scale, rows_per_sample, M, a, "dense_gemm_nt")
     # the plan in force, with a mask or without: colsum rows, the timer name and (through the library's own sizing) the
     # workspace belong to it
-    cs_rows = dense_plan(M, N, K, mode, tokens)[1] if (mode in (3, 5) and want_colsum) else 0
+    image = (dense_plan_image(M, N, K, mode, tokens, srps, drop)
+             if (ss is not None and drop is not None and float(drop) > 0.0 and _dense_image()) else None)
+    if image is not None and not image[0]:
+        image = None                                          # not taken: the former call, the former plan
+    width, slab_rows = (image[5], image[6]) if image is not None else dense_plan(M, N, K, mode, tokens)[:2]
+    cs_rows = slab_rows if (mode in (3, 5) and want_colsum) else 0
     cs = torch.empty((cs_rows, N), dtype=torch.float32, device=a.device) if cs_rows else None
     # a masked launch may choose its tile width on the device (functional.DENSE_NARROW_DROPPED; the library decides which launches)
     entry = lib().octic_dense_gemm_nt_tokens_adaptive if (ss is not None and _dense_narrow()) else lib().octic_dense_gemm_nt_tokens_skip
     t = KERNEL_TIMER.start()
-    if fold_cls and ss is not None and _dense_cls_fold():
+    if image is not None:
+        check(lib().octic_dense_gemm_nt_tokens_image(
+            _p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias), _p(gamma), _p(rs), int(rps),
+            _p(x), _p(out), _p(h), _p(cs), _p(ss), srps, _p(ws), tokens, 0, float(drop), _stream(a)))
+    elif fold_cls and ss is not None and _dense_cls_fold():
         check(lib().octic_dense_gemm_nt_tokens_adaptive_cls(
             _p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias), _p(gamma), _p(rs), int(rps),
             _p(x), _p(out), _p(h), _p(cs), _p(ss), srps, _p(ws), tokens, 1, _stream(a)))
@@ -1388,7 +1421,7 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
         nb = 2 * (M * K + N * K + M * N * (2 if mode in (1, 3, 4, 5) else 1)) + (8 * M * N if mode == 2 else 0)
         # "@320": the launch ran the 256 x 320 tile (kernel symbol dense_nt_kernel<0, 5>), else <mode, 4>
         # (with per-image panels the timed interval also holds the class-token launch behind the panels')
-        wide = "@320" if dense_plan(M, N, K, mode, tokens)[0] == 320 else ""
+        wide = "@320" if width == 320 else ""
         KERNEL_TIMER.stop(t, (name or f"dense_nt_kernel<{mode}>") + wide, nb, 2.0 * M * N * K)
     if mode in (1, 4):
         return c, c2
