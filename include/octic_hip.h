@@ -148,6 +148,18 @@ int octic_layernorm_d8_bwd_cast_skip(const octic_view* g, const octic_view* x, c
                                      const float* const alpha[5], const octic_view* dres, const octic_view* dx,
                                      float* partials, int64_t M, int c, const float* rs, int64_t rows_per_scale, void* gcast,
                                      const float* sample_scale, int64_t rows_per_sample, void* stream);
+/* octic_layernorm_d8_bwd_cast_inplace: octic_layernorm_d8_bwd_cast_skip where dres and dx are ONE buffer (`dx`: on entry the
+ * residual cotangent, on return the stream cotangent).  sample_scale is required (NULL: OCTIC_ENULL), packed rows, c = 32 ...
+ * 160 in steps of 32 (else OCTIC_ESHAPE).  Which rows of `dx` are touched:
+ *   sample_scale != 0 (live row):            read, then written with LN'(g) + dres by the lane that read each address;
+ *   sample_scale == 0, rs != 0 (or rs NULL): read only (dx = dres is what the buffer holds; gcast = bf16(rs * dres));
+ *   sample_scale == 0, rs == 0:              neither read nor written; gcast is an exact zero row.
+ * The promise of sample_scale is that of the _skip calls.  gcast is written for every row; partials, slabs and the order of
+ * every sum are those of octic_layernorm_d8_bwd_cast_skip, and so is every value, up to the sign of an exact zero.       */
+int octic_layernorm_d8_bwd_cast_inplace(const octic_view* g, const octic_view* x, const float* stats,
+                                        const float* const alpha[5], const octic_view* dx, float* partials, int64_t M, int c,
+                                        const float* rs, int64_t rows_per_scale, void* gcast, const float* sample_scale,
+                                        int64_t rows_per_sample, void* stream);
 int octic_layernorm_d8_bwd_finish(const float* partials, int nblk, int c, float* const dalpha[5], float* dbeta,
                                   void* stream);
 /* njobs of the reductions above in ceil(njobs / 48) launches, bit-identical to njobs calls (see octic_dense_finish_batch). */
@@ -547,6 +559,12 @@ int octic_dense_blocks(int64_t rows);
 int octic_dense_resid_layernorm_fwd(const float* x, const void* yb, int yb_dtype, const float* gamma, const float* rs,
                                     int64_t rows_per_scale, float* xout, void* y, int y_dtype, const float* w,
                                     const float* b, float* stats, int64_t rows, int d, float eps, void* stream);
+/* octic_dense_resid_layernorm_fwd_skip: the same call (rs required: NULL is OCTIC_ENULL) that leaves the rows of yb unread
+ * where rs[row / rows_per_scale] == 0: zeros stand in, xout = x + 0.  xout, y and stats are written for every row.  With yb
+ * finite every output equals the plain call, up to the sign of an exact zero.                                          */
+int octic_dense_resid_layernorm_fwd_skip(const float* x, const void* yb, int yb_dtype, const float* gamma, const float* rs,
+                                         int64_t rows_per_scale, float* xout, void* y, int y_dtype, const float* w,
+                                         const float* b, float* stats, int64_t rows, int d, float eps, void* stream);
 int octic_dense_layernorm_fwd(const float* x, void* y, int y_dtype, const float* w, const float* b, float* stats,
                               int64_t rows, int d, float eps, void* stream);
 int octic_dense_layernorm_bwd(const void* gy, int g_dtype, const float* x, const float* w, const float* stats,
@@ -584,6 +602,18 @@ int octic_dense_layernorm_bwd_tail_skip(const void* gy, const float* x, const fl
                                         const float* dres, float* dx, float* partials, const void* yb, const float* gamma,
                                         const float* rs, int64_t rows_per_scale, void* gyb, float* partials2, int64_t rows,
                                         int d, const float* sample_scale, int64_t rows_per_sample, void* stream);
+/* octic_dense_layernorm_bwd_tail_inplace: octic_dense_layernorm_bwd_tail_skip where dres and dx are ONE buffer (`dx`: on
+ * entry the residual cotangent, on return the stream cotangent).  sample_scale is required (NULL: OCTIC_ENULL).  Which rows
+ * of `dx` are touched:
+ *   sample_scale != 0 (live row):            read, then written with LN'(gy) + dres by the lane that read each address;
+ *   sample_scale == 0, rs != 0 (or rs NULL): read only (dx = dres is what the buffer holds; gyb = rs * gamma * dres);
+ *   sample_scale == 0, rs == 0:              neither read nor written; gyb is an exact zero row, yb stays unread.
+ * The promise of sample_scale is that of the _skip call.  gyb is written for every row; slabs and the order of every sum
+ * are those of octic_dense_layernorm_bwd_tail_skip, and so is every value, up to the sign of an exact zero.             */
+int octic_dense_layernorm_bwd_tail_inplace(const void* gy, const float* x, const float* w, const float* stats, float* dx,
+                                           float* partials, const void* yb, const float* gamma, const float* rs,
+                                           int64_t rows_per_scale, void* gyb, float* partials2, int64_t rows, int d,
+                                           const float* sample_scale, int64_t rows_per_sample, void* stream);
 /* octic_dense_gelu_bwd: dh = gelu'(h) * g (exact erf GELU, bf16 [rows, d], d % 8 == 0) and, when partials != NULL,
  * octic_dense_gelu_blocks() slabs [d] of column sums of dh (bias gradient of the projection that produced h;
  * reduce with octic_dense_finish(partials, blocks, d/2, out, out + d/2, NULL)).  Replaces GeluBackward + the

@@ -60,6 +60,8 @@ _PROTOS = {
                                             c_void_p]),
     "octic_layernorm_d8_bwd_cast_skip": (c_int, [VP, VP, c_void_p, c_void_p, VP, VP, c_void_p, c_i64, c_int, c_void_p, c_i64,
                                                  c_void_p, c_void_p, c_i64, c_void_p]),
+    "octic_layernorm_d8_bwd_cast_inplace": (c_int, [VP, VP, c_void_p, c_void_p, VP, c_void_p, c_i64, c_int, c_void_p, c_i64,
+                                                    c_void_p, c_void_p, c_i64, c_void_p]),
     "octic_layernorm_d8_bwd_finish": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "octic_layernorm_d8_bwd_finish_batch": (c_int, [c_void_p, c_int, c_void_p]),
     "octic_sample_blocks": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p]),
@@ -97,11 +99,15 @@ _PROTOS = {
                                           c_float, c_void_p]),
     "octic_dense_resid_layernorm_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_int,
                                                 c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, c_void_p]),
+    "octic_dense_resid_layernorm_fwd_skip": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
+                                                     c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, c_void_p]),
     "octic_dense_layernorm_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_i64, c_int, c_void_p]),
     "octic_dense_layernorm_bwd_tail": (c_int, [c_void_p] * 10 + [c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p]),
     "octic_dense_layernorm_bwd_tail_skip": (c_int, [c_void_p] * 10 + [c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64,
                                                                       c_void_p]),
+    "octic_dense_layernorm_bwd_tail_inplace": (c_int, [c_void_p] * 9 + [c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64,
+                                                                        c_void_p]),
     "octic_dense_finish": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "octic_dense_finish_batch": (c_int, [c_void_p, c_int, c_void_p]),
     "octic_dense_gelu_blocks": (c_int, []),

@@ -93,7 +93,9 @@ __global__ __launch_bounds__(256) void dense_ln_fwd_kernel(const float* __restri
 // Block tail + the LayerNorm that follows it, one row pass: xout = x + rs[row / rps] * gamma * yb (the residual stream after
 // the branch: same expression as scale_residual_fwd_kernel), y = LayerNorm(xout).  The stream is written once and not read
 // back (the two separate kernels move 210 + 126 MB per launch at ViT-H, this one 252).
-template <typename TY, typename TOUT, int NV>
+// SKIPY (rs given): a row whose factor is 0 leaves yb unread - zeros stand in and the arithmetic runs on them unchanged
+// (xout = x + 0 * gamma * 0).  The branch is per row and wave-uniform; xout, y and stats are written for every row.
+template <typename TY, typename TOUT, int NV, bool SKIPY = false>
 __global__ __launch_bounds__(256) void dense_resid_ln_fwd_kernel(const float* __restrict__ x, const TY* __restrict__ yb,
                                                                  const float* __restrict__ gamma, const float* __restrict__ rs,
                                                                  long rps, float* __restrict__ xout, TOUT* __restrict__ y,
@@ -119,12 +121,19 @@ __global__ __launch_bounds__(256) void dense_resid_ln_fwd_kernel(const float* __
     f32x4 xv[NV];
     float s = 0.f;
     const float rsv = rs ? rs[r / rps] : 1.f;
+    bool tail = true;
+    if constexpr (SKIPY) tail = mask_live(rsv);
     if (NV <= 6 && d == NV * 256) {   // every lane has all chunks: the 2 NV loads of the row go out before the first use
       typename Row4<TY>::vec yv[NV];
 #pragma unroll
       for (int i = 0; i < NV; ++i) xv[i] = *(const f32x4*)(xr + (i * 64 + lane) * 4);
+      if (tail) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) yv[i] = Row4<TY>::load_raw(yr_in + (i * 64 + lane) * 4);
+        for (int i = 0; i < NV; ++i) yv[i] = Row4<TY>::load_raw(yr_in + (i * 64 + lane) * 4);
+      } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) yv[i] = typename Row4<TY>::vec{};
+      }
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         f32x4 sc = gm[i];
@@ -141,7 +150,13 @@ __global__ __launch_bounds__(256) void dense_resid_ln_fwd_kernel(const float* __
           const int col = (i * 64 + lane) * 4;
           f32x4 sc = gm[i];
           if (rs) sc *= rsv;
-          xv[i] = *(const f32x4*)(xr + col) + sc * Row4<TY>::load(yr_in + col);
+          if constexpr (SKIPY) {
+            typename Row4<TY>::vec yv = typename Row4<TY>::vec{};
+            if (tail) yv = Row4<TY>::load_raw(yr_in + col);
+            xv[i] = *(const f32x4*)(xr + col) + sc * Row4<TY>::widen(yv);
+          } else {
+            xv[i] = *(const f32x4*)(xr + col) + sc * Row4<TY>::load(yr_in + col);
+          }
           *(f32x4*)(xo + col) = xv[i];
         }
         s += hsum(xv[i]);
@@ -321,13 +336,20 @@ __global__ __launch_bounds__(OCTIC_DLNBWD_WAVES * 64, OCTIC_DLNBWD_WAVES / 4) vo
 // still stored: their readers take all rows).  With the promise kept and x finite every output equals the launch without
 // ns, up to the sign of an exact zero (0 * x, 0 + dres), which no comparison of values sees.  The branches are per row and
 // wave-uniform; row-to-wave assignment, summation order and the slabs do not move.
-template <typename TG, int NV, bool SKIP = false, typename... MASK>      // MASK: (const float* ns, long nrps) under SKIP
+// INPLACE (with SKIP only): dx IS the buffer that holds dres (dres itself is not passed).  A live row loads dres from it and
+// stores dx to it, each lane at its own addresses.  A dead row has dx = dres: nothing is stored, and dres is loaded only
+// where the tail factor is not 0 (gyb = rs * gamma * dres); where it is 0 the row is not touched at all and gyb is the exact
+// zero row that zeros times 0 make.  gyb is written for every row.
+template <bool INPLACE> struct StreamPtr { typedef float* __restrict__ type; };
+template <> struct StreamPtr<true> { typedef float* type; };
+template <typename TG, int NV, bool SKIP = false, bool INPLACE = false, typename... MASK>  // MASK: (const float* ns, long nrps) under SKIP
 __global__ __launch_bounds__(512, 2) void dense_ln_bwd_tail_kernel(
     const TG* __restrict__ gy, const float* __restrict__ x, const float* __restrict__ w,
-    const float* __restrict__ stats, const float* __restrict__ dres, float* __restrict__ dx,
+    const float* __restrict__ stats, const float* __restrict__ dres, typename StreamPtr<INPLACE>::type dx,
     float* __restrict__ partials, const TG* __restrict__ yb, const float* __restrict__ gamma,
     const float* __restrict__ rs, long rps, TG* __restrict__ gyb, float* __restrict__ partials2, long rows, int d,
     MASK... mask) {
+  static_assert(SKIP || !INPLACE, "only the sample mask tells which rows keep their dres");
   extern __shared__ float lds[];             // [2][d] slab image | [d] LayerNorm weights | [d] layer scale
   const float* __restrict__ ns = mask_scale(mask...);
   const long nrps = mask_rows(mask...);
@@ -373,8 +395,18 @@ __global__ __launch_bounds__(512, 2) void dense_ln_bwd_tail_kernel(
         gr[i] = typename Row4<TG>::vec{};
       }
     }
+    if constexpr (INPLACE) {
+      if (live || tail) {
 #pragma unroll
-    for (int i = 0; i < NV; ++i) dr[i] = dres ? *(const f32x4*)(dres + o + i * 256) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < NV; ++i) dr[i] = *(const f32x4*)(dx + o + i * 256);
+      } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) dr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) dr[i] = dres ? *(const f32x4*)(dres + o + i * 256) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     if (tail) {
 #pragma unroll
       for (int i = 0; i < NV; ++i) yr[i] = Row4<TG>::load_raw(yb + o + i * 256);
@@ -402,12 +434,23 @@ __global__ __launch_bounds__(512, 2) void dense_ln_bwd_tail_kernel(
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       f32x4 v = (g[i] - m1 - xh[i] * m2) * rstd;
-      if (dres) v += dr[i];
-      *(f32x4*)(dx + o + i * 256) = v;
+      if (INPLACE || dres) v += dr[i];
+      if constexpr (INPLACE) g[i] = v;                         // (stored below: a branch in here would split the arithmetic)
+      else *(f32x4*)(dx + o + i * 256) = v;
       const f32x4 t = v * sc;                                  // scale_residual_bwd_kernel: g = gout * s
       p1[i] += t;
       p0[i] += t * Row4<TG>::widen(yr[i]);
       Row4<TG>::store(gyb + o + i * 256, t * *(const f32x4*)(gl + (i * 64 + lane) * 4));
+    }
+    if constexpr (INPLACE) {
+      // the partial sums are complete HERE: without this the compiler sinks their updates behind the branch below, away from
+      // the products they are contracted with in the other instantiations, and d gamma loses its bit-equality
+#pragma unroll
+      for (int i = 0; i < NV; ++i) asm volatile("" : "+v"(pw[i]), "+v"(pb[i]), "+v"(p0[i]), "+v"(p1[i]));
+      if (live) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) *(f32x4*)(dx + o + i * 256) = g[i];
+      }
     }
   }
   if (partials) slab_reduce<NV>(lds, partials + (long)blockIdx.x * 2 * d, pw, pb, ok, d);
@@ -762,6 +805,61 @@ __global__ __launch_bounds__(256) void dense_prep_batch_kernel(const octic_dense
 
 using namespace octic;
 
+template <bool SKIPY>
+static int resid_ln_fwd_impl(const float* x, const void* yb, int yb_dtype, const float* gamma, const float* rs,
+                             int64_t rows_per_scale, float* xout, void* y, int y_dtype, const float* w, const float* b,
+                             float* stats, int64_t rows, int d, float eps, void* stream) {
+  if (rows == 0) return OCTIC_OK;
+  if (!x || !yb || !xout || !y || !stats) return OCTIC_ENULL;
+  if (int e = dense_check(rows, d)) return e;
+  if ((yb_dtype != OCTIC_F32 && yb_dtype != OCTIC_BF16) || (y_dtype != OCTIC_F32 && y_dtype != OCTIC_BF16)) return OCTIC_EDTYPE;
+  if (rs && rows_per_scale <= 0) return OCTIC_ESHAPE;
+  long blocks = (rows + 7) / 8;              // 2 rows per wave (41-42 us at ViT-H against 46 with 4: tools/bench_rln.py)
+  if (blocks > 8192) blocks = 8192;
+  hipStream_t s = (hipStream_t)stream;
+  const long rps = rs ? rows_per_scale : 1;
+#define OCTIC_RLN(TYB, TO) \
+  DENSE_NV_SWITCH(dense_nv(d), (dense_resid_ln_fwd_kernel<TYB, TO, NV, SKIPY><<<dim3((unsigned)blocks), dim3(256), 0, s>>>( \
+      x, (const TYB*)yb, gamma, rs, rps, xout, (TO*)y, w, b, stats, rows, d, eps)))
+  if (yb_dtype == OCTIC_BF16 && y_dtype == OCTIC_BF16) { OCTIC_RLN(bf16, bf16); }
+  else if (yb_dtype == OCTIC_BF16) { OCTIC_RLN(bf16, float); }
+  else if (y_dtype == OCTIC_BF16) { OCTIC_RLN(float, bf16); }
+  else { OCTIC_RLN(float, float); }
+#undef OCTIC_RLN
+  return launch_status();
+}
+
+static int ln_bwd_tail_impl(const void* gy, const float* x, const float* w, const float* stats, const float* dres,
+                            float* dx, float* partials, const void* yb, const float* gamma, const float* rs,
+                            int64_t rows_per_scale, void* gyb, float* partials2, int64_t rows, int d,
+                            const float* sample_scale, int64_t rows_per_sample, bool inplace, void* stream) {
+  if (sample_scale && (rows_per_sample <= 0 || rows % rows_per_sample)) return OCTIC_ESHAPE;
+  if (rows == 0) return OCTIC_OK;
+  if (!gy || !x || !stats || !dx || !yb || !gyb) return OCTIC_ENULL;
+  if (int e = dense_check(rows, d)) return e;
+  if (d != dense_nv(d) * 256 || dense_nv(d) > 5) return OCTIC_ESHAPE;     // whole 256-column chunks only (callers fall back)
+  if (rs && rows_per_scale <= 0) return OCTIC_ESHAPE;
+  const int blocks = dense_blocks(rows);
+  const size_t lds = (size_t)4 * d * sizeof(float);
+  hipStream_t s = (hipStream_t)stream;
+  const long rps = rs ? rows_per_scale : 1;
+  if (inplace) {
+    DENSE_NV_SWITCH(dense_nv(d), (dense_ln_bwd_tail_kernel<bf16, NV, true, true><<<dim3(blocks), dim3(512), lds, s>>>(
+        (const bf16*)gy, x, w, stats, nullptr, dx, partials, (const bf16*)yb, gamma, rs, rps, (bf16*)gyb, partials2, rows, d,
+        sample_scale, (long)rows_per_sample)));
+    return launch_status();
+  }
+  if (sample_scale) {
+    DENSE_NV_SWITCH(dense_nv(d), (dense_ln_bwd_tail_kernel<bf16, NV, true><<<dim3(blocks), dim3(512), lds, s>>>(
+        (const bf16*)gy, x, w, stats, dres, dx, partials, (const bf16*)yb, gamma, rs, rps, (bf16*)gyb, partials2, rows, d,
+        sample_scale, (long)rows_per_sample)));
+    return launch_status();
+  }
+  DENSE_NV_SWITCH(dense_nv(d), (dense_ln_bwd_tail_kernel<bf16, NV><<<dim3(blocks), dim3(512), lds, s>>>(
+      (const bf16*)gy, x, w, stats, dres, dx, partials, (const bf16*)yb, gamma, rs, rps, (bf16*)gyb, partials2, rows, d)));
+  return launch_status();
+}
+
 extern "C" {
 
 int octic_dense_layernorm_fwd(const float* x, void* y, int y_dtype, const float* w, const float* b, float* stats,
@@ -789,24 +887,14 @@ int octic_dense_layernorm_fwd_rows(const float* x, void* y, int y_dtype, const f
 int octic_dense_resid_layernorm_fwd(const float* x, const void* yb, int yb_dtype, const float* gamma, const float* rs,
                                     int64_t rows_per_scale, float* xout, void* y, int y_dtype, const float* w,
                                     const float* b, float* stats, int64_t rows, int d, float eps, void* stream) {
-  if (rows == 0) return OCTIC_OK;
-  if (!x || !yb || !xout || !y || !stats) return OCTIC_ENULL;
-  if (int e = dense_check(rows, d)) return e;
-  if ((yb_dtype != OCTIC_F32 && yb_dtype != OCTIC_BF16) || (y_dtype != OCTIC_F32 && y_dtype != OCTIC_BF16)) return OCTIC_EDTYPE;
-  if (rs && rows_per_scale <= 0) return OCTIC_ESHAPE;
-  long blocks = (rows + 7) / 8;              // 2 rows per wave (41-42 us at ViT-H against 46 with 4: tools/bench_rln.py)
-  if (blocks > 8192) blocks = 8192;
-  hipStream_t s = (hipStream_t)stream;
-  const long rps = rs ? rows_per_scale : 1;
-#define OCTIC_RLN(TYB, TO) \
-  DENSE_NV_SWITCH(dense_nv(d), (dense_resid_ln_fwd_kernel<TYB, TO, NV><<<dim3((unsigned)blocks), dim3(256), 0, s>>>( \
-      x, (const TYB*)yb, gamma, rs, rps, xout, (TO*)y, w, b, stats, rows, d, eps)))
-  if (yb_dtype == OCTIC_BF16 && y_dtype == OCTIC_BF16) { OCTIC_RLN(bf16, bf16); }
-  else if (yb_dtype == OCTIC_BF16) { OCTIC_RLN(bf16, float); }
-  else if (y_dtype == OCTIC_BF16) { OCTIC_RLN(float, bf16); }
-  else { OCTIC_RLN(float, float); }
-#undef OCTIC_RLN
-  return launch_status();
+  return resid_ln_fwd_impl<false>(x, yb, yb_dtype, gamma, rs, rows_per_scale, xout, y, y_dtype, w, b, stats, rows, d, eps, stream);
+}
+
+int octic_dense_resid_layernorm_fwd_skip(const float* x, const void* yb, int yb_dtype, const float* gamma, const float* rs,
+                                         int64_t rows_per_scale, float* xout, void* y, int y_dtype, const float* w,
+                                         const float* b, float* stats, int64_t rows, int d, float eps, void* stream) {
+  if (!rs) return OCTIC_ENULL;               // (without factors there is nothing to skip: the plain entry point)
+  return resid_ln_fwd_impl<true>(x, yb, yb_dtype, gamma, rs, rows_per_scale, xout, y, y_dtype, w, b, stats, rows, d, eps, stream);
 }
 
 int octic_dense_blocks(int64_t rows) { return dense_blocks(rows); }
@@ -857,27 +945,18 @@ int octic_dense_layernorm_bwd_tail_skip(const void* gy, const float* x, const fl
                                         const float* dres, float* dx, float* partials, const void* yb, const float* gamma,
                                         const float* rs, int64_t rows_per_scale, void* gyb, float* partials2, int64_t rows,
                                         int d, const float* sample_scale, int64_t rows_per_sample, void* stream) {
-  if (sample_scale && (rows_per_sample <= 0 || rows % rows_per_sample)) return OCTIC_ESHAPE;
-  if (rows == 0) return OCTIC_OK;
-  if (!gy || !x || !stats || !dx || !yb || !gyb) return OCTIC_ENULL;
-  if (int e = dense_check(rows, d)) return e;
-  if (d != dense_nv(d) * 256 || dense_nv(d) > 5) return OCTIC_ESHAPE;     // whole 256-column chunks only (callers fall back)
-  if (rs && rows_per_scale <= 0) return OCTIC_ESHAPE;
-  const int blocks = dense_blocks(rows);
-  const size_t lds = (size_t)4 * d * sizeof(float);
-  hipStream_t s = (hipStream_t)stream;
-  const long rps = rs ? rows_per_scale : 1;
-  if (sample_scale) {
-    DENSE_NV_SWITCH(dense_nv(d), (dense_ln_bwd_tail_kernel<bf16, NV, true><<<dim3(blocks), dim3(512), lds, s>>>(
-        (const bf16*)gy, x, w, stats, dres, dx, partials, (const bf16*)yb, gamma, rs, rps, (bf16*)gyb, partials2, rows, d,
-        sample_scale, (long)rows_per_sample)));
-    return launch_status();
-  }
-  DENSE_NV_SWITCH(dense_nv(d), (dense_ln_bwd_tail_kernel<bf16, NV><<<dim3(blocks), dim3(512), lds, s>>>(
-      (const bf16*)gy, x, w, stats, dres, dx, partials, (const bf16*)yb, gamma, rs, rps, (bf16*)gyb, partials2, rows, d)));
-  return launch_status();
+  return ln_bwd_tail_impl(gy, x, w, stats, dres, dx, partials, yb, gamma, rs, rows_per_scale, gyb, partials2, rows, d,
+                          sample_scale, rows_per_sample, false, stream);
 }
 
+int octic_dense_layernorm_bwd_tail_inplace(const void* gy, const float* x, const float* w, const float* stats, float* dx,
+                                           float* partials, const void* yb, const float* gamma, const float* rs,
+                                           int64_t rows_per_scale, void* gyb, float* partials2, int64_t rows, int d,
+                                           const float* sample_scale, int64_t rows_per_sample, void* stream) {
+  if (!sample_scale) return OCTIC_ENULL;     // (only the mask tells which rows keep their dres)
+  return ln_bwd_tail_impl(gy, x, w, stats, nullptr, dx, partials, yb, gamma, rs, rows_per_scale, gyb, partials2, rows, d,
+                          sample_scale, rows_per_sample, true, stream);
+}
 int octic_dense_finish(const float* partials, int nblocks, int d, float* out0, float* out1, const float* scale1,
                        void* stream) {
   if (!partials) return OCTIC_ENULL;

@@ -433,14 +433,21 @@ __global__ __launch_bounds__(256, 4) void ln_fwd_g8_kernel(const float* __restri
 // to the d alpha / d beta partials.  With the promise kept and x finite every output equals the launch without ns, up to the
 // sign of an exact zero, which no comparison of values sees.  The branch is per row and wave-uniform; row-to-wave
 // assignment, summation order and the slabs do not move.
-template <typename TG, int NV, bool WIDE = false, bool SKIP = false, typename... MASK>  // MASK: (const float* ns, int64_t nrps) under SKIP
+// INPLACE (with SKIP and cg only): dx IS the buffer that holds dres (dres / ldr are not used).  A live row loads dres from it
+// and stores dx to it, each lane at its own addresses.  A dead row has dx = dres: nothing is stored, and dres is loaded only
+// where crs[row / crps] is not 0 (cg = bf16(crs * dres)); where it is 0 the row is not touched at all and cg is the exact
+// zero row that zeros times 0 make.  cg is written for every row.
+template <bool INPLACE> struct LnStreamPtr { typedef float* __restrict__ type; };
+template <> struct LnStreamPtr<true> { typedef float* type; };
+template <typename TG, int NV, bool WIDE = false, bool SKIP = false, bool INPLACE = false, typename... MASK>  // MASK: (const float* ns, int64_t nrps) under SKIP
 __global__ __launch_bounds__(kLnBwdWaves * 64, WIDE ? 2 : OCTIC_LNBWD_OCC) void ln_bwd_g8_kernel(
     const TG* __restrict__ g, int64_t ldg, const float* __restrict__ x, int64_t ldx, const float* __restrict__ stats,
     const float* a0, const float* a1, const float* a2, const float* a3, const float* a4,
-    const float* __restrict__ dres, int64_t ldr, float* __restrict__ dx, int64_t ldd, float* __restrict__ partials,
+    const float* __restrict__ dres, int64_t ldr, typename LnStreamPtr<INPLACE>::type dx, int64_t ldd, float* __restrict__ partials,
     int64_t M, int c, const float* __restrict__ crs = nullptr, int64_t crps = 1, bf16* __restrict__ cg = nullptr,
     int64_t ldc = 0, MASK... mask) {
   static_assert(WIDE || !SKIP, "the sample mask exists in the wide kernel only");
+  static_assert(SKIP || !INPLACE, "only the sample mask tells which rows keep their dres");
   const float* __restrict__ ns = mask_scale(mask...);
   const int64_t nrps = mask_rows(mask...);
   // cg (WIDE only): also store bf16(crs[row / crps] * dx) - the drop-path-scaled bf16 cotangent the backward of the
@@ -497,9 +504,19 @@ __global__ __launch_bounds__(kLnBwdWaves * 64, WIDE ? 2 : OCTIC_LNBWD_OCC) void 
           gr[i] = graw{};
         }
       }
+      if constexpr (INPLACE) {
+        if (live || (crs ? mask_live(crs[m / crps]) : true)) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i)
-        dr[i] = dres ? *(const f32x4*)(dres + m * ldr + lg.col0 + i * lg.step4) : f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int i = 0; i < NV; ++i) dr[i] = *(const f32x4*)(dx + m * ldd + lg.col0 + i * lg.step4);
+        } else {
+#pragma unroll
+          for (int i = 0; i < NV; ++i) dr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+          dr[i] = dres ? *(const f32x4*)(dres + m * ldr + lg.col0 + i * lg.step4) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
     }
     float dot = 0.f, t = 0.f;
 #pragma unroll
@@ -527,7 +544,25 @@ __global__ __launch_bounds__(kLnBwdWaves * 64, WIDE ? 2 : OCTIC_LNBWD_OCC) void 
     const float coef = coefw * dS;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      f32x4 o = (gh[i] - mg) * rstd + xc[i] * coef;
+      f32x4 o;
+      if constexpr (INPLACE) {
+        // a * b + c * d leaves the compiler two contractions, and in this instantiation it would not take the one it takes
+        // in the out-of-place instantiation of the same chunk count (one chunk: round(xc * coef) is the addend of the fma;
+        // two to five: round((gh - mg) * rstd) is).  That one is written out; tests/test_row_inplace_gpu.py holds every
+        // chunk count to the bits of the out-of-place launch.
+        const f32x4 u = gh[i] - mg;
+        if constexpr (NV == 1) {
+          const f32x4 t = xc[i] * coef;
+          o = f32x4{__builtin_fmaf(u[0], rstd, t[0]), __builtin_fmaf(u[1], rstd, t[1]), __builtin_fmaf(u[2], rstd, t[2]),
+                    __builtin_fmaf(u[3], rstd, t[3])};
+        } else {
+          const f32x4 t = u * rstd;
+          o = f32x4{__builtin_fmaf(xc[i][0], coef, t[0]), __builtin_fmaf(xc[i][1], coef, t[1]),
+                    __builtin_fmaf(xc[i][2], coef, t[2]), __builtin_fmaf(xc[i][3], coef, t[3])};
+        }
+      } else {
+        o = (gh[i] - mg) * rstd + xc[i] * coef;
+      }
       if constexpr (WIDE) {
         o += dr[i];
         if (cg) {
@@ -538,7 +573,14 @@ __global__ __launch_bounds__(kLnBwdWaves * 64, WIDE ? 2 : OCTIC_LNBWD_OCC) void 
       } else {
         if (dres) o += *(const f32x4*)(dres + m * ldr + lg.col0 + i * lg.step4);
       }
-      *(f32x4*)(dx + m * ldd + lg.col0 + i * lg.step4) = o;
+      if constexpr (INPLACE) gh[i] = o;                        // (stored below: a branch in here would split the arithmetic)
+      else *(f32x4*)(dx + m * ldd + lg.col0 + i * lg.step4) = o;
+    }
+    if constexpr (INPLACE) {
+      if (live) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) *(f32x4*)(dx + m * ldd + lg.col0 + i * lg.step4) = gh[i];
+      }
     }
   }
   // slab: plane 0 = sum g*xhat for all 8c columns, plane 1 = sum g, A1 columns only (all the finish kernel reads)
@@ -657,8 +699,9 @@ int octic_layernorm_d8_bwd_blocks(int64_t M) { return ln_blocks(M); }
 static int ln_bwd_impl(const octic_view* g, const octic_view* x, const float* stats, const float* const alpha[5],
                        const octic_view* dres, const octic_view* dx, float* partials, int64_t M, int c, int g_dtype,
                        void* stream, const float* crs, int64_t crps, void* cg, const float* ns = nullptr,
-                       int64_t nrps = 0) {
+                       int64_t nrps = 0, bool inplace = false) {
   int e;
+  if (inplace && (!ns || !cg || dres)) return OCTIC_ENULL;     // (dx holds dres; only the mask tells which rows keep it)
   if (ns && (nrps <= 0 || M % nrps)) return OCTIC_ESHAPE;
   if ((e = check_c(c)) || (e = check_view(g, c, g_dtype)) || (e = check_view(x, c, OCTIC_F32)) ||
       (e = check_view(dx, c, OCTIC_F32)))
@@ -692,6 +735,12 @@ static int ln_bwd_impl(const octic_view* g, const octic_view* x, const float* st
     if (OCTIC_LNBWD_WIDE && g_dtype == OCTIC_BF16 && c / 32 <= 5) {
 #define LN_BWD_G8W(N) ln_bwd_g8_kernel<bf16, N, true><<<grid, kLnBwdWaves * 64, smem_g8, s>>>((const bf16*)vg.p[0], vg.ld[0], (const float*)vx.p[0], vx.ld[0], stats, a[0], a[1], a[2], a[3], a[4], rp, vr.ld[0], (float*)vd.p[0], vd.ld[0], partials, M, c, crs, crs ? crps : 1, (bf16*)cg, (int64_t)8 * c)
 #define LN_BWD_G8S(N) ln_bwd_g8_kernel<bf16, N, true, true><<<grid, kLnBwdWaves * 64, smem_g8, s>>>((const bf16*)vg.p[0], vg.ld[0], (const float*)vx.p[0], vx.ld[0], stats, a[0], a[1], a[2], a[3], a[4], rp, vr.ld[0], (float*)vd.p[0], vd.ld[0], partials, M, c, crs, crs ? crps : 1, (bf16*)cg, (int64_t)8 * c, ns, nrps)
+#define LN_BWD_G8I(N) ln_bwd_g8_kernel<bf16, N, true, true, true><<<grid, kLnBwdWaves * 64, smem_g8, s>>>((const bf16*)vg.p[0], vg.ld[0], (const float*)vx.p[0], vx.ld[0], stats, a[0], a[1], a[2], a[3], a[4], nullptr, 0, (float*)vd.p[0], vd.ld[0], partials, M, c, crs, crs ? crps : 1, (bf16*)cg, (int64_t)8 * c, ns, nrps)
+      if (inplace) {
+        switch (c / 32) { case 1: LN_BWD_G8I(1); break; case 2: LN_BWD_G8I(2); break; case 3: LN_BWD_G8I(3); break;
+                          case 4: LN_BWD_G8I(4); break; default: LN_BWD_G8I(5); break; }
+        return launch_status();
+      }
       if (ns) {                             // (every other kernel of this function reads all rows: the mask is a permission)
         switch (c / 32) { case 1: LN_BWD_G8S(1); break; case 2: LN_BWD_G8S(2); break; case 3: LN_BWD_G8S(3); break;
                           case 4: LN_BWD_G8S(4); break; default: LN_BWD_G8S(5); break; }
@@ -699,15 +748,16 @@ static int ln_bwd_impl(const octic_view* g, const octic_view* x, const float* st
       }
       switch (c / 32) { case 1: LN_BWD_G8W(1); break; case 2: LN_BWD_G8W(2); break; case 3: LN_BWD_G8W(3); break;
                         case 4: LN_BWD_G8W(4); break; default: LN_BWD_G8W(5); break; }
+#undef LN_BWD_G8I
 #undef LN_BWD_G8S
 #undef LN_BWD_G8W
       return launch_status();
     }
-    if (cg) return OCTIC_ESHAPE;          // the scaled bf16 copy exists in the wide kernel only
+    if (cg || inplace) return OCTIC_ESHAPE;  // the scaled bf16 copy exists in the wide kernel only, and so does the in-place update
     if (g_dtype == OCTIC_F32) { LN_BWD_G8_NV(float) } else { LN_BWD_G8_NV(bf16) }
     return launch_status();
   }
-  if (cg) return OCTIC_ESHAPE;
+  if (cg || inplace) return OCTIC_ESHAPE;
   if (g_dtype == OCTIC_F32) {
     if (pk) launch_ln_bwd<float, true>(nv, grid, smem, s, vg, vx, stats, a, vr, hd, vd, partials, M, c);
     else launch_ln_bwd<float, false>(nv, grid, smem, s, vg, vx, stats, a, vr, hd, vd, partials, M, c);
@@ -747,6 +797,18 @@ int octic_layernorm_d8_bwd_cast_skip(const octic_view* g, const octic_view* x, c
   if (((uintptr_t)gcast) & 15) return OCTIC_EALIGN;
   return ln_bwd_impl(g, x, stats, alpha, dres, dx, partials, M, c, OCTIC_BF16, stream, rs, rows_per_scale, gcast,
                      sample_scale, rows_per_sample);
+}
+
+int octic_layernorm_d8_bwd_cast_inplace(const octic_view* g, const octic_view* x, const float* stats,
+                                        const float* const alpha[5], const octic_view* dx, float* partials, int64_t M, int c,
+                                        const float* rs, int64_t rows_per_scale, void* gcast, const float* sample_scale,
+                                        int64_t rows_per_sample, void* stream) {
+  if (!gcast || !sample_scale) return OCTIC_ENULL;
+  if (rs && rows_per_scale <= 0) return OCTIC_ESHAPE;
+  if (((uintptr_t)gcast) & 15) return OCTIC_EALIGN;
+  if (c % 32 || c > 160) return OCTIC_ESHAPE;      // the wide kernel's shapes: no other kernel updates the stream in place
+  return ln_bwd_impl(g, x, stats, alpha, nullptr, dx, partials, M, c, OCTIC_BF16, stream, rs, rows_per_scale, gcast,
+                     sample_scale, rows_per_sample, true);
 }
 
 int octic_layernorm_d8_bwd_finish(const float* partials, int nblk, int c, float* const dalpha[5], float* dbeta,

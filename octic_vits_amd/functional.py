@@ -387,13 +387,16 @@ class LinearD8NormFn(torch.autograd.Function):
             dres = None if dy is None else _c(dy.float())
             gn = _c(dyn)
             ns, nrps = row_skip_get(ctx, M)
+            mine = dres is not None and STREAM_GRADS.take(dres)    # (always asked: the entry is this node's to consume)
             if ops.layernorm_bwd_cast_ok(gn, y, cout) and dtype == torch.bfloat16:
                 dy, dal_, dbeta, g = ops.layernorm_bwd_cast(gn, y, stats, alpha, dres, cout, rs32, rps,
-                                                            want_param_grads=has_affine, sample_scale=ns, rows_per_sample=nrps)
+                                                            want_param_grads=has_affine, sample_scale=ns, rows_per_sample=nrps,
+                                                            inplace=mine and ns is not None)
             else:
                 dy, dal_, dbeta = ops.layernorm_bwd(gn, y, stats, alpha, dres, cout, want_param_grads=has_affine,
                                                     sample_scale=ns, rows_per_sample=nrps)
             dal = dal_ if dal_ is not None else dal
+            STREAM_GRADS.offer(dy)                                 # allocated here, or the owned buffer updated in place
         dy = _c(dy)
         if g is None:
             g = ops.cast_rowscale(_c(dy.float()), rs32, rps, dtype, cout)  # cotangent of the branch
@@ -633,6 +636,54 @@ def row_skip_fill(x, scale, rps, rows):
 def row_skip_get(ctx, rows):
     slot = getattr(ctx, "row_skip", None)
     return (None, 0) if slot is None else slot.get(rows)
+
+
+# What the masked backward row kernels still move for the rows of a dropped sample is a copy: dx = dres, read from the incoming
+# stream cotangent and written to a fresh tensor.  With ROW_INPLACE the two are one buffer (include/octic_hip.h:
+# octic_dense_layernorm_bwd_tail_inplace, octic_layernorm_d8_bwd_cast_inplace): live rows are updated in place, dead rows are
+# not written, and not read either where the branch that ended in front of the norm dropped the sample too.  The same switch
+# routes the forward tail to octic_dense_resid_layernorm_fwd_skip (yb unread where rs is 0).  Effective only while
+# ROW_SKIP_DROPPED is on; read once at import from OCTIC_ROW_INPLACE (0 = off).
+ROW_INPLACE = _skip_from_env("OCTIC_ROW_INPLACE")
+
+
+class OwnedStreamGrad:
+    """Which stream cotangent may be written into: only a buffer that a backward node of this package allocated itself and
+    handed to autograd as the cotangent of its stream input, in the backward pass that is still running.  The node that returns
+    it calls offer(); the node that receives a stream cotangent calls take(), which is True for exactly that buffer (same
+    pass, same address, size, dtype and storage) and consumes the entry.  A tensor the caller passed to `.backward(g)`, a sum
+    autograd formed of two cotangents, a cast or a copy is never offered and so never written.  One entry: the stream is a
+    chain, each cotangent has one consumer.  The storage is held until the entry is replaced or the pass ends, so the address
+    cannot be handed to somebody else in between.  The limit: a `retain_grad()` or a tensor hook on a stream tensor INSIDE the
+    package's path keeps a reference to the offered buffer and sees it updated in place; such code sets OCTIC_ROW_INPLACE=0."""
+    __slots__ = ("task", "ptr", "numel", "storage", "armed")
+
+    def __init__(self):
+        self.task, self.ptr, self.numel, self.storage, self.armed = -1, 0, 0, None, -1
+
+    def clear(self):
+        self.task, self.ptr, self.numel, self.storage = -1, 0, 0, None
+
+    def offer(self, dx):
+        if dx is None or not (ROW_INPLACE and ROW_SKIP_DROPPED and ops._in_backward()):
+            return
+        task = torch._C._current_graph_task_id()
+        self.task, self.ptr, self.numel, self.storage = task, dx.data_ptr(), dx.numel(), dx.untyped_storage()
+        if self.armed != task:
+            self.armed = task
+            torch.autograd.Variable._execution_engine.queue_callback(self.clear)
+
+    def take(self, g):
+        st, ptr, numel, task = self.storage, self.ptr, self.numel, self.task
+        if st is None:
+            return False
+        self.clear()
+        return (ROW_INPLACE and ROW_SKIP_DROPPED and ops._in_backward() and task == torch._C._current_graph_task_id()
+                and g.dtype == torch.float32 and g.is_contiguous() and g.data_ptr() == ptr and g.numel() == numel
+                and g.untyped_storage().data_ptr() == st.data_ptr())
+
+
+STREAM_GRADS = OwnedStreamGrad()
 
 
 class AttnPackedFn(torch.autograd.Function):
@@ -1242,7 +1293,8 @@ def _resid_tail_fwd(ctx, x, tag, a2, wb, b, cache, tokens, g32, rs32, rps, nw, n
     br = _gemm_fwd(tag, a2, wb, b, cache, tag, tokens, ds, rps, drop)
     if neps is not None:
         nw32, nb32 = _f32(nw), _f32(nb)
-        out, yn, stats = ops.dense_resid_layernorm_fwd(x2, br, g32, rs32, rps, nw32, nb32, neps, torch.bfloat16)
+        out, yn, stats = ops.dense_resid_layernorm_fwd(x2, br, g32, rs32, rps, nw32, nb32, neps, torch.bfloat16,
+                                                       skip_yb=ROW_INPLACE and ROW_SKIP_DROPPED)
         ctx.set_materialize_grads(False)
         yn = yn.view(x.shape)
         row_skip_attach(ctx, yn)
@@ -1270,9 +1322,11 @@ def _resid_tail_bwd(ctx, tail, gout, gyn, want_norm):
             g2 = _c(gyn).view(out.shape)
             if LN_TAIL_FUSED and ops.dense_ln_bwd_tail_ok(g2, br, out.shape[-1]):
                 ns, nrps = row_skip_get(ctx, g2.shape[0])
+                mine = dres is not None and STREAM_GRADS.take(dres)    # (always asked: the entry is this node's to consume)
                 gout, dnw, dnb, gbr, dgamma, colsum = ops.dense_layernorm_bwd_tail(
                     g2, out, nw32, stats, dres, br, g32, rs32, rps, want_param_grads=want, want_gamma=has_gamma,
-                    want_colsum=has_b, sample_scale=ns, rows_per_sample=nrps)
+                    want_colsum=has_b, sample_scale=ns, rows_per_sample=nrps, inplace=mine and ns is not None)
+                STREAM_GRADS.offer(gout)                               # allocated there, or the owned buffer updated in place
             else:
                 gout, dnw, dnb = ops.dense_layernorm_bwd(g2, out, nw32, stats, dres, want_param_grads=want)
             dnw, dnb = (dnw if has_nw else None), (dnb if has_nb else None)

@@ -292,21 +292,34 @@ def layernorm_bwd_cast_ok(g, x, c):
     return g.dtype == torch.bfloat16 and x.dtype == torch.float32 and c % 32 == 0 and c <= 160
 
 
-def layernorm_bwd_cast(g, x, stats, alpha5, dres, c, rs, rps, want_param_grads=True, sample_scale=None, rows_per_sample=0):
+def layernorm_bwd_cast(g, x, stats, alpha5, dres, c, rs, rps, want_param_grads=True, sample_scale=None, rows_per_sample=0,
+                       inplace=False):
     """layernorm_bwd that also returns bf16(rs[row // rps] * dx): (dx, dalpha5, dbeta, gcast).  sample_scale / rows_per_sample:
-    as in layernorm_bwd (the factor of the branch this norm opens; rs is that of the branch that ends in front of it)."""
+    as in layernorm_bwd (the factor of the branch this norm opens; rs is that of the branch that ends in front of it).
+    inplace (needs the mask and a contiguous f32 dres the caller owns): dres is updated in place and returned as dx
+    (octic_layernorm_d8_bwd_cast_inplace: the rows of a dropped sample are not written, and not read where rs is 0)."""
     M = x.numel() // (8 * c)
     ss, srps = _sample_scale(sample_scale, rows_per_sample, M, x, "layernorm_bwd_cast")
-    dx = torch.empty_like(x)
+    if inplace:
+        if ss is None or dres is None or dres.dtype != torch.float32 or not dres.is_contiguous() or dres.numel() != x.numel():
+            raise ValueError("layernorm_bwd_cast(inplace=True) needs a sample mask and a contiguous float32 dres of x's size")
+        dx = dres
+    else:
+        dx = torch.empty_like(x)
     gc = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     nblk = lib().octic_layernorm_d8_bwd_blocks(M)
     partials = torch.empty((nblk, 2, 8 * c), dtype=torch.float32, device=x.device)
     gv, xv, dv = pview(g, c), pview(x, c), pview(dx, c)
     rv = pview(dres, c) if dres is not None else None
     t = KERNEL_TIMER.start()
-    check(lib().octic_layernorm_d8_bwd_cast_skip(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
-                                                 ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv), _p(partials),
-                                                 M, c, _p(rs), int(rps), _p(gc), _p(ss), srps, _stream(x)))
+    if inplace:
+        check(lib().octic_layernorm_d8_bwd_cast_inplace(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
+                                                        ctypes.byref(dv), _p(partials), M, c, _p(rs), int(rps), _p(gc), _p(ss),
+                                                        srps, _stream(x)))
+    else:
+        check(lib().octic_layernorm_d8_bwd_cast_skip(ctypes.byref(gv), ctypes.byref(xv), _p(stats), _arr5(alpha5),
+                                                     ctypes.byref(rv) if rv is not None else None, ctypes.byref(dv),
+                                                     _p(partials), M, c, _p(rs), int(rps), _p(gc), _p(ss), srps, _stream(x)))
     KERNEL_TIMER.stop(t, "ln_bwd_kernel<bf16>", M * 8 * c * (2 + 8 + (4 if dres is not None else 0) + 2))
     if not want_param_grads or alpha5 is None:
         return dx, None, None, gc
@@ -977,8 +990,9 @@ def dense_layernorm_bwd_rows_(gy, xa, w, stats, g, rowmap, want_param_grads=True
     return dw, db
 
 
-def dense_resid_layernorm_fwd(x, yb, gamma, rs, rps, w, b, eps, out_dtype):
-    """xout = x + rs[row // rps] * gamma * yb ; y = LayerNorm(xout) in one row pass -> (xout f32, y out_dtype, stats)."""
+def dense_resid_layernorm_fwd(x, yb, gamma, rs, rps, w, b, eps, out_dtype, skip_yb=False):
+    """xout = x + rs[row // rps] * gamma * yb ; y = LayerNorm(xout) in one row pass -> (xout f32, y out_dtype, stats).
+    skip_yb (with rs): the rows of yb whose factor is 0 stay unread (octic_dense_resid_layernorm_fwd_skip)."""
     _require_cuda(x)
     d = x.shape[-1]
     rows = x.numel() // d
@@ -986,8 +1000,9 @@ def dense_resid_layernorm_fwd(x, yb, gamma, rs, rps, w, b, eps, out_dtype):
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
     stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
     t = KERNEL_TIMER.start()
-    check(lib().octic_dense_resid_layernorm_fwd(_p(x), _p(yb), dt_code(yb.dtype), _p(gamma), _p(rs), int(rps), _p(xout), _p(y),
-                                                dt_code(out_dtype), _p(w), _p(b), _p(stats), rows, d, float(eps), _stream(x)))
+    fn = lib().octic_dense_resid_layernorm_fwd_skip if (skip_yb and rs is not None) else lib().octic_dense_resid_layernorm_fwd
+    check(fn(_p(x), _p(yb), dt_code(yb.dtype), _p(gamma), _p(rs), int(rps), _p(xout), _p(y), dt_code(out_dtype), _p(w), _p(b),
+             _p(stats), rows, d, float(eps), _stream(x)))
     KERNEL_TIMER.stop(t, f"dense_resid_ln_fwd_kernel<{_DTN[out_dtype]}>", rows * d * (8 + yb.element_size() + y.element_size()))
     return xout, y, stats
 
@@ -1018,24 +1033,36 @@ def dense_ln_bwd_tail_ok(gy, yb, d):
 
 
 def dense_layernorm_bwd_tail(gy, x, w, stats, dres, yb, gamma, rs, rps, want_param_grads=True, want_gamma=True,
-                             want_colsum=True, sample_scale=None, rows_per_sample=0):
+                             want_colsum=True, sample_scale=None, rows_per_sample=0, inplace=False):
     """dense_layernorm_bwd followed by scale_residual_bwd on its result, one row pass.
     Returns (dx f32, dw, db, gyb bf16 = rs*gamma*dx, dgamma, gamma * colsum(rs*dx)).
     sample_scale / rows_per_sample: the factor of the branch this norm opens, a promise that the rows of gy are zero where it
     is 0 (octic_dense_layernorm_bwd_tail_skip: those rows of gy, x and stats stay unread, and yb's where rs is 0); a malformed
-    mask is a ValueError."""
+    mask is a ValueError.
+    inplace (needs the mask and a contiguous f32 dres the caller owns): dres is updated in place and returned as dx
+    (octic_dense_layernorm_bwd_tail_inplace: the rows of a dropped sample are not written, and not read where rs is 0)."""
     d = x.shape[-1]
     rows = x.numel() // d
     ss, srps = _sample_scale(sample_scale, rows_per_sample, rows, x, "dense_layernorm_bwd_tail")
-    dx = torch.empty_like(x)
+    if inplace:
+        if ss is None or dres is None or dres.dtype != torch.float32 or not dres.is_contiguous() or dres.numel() != x.numel():
+            raise ValueError("dense_layernorm_bwd_tail(inplace=True) needs a sample mask and a contiguous float32 dres of x's size")
+        dx = dres
+    else:
+        dx = torch.empty_like(x)
     gyb = torch.empty(x.shape, dtype=yb.dtype, device=x.device)
     nblk = lib().octic_dense_blocks(rows)
     p1 = torch.empty((nblk, 2, d), dtype=torch.float32, device=x.device) if want_param_grads else None
     want2 = want_gamma or want_colsum
     p2 = torch.empty((nblk, 2, d), dtype=torch.float32, device=x.device) if want2 else None
     t = KERNEL_TIMER.start()
-    check(lib().octic_dense_layernorm_bwd_tail_skip(_p(gy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(p1), _p(yb), _p(gamma),
-                                                    _p(rs), int(rps), _p(gyb), _p(p2), rows, d, _p(ss), srps, _stream(x)))
+    if inplace:
+        check(lib().octic_dense_layernorm_bwd_tail_inplace(_p(gy), _p(x), _p(w), _p(stats), _p(dx), _p(p1), _p(yb), _p(gamma),
+                                                           _p(rs), int(rps), _p(gyb), _p(p2), rows, d, _p(ss), srps, _stream(x)))
+    else:
+        check(lib().octic_dense_layernorm_bwd_tail_skip(_p(gy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(p1), _p(yb),
+                                                        _p(gamma), _p(rs), int(rps), _p(gyb), _p(p2), rows, d, _p(ss), srps,
+                                                        _stream(x)))
     KERNEL_TIMER.stop(t, "dense_ln_bwd_tail_kernel<bf16>", rows * d * (2 + 8 + (4 if dres is not None else 0) + 4))
     dw = db = dgamma = colsum = None
     if want_param_grads:
