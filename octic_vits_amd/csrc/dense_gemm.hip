@@ -1590,11 +1590,267 @@ inline DgImage dense_plan_image(const DgTokPlan& tp, int M, int N, int K, int cu
 
 using namespace octic;
 
-extern "C" {
+// ---------------------------------------------------------------------------------------------------------------
+// The resolved launch.  Every entry point and every plan / order query describes its problem as a DgRequest; dense_resolve turns
+// it into the one DgLaunch that dense_launch runs, the plan queries read and the order queries walk.  The policy above (dense_plan*)
+// is consulted here and nowhere else.  Precedence:
+//   1. dense_plan_image takes the launch (a mask, drop > 0) and folds:  dense_nt_image_cls_kernel, no class-token tail;
+//   2. ... takes it without folding (route + 8, K not foldable):         the plan is replaced, then as below (4);
+//   3. adaptive && fold_cls && the fold takes it:                        dense_nt_adaptive_cls_kernel, no tail;
+//      adaptive && eligible:                                             dense_nt_adaptive_kernel + the tail;
+//   4. skip (a mask, not the fused residual tail, the bitmap's panels):  dense_nt_kernel<MODE, NT, true> + the tail;
+//   5. otherwise                                                         dense_nt_kernel<MODE, NT> + the tail.
+// The tail exists with per-image panels only: dense_cls_kernel, or the part + sum pair where dense_cls_two_launches says so, a
+// workspace is given and the main launch splits nothing (the partial tiles live where split-K slabs would).
+enum { DG_FAM_PLAIN, DG_FAM_MASKED, DG_FAM_ADAPTIVE, DG_FAM_ADAPTIVE_CLS, DG_FAM_IMAGE_CLS, DG_FAM_CLS_TAIL };
+enum { DG_TAIL_NONE, DG_TAIL_ONE, DG_TAIL_TWO };
+struct DgRequest { int M, N, K, mode, tokens; bool masked; int rows_per_sample; bool adaptive, fold_cls; double drop; bool workspace; };
+struct DgLaunch {
+  int family, tail;                             // DG_FAM_* of the main launch, DG_TAIL_*
+  DgPlan p;                                     // the plan in force
+  bool moved;                                   // dense_plan_image replaced dense_plan_tokens' plan
+  bool image;                                   // per-image panels (either way)
+  int images, m_stride, m_base;
+  bool skip;                                    // the kernels read the mask
+  int grid, lds, cus;                           // workgroups and dynamic LDS bytes of the main launch; workgroup slots planned for
+  int tile_wgs, wgs, per_wg;                    // grid = tile workgroups + class-token workgroups; items of the busiest of those
+  int tiles_n_narrow, narrow_force, max_live;   // the adaptive launch's (dense_plan_adaptive)
+  int width, slab_rows;                         // tile width (256 | 320), colsum slab rows of modes 3 / 5
+};
+
+static int dg_lds(int family, int nt) {
+  if (family == DG_FAM_CLS_TAIL) return 0;
+  return (nt == 5 ? DgGeom<5>::LDS : DgGeom<4>::LDS) + (family == DG_FAM_PLAIN ? 0 : kDgMaskWords * 8);   // the live bitmap sits behind the ring
+}
+// two slab rows per panel; with per-image panels one more per class-token row tile behind them
+static int dg_slab_rows(int M, bool image, int images) { return image ? 2 * images + (images + 15) / 16 : 2 * ((M + DG_BM - 1) / DG_BM); }
+
+static DgLaunch dense_resolve(const DgRequest& r, int cus) {
+  DgLaunch L = {};
+  DgTokPlan tp = dense_plan_tokens(r.M, r.N, r.K, cus, r.mode, r.tokens);
+  const bool masked = r.masked && r.mode != DG_RESID;
+  const DgImage img = dense_plan_image(tp, r.M, r.N, r.K, cus, r.mode, r.tokens, masked && r.drop > 0.0, r.rows_per_sample, r.drop);
+  if (img.taken) {
+    tp.p = img.p;
+    tp.image = true;
+    tp.images = img.images;
+  }
+  L.p = tp.p; L.moved = img.taken; L.image = tp.image; L.images = tp.images; L.cus = cus;
+  L.m_stride = tp.image ? r.tokens : DG_BM;
+  L.m_base = tp.image ? 1 : 0;
+  // the masked kernels take every mode but the fused residual tail, up to the bitmap's panels; anything else computes every row
+  L.skip = masked && L.p.tiles_m <= kDgMaskCap;
+  const DgAdaptive ad = dense_plan_adaptive(tp, r.N, r.mode, cus, L.skip);
+  const DgFold fold = dense_plan_fold(ad, tp.images, r.N, r.K);
+  L.tiles_n_narrow = ad.tiles_n_narrow; L.narrow_force = ad.force; L.max_live = ad.max_live;
+  L.grid = L.p.grid;
+  if (img.taken && img.fold) {
+    L.family = DG_FAM_IMAGE_CLS; L.grid = img.grid; L.wgs = img.wgs; L.per_wg = img.per_wg;
+  } else if (r.adaptive && r.fold_cls && fold.taken) {
+    L.family = DG_FAM_ADAPTIVE_CLS; L.grid = fold.grid; L.wgs = fold.wgs; L.per_wg = fold.per_wg;
+  } else if (r.adaptive && ad.eligible) {
+    L.family = DG_FAM_ADAPTIVE; L.grid = ad.grid;         // the tiles of either width: workgroups past the chosen one return
+  } else {
+    L.family = L.skip ? DG_FAM_MASKED : DG_FAM_PLAIN;
+  }
+  L.tile_wgs = L.grid - L.wgs;
+  L.lds = dg_lds(L.family, L.p.nt);
+  const bool folded = L.family == DG_FAM_IMAGE_CLS || L.family == DG_FAM_ADAPTIVE_CLS;
+  L.tail = folded || !tp.image ? DG_TAIL_NONE
+         : dense_cls_two_launches(r.mode, r.N, r.K) && r.workspace && L.p.split <= 1 ? DG_TAIL_TWO : DG_TAIL_ONE;
+  L.width = L.p.nt == 5 ? 320 : 256;
+  L.slab_rows = dg_slab_rows(r.M, L.image, L.images);
+  return L;
+}
+
+// ---- the kernels: one table for the one-time LDS attribute pass and for the launches.  Exactly the instantiations listed exist;
+// a (family, mode, tile width) with no entry is refused with OCTIC_ESHAPE.
+struct DgKernel { int family, mode, nt; const void* fn; int ints; };        // ints: the kernel's int parameters behind its DgArgs
+template <class... I>
+static DgKernel dg_entry(int family, int mode, int nt, void (*fn)(DgArgs, I...)) {
+  static_assert((std::is_same<I, int>::value && ...), "dg_run passes a DgArgs and ints");
+  return {family, mode, nt, (const void*)fn, (int)sizeof...(I)};
+}
+static const DgKernel* dg_kernel(int family, int mode, int nt, bool set_attributes = false) {
+  static const DgKernel table[] = {
+      dg_entry(DG_FAM_PLAIN, DG_PLAIN, 4, dense_nt_kernel<DG_PLAIN, 4>),
+      dg_entry(DG_FAM_PLAIN, DG_PLAIN, 5, dense_nt_kernel<DG_PLAIN, 5>),
+      dg_entry(DG_FAM_PLAIN, DG_GELU, 4, dense_nt_kernel<DG_GELU, 4>),
+      dg_entry(DG_FAM_PLAIN, DG_RESID, 4, dense_nt_kernel<DG_RESID, 4>),
+      dg_entry(DG_FAM_PLAIN, DG_DGELU, 4, dense_nt_kernel<DG_DGELU, 4>),
+      dg_entry(DG_FAM_PLAIN, DG_GELUF, 4, dense_nt_kernel<DG_GELUF, 4>),
+      dg_entry(DG_FAM_PLAIN, DG_DFACT, 4, dense_nt_kernel<DG_DFACT, 4>),
+      dg_entry(DG_FAM_PLAIN, DG_GELUO, 4, dense_nt_kernel<DG_GELUO, 4>),
+      dg_entry(DG_FAM_MASKED, DG_PLAIN, 4, dense_nt_kernel<DG_PLAIN, 4, true>),
+      dg_entry(DG_FAM_MASKED, DG_PLAIN, 5, dense_nt_kernel<DG_PLAIN, 5, true>),
+      dg_entry(DG_FAM_MASKED, DG_GELU, 4, dense_nt_kernel<DG_GELU, 4, true>),
+      dg_entry(DG_FAM_MASKED, DG_DGELU, 4, dense_nt_kernel<DG_DGELU, 4, true>),
+      dg_entry(DG_FAM_MASKED, DG_GELUF, 4, dense_nt_kernel<DG_GELUF, 4, true>),
+      dg_entry(DG_FAM_MASKED, DG_DFACT, 4, dense_nt_kernel<DG_DFACT, 4, true>),
+      dg_entry(DG_FAM_MASKED, DG_GELUO, 4, dense_nt_kernel<DG_GELUO, 4, true>),
+      dg_entry(DG_FAM_ADAPTIVE, DG_PLAIN, 5, dense_nt_adaptive_kernel),
+      dg_entry(DG_FAM_ADAPTIVE_CLS, DG_PLAIN, 5, dense_nt_adaptive_cls_kernel),
+      dg_entry(DG_FAM_IMAGE_CLS, DG_PLAIN, 4, dense_nt_image_cls_kernel<DG_PLAIN>),
+      dg_entry(DG_FAM_IMAGE_CLS, DG_GELUF, 4, dense_nt_image_cls_kernel<DG_GELUF>),
+      dg_entry(DG_FAM_IMAGE_CLS, DG_DFACT, 4, dense_nt_image_cls_kernel<DG_DFACT>),
+      dg_entry(DG_FAM_CLS_TAIL, DG_PLAIN, 0, dense_cls_kernel<DG_PLAIN>),
+      dg_entry(DG_FAM_CLS_TAIL, DG_GELU, 0, dense_cls_kernel<DG_GELU>),
+      dg_entry(DG_FAM_CLS_TAIL, DG_DGELU, 0, dense_cls_kernel<DG_DGELU>),
+      dg_entry(DG_FAM_CLS_TAIL, DG_GELUF, 0, dense_cls_kernel<DG_GELUF>),
+      dg_entry(DG_FAM_CLS_TAIL, DG_DFACT, 0, dense_cls_kernel<DG_DFACT>),
+      dg_entry(DG_FAM_CLS_TAIL, DG_GELUO, 0, dense_cls_kernel<DG_GELUO>),
+  };
+  const DgKernel* found = nullptr;
+  for (const DgKernel& k : table) {
+    if (set_attributes && dg_lds(k.family, k.nt) > 0)
+      (void)hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, dg_lds(k.family, k.nt));
+    if (k.family == family && k.mode == mode && k.nt == nt) found = &k;
+  }
+  if (set_attributes) (void)hipGetLastError();
+  return found;
+}
+template <class... I>
+static int dg_run(const DgKernel* k, int grid, int threads, int lds, hipStream_t s, DgArgs a, I... v) {
+  if (!k || k->ints != (int)sizeof...(I)) return OCTIC_ESHAPE;
+  void* args[] = {&a, &v...};
+  (void)hipLaunchKernel(k->fn, dim3(grid), dim3(threads), args, lds, s);          // (its status: launch_status())
+  return OCTIC_OK;
+}
+
+// the shape every query answers for; a mask is rows_per_sample rows per sample over whole samples
+static bool dg_shape_ok(int M, int N, int K) { return M > 0 && N > 0 && K >= 2 * DG_BK; }
+static bool dg_mask_ok(int M, int rows_per_sample) { return rows_per_sample > 0 && M > 0 && (M % rows_per_sample) == 0; }
 
 // CUs of the current device (the split-K parts of a tile wait for each other: the plan must not assume more workgroup
 // slots than the device has); 256 when no device is visible (host-only callers sizing a workspace)
 static int dense_cus() { return device_cus(); }
+
+// what an entry point would launch for this problem (the queries: no workspace, which moves nothing they report)
+static DgLaunch dense_query(int M, int N, int K, int mode, int tokens, bool masked, int rows_per_sample, bool adaptive, bool fold_cls,
+                            double drop) {
+  const DgRequest r = {M, N, K, mode, tokens, masked, rows_per_sample, adaptive, fold_cls, drop, false};
+  return dense_resolve(r, dense_cus());
+}
+
+// mode: 0 plain (C = A B^T + bias), 1 GELU (C = pre-activation, C2 = gelu(C)), 2 RESID (C = branch, OUT = X + rs*gamma*C),
+// 3 DGELU (C = gelu'(H) * (A B^T); colsum != NULL: octic_dense_gemm_colsum_rows() slabs [N] of column sums of C),
+// 4 GELUF (C = gelu'(pre-activation), C2 = gelu(pre-activation)), 5 DFACT (C = H * (A B^T), H = the factor of mode 4),
+// 6 GELUO (C = gelu(pre-activation) only: passes without a backward).
+// sample_scale / rows_per_sample: the stochastic-depth mask (see dense_item_masked); NULL = the unmasked launch.
+// adaptive / fold_cls / image_drop: what the entry point allows (DgRequest).  Validate, resolve, fill DgArgs, launch.
+static int dense_launch(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
+                        void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
+                        const float* X, float* OUT, const void* H, float* colsum, const float* sample_scale,
+                        int rows_per_sample, void* workspace, int tokens, void* stream, bool adaptive, bool fold_cls = false,
+                        double image_drop = 0.0) {
+  if (!A || !B || !C) return OCTIC_ENULL;
+  if (sample_scale && !dg_mask_ok(M, rows_per_sample)) return OCTIC_ESHAPE;
+  if (sample_scale && (((uintptr_t)sample_scale) & 3)) return OCTIC_EALIGN;
+  // (ldc % 8: every epilogue moves 8 bf16 = 16 bytes of a row of C / C2 / H per lane, from column offsets that are multiples of 8)
+  if (M <= 0 || N <= 0 || K <= 0 || (K % DG_BK) || K < 2 * DG_BK || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OCTIC_ESHAPE;
+  // buffer descriptors and per-lane offsets are 32-bit: operands of 2 GiB or more are refused (callers fall back to
+  // the BLAS library) instead of wrapping
+  if ((int64_t)M * lda * 2 >= (1ll << 31) || (int64_t)N * ldb * 2 >= (1ll << 31)) return OCTIC_ESHAPE;
+  if ((((uintptr_t)A) | ((uintptr_t)B)) & 15) return OCTIC_EALIGN;
+  if ((mode == DG_GELU || mode == DG_GELUF) && !C2) return OCTIC_ENULL;
+  if (mode == DG_RESID && (!X || !OUT || (rs && rps <= 0))) return OCTIC_ENULL;
+  if ((mode == DG_DGELU || mode == DG_DFACT) && !H) return OCTIC_ENULL;
+
+  const DgRequest r = {M, N, K, mode, tokens, sample_scale != nullptr, rows_per_sample, adaptive, fold_cls, image_drop, workspace != nullptr};
+  const DgLaunch L = dense_resolve(r, dense_cus());
+  const DgPlan& p = L.p;
+
+  DgArgs a = {};
+  a.A = (const bf16*)A; a.B = (const bf16*)B; a.lda = lda; a.ldb = ldb; a.M = M; a.N = N; a.K = K;
+  a.C = (bf16*)C; a.C2 = (bf16*)C2; a.ldc = ldc; a.bias = bias; a.gamma = gamma; a.rs = rs; a.rps = rs ? rps : 1;
+  a.X = X; a.OUT = OUT; a.H = (const bf16*)H; a.colsum = (mode == DG_DGELU || mode == DG_DFACT) ? colsum : nullptr;
+  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.full_tiles = p.full; a.split = p.split; a.tail_pad = p.tail_pad;
+  a.m_stride = L.m_stride;
+  a.m_base = L.m_base;
+  a.sample_scale = L.skip ? sample_scale : nullptr;
+  a.rows_per_sample = L.skip ? rows_per_sample : 0;
+  a.tiles_n_narrow = L.tiles_n_narrow; a.cus = L.cus; a.narrow_force = L.narrow_force;      // (the adaptive kernels' alone)
+  if (p.split > 1) {
+    if (!workspace) return OCTIC_ENULL;
+    if (p.rem * 4 > DG_TICKET_BYTES) return OCTIC_ESHAPE;
+    a.tickets = (int*)workspace;
+    a.slabs = (float*)((char*)workspace + DG_TICKET_BYTES);
+  }
+
+  hipStream_t s = (hipStream_t)stream;
+  static DeviceOnce once;
+  const DgKernel* const k = dg_kernel(L.family, mode, p.nt, once.first());
+  const int cr0 = 2 * L.images;                                // colsum slab rows of the class-token rows: behind the panels'
+  int rc;
+  if (L.family == DG_FAM_IMAGE_CLS) rc = dg_run(k, L.grid, 512, L.lds, s, a, tokens, L.images, L.tile_wgs, L.wgs, cr0);
+  else if (L.family == DG_FAM_ADAPTIVE_CLS) rc = dg_run(k, L.grid, 512, L.lds, s, a, tokens, L.images, L.tile_wgs, L.wgs);
+  else rc = dg_run(k, L.grid, 512, L.lds, s, a);
+  if (rc != OCTIC_OK) return rc;
+  if (L.tail == DG_TAIL_TWO) {
+    const int rows_pad = (L.images + 63) / 64 * 64;
+    float* part = (float*)((char*)workspace + DG_TICKET_BYTES);
+    // 64 or 80 columns per workgroup: whichever keeps the grid within ONE workgroup per CU (a CU sustains ~25 GB/s of
+    // first-touch loads: 320 workgroups on 256 CUs took 14.1 us where 240 took 8.2)
+    const int per64 = (N / 64) * (K / CLS_KSLICE) * (rows_pad / 64);
+    const int nw = (per64 > L.cus && (N % 80) == 0 && (N / 80) * (K / CLS_KSLICE) * (rows_pad / 64) <= L.cus) ? 5 : 4;
+    dense_cls_part_kernel<<<(N / (16 * nw)) * (K / CLS_KSLICE) * (rows_pad / 64), 64 * nw, 0, s>>>(a, tokens, L.images, rows_pad, part);
+    dense_cls_sum_kernel<<<(L.images * (N / 4) + 255) / 256, 256, 0, s>>>(a, tokens, L.images, rows_pad, part);
+  } else if (L.tail == DG_TAIL_ONE) {
+    // the class-token rows: row b * tokens of A / C / C2 / H
+    rc = dg_run(dg_kernel(DG_FAM_CLS_TAIL, mode, 0), (N / 16) * ((L.images + 15) / 16), 64 * dense_cls_waves(K), 0, s, a, tokens,
+                L.images, cr0);
+    if (rc != OCTIC_OK) return rc;
+  }
+  return launch_status();
+}
+
+// ---- the order queries: one walker.  It builds the live bitmap from a HOST mask and takes blockIdx through the resolved
+// launch's own mapping (dg_fold_wg, dense_item_masked / dense_item_adaptive, dg_fold_item - the functions the kernels call).
+struct DgOrderOut {
+  int cap; int *tm, *tn, *part, *split, *dead, *width;        // one entry per workgroup (each may be NULL), *width = 256 | 320
+  int cls_cap; int *cls_rt, *cls_ct;                          // per_wg entries per class-token workgroup (each may be NULL)
+};
+static int dense_walk(const DgLaunch& L, int M, int N, int K, const float* sample_scale, int rows_per_sample, const DgOrderOut& o) {
+  if (o.cap < L.grid || ((o.cls_rt || o.cls_ct) && o.cls_cap < L.wgs * L.per_wg)) return OCTIC_ESHAPE;
+  const DgPlan& p = L.p;
+  const bool adaptive = L.family == DG_FAM_ADAPTIVE || L.family == DG_FAM_ADAPTIVE_CLS;
+  unsigned long long bm[kDgMaskWords] = {};
+  for (int tm = 0; tm < p.tiles_m; ++tm)
+    if (dg_panel_live(sample_scale, rows_per_sample, M, L.m_stride, L.m_base, tm)) bm[tm >> 6] |= 1ull << (tm & 63);
+  const int ipp = L.wgs > 0 ? dg_fold_ipp(K / CLS_KSLICE) : 1, ntn = N >> 4, items = dg_fold_items(N, L.images);
+  bool narrow = adaptive && dg_adaptive_narrow(dg_live_panels(bm, p.tiles_m), L.tiles_n_narrow, L.cus, L.narrow_force);
+  for (int bid = 0; bid < L.grid; ++bid) {
+    int tile = -1, tm = -1, tn = -1, rem_idx = -1, part = 0;
+    bool dead = false;
+    const int cw = dg_fold_wg(bid, L.tile_wgs);
+    if (cw >= 0) {
+      for (int e = 0; e < L.per_wg; ++e) {
+        const int item = dg_fold_item(items, ipp, L.wgs, cw, e / ipp, e % ipp);
+        if (o.cls_rt) o.cls_rt[cw * L.per_wg + e] = item >= 0 ? item / ntn : -1;
+        if (o.cls_ct) o.cls_ct[cw * L.per_wg + e] = item >= 0 ? item % ntn : -1;
+      }
+    } else if (adaptive) {
+      dense_item_adaptive(p.tiles_m, p.tiles_n, L.tiles_n_narrow, L.cus, L.narrow_force, bid, bm, narrow, tile, dead);
+    } else {
+      dense_item_masked(p.tiles_m, p.tiles_n, p.full, p.split, p.tail_pad, bid, bm, tile, rem_idx, part, dead);
+    }
+    if (tile >= 0) dg_tile_panel(p.tiles_m, narrow ? L.tiles_n_narrow : p.tiles_n, tile, tm, tn);
+    if (o.tm) o.tm[bid] = tm;
+    if (o.tn) o.tn[bid] = tn;
+    if (o.part) o.part[bid] = part;
+    if (o.split) o.split[bid] = rem_idx >= 0 ? 1 : 0;
+    if (o.dead) o.dead[bid] = dead ? 1 : 0;
+  }
+  if (o.width) *o.width = narrow ? 256 : 320;
+  return L.grid;
+}
+// the order queries' shared front: what they refuse before a launch is resolved
+static int dense_order_check(int M, int N, int K, const float* sample_scale, int rows_per_sample) {
+  if (!sample_scale) return OCTIC_ENULL;
+  return dg_shape_ok(M, N, K) && dg_mask_ok(M, rows_per_sample) ? OCTIC_OK : OCTIC_ESHAPE;
+}
+
+extern "C" {
 
 // enough for either tile width (the plain mode may pick the 320-wide tile, the fused tails use the 256-wide one)
 int64_t octic_dense_gemm_workspace_bytes(int M, int N, int K) {
@@ -1624,182 +1880,24 @@ int64_t octic_dense_gemm_workspace_bytes(int M, int N, int K) {
 // + the class-token kernel, out[3] = workgroups of the main launch
 int octic_dense_gemm_plan(int M, int N, int K, int mode, int tokens, int* out) {
   if (!out) return OCTIC_ENULL;
-  if (M <= 0 || N <= 0 || K < 2 * DG_BK) { out[0] = 256; out[1] = 0; out[2] = 0; out[3] = 0; return OCTIC_OK; }
-  const DgTokPlan t = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
-  out[0] = t.p.nt == 5 ? 320 : 256;
-  out[1] = t.image ? 2 * t.images + (t.images + 15) / 16 : 2 * ((M + DG_BM - 1) / DG_BM);
-  out[2] = t.image ? 1 : 0;
-  out[3] = t.p.grid;
+  if (!dg_shape_ok(M, N, K)) { out[0] = 256; out[1] = 0; out[2] = 0; out[3] = 0; return OCTIC_OK; }
+  const DgLaunch L = dense_query(M, N, K, mode, tokens, false, 0, false, false, 0.0);
+  out[0] = L.width;
+  out[1] = L.slab_rows;
+  out[2] = L.image ? 1 : 0;
+  out[3] = L.grid;
   return OCTIC_OK;
 }
 
+// (the width of the classic plan: per-image panels are not asked about)
 int octic_dense_gemm_tile(int M, int N, int K, int mode) {
-  if (M <= 0 || N <= 0 || K < 2 * DG_BK) return 256;
+  if (!dg_shape_ok(M, N, K)) return 256;
   return dense_plan(M, N, K, dense_cus(), mode).nt == 5 ? 320 : 256;
 }
 
 int octic_dense_gemm_colsum_rows(int M, int N, int K) {
   (void)N; (void)K;
-  return 2 * ((M + DG_BM - 1) / DG_BM);
-}
-
-// mode: 0 plain (C = A B^T + bias), 1 GELU (C = pre-activation, C2 = gelu(C)), 2 RESID (C = branch, OUT = X + rs*gamma*C),
-// 3 DGELU (C = gelu'(H) * (A B^T); colsum != NULL: octic_dense_gemm_colsum_rows() slabs [N] of column sums of C),
-// 4 GELUF (C = gelu'(pre-activation), C2 = gelu(pre-activation)), 5 DFACT (C = H * (A B^T), H = the factor of mode 4),
-// 6 GELUO (C = gelu(pre-activation) only: passes without a backward).
-// sample_scale / rows_per_sample: the stochastic-depth mask (see dense_item_masked); NULL = the unmasked launch.
-// adaptive: an eligible masked launch (dense_plan_adaptive) chooses its tile width on the device; anything else is untouched.
-static int dense_launch(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
-                        void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
-                        const float* X, float* OUT, const void* H, float* colsum, const float* sample_scale,
-                        int rows_per_sample, void* workspace, int tokens, void* stream, bool adaptive, bool fold_cls = false,
-                        double image_drop = 0.0) {
-  if (!A || !B || !C) return OCTIC_ENULL;
-  if (sample_scale && (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0)) return OCTIC_ESHAPE;
-  if (sample_scale && (((uintptr_t)sample_scale) & 3)) return OCTIC_EALIGN;
-  // (ldc % 8: every epilogue moves 8 bf16 = 16 bytes of a row of C / C2 / H per lane, from column offsets that are multiples of 8)
-  if (M <= 0 || N <= 0 || K <= 0 || (K % DG_BK) || K < 2 * DG_BK || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OCTIC_ESHAPE;
-  // buffer descriptors and per-lane offsets are 32-bit: operands of 2 GiB or more are refused (callers fall back to
-  // the BLAS library) instead of wrapping
-  if ((int64_t)M * lda * 2 >= (1ll << 31) || (int64_t)N * ldb * 2 >= (1ll << 31)) return OCTIC_ESHAPE;
-  if ((((uintptr_t)A) | ((uintptr_t)B)) & 15) return OCTIC_EALIGN;
-  if ((mode == DG_GELU || mode == DG_GELUF) && !C2) return OCTIC_ENULL;
-  if (mode == DG_RESID && (!X || !OUT || (rs && rps <= 0))) return OCTIC_ENULL;
-  if ((mode == DG_DGELU || mode == DG_DFACT) && !H) return OCTIC_ENULL;
-  DgArgs a = {};
-  a.A = (const bf16*)A; a.B = (const bf16*)B; a.lda = lda; a.ldb = ldb; a.M = M; a.N = N; a.K = K;
-  a.C = (bf16*)C; a.C2 = (bf16*)C2; a.ldc = ldc; a.bias = bias; a.gamma = gamma; a.rs = rs; a.rps = rs ? rps : 1;
-  a.X = X; a.OUT = OUT; a.H = (const bf16*)H; a.colsum = (mode == DG_DGELU || mode == DG_DFACT) ? colsum : nullptr;
-  DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
-  // image_drop > 0 (octic_dense_gemm_nt_tokens_image): a masked launch may leave classic panels for per-image ones
-  const DgImage img = dense_plan_image(tp, M, N, K, dense_cus(), mode, tokens, sample_scale != nullptr && mode != DG_RESID && image_drop > 0.0,
-                                       rows_per_sample, image_drop);
-  if (img.taken) {
-    tp.p = img.p;
-    tp.image = true;
-    tp.images = img.images;
-  }
-  const DgPlan p = tp.p;
-  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.full_tiles = p.full; a.split = p.split; a.tail_pad = p.tail_pad;
-  a.m_stride = tp.image ? tokens : DG_BM;
-  a.m_base = tp.image ? 1 : 0;
-  // the masked kernels take every mode but the fused residual tail, up to the bitmap's panels; anything else computes every row
-  const bool skip = sample_scale != nullptr && mode != DG_RESID && p.tiles_m <= kDgMaskCap;
-  a.sample_scale = skip ? sample_scale : nullptr;
-  a.rows_per_sample = skip ? rows_per_sample : 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (p.split > 1) {
-    if (!workspace) return OCTIC_ENULL;
-    if (p.rem * 4 > DG_TICKET_BYTES) return OCTIC_ESHAPE;
-    a.tickets = (int*)workspace;
-    a.slabs = (float*)((char*)workspace + DG_TICKET_BYTES);
-  }
-  const int smem = DgGeom<4>::LDS, smem5 = DgGeom<5>::LDS, bmb = kDgMaskWords * 8;
-  static DeviceOnce once;
-  if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_PLAIN, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_PLAIN, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, smem5);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELU, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_RESID, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_DGELU, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUF, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_DFACT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUO, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_PLAIN, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_PLAIN, 5, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem5 + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELU, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_DGELU, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUF, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_DFACT, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_kernel<DG_GELUO, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_adaptive_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem5 + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_adaptive_cls_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem5 + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_image_cls_kernel<DG_PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_image_cls_kernel<DG_GELUF>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
-    (void)hipFuncSetAttribute((const void*)dense_nt_image_cls_kernel<DG_DFACT>, hipFuncAttributeMaxDynamicSharedMemorySize, smem + bmb);
-    (void)hipGetLastError();
-  }
-  if (img.taken && img.fold) {
-    // the masked launch on per-image panels with the class-token workgroups behind its tiles: ONE launch, no dense_cls_* launch
-    const int cr0 = 2 * img.images;
-    switch (mode) {
-      case DG_PLAIN: dense_nt_image_cls_kernel<DG_PLAIN><<<img.grid, 512, smem + bmb, s>>>(a, tokens, img.images, img.tile_wgs, img.wgs, cr0); break;
-      case DG_GELUF: dense_nt_image_cls_kernel<DG_GELUF><<<img.grid, 512, smem + bmb, s>>>(a, tokens, img.images, img.tile_wgs, img.wgs, cr0); break;
-      case DG_DFACT: dense_nt_image_cls_kernel<DG_DFACT><<<img.grid, 512, smem + bmb, s>>>(a, tokens, img.images, img.tile_wgs, img.wgs, cr0); break;
-      default: return OCTIC_ESHAPE;
-    }
-    return launch_status();
-  }
-  const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), skip);
-  const DgFold fold = dense_plan_fold(ad, tp.images, N, K);
-  if (adaptive && fold_cls && fold.taken) {
-    // the adaptive launch below with the class-token workgroups behind its tiles: ONE launch, no dense_cls_* launch
-    a.tiles_n_narrow = ad.tiles_n_narrow;
-    a.cus = dense_cus();
-    a.narrow_force = ad.force;
-    dense_nt_adaptive_cls_kernel<<<fold.grid, 512, smem5 + bmb, s>>>(a, tokens, tp.images, fold.tile_wgs, fold.wgs);
-    return launch_status();
-  }
-  if (adaptive && ad.eligible) {
-    // same plan, same panels; the grid covers the tiles of either width and the workgroups past the chosen one return
-    a.tiles_n_narrow = ad.tiles_n_narrow;
-    a.cus = dense_cus();
-    a.narrow_force = ad.force;
-    dense_nt_adaptive_kernel<<<ad.grid, 512, smem5 + bmb, s>>>(a);
-  } else
-  if (skip) {
-    // same plan, same grid; the live bitmap sits behind the ring
-    switch (mode) {
-      case DG_PLAIN:
-        if (p.nt == 5) dense_nt_kernel<DG_PLAIN, 5, true><<<p.grid, 512, smem5 + bmb, s>>>(a);
-        else dense_nt_kernel<DG_PLAIN, 4, true><<<p.grid, 512, smem + bmb, s>>>(a);
-        break;
-      case DG_GELU: dense_nt_kernel<DG_GELU, 4, true><<<p.grid, 512, smem + bmb, s>>>(a); break;
-      case DG_DGELU: dense_nt_kernel<DG_DGELU, 4, true><<<p.grid, 512, smem + bmb, s>>>(a); break;
-      case DG_GELUF: dense_nt_kernel<DG_GELUF, 4, true><<<p.grid, 512, smem + bmb, s>>>(a); break;
-      case DG_DFACT: dense_nt_kernel<DG_DFACT, 4, true><<<p.grid, 512, smem + bmb, s>>>(a); break;
-      case DG_GELUO: dense_nt_kernel<DG_GELUO, 4, true><<<p.grid, 512, smem + bmb, s>>>(a); break;
-      default: return OCTIC_ESHAPE;
-    }
-  } else
-  switch (mode) {
-    case DG_PLAIN:
-      if (p.nt == 5) dense_nt_kernel<DG_PLAIN, 5><<<p.grid, 512, smem5, s>>>(a);
-      else dense_nt_kernel<DG_PLAIN, 4><<<p.grid, 512, smem, s>>>(a);
-      break;
-    case DG_GELU: dense_nt_kernel<DG_GELU, 4><<<p.grid, 512, smem, s>>>(a); break;
-    case DG_RESID: dense_nt_kernel<DG_RESID, 4><<<p.grid, 512, smem, s>>>(a); break;
-    case DG_DGELU: dense_nt_kernel<DG_DGELU, 4><<<p.grid, 512, smem, s>>>(a); break;
-    case DG_GELUF: dense_nt_kernel<DG_GELUF, 4><<<p.grid, 512, smem, s>>>(a); break;
-    case DG_DFACT: dense_nt_kernel<DG_DFACT, 4><<<p.grid, 512, smem, s>>>(a); break;
-    case DG_GELUO: dense_nt_kernel<DG_GELUO, 4><<<p.grid, 512, smem, s>>>(a); break;
-    default: return OCTIC_ESHAPE;
-  }
-  if (tp.image && dense_cls_two_launches(mode, N, K) && workspace && p.split <= 1) {
-    // (the partial tiles live where split-K slabs would: only with a main launch that splits nothing - N = 1280 at any batch
-    // that takes per-image panels; otherwise the single launch below)
-    const int rows_pad = (tp.images + 63) / 64 * 64;
-    float* part = (float*)((char*)workspace + DG_TICKET_BYTES);
-    // 64 or 80 columns per workgroup: whichever keeps the grid within ONE workgroup per CU (a CU sustains ~25 GB/s of
-    // first-touch loads: 320 workgroups on 256 CUs took 14.1 us where 240 took 8.2)
-    const int cus = dense_cus(), per64 = (N / 64) * (K / CLS_KSLICE) * (rows_pad / 64);
-    const int nw = (per64 > cus && (N % 80) == 0 && (N / 80) * (K / CLS_KSLICE) * (rows_pad / 64) <= cus) ? 5 : 4;
-    dense_cls_part_kernel<<<(N / (16 * nw)) * (K / CLS_KSLICE) * (rows_pad / 64), 64 * nw, 0, s>>>(a, tokens, tp.images, rows_pad, part);
-    dense_cls_sum_kernel<<<(tp.images * (N / 4) + 255) / 256, 256, 0, s>>>(a, tokens, tp.images, rows_pad, part);
-  } else if (tp.image) {
-    // the class-token rows: row b * tokens of A / C / C2 / H, colsum slab rows behind the panels' 2 * images
-    const int grid = (N / 16) * ((tp.images + 15) / 16), cr0 = 2 * tp.images, thr = 64 * dense_cls_waves(K);
-    switch (mode) {
-      case DG_PLAIN: dense_cls_kernel<DG_PLAIN><<<grid, thr, 0, s>>>(a, tokens, tp.images, cr0); break;
-      case DG_GELU: dense_cls_kernel<DG_GELU><<<grid, thr, 0, s>>>(a, tokens, tp.images, cr0); break;
-      case DG_DGELU: dense_cls_kernel<DG_DGELU><<<grid, thr, 0, s>>>(a, tokens, tp.images, cr0); break;
-      case DG_GELUF: dense_cls_kernel<DG_GELUF><<<grid, thr, 0, s>>>(a, tokens, tp.images, cr0); break;
-      case DG_DFACT: dense_cls_kernel<DG_DFACT><<<grid, thr, 0, s>>>(a, tokens, tp.images, cr0); break;
-      case DG_GELUO: dense_cls_kernel<DG_GELUO><<<grid, thr, 0, s>>>(a, tokens, tp.images, cr0); break;
-      default: return OCTIC_ESHAPE;
-    }
-  }
-  return launch_status();
+  return dg_slab_rows(M, false, 0);
 }
 
 int octic_dense_gemm_nt_tokens_skip(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
@@ -1830,154 +1928,6 @@ int octic_dense_gemm_nt_tokens_adaptive_cls(const void* A, const void* B, int M,
                       rows_per_sample, workspace, tokens, stream, true, fold_cls != 0);
 }
 
-int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
-                               void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
-                               const float* X, float* OUT, const void* H, float* colsum, void* workspace, int tokens,
-                               void* stream) {
-  return octic_dense_gemm_nt_tokens_skip(A, B, M, N, K, lda, ldb, mode, C, C2, ldc, bias, gamma, rs, rps, X, OUT, H, colsum,
-                                         nullptr, 0, workspace, tokens, stream);
-}
-
-// The plan in force for a masked launch: the unmasked launch's (a mask changes which workgroup takes which tile, nothing else).
-int octic_dense_gemm_plan_dropped(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out) {
-  if (!out) return OCTIC_ENULL;
-  if (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0) return OCTIC_ESHAPE;
-  return octic_dense_gemm_plan(M, N, K, mode, tokens, out);
-}
-
-// What a masked launch gives each workgroup, in blockIdx order, by the kernel's own mapping (dense_item_masked): sample_scale is
-// a HOST array here.  out_tm / out_tn = the tile (-1 = a padding workgroup), out_part = K part (0 for full tiles), out_split = 1
-// for an item of the split-K front, out_dead = 1 for a dead tile; each may be NULL.  `cap` = entries the arrays hold.  Returns
-// the number of workgroups; OCTIC_ESHAPE for a launch the masked kernel does not take (the unmasked kernel runs it) or cap < that.
-int octic_dense_gemm_order_dropped(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
-                                   int cap, int* out_tm, int* out_tn, int* out_part, int* out_split, int* out_dead) {
-  if (!sample_scale) return OCTIC_ENULL;
-  if (M <= 0 || N <= 0 || K < 2 * DG_BK || rows_per_sample <= 0 || (M % rows_per_sample) != 0 || mode == DG_RESID) return OCTIC_ESHAPE;
-  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
-  const DgPlan p = tp.p;
-  if (p.tiles_m > kDgMaskCap || cap < p.grid) return OCTIC_ESHAPE;
-  unsigned long long bm[kDgMaskWords] = {};
-  for (int tm = 0; tm < p.tiles_m; ++tm)
-    if (dg_panel_live(sample_scale, rows_per_sample, M, tp.image ? tokens : DG_BM, tp.image ? 1 : 0, tm)) bm[tm >> 6] |= 1ull << (tm & 63);
-  for (int bid = 0; bid < p.grid; ++bid) {
-    int tile, rem_idx, part, tm = -1, tn = -1;
-    bool dead;
-    dense_item_masked(p.tiles_m, p.tiles_n, p.full, p.split, p.tail_pad, bid, bm, tile, rem_idx, part, dead);
-    if (tile >= 0) dg_tile_panel(p.tiles_m, p.tiles_n, tile, tm, tn);
-    if (out_tm) out_tm[bid] = tm;
-    if (out_tn) out_tn[bid] = tn;
-    if (out_part) out_part[bid] = part;
-    if (out_split) out_split[bid] = rem_idx >= 0 ? 1 : 0;
-    if (out_dead) out_dead[bid] = dead ? 1 : 0;
-  }
-  return p.grid;
-}
-
-// What octic_dense_gemm_nt_tokens_adaptive does with a masked launch of this problem: out[0] = 1 if the adaptive kernel takes it
-// (else it is octic_dense_gemm_nt_tokens_skip), out[1] = workgroups of the main launch, out[2] / out[3] = the two tile widths
-// (320, 256), out[4] = the largest live-panel count that still runs the 256-wide tile under the rule (-1: 256 does not divide N).
-int octic_dense_gemm_plan_adaptive(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out) {
-  if (!out) return OCTIC_ENULL;
-  if (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0 || N <= 0 || K < 2 * DG_BK) return OCTIC_ESHAPE;
-  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
-  const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), mode != DG_RESID);
-  out[0] = ad.eligible ? 1 : 0;
-  out[1] = ad.grid;
-  out[2] = 320;
-  out[3] = 256;
-  out[4] = ad.max_live;
-  return OCTIC_OK;
-}
-
-// What the adaptive launch gives each workgroup, in blockIdx order, by the kernel's own functions (dense_item_adaptive):
-// sample_scale is a HOST array.  out_tm / out_tn = the tile at the chosen width (-1 = the workgroup returns), out_dead = 1 for a
-// dead tile (each may be NULL, `cap` entries), *out_width = 256 | 320.  Returns the number of workgroups; OCTIC_ESHAPE for a
-// launch the adaptive kernel does not take or cap < that.
-int octic_dense_gemm_order_adaptive(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
-                                    int cap, int* out_tm, int* out_tn, int* out_dead, int* out_width) {
-  if (!sample_scale) return OCTIC_ENULL;
-  if (M <= 0 || N <= 0 || K < 2 * DG_BK || rows_per_sample <= 0 || (M % rows_per_sample) != 0) return OCTIC_ESHAPE;
-  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
-  const DgPlan p = tp.p;
-  const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), true);
-  if (!ad.eligible || cap < ad.grid) return OCTIC_ESHAPE;
-  unsigned long long bm[kDgMaskWords] = {};
-  for (int tm = 0; tm < p.tiles_m; ++tm)
-    if (dg_panel_live(sample_scale, rows_per_sample, M, tokens, 1, tm)) bm[tm >> 6] |= 1ull << (tm & 63);
-  bool narrow = false;
-  for (int bid = 0; bid < ad.grid; ++bid) {
-    int tile, tm = -1, tn = -1;
-    bool dead;
-    dense_item_adaptive(p.tiles_m, p.tiles_n, ad.tiles_n_narrow, dense_cus(), ad.force, bid, bm, narrow, tile, dead);
-    if (tile >= 0) dg_tile_panel(p.tiles_m, narrow ? ad.tiles_n_narrow : p.tiles_n, tile, tm, tn);
-    if (out_tm) out_tm[bid] = tm;
-    if (out_tn) out_tn[bid] = tn;
-    if (out_dead) out_dead[bid] = dead ? 1 : 0;
-  }
-  if (out_width) *out_width = narrow ? 256 : 320;
-  return ad.grid;
-}
-
-// What octic_dense_gemm_nt_tokens_adaptive_cls (fold_cls != 0) does with a masked launch of this problem: out[0] = 1 if the folded
-// kernel takes it (else it is the adaptive call), out[1] = workgroups of the launch, out[2] = class-token workgroups among them
-// (the last ones), out[3] = class-token items (16 rows x 16 columns) of the busiest of those, out[4] = tile workgroups in front.
-int octic_dense_gemm_plan_adaptive_cls(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out) {
-  if (!out) return OCTIC_ENULL;
-  if (rows_per_sample <= 0 || M <= 0 || (M % rows_per_sample) != 0 || N <= 0 || K < 2 * DG_BK) return OCTIC_ESHAPE;
-  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
-  const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), mode != DG_RESID);
-  const DgFold f = dense_plan_fold(ad, tp.images, N, K);
-  out[0] = f.taken ? 1 : 0;
-  out[1] = f.grid;
-  out[2] = f.wgs;
-  out[3] = f.per_wg;
-  out[4] = f.tile_wgs;
-  return OCTIC_OK;
-}
-
-// What the folded launch gives each workgroup, in blockIdx order, by the kernel's own functions (dg_fold_wg, dense_item_adaptive,
-// dg_fold_item): sample_scale is a HOST array.  out_tm / out_tn / out_dead / out_width: as octic_dense_gemm_order_adaptive, one
-// entry per workgroup (`cap` entries; -1 / 0 for a class-token workgroup).  out_cls_rt / out_cls_ct: row tile and column tile of
-// the class-token items, per_wg (out[3] of the plan) entries per class-token workgroup in the order it takes them, -1 = none
-// (`cls_cap` entries each; each may be NULL).  Returns the number of workgroups; OCTIC_ESHAPE for a launch the folded kernel does
-// not take or a cap too small.
-int octic_dense_gemm_order_adaptive_cls(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
-                                        int cap, int* out_tm, int* out_tn, int* out_dead, int* out_width, int cls_cap,
-                                        int* out_cls_rt, int* out_cls_ct) {
-  if (!sample_scale) return OCTIC_ENULL;
-  if (M <= 0 || N <= 0 || K < 2 * DG_BK || rows_per_sample <= 0 || (M % rows_per_sample) != 0) return OCTIC_ESHAPE;
-  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
-  const DgPlan p = tp.p;
-  const DgAdaptive ad = dense_plan_adaptive(tp, N, mode, dense_cus(), true);
-  const DgFold f = dense_plan_fold(ad, tp.images, N, K);
-  if (!f.taken || cap < f.grid || ((out_cls_rt || out_cls_ct) && cls_cap < f.wgs * f.per_wg)) return OCTIC_ESHAPE;
-  unsigned long long bm[kDgMaskWords] = {};
-  for (int tm = 0; tm < p.tiles_m; ++tm)
-    if (dg_panel_live(sample_scale, rows_per_sample, M, tokens, 1, tm)) bm[tm >> 6] |= 1ull << (tm & 63);
-  const int nks = K / CLS_KSLICE, ipp = dg_fold_ipp(nks), ntn = N >> 4, items = dg_fold_items(N, tp.images);
-  bool narrow = dg_adaptive_narrow(dg_live_panels(bm, p.tiles_m), ad.tiles_n_narrow, dense_cus(), ad.force);
-  for (int bid = 0; bid < f.grid; ++bid) {
-    int tile = -1, tm = -1, tn = -1;
-    bool dead = false;
-    const int cw = dg_fold_wg(bid, f.tile_wgs);
-    if (cw < 0) {
-      dense_item_adaptive(p.tiles_m, p.tiles_n, ad.tiles_n_narrow, dense_cus(), ad.force, bid, bm, narrow, tile, dead);
-      if (tile >= 0) dg_tile_panel(p.tiles_m, narrow ? ad.tiles_n_narrow : p.tiles_n, tile, tm, tn);
-    } else {
-      for (int e = 0; e < f.per_wg; ++e) {
-        const int item = dg_fold_item(items, ipp, f.wgs, cw, e / ipp, e % ipp);
-        if (out_cls_rt) out_cls_rt[cw * f.per_wg + e] = item >= 0 ? item / ntn : -1;
-        if (out_cls_ct) out_cls_ct[cw * f.per_wg + e] = item >= 0 ? item % ntn : -1;
-      }
-    }
-    if (out_tm) out_tm[bid] = tm;
-    if (out_tn) out_tn[bid] = tn;
-    if (out_dead) out_dead[bid] = dead ? 1 : 0;
-  }
-  if (out_width) *out_width = narrow ? 256 : 320;
-  return f.grid;
-}
-
 // octic_dense_gemm_nt_tokens_adaptive_cls for a launch under the mask of a branch that drops a sample with probability `drop`:
 // a launch that call keeps on classic panels may run on per-image panels with its class-token rows folded (dense_plan_image,
 // dense_nt_image_cls_kernel); drop <= 0, no mask, or any launch dense_plan_image does not take: exactly that call
@@ -1990,65 +1940,12 @@ int octic_dense_gemm_nt_tokens_image(const void* A, const void* B, int M, int N,
                       rows_per_sample, workspace, tokens, stream, true, fold_cls != 0, drop > 0.0 ? drop : 0.0);
 }
 
-// What octic_dense_gemm_nt_tokens_image does with a launch of this problem (masked != 0: a sample_scale is given): out[0] = 1 if it
-// leaves the former call's plan for per-image panels, out[1] = workgroups of the main launch, out[2] = class-token workgroups among
-// them (the last ones; 0 = the class-token rows have a launch of their own, or the plan is the former call's), out[3] = class-token
-// items of the busiest of those, out[4] = tile workgroups in front, out[5] = tile width of the plan in force (256 | 320), out[6] =
-// colsum slab rows of modes 3 / 5 under the plan in force, out[7] = 1 if the plan in force is per-image panels (either call's).
-int octic_dense_gemm_plan_image(int M, int N, int K, int mode, int tokens, int rows_per_sample, int masked, double drop, int* out) {
-  if (!out) return OCTIC_ENULL;
-  if (M <= 0 || N <= 0 || K < 2 * DG_BK) return OCTIC_ESHAPE;
-  if (masked && (rows_per_sample <= 0 || (M % rows_per_sample) != 0)) return OCTIC_ESHAPE;
-  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
-  const DgImage d = dense_plan_image(tp, M, N, K, dense_cus(), mode, tokens, masked != 0 && mode != DG_RESID && drop > 0.0, rows_per_sample, drop);
-  const bool image = d.taken || tp.image;
-  const int images = d.taken ? d.images : tp.images;
-  out[0] = d.taken ? 1 : 0;
-  out[1] = d.grid;
-  out[2] = d.wgs;
-  out[3] = d.per_wg;
-  out[4] = d.taken ? d.tile_wgs : tp.p.grid;
-  out[5] = d.p.nt == 5 ? 320 : 256;
-  out[6] = image ? 2 * images + (images + 15) / 16 : 2 * ((M + DG_BM - 1) / DG_BM);
-  out[7] = image ? 1 : 0;
-  return OCTIC_OK;
-}
-
-// What a launch that octic_dense_gemm_plan_image reports taken gives each workgroup, in blockIdx order, by the kernel's own functions
-// (dg_fold_wg, dense_item_masked, dg_fold_item): sample_scale is a HOST array.  out_tm / out_tn / out_dead: one entry per workgroup
-// (`cap` entries; -1 / -1 / 0 for a class-token workgroup); out_cls_rt / out_cls_ct: as octic_dense_gemm_order_adaptive_cls.  Returns
-// the number of workgroups; OCTIC_ESHAPE for a launch not taken or a cap too small.
-int octic_dense_gemm_order_image(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample, double drop,
-                                 int cap, int* out_tm, int* out_tn, int* out_dead, int cls_cap, int* out_cls_rt, int* out_cls_ct) {
-  if (!sample_scale) return OCTIC_ENULL;
-  if (M <= 0 || N <= 0 || K < 2 * DG_BK || rows_per_sample <= 0 || (M % rows_per_sample) != 0) return OCTIC_ESHAPE;
-  const DgTokPlan tp = dense_plan_tokens(M, N, K, dense_cus(), mode, tokens);
-  const DgImage d = dense_plan_image(tp, M, N, K, dense_cus(), mode, tokens, mode != DG_RESID && drop > 0.0, rows_per_sample, drop);
-  if (!d.taken || cap < d.grid || ((out_cls_rt || out_cls_ct) && cls_cap < d.wgs * d.per_wg)) return OCTIC_ESHAPE;
-  const DgPlan& p = d.p;
-  unsigned long long bm[kDgMaskWords] = {};
-  for (int tm = 0; tm < p.tiles_m; ++tm)
-    if (dg_panel_live(sample_scale, rows_per_sample, M, tokens, 1, tm)) bm[tm >> 6] |= 1ull << (tm & 63);
-  const int nks = K / CLS_KSLICE, ipp = d.wgs > 0 ? dg_fold_ipp(nks) : 1, ntn = N >> 4, items = dg_fold_items(N, d.images);
-  for (int bid = 0; bid < d.grid; ++bid) {
-    int tile = -1, tm = -1, tn = -1, rem_idx, part;
-    bool dead = false;
-    const int cw = dg_fold_wg(bid, d.tile_wgs);
-    if (cw < 0) {
-      dense_item_masked(p.tiles_m, p.tiles_n, p.full, 1, 0, bid, bm, tile, rem_idx, part, dead);
-      if (tile >= 0) dg_tile_panel(p.tiles_m, p.tiles_n, tile, tm, tn);
-    } else {
-      for (int e = 0; e < d.per_wg; ++e) {
-        const int item = dg_fold_item(items, ipp, d.wgs, cw, e / ipp, e % ipp);
-        if (out_cls_rt) out_cls_rt[cw * d.per_wg + e] = item >= 0 ? item / ntn : -1;
-        if (out_cls_ct) out_cls_ct[cw * d.per_wg + e] = item >= 0 ? item % ntn : -1;
-      }
-    }
-    if (out_tm) out_tm[bid] = tm;
-    if (out_tn) out_tn[bid] = tn;
-    if (out_dead) out_dead[bid] = dead ? 1 : 0;
-  }
-  return d.grid;
+int octic_dense_gemm_nt_tokens(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
+                               void* C2, int64_t ldc, const float* bias, const float* gamma, const float* rs, int64_t rps,
+                               const float* X, float* OUT, const void* H, float* colsum, void* workspace, int tokens,
+                               void* stream) {
+  return octic_dense_gemm_nt_tokens_skip(A, B, M, N, K, lda, ldb, mode, C, C2, ldc, bias, gamma, rs, rps, X, OUT, H, colsum,
+                                         nullptr, 0, workspace, tokens, stream);
 }
 
 int octic_dense_gemm_nt(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int mode, void* C,
@@ -2058,4 +1955,87 @@ int octic_dense_gemm_nt(const void* A, const void* B, int M, int N, int K, int64
                                     workspace, 0, stream);
 }
 
+// The plan in force for a masked launch: the unmasked launch's (a mask changes which workgroup takes which tile, nothing else).
+int octic_dense_gemm_plan_dropped(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out) {
+  if (!out) return OCTIC_ENULL;
+  if (!dg_mask_ok(M, rows_per_sample)) return OCTIC_ESHAPE;
+  return octic_dense_gemm_plan(M, N, K, mode, tokens, out);
+}
+
+// The plan and order queries below read fields of the resolved launch or walk it; include/octic_hip.h documents what each reports.
+int octic_dense_gemm_plan_adaptive(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out) {
+  if (!out) return OCTIC_ENULL;
+  if (!dg_mask_ok(M, rows_per_sample) || !dg_shape_ok(M, N, K)) return OCTIC_ESHAPE;
+  const DgLaunch L = dense_query(M, N, K, mode, tokens, true, rows_per_sample, true, false, 0.0);
+  out[0] = L.family == DG_FAM_ADAPTIVE ? 1 : 0;
+  out[1] = L.grid;
+  out[2] = 320;
+  out[3] = 256;
+  out[4] = L.max_live;
+  return OCTIC_OK;
+}
+
+int octic_dense_gemm_plan_adaptive_cls(int M, int N, int K, int mode, int tokens, int rows_per_sample, int* out) {
+  if (!out) return OCTIC_ENULL;
+  if (!dg_mask_ok(M, rows_per_sample) || !dg_shape_ok(M, N, K)) return OCTIC_ESHAPE;
+  const DgLaunch L = dense_query(M, N, K, mode, tokens, true, rows_per_sample, true, true, 0.0);
+  out[0] = L.family == DG_FAM_ADAPTIVE_CLS ? 1 : 0;
+  out[1] = L.grid;
+  out[2] = L.wgs;
+  out[3] = L.per_wg;
+  out[4] = L.tile_wgs;
+  return OCTIC_OK;
+}
+
+// (where the launch is not taken the workgroups are the former call's, as octic_dense_gemm_plan reports them: no adaptive grid)
+int octic_dense_gemm_plan_image(int M, int N, int K, int mode, int tokens, int rows_per_sample, int masked, double drop, int* out) {
+  if (!out) return OCTIC_ENULL;
+  if (!dg_shape_ok(M, N, K) || (masked && !dg_mask_ok(M, rows_per_sample))) return OCTIC_ESHAPE;
+  const DgLaunch L = dense_query(M, N, K, mode, tokens, masked != 0, rows_per_sample, false, false, drop);
+  out[0] = L.moved ? 1 : 0;
+  out[1] = L.grid;
+  out[2] = L.wgs;
+  out[3] = L.per_wg;
+  out[4] = L.tile_wgs;
+  out[5] = L.width;
+  out[6] = L.slab_rows;
+  out[7] = L.image ? 1 : 0;
+  return OCTIC_OK;
+}
+
+// a launch the masked kernel does not take (the unmasked kernel runs it) is refused
+int octic_dense_gemm_order_dropped(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
+                                   int cap, int* out_tm, int* out_tn, int* out_part, int* out_split, int* out_dead) {
+  if (const int rc = dense_order_check(M, N, K, sample_scale, rows_per_sample)) return rc;
+  const DgLaunch L = dense_query(M, N, K, mode, tokens, true, rows_per_sample, false, false, 0.0);
+  if (L.family != DG_FAM_MASKED) return OCTIC_ESHAPE;
+  return dense_walk(L, M, N, K, sample_scale, rows_per_sample, {cap, out_tm, out_tn, out_part, out_split, out_dead, nullptr, 0, nullptr, nullptr});
+}
+
+int octic_dense_gemm_order_adaptive(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
+                                    int cap, int* out_tm, int* out_tn, int* out_dead, int* out_width) {
+  if (const int rc = dense_order_check(M, N, K, sample_scale, rows_per_sample)) return rc;
+  const DgLaunch L = dense_query(M, N, K, mode, tokens, true, rows_per_sample, true, false, 0.0);
+  if (L.family != DG_FAM_ADAPTIVE) return OCTIC_ESHAPE;
+  return dense_walk(L, M, N, K, sample_scale, rows_per_sample, {cap, out_tm, out_tn, nullptr, nullptr, out_dead, out_width, 0, nullptr, nullptr});
+}
+
+int octic_dense_gemm_order_adaptive_cls(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample,
+                                        int cap, int* out_tm, int* out_tn, int* out_dead, int* out_width, int cls_cap,
+                                        int* out_cls_rt, int* out_cls_ct) {
+  if (const int rc = dense_order_check(M, N, K, sample_scale, rows_per_sample)) return rc;
+  const DgLaunch L = dense_query(M, N, K, mode, tokens, true, rows_per_sample, true, true, 0.0);
+  if (L.family != DG_FAM_ADAPTIVE_CLS) return OCTIC_ESHAPE;
+  return dense_walk(L, M, N, K, sample_scale, rows_per_sample, {cap, out_tm, out_tn, nullptr, nullptr, out_dead, out_width, cls_cap, out_cls_rt, out_cls_ct});
+}
+
+int octic_dense_gemm_order_image(int M, int N, int K, int mode, int tokens, const float* sample_scale, int rows_per_sample, double drop,
+                                 int cap, int* out_tm, int* out_tn, int* out_dead, int cls_cap, int* out_cls_rt, int* out_cls_ct) {
+  if (const int rc = dense_order_check(M, N, K, sample_scale, rows_per_sample)) return rc;
+  const DgLaunch L = dense_query(M, N, K, mode, tokens, true, rows_per_sample, false, false, drop);
+  if (!L.moved) return OCTIC_ESHAPE;
+  return dense_walk(L, M, N, K, sample_scale, rows_per_sample, {cap, out_tm, out_tn, nullptr, nullptr, out_dead, nullptr, cls_cap, out_cls_rt, out_cls_ct});
+}
+
 }  // extern "C"
+

@@ -1393,6 +1393,23 @@ def _dense_image():
     return functional.DENSE_NT_SKIP_DROPPED and functional.DENSE_IMAGE_DROPPED
 
 
+def _dense_entry(M, N, K, mode, tokens, ss, srps, fold_cls, drop):
+    """(C entry point, its arguments between `tokens` and the stream, tile width, colsum slab rows) of a dense_gemm_nt call: the
+    switches of functional pick the entry (the library decides which launches it changes); width and slab rows are the plan's in
+    force, with a mask or without - colsum rows and the timer name belong to it."""
+    if ss is not None and drop is not None and float(drop) > 0.0 and _dense_image():
+        image = dense_plan_image(M, N, K, mode, tokens, srps, drop)
+        if image[0]:                                          # (not taken: the former call, the former plan)
+            return lib().octic_dense_gemm_nt_tokens_image, (0, float(drop)), image[5], image[6]
+    width, slab_rows = dense_plan(M, N, K, mode, tokens)[:2]
+    if ss is not None and fold_cls and _dense_cls_fold():
+        return lib().octic_dense_gemm_nt_tokens_adaptive_cls, (1,), width, slab_rows
+    # a masked launch may choose its tile width on the device (functional.DENSE_NARROW_DROPPED)
+    if ss is not None and _dense_narrow():
+        return lib().octic_dense_gemm_nt_tokens_adaptive, (), width, slab_rows
+    return lib().octic_dense_gemm_nt_tokens_skip, (), width, slab_rows
+
+
 def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h=None, name=None, want_colsum=False,
                   tokens=0, sample_scale=None, rows_per_sample=0, fold_cls=False, drop=None):
     """C[M,N] = a[M,K] @ b[N,K]^T on the hand-written MFMA kernel (csrc/dense_gemm.hip) with a fused tail:
@@ -1421,29 +1438,12 @@ def dense_gemm_nt(a, b, mode=0, bias=None, gamma=None, rs=None, rps=1, x=None, h
     if sample_scale is not None and mode == 2:
         raise ValueError("dense_gemm_nt: the fused residual tail (mode 2) takes no sample_scale")
     ss, srps = _sample_scale(sample_scale, rows_per_sample, M, a, "dense_gemm_nt")
-    # the plan in force, with a mask or without: colsum rows, the timer name and (through the library's own sizing) the
-    # workspace belong to it
-    image = (dense_plan_image(M, N, K, mode, tokens, srps, drop)
-             if (ss is not None and drop is not None and float(drop) > 0.0 and _dense_image()) else None)
-    if image is not None and not image[0]:
-        image = None                                          # not taken: the former call, the former plan
-    width, slab_rows = (image[5], image[6]) if image is not None else dense_plan(M, N, K, mode, tokens)[:2]
+    entry, extra, width, slab_rows = _dense_entry(M, N, K, mode, tokens, ss, srps, fold_cls, drop)
     cs_rows = slab_rows if (mode in (3, 5) and want_colsum) else 0
     cs = torch.empty((cs_rows, N), dtype=torch.float32, device=a.device) if cs_rows else None
-    # a masked launch may choose its tile width on the device (functional.DENSE_NARROW_DROPPED; the library decides which launches)
-    entry = lib().octic_dense_gemm_nt_tokens_adaptive if (ss is not None and _dense_narrow()) else lib().octic_dense_gemm_nt_tokens_skip
     t = KERNEL_TIMER.start()
-    if image is not None:
-        check(lib().octic_dense_gemm_nt_tokens_image(
-            _p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias), _p(gamma), _p(rs), int(rps),
-            _p(x), _p(out), _p(h), _p(cs), _p(ss), srps, _p(ws), tokens, 0, float(drop), _stream(a)))
-    elif fold_cls and ss is not None and _dense_cls_fold():
-        check(lib().octic_dense_gemm_nt_tokens_adaptive_cls(
-            _p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias), _p(gamma), _p(rs), int(rps),
-            _p(x), _p(out), _p(h), _p(cs), _p(ss), srps, _p(ws), tokens, 1, _stream(a)))
-    else:
-        check(entry(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias), _p(gamma), _p(rs), int(rps),
-                    _p(x), _p(out), _p(h), _p(cs), _p(ss), srps, _p(ws), tokens, _stream(a)))
+    check(entry(_p(a), _p(b), M, N, K, a.stride(0), b.stride(0), mode, _p(c), _p(c2), N, _p(bias), _p(gamma), _p(rs), int(rps),
+                _p(x), _p(out), _p(h), _p(cs), _p(ss), srps, _p(ws), tokens, *extra, _stream(a)))
     if t is not None:
         nb = 2 * (M * K + N * K + M * N * (2 if mode in (1, 3, 4, 5) else 1)) + (8 * M * N if mode == 2 else 0)
         # "@320": the launch ran the 256 x 320 tile (kernel symbol dense_nt_kernel<0, 5>), else <mode, 4>
