@@ -1205,6 +1205,35 @@ int octic_mix_targets(const int64_t* labels, const octic_mix_row* table, int B, 
 int octic_mix_bce(const void* logits, int dtype, int64_t ldl, const int64_t* labels, const octic_mix_row* table, int B, int row0,
                   int rows, int num_classes, float on, float off, int binarize, float* loss, const float* gscale,
                   void* dlogits, int64_t ldd, void* workspace, void* stream);
+/* The soft-target cross entropy of the reference loop without --bce-loss (timm's SoftTargetCrossEntropy, deit/main.py:372-374)
+ * of logits [rows, num_classes] (f32 or bf16, row stride ldl >= num_classes) against the NON-binarised targets t that
+ * octic_mix_targets would write for the same arguments, without materialising them; labels, table, B, row0, rows as for
+ * octic_mix_bce.  With the identity table (partner = the row itself, lam = 1) and on = 1 - s + s / C, off = s / C it is timm's
+ * LabelSmoothingCrossEntropy(s), at s = 0 nn.CrossEntropyLoss (main.py:375-378).  Per row, m = max x, se = sum expf(x - m),
+ * S = sum t, and   row = S (m + log se) - sum t x:   the exponentials and targets in f32, the sums over the row and the row
+ * value in f64 in a fixed order that depends on num_classes and the dtype only (not on ldl, alignment or rows) - so finite logits
+ * of any size the dtype holds give a finite row value; a non-finite logit gives a non-finite loss.  Each output is optional (not both
+ * NULL):  loss[0] (DEVICE f32) = the mean of the row values over rows, needs workspace (rows doubles, 8-byte aligned);
+ * dlogits (the logits' dtype, row stride ldd) = gscale[0] (S expf(x - m) / se - t) / rows, gscale a DEVICE f32 (NULL = 1).
+ * One workgroup per row.  num_classes >= 2, any value: up to 24576 the row is read from memory once and kept in registers (two
+ * instantiations: up to 2048, up to 24576); above that every pass re-reads it (three reads, one for a loss-only or two for a
+ * gradient-only call less).  16-byte accesses where the operand's base and row stride are multiples of 16 bytes, element
+ * accesses otherwise and at a row's ragged end; nothing outside [row start, row start + num_classes) is touched.          */
+int octic_mix_ce(const void* logits, int dtype, int64_t ldl, const int64_t* labels, const octic_mix_row* table, int B, int row0,
+                 int rows, int num_classes, float on, float off, float* loss, const float* gscale, void* dlogits, int64_t ldd,
+                 void* workspace, void* stream);
+/* The loss of --cosub (deit/engine.py:50-65): logits [2 rows, num_classes] (f32 or bf16, row stride ldl) - row r is the first
+ * pass of batch sample row0 + r, row rows + r its second pass; a, b = the two halves.  With t as for octic_mix_bce (binarised when
+ * binarize != 0) and bce(x, t) its per-element expression:
+ *   loss[0] = 0.25 [ mean bce(a, t) + mean bce(b, t) + mean bce(a, sigmoid(b)) + mean bce(b, sigmoid(a)) ],
+ * each mean over rows num_classes elements, the sigmoid targets constants (`.detach()`); f64 sums in a fixed order.
+ *   dlogits [2 rows, num_classes] (row stride ldd): da = gscale[0] 0.25 / (rows num_classes) [ (sigmoid(a) - t) + (sigmoid(a) -
+ *   sigmoid(b)) ], db its mirror image.
+ * One launch reads both halves once and writes both gradients; exchanging the halves exchanges the gradients and keeps the loss,
+ * bit for bit.  Outputs, gscale and workspace (rows doubles) as for octic_mix_bce.  num_classes >= 2.                     */
+int octic_cosub_bce(const void* logits, int dtype, int64_t ldl, const int64_t* labels, const octic_mix_row* table, int B, int row0,
+                    int rows, int num_classes, float on, float off, int binarize, float* loss, const float* gscale, void* dlogits,
+                    int64_t ldd, void* workspace, void* stream);
 
 /* ---- 3-Augment of the DeiT-III recipe on uint8 batches (deit/augment.py:90-123 behind the crop) ---------------------------
  * RandomHorizontalFlip, RandomChoice(grayscale, solarize, Gaussian blur), ColorJitter(brightness, contrast, saturation),

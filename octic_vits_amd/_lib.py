@@ -276,6 +276,10 @@ _PROTOS = {
     "octic_mix_targets": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p]),
     "octic_mix_bce": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
                               c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
+    "octic_mix_ce": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
+                             c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
+    "octic_cosub_bce": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
+                                c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     "octic_augment_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
     "octic_augment_u8": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_float] * 6 + [c_int, c_int, c_int, c_void_p, c_void_p]),
     "octic_dino_resize_coeffs": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -38,7 +38,8 @@ import torch
 
 from . import ops
 
-__all__ = ["Mixup", "MixParams", "mix_images", "mix_targets", "mix_bce_loss", "TableUploader"]
+__all__ = ["Mixup", "MixParams", "mix_images", "mix_targets", "mix_bce_loss", "mix_ce_loss", "cosub_bce_loss", "smoothing_on_off",
+           "TableUploader"]
 
 
 @dataclass
@@ -292,6 +293,80 @@ def mix_bce_loss(logits, labels, table, on=1.0, off=0.0, binarize=True, row0=0):
     if logits.stride(1) != 1:
         logits = logits.contiguous()
     return _MixBceFn.apply(logits, labels, table, float(on), float(off), bool(binarize), int(row0))
+
+
+def smoothing_on_off(smoothing, num_classes):
+    """timm's one-hot values for label smoothing ``s`` over C classes: ``off = s / C``, ``on = 1 - s + off``; returns (on, off).
+    ``mix_ce_loss`` with these and the identity table (``MixParams.identity(B)``) is ``LabelSmoothingCrossEntropy(s)``, at
+    ``s = 0`` plain cross entropy."""
+    off = smoothing / num_classes
+    return 1. - smoothing + off, off
+
+
+def _loss_logits(what, logits, rows_multiple=1):
+    ops._require_cuda(logits)
+    if logits.dim() != 2 or logits.shape[0] % rows_multiple:
+        raise ValueError(f"{what}: logits must be [{'2 ' if rows_multiple == 2 else ''}rows, num_classes]")
+    return logits if logits.stride(1) == 1 else logits.contiguous()
+
+
+class _MixCeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, table, on, off, row0):
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        ws = torch.empty(logits.shape[0], dtype=torch.float64, device=logits.device)
+        ops.mix_ce(logits, labels, table, on, off, row0=row0, loss=loss, workspace=ws)
+        ctx.save_for_backward(logits, labels, table)
+        ctx.args = (on, off, row0)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        logits, labels, table = ctx.saved_tensors
+        on, off, row0 = ctx.args
+        g = grad.to(torch.float32).reshape(1).contiguous()     # (stays on the device, as in _MixBceFn)
+        d = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device)
+        ops.mix_ce(logits, labels, table, on, off, row0=row0, gscale=g, dlogits=d)
+        return d, None, None, None, None, None
+
+
+def mix_ce_loss(logits, labels, table, on=1.0, off=0.0, row0=0):
+    """timm's ``SoftTargetCrossEntropy()(logits.float(), targets)`` = ``sum(-targets * log_softmax(logits), -1).mean()`` for the
+    NON-binarised targets ``mix_targets(labels, table, C, on, off, False, row0, rows)`` without materialising them; logits f32 or
+    bf16 [rows, C], differentiable in the logits (the gradient comes back in their dtype, scaled by the incoming gradient on the
+    device).  With the identity table and ``smoothing_on_off(s, C)`` it is ``LabelSmoothingCrossEntropy(s)``."""
+    logits = _loss_logits("mix_ce_loss", logits)
+    return _MixCeFn.apply(logits, labels, table, float(on), float(off), int(row0))
+
+
+class _CosubBceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, table, on, off, binarize, row0):
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        ws = torch.empty(logits.shape[0] // 2, dtype=torch.float64, device=logits.device)
+        ops.cosub_bce(logits, labels, table, on, off, binarize, row0=row0, loss=loss, workspace=ws)
+        ctx.save_for_backward(logits, labels, table)
+        ctx.args = (on, off, binarize, row0)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        logits, labels, table = ctx.saved_tensors
+        on, off, binarize, row0 = ctx.args
+        g = grad.to(torch.float32).reshape(1).contiguous()
+        d = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device)
+        ops.cosub_bce(logits, labels, table, on, off, binarize, row0=row0, gscale=g, dlogits=d)
+        return d, None, None, None, None, None, None
+
+
+def cosub_bce_loss(logits, labels, table, on, off, binarize, row0=0):
+    """The loss of the reference's ``--cosub`` (deit/engine.py:60-65) for logits [2 rows, C] of a batch that was doubled with
+    ``torch.cat((x, x))`` - ``a, b = logits.chunk(2)`` are the two stochastic-depth passes of the same samples:
+    ``0.25 (bce(a, t) + bce(b, t) + bce(a, sigmoid(b).detach()) + bce(b, sigmoid(a).detach()))`` with ``bce`` =
+    ``nn.BCEWithLogitsLoss()`` and t the targets ``mix_targets(labels, table, C, on, off, binarize, row0, rows)``, never
+    materialised.  One launch for the value, one for both halves' gradient (in the logits' dtype)."""
+    logits = _loss_logits("cosub_bce_loss", logits, 2)
+    return _CosubBceFn.apply(logits, labels, table, float(on), float(off), bool(binarize), int(row0))
 
 
 class TableUploader:

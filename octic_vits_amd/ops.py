@@ -2090,6 +2090,47 @@ def mix_bce(logits, labels, table, on, off, binarize, row0=0, loss=None, workspa
     KERNEL_TIMER.stop(t, f"mix_bce_kernel<{_DTN[logits.dtype]}>", logits.numel() * logits.element_size() * (2 if dlogits is not None else 1))
 
 
+def _criterion_args(what, logits, logit_rows, rows, labels, table, loss, workspace, dlogits):
+    _require_cuda(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] != logit_rows:
+        raise ValueError(f"{what}: logits must be [{logit_rows}, num_classes] with contiguous columns")
+    B = _mix_labels(labels).numel()
+    _mix_table(table, B)
+    if dlogits is not None and (dlogits.dtype != logits.dtype or dlogits.shape != logits.shape or dlogits.stride(1) != 1):
+        raise ValueError(f"{what}: dlogits must have the logits' shape and dtype")
+    if loss is not None and (loss.dtype != torch.float32 or workspace is None or workspace.dtype != torch.float64
+                             or workspace.numel() < rows):
+        raise ValueError(f"{what}: the loss is an f32 scalar and needs a workspace of rows f64")
+    return B
+
+
+def mix_ce(logits, labels, table, on, off, row0=0, loss=None, workspace=None, gscale=None, dlogits=None):
+    """The soft-target cross entropy of logits [rows, num_classes] (f32 / bf16, unit column stride) against the NON-binarised mixed
+    targets of the batch rows row0 ..: loss (f32 scalar, with workspace = rows f64) and / or dlogits (the logits' dtype) scaled by
+    gscale."""
+    rows = logits.shape[0] if logits.dim() == 2 else 0
+    B = _criterion_args("mix_ce", logits, rows, rows, labels, table, loss, workspace, dlogits)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_mix_ce(_p(logits), dt_code(logits.dtype), logits.stride(0), _p(labels), _p(table), B, int(row0), rows,
+                             logits.shape[1], float(on), float(off), _p(loss), _p(gscale), _p(dlogits),
+                             dlogits.stride(0) if dlogits is not None else 0, _p(workspace), _stream(logits)))
+    KERNEL_TIMER.stop(t, f"mix_ce_kernel<{_DTN[logits.dtype]}>", logits.numel() * logits.element_size() * (2 if dlogits is not None else 1))
+
+
+def cosub_bce(logits, labels, table, on, off, binarize, row0=0, loss=None, workspace=None, gscale=None, dlogits=None):
+    """The four-term cosub loss of logits [2 rows, num_classes] (first passes, then second passes of the batch rows row0 ..):
+    loss (f32 scalar, with workspace = rows f64) and / or dlogits [2 rows, num_classes] scaled by gscale."""
+    if logits.dim() != 2 or logits.shape[0] % 2:
+        raise ValueError("cosub_bce: logits must be [2 rows, num_classes]: the two passes of every sample")
+    rows = logits.shape[0] // 2
+    B = _criterion_args("cosub_bce", logits, 2 * rows, rows, labels, table, loss, workspace, dlogits)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_cosub_bce(_p(logits), dt_code(logits.dtype), logits.stride(0), _p(labels), _p(table), B, int(row0), rows,
+                                logits.shape[1], float(on), float(off), int(bool(binarize)), _p(loss), _p(gscale), _p(dlogits),
+                                dlogits.stride(0) if dlogits is not None else 0, _p(workspace), _stream(logits)))
+    KERNEL_TIMER.stop(t, f"cosub_bce_kernel<{_DTN[logits.dtype]}>", logits.numel() * logits.element_size() * (2 if dlogits is not None else 1))
+
+
 # ------------------------------------------------------------------------------------------ 3-Augment on uint8 (csrc/augment.hip)
 def augment_workspace(B, H, W, device):
     """The int32 workspace octic_augment_u8 needs for a [B, H, W, 3] batch."""

@@ -1031,7 +1031,7 @@ class Trainer:
     def __init__(self, model, lr=3e-3, weight_decay=0.02, ema_decay=0.99996, distributed=False, local_rank=0,
                  fused_optimizer=True, tuned_gemms=True, opt_eps=1e-8, accum_steps=1, bf16_buckets=False,
                  autocast=True, check_every=1, device_type=None, bucket_cap_mb=None, segment_graphs=0, ddp_proxy=None,
-                 own_reducer=None, mixup=None, fused_loss=True, augment=None):
+                 own_reducer=None, mixup=None, fused_loss=True, augment=None, loss="bce", smoothing=0.0, cosub=False):
         """mixup: a ``mixup.Mixup`` (GPU only) - ``step`` / ``capture`` / ``GraphedStep.replay`` then take ``(images, int64 labels
         [B])``: every step draws the Mixup / CutMix parameters on the host, uploads them as one small device table (pinned ring,
         no stream drain), mixes the WHOLE batch once with the HIP kernels of csrc/mixup.hip and takes the recipe's BCE loss
@@ -1039,6 +1039,23 @@ class Trainer:
         come from ``mixup.mix_bce_loss`` without materialised targets; False materialises them (``mixup.mix_targets``) for
         ``nn.BCEWithLogitsLoss``.  Data parallel: every rank owns its ``Mixup``, seeded ``seed + rank`` as the reference seeds
         its ranks.  None: the caller mixes, ``step`` takes float multi-hot targets as before.
+        loss: the criterion of the reference loop (deit/main.py:370-381).  ``"bce"`` (``--bce-loss``, the default): as above.
+        ``"ce"`` with ``mixup``: timm's ``SoftTargetCrossEntropy`` against the mixed targets (NOT binarised) with the ``Mixup``'s own
+        ``on_off()`` - ``mixup.mix_ce_loss``, one row kernel (main.py:372-374).  ``"ce"`` without ``mixup``: ``step`` takes int64 labels
+        [B] and the same kernel runs through a resident identity table with ``mixup.smoothing_on_off(smoothing, C)`` - timm's
+        ``LabelSmoothingCrossEntropy(smoothing)``, at ``smoothing = 0`` ``nn.CrossEntropyLoss`` (main.py:375-378; GPU only); dense
+        float targets [B, C] are still accepted there and take the stock composition ``sum(-t * log_softmax(x), -1).mean()`` with
+        no kernel of ours (the caller mixed: there is no table to read).  smoothing: used by ``loss="ce"`` without ``mixup`` only
+        (with ``mixup`` the smoothing is the ``Mixup``'s ``label_smoothing``).
+        cosub: the reference's ``--cosub`` (deit/engine.py:50-65); needs ``mixup`` (the reference loop cannot run it on integer
+        targets either).  The mixed batch is doubled on the device, the model sees 2 B rows - two stochastic-depth passes of every
+        sample - and the loss is ``mixup.cosub_bce_loss``: four BCE terms, two against the mixed targets (binarised when ``loss ==
+        "bce"``, soft when ``"ce"``) and two against the other pass's detached sigmoid.  The reference replaces the criterion by
+        ``BCEWithLogitsLoss`` under ``--cosub`` whatever was chosen (engine.py:40-41): so does this, ``loss`` only says whether the
+        targets are binarised (the reference's ``--bce-loss`` at engine.py:53-54).  Refused with ``accum_steps > 1`` and
+        ``segment_graphs``: a chunked 2 B batch would separate the pairs.
+        With ``fused_loss=False`` every one of these materialises ``mixup.mix_targets`` and runs the stock torch composition: the A/B
+        arm.
         augment: an ``augment.ThreeAugment`` (GPU only) - ``step`` / ``capture`` / ``GraphedStep.replay`` then take the decoded,
         cropped batch as uint8 [B, H, W, 3]: every step draws the flip / op / jitter parameters on the host, uploads them as a second
         small device table and runs the kernels of csrc/augment.hip on the WHOLE batch in front of the mix; their normalised f32
@@ -1056,6 +1073,17 @@ class Trainer:
         others add to them, the collectives follow the last one).  None = wherever it applies: f32 buckets, f32 master
         parameters, no segment graphs; everything else goes through DistributedDataParallel as before."""
         self.raw_model = model
+        if loss not in ("bce", "ce"):
+            raise ValueError(f"Trainer: loss must be 'bce' or 'ce', got {loss!r}")
+        if not 0.0 <= float(smoothing) < 1.0:
+            raise ValueError(f"Trainer: smoothing must lie in [0, 1), got {smoothing!r}")
+        if cosub and mixup is None:
+            raise ValueError("Trainer(cosub=True) needs mixup=: the cosub loss is taken against mixed float targets (the reference "
+                             "loop cannot run --cosub on integer targets either)")
+        if cosub and (int(accum_steps) > 1 or segment_graphs):
+            raise ValueError("Trainer(cosub=True) with accum_steps > 1 or segment_graphs: a chunked 2 B batch would separate the two "
+                             "passes of a sample; run cosub on whole batches")
+        self.loss, self.smoothing, self.cosub, self._label_tables = loss, float(smoothing), bool(cosub), {}
         self.mixup, self.fused_loss, self._mix_tables = mixup, bool(fused_loss), {}
         if mixup is not None and (device_type or next(model.parameters()).device.type) != "cuda":
             raise RuntimeError("Trainer(mixup=...): Mixup / CutMix run on the GPU only (HIP kernels, no CPU fallback)")
@@ -1104,7 +1132,7 @@ class Trainer:
         else:
             self.optimizer = Lamb(groups, lr=lr, eps=opt_eps, weight_decay=weight_decay)
             self.ema = ModelEma(model, ema_decay) if ema_decay else None
-        self.criterion = nn.BCEWithLogitsLoss()
+        self.criterion = nn.BCEWithLogitsLoss() if loss == "bce" else _soft_target_ce
         self._watch = _LossWatch(self.device_type)
 
     def _wrap_ddp(self):
@@ -1192,6 +1220,8 @@ class Trainer:
     def _loss(self, outputs, targets):
         if isinstance(targets, _MixedTargets):          # the fused loss reads the logits in their own dtype
             return targets.loss(outputs)
+        if self.cosub:                                  # (fused_loss=False: materialised targets, the reference's four terms)
+            return _cosub_stock(outputs.float(), targets)
         return self.criterion(outputs.float(), targets)
 
     @staticmethod
@@ -1253,14 +1283,48 @@ class Trainer:
 
     def _mix_batch(self, samples, labels):
         """The launches of the mix (also what ``capture`` records): the whole batch mixed once, out of place, and the targets
-        as ``_MixedTargets`` (fused loss) or a materialised, binarised [B, num_classes] tensor."""
+        as ``_MixedTargets`` (fused loss) or a materialised [B, num_classes] tensor, binarised for ``loss="bce"``.  ``cosub``: the
+        mixed batch twice, [2 B, ...]."""
         from . import mixup as M
         table = self._mix_table(samples.shape[0], samples.device).table
-        mixed = M.mix_images(samples, table)
+        if self.cosub:                                  # torch.cat((x, x)) of engine.py:51: mixed into the first half, copied
+            B = samples.shape[0]
+            mixed = torch.empty((2 * B,) + tuple(samples.shape[1:]), dtype=samples.dtype, device=samples.device)
+            M.mix_images(samples, table, out=mixed[:B])
+            mixed[B:].copy_(mixed[:B])
+        else:
+            mixed = M.mix_images(samples, table)
         on, off = self.mixup.on_off()
+        kind = "cosub" if self.cosub else self.loss
         if self.fused_loss:
-            return mixed, _MixedTargets(labels, table, on, off)
-        return mixed, M.mix_targets(labels, table, self.mixup.num_classes, on=on, off=off, binarize=True)
+            return mixed, _MixedTargets(labels, table, on, off, kind=kind, binarize=self.loss == "bce")
+        return mixed, M.mix_targets(labels, table, self.mixup.num_classes, on=on, off=off, binarize=self.loss == "bce")
+
+    def _takes_labels(self, targets):
+        """``loss="ce"`` without ``mixup``: int64 class labels go through the fused loss, dense float targets do not."""
+        return self.mixup is None and self.loss == "ce" and torch.is_tensor(targets) and targets.dtype == torch.int64
+
+    def _label_check(self, samples, labels):
+        if labels.dim() != 1 or labels.shape[0] != samples.shape[0]:
+            raise TypeError(f"Trainer(loss='ce'): step takes int64 class labels [B] or float targets [B, C], got int64 "
+                            f"{tuple(labels.shape)}")
+        if not labels.is_cuda:
+            raise RuntimeError("Trainer(loss='ce'): the loss against int64 labels runs on the GPU only (HIP kernel, no CPU "
+                               "fallback); float targets [B, C] take the torch composition anywhere")
+
+    def _label_targets(self, labels):
+        """``loss="ce"`` on class labels (also what ``capture`` records): the labels behind the resident identity table - nothing is
+        mixed - as ``_MixedTargets`` (fused: ``on`` / ``off`` follow from the logits' width) or materialised by ``mix_targets``."""
+        from . import mixup as M
+        B = labels.shape[0]
+        table = self._label_tables.get((B, labels.device))
+        if table is None:
+            table = self._label_tables[(B, labels.device)] = torch.from_numpy(M.MixParams.identity(B).table()).to(labels.device)
+        if self.fused_loss:
+            return _MixedTargets(labels, table, None, None, kind="ce", binarize=False, smoothing=self.smoothing)
+        nc = self.raw_model.num_classes
+        on, off = M.smoothing_on_off(self.smoothing, nc)
+        return M.mix_targets(labels, table, nc, on=on, off=off, binarize=False)
 
     def _batched_finishes(self, first_of_many=False):
         """The parameter-gradient slab reductions of the backward pass as one batched launch at its end
@@ -1320,6 +1384,8 @@ class Trainer:
             self.augment.check_batch(samples, "Trainer(augment=...)")
         if self.mixup is not None:
             self._mix_check(samples.offsets if packed else samples, targets)
+        elif self._takes_labels(targets):
+            self._label_check(samples.offsets if packed else samples, targets)
         self.model.train()
         # engine.py:67-71 two steps late on a pinned host copy (_LossWatch): no stream drain per step
         self._steps += 1
@@ -1334,6 +1400,8 @@ class Trainer:
         if self.mixup is not None:
             self._mix_draw(samples)
             samples, targets = self._mix_batch(samples, targets)
+        elif self._takes_labels(targets):
+            targets = self._label_targets(targets)
         k = self.accum_steps
         if k > 1 and self.segmented is not None and self.segmented.graphed:
             # Graphed slices hand autograd the SAME static gradient buffers every backward: with .grad = None the first
@@ -1409,6 +1477,8 @@ class Trainer:
             # sx / sy are the staging images and labels; the parameter table is the third static input (``_mix_table``):
             # ``GraphedStep.replay`` refills all three in front of the replay, the mix kernels and the loss are in the graph
             self._mix_check(samples.offsets if self._is_packed(samples) else samples, targets)
+        elif self._takes_labels(targets):               # loss="ce" on class labels: sy holds them, the loss reads them in the graph
+            self._label_check(samples.offsets if self._is_packed(samples) else samples, targets)
         sy = targets.clone()
         if self._is_packed(samples):                    # decoded sources: the warm-up steps crop them as eager steps do (the same
             for _ in range(max(1, warmup)):             # draws); the graph's input is the uint8 staging batch the crop launch of
@@ -1445,6 +1515,8 @@ class Trainer:
                 sx = self._aug_batch(sx)
             if self.mixup is not None:
                 sx, sy = self._mix_batch(sx, sy)
+            elif self._takes_labels(sy):
+                sy = self._label_targets(sy)
             if self.accum_steps > 1:
                 loss = self._accumulate(sx, sy)           # (k forward / backward passes over the chunks of the static batch)
             else:
@@ -1486,23 +1558,50 @@ class _FinishScope:
 
 class _MixedTargets:
     """The mixed targets of the batch rows row0 .. row0 + rows - 1 as (labels of the WHOLE batch, parameter table) - never
-    materialised: ``loss`` is ``mixup.mix_bce_loss`` against their binarised form.  ``chunk`` cuts them like ``Tensor.chunk``
-    cuts the images (gradient accumulation mixes the whole batch once; a chunk's partners may lie in another chunk)."""
+    materialised.  ``kind`` says which loss ``loss`` takes against them: ``"bce"`` - ``mixup.mix_bce_loss`` against their binarised
+    form; ``"ce"`` - ``mixup.mix_ce_loss`` against the soft targets (``on`` / ``off`` None: ``smoothing_on_off(smoothing, C)`` for the
+    logits' C, the label-smoothing cross entropy on class labels); ``"cosub"`` - ``mixup.cosub_bce_loss`` on logits of 2 rows rows,
+    binarised or not.  ``chunk`` cuts them like ``Tensor.chunk`` cuts the images (gradient accumulation mixes the whole batch once;
+    a chunk's partners may lie in another chunk); the cosub pairs cannot be chunked."""
 
-    def __init__(self, labels, table, on, off, row0=0, rows=None):
+    def __init__(self, labels, table, on, off, row0=0, rows=None, kind="bce", binarize=True, smoothing=0.0):
         self.labels, self.table, self.on, self.off, self.row0 = labels, table, on, off, row0
         self.rows = labels.shape[0] - row0 if rows is None else rows
+        self.kind, self.binarize, self.smoothing = kind, binarize, smoothing
 
     def chunk(self, k):
+        if self.kind == "cosub":
+            raise RuntimeError("Trainer(cosub=True): the doubled batch is not chunked (a chunk would separate the pairs)")
         size = -(-self.rows // k)
-        return [_MixedTargets(self.labels, self.table, self.on, self.off, self.row0 + o, min(size, self.rows - o))
+        return [_MixedTargets(self.labels, self.table, self.on, self.off, self.row0 + o, min(size, self.rows - o), self.kind,
+                              self.binarize, self.smoothing)
                 for o in range(0, self.rows, size)]
 
     def loss(self, logits):
-        from .mixup import mix_bce_loss
-        if logits.shape[0] != self.rows:
+        from . import mixup as M
+        if logits.shape[0] != (2 * self.rows if self.kind == "cosub" else self.rows):
             raise ValueError("Trainer: the logits do not match the mixed targets' rows")
-        return mix_bce_loss(logits, self.labels, self.table, on=self.on, off=self.off, binarize=True, row0=self.row0)
+        if self.kind == "bce":
+            return M.mix_bce_loss(logits, self.labels, self.table, on=self.on, off=self.off, binarize=True, row0=self.row0)
+        if self.kind == "cosub":
+            return M.cosub_bce_loss(logits, self.labels, self.table, self.on, self.off, self.binarize, row0=self.row0)
+        on, off = (self.on, self.off) if self.on is not None else M.smoothing_on_off(self.smoothing, logits.shape[1])
+        return M.mix_ce_loss(logits, self.labels, self.table, on=on, off=off, row0=self.row0)
+
+
+def _soft_target_ce(logits, targets):
+    """timm's ``SoftTargetCrossEntropy`` on dense targets: the stock composition (no kernel of ours)."""
+    return torch.sum(-targets * torch.nn.functional.log_softmax(logits, dim=-1), dim=-1).mean()
+
+
+def _cosub_stock(logits, targets):
+    """deit/engine.py:61-65 on materialised targets: the four BCE terms of ``--cosub`` with stock torch."""
+    bce = torch.nn.functional.binary_cross_entropy_with_logits
+    a, b = torch.split(logits, logits.shape[0] // 2, dim=0)
+    loss = 0.25 * bce(a, targets)
+    loss = loss + 0.25 * bce(b, targets)
+    loss = loss + 0.25 * bce(a, b.detach().sigmoid())
+    return loss + 0.25 * bce(b, a.detach().sigmoid())
 
 
 class GraphedStep:
