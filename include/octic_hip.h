@@ -966,6 +966,29 @@ int octic_sinkhorn_rows(const void* x, int x_dtype, int64_t ldx, float inv_temp,
 int octic_sinkhorn_final(const void* x, int x_dtype, int64_t ldx, float inv_temp, const float* u, float* out, int64_t rows,
                          int K, void* stream);
 
+/* ---- KoLeo regularizer of the DINOv2 objective (dinov2/loss/koleo_loss.py:18-48), one forward and one backward launch ------
+ * x is [groups * n, D] f32 or bf16 with element stride 1, row stride ldx >= D and 16-byte aligned rows, read as `groups`
+ * independent groups of n consecutive rows (the recipe: the two global crops).  All arithmetic is f32 after one widening.  Per
+ * row i of a group: inv[i] = 1 / max(||x_i||, eps), xh_i = x_i inv[i]; nn[i] = the group-local index of the row j != i with the
+ * largest xh_i . xh_j - on equal dots the LOWEST j (torch.max leaves ties unspecified: this rule is ours), a NaN dot counts as
+ * -inf, the row itself is excluded; dist[i] = ||xh_i - xh_nn[i] + 1e-8|| (nn.PairwiseDistance adds its eps to every element);
+ * term[i] = -log(dist[i] + eps).  The loss of a group is the mean of its terms, taken by the caller.
+ * octic_koleo_bwd: from gterm = d loss / d term and the saved x, nn, inv, dist: G_i = c_i e_i - sum over the j with nn[j] == i
+ * (ascending, gathered by the workgroup of row i: no atomics) of c_j e_j, c = -gterm / (dist + eps), e = (xh - xh_nn + 1e-8) /
+ * dist; then autograd's F.normalize: dx_i = (G_i - xh_i (xh_i . G_i)) inv[i] where ||x_i|| >= eps, G_i / eps below it; dx in
+ * x's dtype, rounded once, row stride lddx >= D, 16-byte aligned rows.
+ * A row's nn, term and dx depend on the rows of its own group, n and D only - not on groups, the group's position, the row
+ * strides or the rest of the batch - and two calls are bitwise equal (fixed summation orders).
+ * octic_koleo_ok: 1 where the kernels take the shape, else 0 - the only place the range lives: groups >= 1, 2 <= n <= 256,
+ * 8 <= D <= 4096, D % 8 == 0, groups * n < 2^31.  The entry points return OCTIC_ENULL, OCTIC_EDTYPE, OCTIC_ESHAPE (a shape
+ * octic_koleo_ok refuses, ldx or lddx < D) and OCTIC_EALIGN before any launch. */
+int octic_koleo_ok(int64_t groups, int64_t n, int64_t D);
+int octic_koleo_fwd(const void* x, int x_dtype, int64_t ldx, int64_t groups, int64_t n, int64_t D, float eps, float* term,
+                    int32_t* nn, float* inv, float* dist, void* stream);
+int octic_koleo_bwd(const void* x, int x_dtype, int64_t ldx, int64_t groups, int64_t n, int64_t D, float eps,
+                    const float* gterm, const int32_t* nn, const float* inv, const float* dist, void* dx, int64_t lddx,
+                    void* stream);
+
 /* ---- linear-probe evaluation of a frozen backbone (dinov2/eval/linear.py) ----------------------------------------------
  * The grid of nn.Linear(K_h, C) classifiers of setup_linear_classifiers (linear.py:237-258) as one launch per stage over
  * all classifiers.  Every classifier reads a column range [col0, col0 + K) of one f32 feature row

@@ -829,6 +829,33 @@ def loss_rows_ok(t):
     return t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) and t.shape[-1] % 8 == 0 and not torch.compiler.is_compiling()
 
 
+class KoLeoFn(torch.autograd.Function):
+    """KoLeo terms of x [groups * n, D] (f32 / bf16), read as `groups` independent groups of n consecutive rows -> [groups * n]
+    f32, term_i = -log(||xh_i - xh_nn(i) + 1e-8|| + eps) with xh the rows normalised with F.normalize's eps and nn(i) the nearest
+    other row of the group (largest dot, lowest index on ties).  One launch forward, one backward (csrc/koleo.hip) -
+    dinov2/loss/koleo_loss.py:25-48; the loss of a group is the mean of its terms."""
+
+    @staticmethod
+    def forward(ctx, x, groups, eps=1e-8):
+        term, nn, inv, dist = ops.koleo_fwd(x, groups, eps)
+        ctx.save_for_backward(x, nn, inv, dist)
+        ctx.groups, ctx.eps = groups, eps
+        return term
+
+    @staticmethod
+    def backward(ctx, g):
+        x, nn, inv, dist = ctx.saved_tensors
+        return ops.koleo_bwd(x, ctx.groups, g, nn, inv, dist, ctx.eps).view(x.shape), None, None
+
+
+def koleo_rows_ok(x, groups):
+    """x takes the KoLeo kernels as `groups` groups of consecutive rows: a 2-D GPU tensor, f32 / bf16, unit column stride, not
+    under torch.compile tracing, and a shape octic_koleo_ok admits."""
+    return bool(x.dim() == 2 and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.stride(1) == 1
+                and not torch.compiler.is_compiling() and groups >= 1 and x.shape[0] % groups == 0
+                and ops.koleo_ok(groups, x.shape[0] // groups, x.shape[1]))
+
+
 class DenseLayerNormFn(torch.autograd.Function):
     """nn.LayerNorm over the last dim of an f32 residual stream, result in the compute dtype.  Returns (y, x): the
     second output is the stream itself, to be used for the residual connection, so that the residual cotangent

@@ -1174,6 +1174,53 @@ def sinkhorn_final(x, inv_temp, u):
     return out
 
 
+def koleo_ok(groups, n, D):
+    """The KoLeo kernels of csrc/koleo.hip take `groups` groups of n rows of D elements (octic_koleo_ok: the only place the range
+    lives)."""
+    return bool(lib().octic_koleo_ok(int(groups), int(n), int(D)))
+
+
+def _koleo_rows2d(x, groups):
+    """x [groups * n, D] f32 / bf16 as (view with unit column stride and 16-byte aligned rows, n, D, row stride)."""
+    _require_cuda(x)
+    if x.dim() != 2 or groups < 1 or x.shape[0] % groups:
+        raise ValueError("koleo: x must be [groups * n, D]")
+    if x.stride(1) != 1 or x.data_ptr() % 16 or (x.stride(0) * x.element_size()) % 16:
+        x = x.contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone(memory_format=torch.contiguous_format)
+    return x, x.shape[0] // groups, x.shape[1], x.stride(0)
+
+
+def koleo_fwd(x, groups, eps=1e-8):
+    """KoLeo terms of `groups` independent groups of consecutive rows of x [groups * n, D] (f32 / bf16) in one launch:
+    (term [rows] f32 = -log(dist + eps), nn [rows] int32 = group-local index of the nearest other row of the group by the dot of
+    the normalised rows, lowest index on ties, inv [rows] f32 = 1 / max(||x_i||, eps), dist [rows] f32 = ||xh_i - xh_nn + 1e-8||)."""
+    x2, n, D, ld = _koleo_rows2d(x, groups)
+    rows = groups * n
+    term, inv, dist = (torch.empty(rows, dtype=torch.float32, device=x.device) for _ in range(3))
+    nn = torch.empty(rows, dtype=torch.int32, device=x.device)
+    tk = KERNEL_TIMER.start()
+    check(lib().octic_koleo_fwd(_p(x2), dt_code(x2.dtype), ld, groups, n, D, float(eps), _p(term), _p(nn), _p(inv), _p(dist),
+                                _stream(x)))
+    KERNEL_TIMER.stop(tk, f"koleo_fwd_kernel<{_DTN[x2.dtype]}>", rows * (n + 1) * D * x2.element_size())
+    return term, nn, inv, dist
+
+
+def koleo_bwd(x, groups, gterm, nn, inv, dist, eps=1e-8):
+    """d loss / d x for koleo_fwd from gterm = d loss / d term [rows], in x's dtype ([groups * n, D] contiguous); the rows that
+    chose row i are gathered in ascending order by its workgroup (no atomics)."""
+    x2, n, D, ld = _koleo_rows2d(x, groups)
+    rows = groups * n
+    dx = torch.empty((rows, D), dtype=x2.dtype, device=x.device)
+    gterm = gterm.reshape(-1).float().contiguous()
+    tk = KERNEL_TIMER.start()
+    check(lib().octic_koleo_bwd(_p(x2), dt_code(x2.dtype), ld, groups, n, D, float(eps), _p(gterm), _p(nn), _p(inv), _p(dist),
+                                _p(dx), D, _stream(x)))
+    KERNEL_TIMER.stop(tk, f"koleo_bwd_kernel<{_DTN[x2.dtype]}>", rows * 4 * D * x2.element_size())
+    return dx
+
+
 def scale_residual_fwd(x, y, gamma, rs, rps):
     """out = x + rs[row // rps] * gamma * y   (x f32, y f32/bf16, same shape [..., d])."""
     _require_cuda(x)

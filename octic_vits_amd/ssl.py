@@ -6,7 +6,8 @@ Same classes, constructor arguments, ``state_dict`` keys and arithmetic as the r
 FSDP (parameters and optimizer state of a ViT-H student + teacher are ~13 GB: nothing to shard on a 288 GB device; the
 student is wrapped in DistributedDataParallel by ``SSLTrainer`` when a process group exists, the centre statistics are
 all-reduced as in the reference).  The backbones run on the HIP engine (octic blocks, attention, standard half); the
-heads and losses are a few small dense ops per step and stay on torch.
+heads are a few small dense ops per step and stay on torch; the losses' row passes run on csrc/ssl_loss.hip (the prototype axis
+of the DINO / iBOT terms, both centerings) and csrc/koleo.hip (the KoLeo regularizer) under ``FUSED_LOSS_ROWS``.
 
 Local crops (96 x 96 on a 224 model) need the positional-embedding resize branch, which raises TypeError in the
 reference as shipped (tuple patch size); ``OcticDinoVisionTransformer`` here implements the evident intent
@@ -23,7 +24,7 @@ import torch.nn.functional as F
 
 from . import functional as _OF
 
-FUSED_LOSS_ROWS = True      # GPU: the prototype-axis passes of the DINO / iBOT terms, both centerings, on csrc/ssl_loss.hip (False: the eager composition)
+FUSED_LOSS_ROWS = True      # GPU: the prototype-axis passes of the DINO / iBOT terms, both centerings, on csrc/ssl_loss.hip and the KoLeo term on csrc/koleo.hip (False: the eager composition)
 
 
 def _world():
@@ -254,11 +255,20 @@ class KoLeoLoss(nn.Module):
         return torch.max(dots, dim=1)[1]
 
     def forward(self, student_output, eps=1e-8):
+        if FUSED_LOSS_ROWS and _OF.koleo_rows_ok(student_output, 1):
+            return _OF.KoLeoFn.apply(student_output, 1, eps).mean()
         with torch.autocast(device_type=student_output.device.type, enabled=False):
             student_output = F.normalize(student_output.float(), eps=eps, p=2, dim=-1)
             idx = self.pairwise_NNs_inner(student_output)
             distances = self.pdist(student_output, student_output[idx])
             return -torch.log(distances + eps).mean()
+
+    def forward_groups(self, student_output, groups, eps=1e-8):
+        """The losses [groups] of the `groups` chunks of consecutive rows (``forward`` on each of ``chunk(groups)``): one forward
+        and one backward launch for all of them where the kernels take the shape."""
+        if FUSED_LOSS_ROWS and _OF.koleo_rows_ok(student_output, groups):
+            return _OF.KoLeoFn.apply(student_output, groups, eps).view(groups, -1).mean(1)
+        return torch.stack([self.forward(p, eps) for p in student_output.chunk(groups)])
 
 
 # ------------------------------------------------------------------------------------------ data side
@@ -472,7 +482,7 @@ class SSLMetaArch(nn.Module):
             loss_dict["dino_global_crops_loss"] = l
             total = total + self.dino_loss_weight * l
             if self.do_koleo:
-                k = self.koleo_loss_weight * sum(self.koleo_loss(p) for p in sg["x_norm_clstoken"].chunk(2))
+                k = self.koleo_loss_weight * sum(self.koleo_loss.forward_groups(sg["x_norm_clstoken"], 2).unbind(0))
                 total = total + k
                 loss_dict["koleo_loss"] = k / loss_scales
         if self.do_ibot:
