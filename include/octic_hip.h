@@ -1196,6 +1196,35 @@ int octic_knn_vote(const float* sim, const int32_t* idx, int64_t ldi, int64_t n,
                    int C, float inv_T, const int* ks, int nk, float* probas, const int64_t* targets, int64_t* counters,
                    void* stream);
 
+/* ---- top-k accuracy counters of the evaluations (dinov2/eval/metrics.py; csrc/topk_metric.hip) ------------------------------
+ * MulticlassAccuracy(average = micro | macro | none, top_k = k), ImageNetReaLAccuracy and the class mapping of
+ * LinearPostprocessor (linear.py:219-230: preds[:, class_mapping]) on f32 score rows scores[g, r, :] - G groups of n rows of C
+ * columns at scores + g ld_g + r ld_r (element strides, >= C where there is more than one row / group): the [classifiers, B, C]
+ * logits of octic_probe_forward and the [nk, n, C] probas of octic_knn_vote both fit without a copy.
+ * octic_topk_rank: class_map is a nullable DEVICE int32 [Cm] (NULL: identity, Cm must equal C); candidate j < Cm is class j with
+ * score s_j = scores[g, r, class_map[j]].  The host cannot see the mapping: the caller guarantees entries in [0, C) (an entry
+ * outside reads nothing and scores -inf).  targets is DEVICE int64 [n, A], 1 <= A <= OCTIC_TOPK_MAX_TARGETS, shared by all
+ * groups; a value outside [0, Cm) is an undefined target (the reference pads with -1).  rank int32 [G, n, A], every element
+ * written: for a defined target t the number of candidates that come before candidate t, for an undefined one Cm.
+ *   order 0: j comes before t iff s_j > s_t                              (octic_probe_ce's rank: a tied target is a hit)
+ *   order 1: j comes before t iff s_j > s_t or (s_j == s_t and j < t)    (octic_knn_vote's ranking: index ascending on ties)
+ * A NaN score counts as -inf.  One wave per (group, row), one pass over the candidates for all A targets.
+ * octic_topk_count ADDS the ranks of one update to DEVICE int64 counters (64-bit integer atomics: the counters do not depend on
+ * the launch shape or on how the rows were split into calls).  ks: HOST array of nk <= 8 strictly ascending values >= 1.
+ *   OCTIC_TOPK_ANY   counters [G, 1 + nk]:     [g, 0] += rows with at least one defined target, [g, 1 + i] += rows where some
+ *                                              defined target has rank < ks[i]            (micro accuracy; ReaL with A > 1)
+ *   OCTIC_TOPK_CLASS counters [G, Cm, 1 + nk]: A must be 1 and targets (the same [n]) is read again: [g, c, 0] += rows whose
+ *                                              target is c, [g, c, 1 + i] += those of them with rank < ks[i]
+ * Limits, refused with OCTIC_ESHAPE before any launch: G, n >= 1, G n A < 2^31, 1 <= C < 2^31, 1 <= Cm < 2^31, order 0 | 1,
+ * strides as above; OCTIC_ENULL / OCTIC_EALIGN (4-byte scores, map and ranks, 8-byte targets and counters) likewise.          */
+#define OCTIC_TOPK_MAX_TARGETS 32
+#define OCTIC_TOPK_ANY 0
+#define OCTIC_TOPK_CLASS 1
+int octic_topk_rank(const float* scores, int64_t ld_g, int64_t ld_r, int64_t G, int64_t n, int64_t C, const int32_t* class_map,
+                    int64_t Cm, const int64_t* targets, int A, int order, int32_t* rank, void* stream);
+int octic_topk_count(const int32_t* rank, int64_t G, int64_t n, int A, int64_t Cm, const int64_t* targets, int mode, const int* ks,
+                     int nk, int64_t* counters, void* stream);
+
 /* ---- Mixup / CutMix and the BCE loss of the DeiT-III recipe (timm/data/mixup.py; deit/engine.py:47-59) -----------------
  * The host draws the per-sample parameters and uploads them as a DEVICE table of B rows; the kernels take everything about
  * the draw from it (never from arguments), so one captured launch serves every replay.  A row whose partner is outside

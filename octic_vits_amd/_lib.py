@@ -277,6 +277,10 @@ _PROTOS = {
                                c_void_p, c_void_p]),
     "octic_knn_vote": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p, c_i64, c_int, c_float, ctypes.POINTER(c_int),
                                c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "octic_topk_rank": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p,
+                                c_void_p]),
+    "octic_topk_count": (c_int, [c_void_p, c_i64, c_i64, c_int, c_i64, c_void_p, c_int, ctypes.POINTER(c_int), c_int, c_void_p,
+                                 c_void_p]),
     "octic_mix_images": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "octic_mix_targets": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p]),
     "octic_mix_bce": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int,

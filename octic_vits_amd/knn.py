@@ -11,7 +11,7 @@ layout and the ``k_list`` rule, results keyed ``(n_per_class, k)`` and averaged 
 What is ours: the order of equal similarities (lower training row first; ``torch.topk`` leaves it open) and of equal probas
 (lower class first); hit counters that stay on the device until the end of the evaluation, as ``LinearProbe.evaluate``.
 
-Refused loudly: accuracy averaging other than MEAN_ACCURACY, ``gather_on_cpu``, a process group of more than one rank (the
+Refused loudly: accuracy averaging other than MEAN_ACCURACY (``octic_vits_amd.metrics.eval_knn`` takes the others), ``gather_on_cpu``, a process group of more than one rank (the
 reference shards the training features over ranks; this is a one-GPU evaluation), max(nb_knn) above the kernel's limit or above
 the number of training rows, a feature width that is no multiple of 64, CPU tensors ("GPU only": there is no CPU fallback).
 """
@@ -30,7 +30,8 @@ def _single_rank():
 
 def _check_options(accuracy_averaging, gather_on_cpu):
     if str(getattr(accuracy_averaging, "value", accuracy_averaging)) != "mean_accuracy":
-        raise NotImplementedError(f"octic_vits_amd.knn: accuracy averaging {accuracy_averaging!r} (only mean_accuracy)")
+        raise NotImplementedError(f"octic_vits_amd.knn: accuracy averaging {accuracy_averaging!r} (only mean_accuracy; every "
+                                  "other averaging is octic_vits_amd.metrics.eval_knn / eval_knn_features)")
     if gather_on_cpu:
         raise NotImplementedError("octic_vits_amd.knn: gather_on_cpu (the training features stay on the device)")
     _single_rank()

@@ -2071,6 +2071,93 @@ def knn_vote(sim, idx, labels, num_classes, inv_T, ks, out=None, targets=None, c
     return out
 
 
+# ------------------------------------------------------------------------------------------ top-k accuracy counters (csrc/topk_metric.hip)
+TOPK_MAX_TARGETS = 32          # OCTIC_TOPK_MAX_TARGETS of include/octic_hip.h
+TOPK_ANY, TOPK_CLASS = 0, 1    # OCTIC_TOPK_ANY / OCTIC_TOPK_CLASS
+TOPK_ORDER_STRICT, TOPK_ORDER_INDEX = 0, 1
+
+
+def topk_shapes(scores, targets):
+    """(G, n, C, A) of a scores [n, C] | [G, n, C] / targets [n] | [n, A] pair; raises ValueError for anything else.  Looks at
+    shapes only, so it runs on CPU tensors too."""
+    if scores.dim() not in (2, 3) or targets.dim() not in (1, 2):
+        raise ValueError("topk metric: scores must be [n, C] or [G, n, C] and targets [n] or [n, A]")
+    G = scores.shape[0] if scores.dim() == 3 else 1
+    n, C = scores.shape[-2], scores.shape[-1]
+    A = targets.shape[1] if targets.dim() == 2 else 1
+    if targets.shape[0] != n:
+        raise ValueError(f"topk metric: {targets.shape[0]} target rows for {n} score rows")
+    if not 1 <= A <= TOPK_MAX_TARGETS:
+        raise ValueError(f"topk metric: 1 .. {TOPK_MAX_TARGETS} targets per row, got {A}")
+    if C < 1 or G * n * A >= 2 ** 31 or C >= 2 ** 31:
+        raise ValueError("topk metric: at least one column, and groups * rows * targets and columns below 2^31")
+    return G, n, C, A
+
+
+def topk_rank(scores, targets, class_map=None, order=TOPK_ORDER_STRICT, out=None):
+    """int32 [G, n, A]: for every target the number of candidates that come before it among the row's candidates
+    ``scores[g, r, class_map[j]]`` (class_map None: all C columns), Cm for a target outside [0, Cm).  scores f32 [n, C] or
+    [G, n, C] with unit column stride (any row / group stride: no copy), targets int64 [n] or [n, A] contiguous, class_map a
+    contiguous int32 [Cm] on the device whose entries the CALLER has checked to lie in [0, C).  order: TOPK_ORDER_STRICT (a score
+    strictly greater comes before) or TOPK_ORDER_INDEX (... or an equal score at a lower candidate index)."""
+    G, n, C, A = topk_shapes(scores, targets)
+    _require_cuda(scores)
+    if scores.dtype != torch.float32 or scores.stride(-1) != 1:
+        raise ValueError("topk_rank: scores must be f32 with unit column stride")
+    if targets.dtype != torch.int64 or not targets.is_contiguous() or targets.device != scores.device:
+        raise ValueError("topk_rank: targets must be a contiguous int64 tensor on the device of scores")
+    Cm = C
+    if class_map is not None:
+        if class_map.dtype != torch.int32 or class_map.dim() != 1 or not class_map.is_contiguous() or class_map.device != scores.device \
+                or not class_map.numel():
+            raise ValueError("topk_rank: class_map must be a contiguous, non-empty int32 [Cm] on the device of scores")
+        Cm = class_map.numel()
+    if order not in (TOPK_ORDER_STRICT, TOPK_ORDER_INDEX):
+        raise ValueError("topk_rank: order is TOPK_ORDER_STRICT or TOPK_ORDER_INDEX")
+    if out is None:
+        out = torch.empty(G, n, A, dtype=torch.int32, device=scores.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (G, n, A) or not out.is_contiguous() or out.device != scores.device:
+        raise ValueError("topk_rank: out must be a contiguous int32 [G, n, A]")
+    if n:
+        ld_r = scores.stride(-2) if n > 1 else C
+        ld_g = scores.stride(0) if scores.dim() == 3 and G > 1 else n * max(ld_r, C)
+        t = KERNEL_TIMER.start()
+        check(lib().octic_topk_rank(_p(scores), ld_g, ld_r, G, n, C, _p(class_map), Cm, _p(targets), A, order, _p(out),
+                                    _stream(scores)))
+        KERNEL_TIMER.stop(t, "topk_rank_kernel", G * n * (4 * Cm + 4 * A) + 8 * n * A + (4 * Cm if class_map is not None else 0))
+    return out
+
+
+def topk_count(rank, counters, ks, mode=TOPK_ANY, num_classes=None, targets=None):
+    """Adds the ranks of one update (int32 [G, n, A] of topk_rank over num_classes candidates) to the int64 device counters:
+    TOPK_ANY [G, 1 + len(ks)] (rows with a defined target, then rows with a rank below each k), TOPK_CLASS [G, num_classes,
+    1 + len(ks)] (per target class; A == 1, targets as given to topk_rank).  ks: 1 .. 8 strictly ascending values >= 1."""
+    _require_cuda(rank)
+    ks = [int(k) for k in ks]
+    if rank.dtype != torch.int32 or rank.dim() != 3 or not rank.is_contiguous():
+        raise ValueError("topk_count: rank must be a contiguous int32 [G, n, A]")
+    G, n, A = rank.shape
+    Cm = int(num_classes)
+    if not ks or len(ks) > 8 or ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError("topk_count: ks must be 1 .. 8 strictly ascending values >= 1")
+    want = (G, 1 + len(ks)) if mode == TOPK_ANY else (G, Cm, 1 + len(ks))
+    if counters.dtype != torch.int64 or tuple(counters.shape) != want or not counters.is_contiguous() or counters.device != rank.device:
+        raise ValueError(f"topk_count: counters must be a contiguous int64 {list(want)} on the device of rank")
+    if mode == TOPK_CLASS:
+        if A != 1:
+            raise ValueError("topk_count: per-class counters take one target per row")
+        if targets is None or targets.dtype != torch.int64 or targets.numel() != n or not targets.is_contiguous() \
+                or targets.device != rank.device:
+            raise ValueError("topk_count: per-class counters need the contiguous int64 [n] targets on the device of rank")
+    elif mode != TOPK_ANY:
+        raise ValueError("topk_count: mode is TOPK_ANY or TOPK_CLASS")
+    if n:
+        t = KERNEL_TIMER.start()
+        check(lib().octic_topk_count(_p(rank), G, n, A, Cm, _p(targets if mode == TOPK_CLASS else None), mode,
+                                     (ctypes.c_int * len(ks))(*ks), len(ks), _p(counters), _stream(rank)))
+        KERNEL_TIMER.stop(t, "topk_count_kernel", 4 * G * n * A)
+
+
 # ------------------------------------------------------------------------------------------ Mixup / CutMix + BCE (csrc/mixup.hip)
 def _mix_table(table, B):
     _require_cuda(table)

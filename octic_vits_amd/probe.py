@@ -240,9 +240,11 @@ class LinearProbe:
         the first strict maximum of top-1 in dictionary order, starting from 0.  batches: iterable of (images, labels), or
         of (feature rows, labels) with on_features=True."""
         if str(getattr(metric_type, "value", metric_type)) != "mean_accuracy":
-            raise NotImplementedError(f"LinearProbe.evaluate: metric type {metric_type!r} (only mean_accuracy)")
+            raise NotImplementedError(f"LinearProbe.evaluate: metric type {metric_type!r} (only mean_accuracy; every other type "
+                                      "is octic_vits_amd.metrics.evaluate_linear_classifiers)")
         if class_mapping is not None:
-            raise NotImplementedError("LinearProbe.evaluate: class mappings")
+            raise NotImplementedError("LinearProbe.evaluate: class mappings (octic_vits_amd.metrics.evaluate_linear_classifiers "
+                                      "takes one)")
         self._need_gpu()
         self.loss_sum.zero_()
         self.topk.zero_()
