@@ -7,6 +7,11 @@ Tolerances (stated per check):
   bf16 path : operands rounded to bf16 (8 bit mantissa, rel 2^-9 = 2e-3 per element), f32 accumulate,
               bf16 outputs -> compare against the oracle evaluated on the SAME bf16-rounded inputs,
               atol/rtol 2e-2 of the output scale.
+
+These are parity checks at a few training shapes.  Edge coverage of the elementwise and permutation kernels (D8-GELU, head
+pack / unpack, cast_rowscale, handoff_cat, power spectrum, im2col, colsum_a1, the weight preparations: every template instance,
+layout, grid-stride and tile edge, exact or oracle-derived bars) is in tests/test_elementwise_matrix_gpu.py; LayerNormD8 and the
+LinearD8 GEMMs have test_layernorm_d8_matrix_gpu.py and test_linear_d8_matrix_gpu.py.
 """
 import math
 
