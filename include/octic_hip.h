@@ -989,6 +989,32 @@ int octic_koleo_bwd(const void* x, int x_dtype, int64_t ldx, int64_t groups, int
                     const float* gterm, const int32_t* nn, const float* inv, const float* dist, void* dx, int64_t lddx,
                     void* stream);
 
+/* ---- input rows of a DINO / iBOT head call (dinov2/train/ssl_meta_arch.py:226-267) ----------------------------------------
+ * octic_head_rows: segments_dev is a DEVICE table of 1 .. 4 octic_head_segment.  Row r < n of a segment is source row
+ * j = idx ? idx[r] : r, which sits at base + (j / inner) * outer_ld + (j % inner) * inner_ld elements (the class tokens
+ * x_norm[:, 0]: inner 1, outer_ld = T D; the masked patch tokens x_norm[:, 1 + R:].flatten(0, 1)[idx]: inner = the patches of an
+ * image, outer_ld = T D, inner_ld = D, base at the first patch token), and belongs to row out_row0 + r of out [rows_out, D]
+ * (dtype OCTIC_F32 / OCTIC_BF16, element stride 1, row stride ldo >= D).  scatter == 0: the source rows are copied to out and
+ * every row of out that no segment covers is written as +0 (the padding up to `upperbound`).  scatter != 0: the rows of out
+ * (cotangents) are written back to their sources with plain stores - indices are distinct, as mask_indices_list is; the caller
+ * zero-fills the destination once.  A row whose j lies outside [0, src_rows) is +0 in the gather and skipped by the scatter.
+ * Rows move as 16-byte chunks: the bytes of a row do not depend on the row count, the row's position or its neighbours; no
+ * atomics.  The host cannot see the table: 16-byte aligned source rows and segments that do not overlap in out are the
+ * caller's to keep.  8 <= D <= 2^20, D % 8 == 0, 1 <= rows_out < 2^31, 1 <= n_segments <= 4.  OCTIC_ENULL, OCTIC_EDTYPE,
+ * OCTIC_ESHAPE (also ldo < D) and OCTIC_EALIGN (out or its row stride off 16 bytes) are returned before any launch. */
+typedef struct octic_head_segment {
+  const void* base;      /* first source row (dtype elements)                                  */
+  const int64_t* idx;    /* [n] source row indices on the device, or NULL = 0 .. n-1            */
+  int64_t n;             /* rows of the segment                                                 */
+  int64_t inner;         /* source rows per outer step (>= 1)                                   */
+  int64_t outer_ld;      /* elements between outer steps                                        */
+  int64_t inner_ld;      /* elements between the rows of one outer step                         */
+  int64_t out_row0;      /* first row of out the segment owns                                   */
+  int64_t src_rows;      /* addressable source rows: j outside [0, src_rows) is never touched   */
+} octic_head_segment;
+int octic_head_rows(const octic_head_segment* segments_dev, int n_segments, int64_t rows_out, int64_t D, int dtype, void* out,
+                    int64_t ldo, int scatter, void* stream);
+
 /* ---- linear-probe evaluation of a frozen backbone (dinov2/eval/linear.py) ----------------------------------------------
  * The grid of nn.Linear(K_h, C) classifiers of setup_linear_classifiers (linear.py:237-258) as one launch per stage over
  * all classifiers.  Every classifier reads a column range [col0, col0 + K) of one f32 feature row

@@ -138,6 +138,7 @@ _PROTOS = {
                                 c_void_p]),
     "octic_koleo_bwd": (c_int, [c_void_p, c_int, c_i64, c_i64, c_i64, c_i64, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_i64, c_void_p]),
+    "octic_head_rows": (c_int, [c_void_p, c_int, c_i64, c_i64, c_int, c_void_p, c_i64, c_int, c_void_p]),
     "octic_scale_residual_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int,
                                          c_void_p]),
     "octic_scale_residual_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_void_p,

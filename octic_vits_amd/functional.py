@@ -1600,6 +1600,57 @@ class DenseSwigluFn(torch.autograd.Function):
 
 
 # -------------------------------------------------------------------------------------- hand-off
+# ------------------------------------------------------------------ input rows of the DINO / iBOT heads (ssl.HEAD_HIP)
+class HeadRowsFn(torch.autograd.Function):
+    """The input rows of a DINO / iBOT head call (dinov2/train/ssl_meta_arch.py:226-267: new_zeros + index_select + copy_ + cat)
+    as ONE gather launch: out [rows_out, D] in the sources' dtype, source s - [n, D], or [B, P, D] read as its B * P rows - taken
+    through specs[s] = (idx or None, out_row0) into out[out_row0 : out_row0 + n], every other row +0.  Backward: one scatter
+    launch of the cotangent rows into the sources' gradients (plain stores: the indices are distinct, as mask_indices_list is),
+    an indexed source's gradient zero-filled once."""
+
+    @staticmethod
+    def forward(ctx, rows_out, specs, *sources):
+        out = torch.empty((rows_out, sources[0].shape[-1]), dtype=sources[0].dtype, device=sources[0].device)
+        ops.head_rows([(s.detach(), idx, r0) for s, (idx, r0) in zip(sources, specs)], out)
+        ctx.specs = specs
+        ctx.shapes = [s.shape for s in sources]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g2 = ops._aligned_rows2d(g, "head_rows")
+        grads, segs = [], []
+        for need, shape, (idx, r0) in zip(ctx.needs_input_grad[2:], ctx.shapes, ctx.specs):
+            if not need:
+                grads.append(None)
+                continue
+            gs = (torch.empty if idx is None else torch.zeros)(shape, dtype=g2.dtype, device=g2.device)
+            grads.append(gs)
+            segs.append((gs, idx, r0))
+        if segs:
+            ops.head_rows(segs, g2, scatter=True)
+        return (None, None, *grads)
+
+
+def head_rows_ok(rows_out, specs, sources):
+    """HeadRowsFn takes these sources: GPU tensors of one f32 / bf16 dtype and width, [n, D] or [B, P, D] with unit column stride
+    and 16-byte aligned rows, at least one row each, int64 indices on the device, at most four of them, not under torch.compile
+    tracing."""
+    if torch.compiler.is_compiling() or not 1 <= len(sources) <= ops.HEAD_ROWS_MAX_SEGMENTS or rows_out < 1:
+        return False
+    s0 = sources[0]
+    D, es = s0.shape[-1], s0.element_size()
+    if not s0.is_cuda or s0.dtype not in (torch.float32, torch.bfloat16) or D < 8 or D % 8:
+        return False
+    for s, (idx, _) in zip(sources, specs):
+        if (s.device != s0.device or s.dtype != s0.dtype or s.dim() not in (2, 3) or s.shape[-1] != D or s.numel() == 0
+                or s.stride(-1) != 1 or s.data_ptr() % 16 or any((ld * es) % 16 for ld in s.stride()[:-1])):
+            return False
+        if idx is not None and not (idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()):
+            return False
+    return True
+
+
 class HandoffCatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, c, out_dtype):

@@ -1221,6 +1221,80 @@ def koleo_bwd(x, groups, gterm, nn, inv, dist, eps=1e-8):
     return dx
 
 
+# ------------------------------------------------------------------ input rows of the DINO / iBOT heads (csrc/dino_head.hip)
+def _aligned_rows2d(x, what):
+    """x [rows, D] f32 / bf16 as a view with unit column stride and 16-byte aligned rows (a copy where it has neither)."""
+    _require_cuda(x)
+    if x.dim() != 2:
+        raise ValueError(f"{what}: expected [rows, D], got {tuple(x.shape)}")
+    dt_code(x.dtype)
+    if x.stride(1) != 1 or x.data_ptr() % 16 or (x.shape[0] > 1 and (x.stride(0) * x.element_size()) % 16):
+        x = x.contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone(memory_format=torch.contiguous_format)
+    return x
+
+
+def _ldrow(x):
+    """Row stride of a 2-D view (a one-row tensor's stride is whatever torch left there)."""
+    return x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1])
+
+
+HEAD_ROWS_MAX_SEGMENTS = 4
+_HEAD_TABLES = {}
+
+
+def _head_segment(src, idx, out_row0, D, dtype):
+    """One octic_head_segment (8 int64 words) for the rows of src - [n, D], or [B, P, D] read as its B * P rows - taken through
+    idx (int64 on the device) or in order."""
+    if src.dtype != dtype or src.shape[-1] != D or src.dim() not in (2, 3) or src.stride(-1) != 1:
+        raise ValueError(f"head_rows: sources must be {dtype} [n, {D}] or [B, P, {D}] with unit column stride, got "
+                         f"{tuple(src.shape)} {src.dtype}")
+    es = src.element_size()
+    if src.dim() == 2:
+        src_rows, inner, outer_ld, inner_ld = src.shape[0], 1, src.stride(0), 0
+        lds = (outer_ld,) if src_rows > 1 else ()
+    else:
+        src_rows, inner, outer_ld, inner_ld = src.shape[0] * src.shape[1], src.shape[1], src.stride(0), src.stride(1)
+        lds = ((outer_ld,) if src.shape[0] > 1 else ()) + ((inner_ld,) if src.shape[1] > 1 else ())
+    if src.data_ptr() % 16 or any((ld * es) % 16 for ld in lds):
+        raise ValueError("head_rows: source rows must be 16-byte aligned")
+    if idx is not None and (not idx.is_cuda or idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous()):
+        raise ValueError("head_rows: idx must be a contiguous int64 vector on the device")
+    n = src_rows if idx is None else idx.numel()
+    return (src.data_ptr(), 0 if idx is None else idx.data_ptr(), n, max(inner, 1), outer_ld, inner_ld, int(out_row0), src_rows)
+
+
+def head_rows(segments, out, scatter=False):
+    """The head's input rows (octic_head_rows).  segments: up to four (src, idx or None, out_row0) - see _head_segment; the rows
+    of a segment own out[out_row0 : out_row0 + n].  scatter False: out [rows_out, D] receives the source rows, every row no
+    segment covers is +0.  scatter True: the rows of out are written back to their sources (distinct indices: plain stores); the
+    sources are edited in place."""
+    import numpy as np
+    _require_cuda(out)
+    if out.dim() != 2 or out.stride(1) != 1 or not 1 <= len(segments) <= HEAD_ROWS_MAX_SEGMENTS:
+        raise ValueError("head_rows: out must be [rows_out, D] with unit column stride, with 1 .. 4 segments")
+    rows_out, D = out.shape
+    words = [_head_segment(src, idx, r0, D, out.dtype) for src, idx, r0 in segments]
+    spans = sorted((w[6], w[6] + w[2]) for w in words if w[2])
+    if any(a < 0 or b > rows_out for a, b in spans) or any(spans[i][1] > spans[i + 1][0] for i in range(len(spans) - 1)):
+        raise ValueError("head_rows: segments must lie inside out and not overlap")
+    key = (out.device, tuple(words))
+    table = _HEAD_TABLES.get(key)
+    if table is None:                              # (activations keep their addresses from step to step: one upload per layout)
+        if len(_HEAD_TABLES) >= 256:
+            _HEAD_TABLES.clear()
+        host = torch.from_numpy(np.asarray(words, dtype=np.int64).reshape(-1)).pin_memory()
+        table = _HEAD_TABLES[key] = host.to(out.device, non_blocking=True)
+    tk = KERNEL_TIMER.start()
+    check(lib().octic_head_rows(_p(table), len(words), rows_out, D, dt_code(out.dtype), _p(out), _ldrow(out), int(bool(scatter)),
+                                _stream(out)))
+    moved = rows_out if not scatter else sum(w[2] for w in words)
+    KERNEL_TIMER.stop(tk, f"head_rows_kernel<{'scatter' if scatter else 'gather'},{_DTN[out.dtype]}>",
+                      2 * moved * D * out.element_size())
+    return out
+
+
 def scale_residual_fwd(x, y, gamma, rs, rps):
     """out = x + rs[row // rps] * gamma * y   (x f32, y f32/bf16, same shape [..., d])."""
     _require_cuda(x)

@@ -6,8 +6,9 @@ Same classes, constructor arguments, ``state_dict`` keys and arithmetic as the r
 FSDP (parameters and optimizer state of a ViT-H student + teacher are ~13 GB: nothing to shard on a 288 GB device; the
 student is wrapped in DistributedDataParallel by ``SSLTrainer`` when a process group exists, the centre statistics are
 all-reduced as in the reference).  The backbones run on the HIP engine (octic blocks, attention, standard half); the
-heads are a few small dense ops per step and stay on torch; the losses' row passes run on csrc/ssl_loss.hip (the prototype axis
-of the DINO / iBOT terms, both centerings) and csrc/koleo.hip (the KoLeo regularizer) under ``FUSED_LOSS_ROWS``.
+heads are a few small dense ops per step and stay on torch, their input rows are assembled by csrc/dino_head.hip under
+``HEAD_HIP``; the losses' row passes run on csrc/ssl_loss.hip (the prototype axis of the DINO / iBOT terms, both centerings) and
+csrc/koleo.hip (the KoLeo regularizer) under ``FUSED_LOSS_ROWS``.
 
 Local crops (96 x 96 on a 224 model) need the positional-embedding resize branch, which raises TypeError in the
 reference as shipped (tuple patch size); ``OcticDinoVisionTransformer`` here implements the evident intent
@@ -25,6 +26,8 @@ import torch.nn.functional as F
 from . import functional as _OF
 
 FUSED_LOSS_ROWS = True      # GPU: the prototype-axis passes of the DINO / iBOT terms, both centerings, on csrc/ssl_loss.hip and the KoLeo term on csrc/koleo.hip (False: the eager composition)
+
+HEAD_HIP = True             # GPU: the input rows of the DINO / iBOT head calls (class tokens | masked patch tokens | zero padding) as one gather launch of csrc/dino_head.hip, one scatter launch backward (False: new_zeros + index_select + copy_ + cat)
 
 
 def _world():
@@ -395,6 +398,18 @@ class SSLMetaArch(nn.Module):
         self.teacher.eval()
         return self
 
+    @staticmethod
+    def _head_rows(rows_out, *segments):
+        """The input rows of a head call as one functional.HeadRowsFn gather - segments: (source, int64 indices or None, first
+        output row) - where HEAD_HIP is on and the kernel takes the sources (functional.head_rows_ok: GPU, f32 / bf16, 16-byte
+        aligned rows, not under torch.compile tracing); None otherwise: the caller then runs the stock assembly.  The rows are the
+        stock assembly's bit for bit, so the switch needs no autocast or shape condition of the head."""
+        sources = [s for s, _, _ in segments]
+        specs = tuple((idx, r0) for _, idx, r0 in segments)
+        if not HEAD_HIP or not _OF.head_rows_ok(rows_out, specs, sources):
+            return None
+        return _OF.HeadRowsFn.apply(rows_out, specs, *sources)
+
     def _student_forward(self, global_crops, local_crops, masks):
         """Backbone on both crop sets + the shared head on [local cls | global cls | masked patch tokens] in one call
         (ssl_meta_arch.py:226-267).  One function so that DistributedDataParallel sees a single forward."""
@@ -415,25 +430,31 @@ class SSLMetaArch(nn.Module):
 
         with torch.no_grad():
             tout = self.teacher.backbone(global_crops, is_training=True)
-            tcls = tout["x_norm_clstoken"].chunk(n_global_crops)
-            tcls = torch.cat((tcls[1], tcls[0]))                  # reversed so crop A is matched with crop B
+            tc0, tc1 = tout["x_norm_clstoken"].chunk(n_global_crops)
+            tcls = lambda: torch.cat((tc1, tc0))                  # reversed so crop A is matched with crop B
             tpatch = tout["x_norm_patchtokens"]
-            n_cls = tcls.shape[0]
+            n_cls = tc0.shape[0] + tc1.shape[0]
             masked_teacher = masked_teacher_centered = None
             if self.do_ibot and not self.ibot_separate_head:
-                buf = tpatch.new_zeros(upperbound + n_cls, tpatch.shape[-1])
-                buf[:n_cls].copy_(tcls)
-                torch.index_select(tpatch.flatten(0, 1), dim=0, index=mask_indices_list,
-                                   out=buf[n_cls:n_cls + n_masked_patches])
+                # crop B's class tokens | crop A's | masked patch tokens | +0 up to upperbound: one gather launch on the engine
+                buf = self._head_rows(upperbound + n_cls, (tc1, None, 0), (tc0, None, tc1.shape[0]),
+                                      (tpatch, mask_indices_list, n_cls))
+                if buf is None:
+                    buf = tpatch.new_zeros(upperbound + n_cls, tpatch.shape[-1])
+                    buf[:n_cls].copy_(tcls())
+                    torch.index_select(tpatch.flatten(0, 1), dim=0, index=mask_indices_list,
+                                       out=buf[n_cls:n_cls + n_masked_patches])
                 after = self.teacher.dino_head(buf)
                 tcls_after, masked_teacher = after[:n_cls], after[n_cls:n_cls + n_masked_patches]
             elif self.do_ibot:
-                buf = tpatch.new_zeros(upperbound, tpatch.shape[-1])
-                torch.index_select(tpatch.flatten(0, 1), dim=0, index=mask_indices_list, out=buf[:n_masked_patches])
-                tcls_after = self.teacher.dino_head(tcls)
+                buf = self._head_rows(upperbound, (tpatch, mask_indices_list, 0))
+                if buf is None:
+                    buf = tpatch.new_zeros(upperbound, tpatch.shape[-1])
+                    torch.index_select(tpatch.flatten(0, 1), dim=0, index=mask_indices_list, out=buf[:n_masked_patches])
+                tcls_after = self.teacher.dino_head(tcls())
                 masked_teacher = self.teacher.ibot_head(buf)[:n_masked_patches]
             else:
-                tcls_after = self.teacher.dino_head(tcls)
+                tcls_after = self.teacher.dino_head(tcls())
             if self.centering == "centering":
                 t_dino = self.dino_loss.softmax_center_teacher(tcls_after, teacher_temp=teacher_temp).view(
                     n_global_crops, -1, *tcls_after.shape[1:])
@@ -455,17 +476,29 @@ class SSLMetaArch(nn.Module):
         loss_dict, total = {}, 0
         sg, sl = (self._student_call or self._student_forward)(global_crops, local_crops, masks)
         pieces = [sl["x_norm_clstoken"], sg["x_norm_clstoken"]]
+        sizes = [p.shape[0] for p in pieces]
+        segments = [(pieces[0], None, 0), (pieces[1], None, sizes[0])]
         student_masked_after = None
-        if self.do_ibot:
-            sp = sg["x_norm_patchtokens"]
+
+        def masked_rows(sp):                                      # the stock assembly of the masked patch tokens + padding
             buf = sp.new_zeros(upperbound, sp.shape[-1])
             buf[:n_masked_patches].copy_(torch.index_select(sp.flatten(0, 1), dim=0, index=mask_indices_list))
+            return buf
+
+        if self.do_ibot:
+            sp = sg["x_norm_patchtokens"]
             if not self.ibot_separate_head:
-                pieces.append(buf)
+                segments.append((sp, mask_indices_list, sum(sizes)))
+                sizes.append(upperbound)
             else:
-                student_masked_after = self.student.ibot_head(buf)[:n_masked_patches]
-        # fmha.BlockDiagonalMask.from_tensor_list / split around the head = concatenate along tokens, split back
-        outs = list(self.student.dino_head(torch.cat(pieces, dim=0)).split([p.shape[0] for p in pieces], dim=0))
+                buf = self._head_rows(upperbound, (sp, mask_indices_list, 0))
+                student_masked_after = self.student.ibot_head(masked_rows(sp) if buf is None else buf)[:n_masked_patches]
+        # fmha.BlockDiagonalMask.from_tensor_list / split around the head = concatenate along tokens, split back; on the engine
+        # local cls | global cls | masked patches | +0 up to upperbound is one gather launch (functional.HeadRowsFn)
+        rows = self._head_rows(sum(sizes), *segments)
+        if rows is None:
+            rows = torch.cat(pieces + ([masked_rows(sp)] if len(segments) == 3 else []), dim=0)
+        outs = list(self.student.dino_head(rows).split(sizes, dim=0))
         sl_after, sg_after = outs.pop(0), outs.pop(0)
         if self.do_ibot and not self.ibot_separate_head:
             student_masked_after = outs.pop(0)[:n_masked_patches]
