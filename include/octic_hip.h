@@ -1465,6 +1465,46 @@ int octic_crop_resize_u8(const uint8_t* data, int64_t data_bytes, const octic_cr
                          int64_t coef_len, int N, int OH, int OW, void* dst, int dtype_out, float mean0, float mean1,
                          float mean2, float std0, float std1, float std2, void* stream);
 
+/* ---- linear depth head of the DINOv2 hub (dinov2/hub/depthers.py:36-67; hub/depth/decode_heads.py: BNHead, depth_pred;
+ *      csrc/depth.hip) -------------------------------------------------------------------------------------------------
+ * The reference upsamples the [patch | class token] channels of 1 or 4 layers u = 4 times and projects the large tensor to
+ * 256 bins.  Projection and bilinear resize commute and the class-token half is one bias vector per image, so the engine
+ * projects at patch resolution (octic_depth_logits) and resizes, normalises and takes the expectation in one pass
+ * (octic_depth_expect); neither the concatenated nor the upsampled tensor exists.
+ * Limits (octic_depth_ok / octic_depth_plan are the only place they live): D % 64 == 0, 64 <= D <= 4096, layers 1 .. 4,
+ * n_bins == 256, upsample 1 | 2 | 4 (the scale is exact in f32), B, h, w >= 1, h w upsample^2 < 2^31, fewer than 2^31
+ * workgroups.  Strides are multiples of 4 floats, operand rows 16-byte aligned.  OCTIC_ENULL, OCTIC_ESHAPE and OCTIC_EALIGN are
+ * returned before any launch.  All offsets are 64-bit.  No atomics: results are bitwise reproducible and an image's map does
+ * not depend on its batch mates or its place in the batch.
+ * octic_depth_ok: 1 where the kernels take (D, layers, n_bins, upsample), else 0.
+ * octic_depth_plan: out[0] = patch rows per workgroup of the logits launch (a workgroup never leaves its image), out[1] = its
+ * workgroups = B ceil(h w / out[0]), out[2] = summation chains per logit = layers D / 64, out[3] = workgroups of the
+ * expectation launch.  OCTIC_ESHAPE exactly where the launchers refuse by shape.                                            */
+int octic_depth_ok(int D, int layers, int n_bins, int upsample);
+int octic_depth_plan(int64_t B, int h, int w, int D, int layers, int n_bins, int upsample, int out[4]);
+/* Lo [B, h w, 256] dense f32: Lo[b, p, k] = sum_l patch_l[b, p, :] . W[k, 2 D l : 2 D l + D]
+ *                                          + (bias[k] + sum_l cls_l[b, :] . W[k, 2 D l + D : 2 D l + 2 D]).
+ * patch / patch_ldb / patch_ldr / cls / cls_ldb: HOST arrays of `layers` entries - the patch-token rows of layer l start at
+ * patch[l], image b at + b patch_ldb[l], row p at + p patch_ldr[l] floats (>= D); the class token of image b at
+ * cls[l] + b cls_ldb[l]: the views out[:, 1 + R:] and out[:, 0] of a [B, T, D] block output, read in place.  W: DEVICE f32
+ * [256, 2 D layers] contiguous in the reference's channel order (per layer the patch half, then the class-token half);
+ * bias DEVICE f32 [256]; image_bias: DEVICE f32 [B, 256] workspace, on return the per-image term in brackets above.
+ * Arithmetic contract (exact-f32 MFMA = fmaf): the per-image term is 64 fmaf chains - chain i takes the column quads
+ * 4 i + 256 j (j ascending) of layer 0, then of layer 1, ... - added by a butterfly over offsets 32, 16, 8, 4, 2, 1, plus
+ * bias[k]; a logit is layers D / 64 fmaf chains of 64 consecutive columns, each started from zero, added in ascending
+ * (layer, column) order to a zero accumulator, plus the per-image term.  Both orders depend on (layers, D) alone.           */
+int octic_depth_logits(const float* const* patch, const int64_t* patch_ldb, const int64_t* patch_ldr, const float* const* cls,
+                       const int64_t* cls_ldb, int layers, int64_t B, int h, int w, int D, const float* W, const float* bias,
+                       int n_bins, float* image_bias, float* Lo, void* stream);
+/* depth [B, upsample h, upsample w] f32 from Lo: per output pixel the up-to-four source cells under torch's
+ * upsample_bilinear2d weights for align_corners = False (src = (dst + 0.5) / upsample - 0.5 clamped below at 0,
+ * i0 = floor(src), i1 = min(i0 + 1, n - 1), upper weight src - i0; horizontal pairs first, then the vertical pair), per bin
+ * z = (v < 0 ? 0 : v) + 0.1f (NaN stays NaN, as torch.relu), depth = sum_k bins[k] z_k / sum_k z_k clamped to
+ * [min_depth, max_depth] (NaN passes, as torch.clamp).  bins: DEVICE f32 [256], 16-byte aligned (the host's torch.linspace).
+ * Sums: lane i adds bins 4 i .. 4 i + 3 in order, the 64 lane sums by a butterfly over offsets 32 .. 1.                     */
+int octic_depth_expect(const float* Lo, int64_t B, int h, int w, int n_bins, int upsample, const float* bins, float min_depth,
+                       float max_depth, float* depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ class OcticView(ctypes.Structure):
 
 
 PtrArray5 = c_void_p * 5
+PtrArray4, I64Array4 = c_void_p * 4, c_i64 * 4     # the per-layer operand tables of octic_depth_logits
 VP = ctypes.POINTER(OcticView)
 
 # name -> (restype, argtypes)
@@ -300,6 +301,12 @@ _PROTOS = {
     "octic_crop_resize_max_taps": (c_int, [c_int]),
     "octic_crop_resize_rows": (c_int, []),
     "octic_crop_resize_u8": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_int] + [c_float] * 6 + [c_void_p]),
+    "octic_depth_ok": (c_int, [c_int, c_int, c_int, c_int]),
+    "octic_depth_plan": (c_int, [c_i64, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    # patch / patch_ldb / patch_ldr / cls / cls_ldb are HOST arrays of `layers` entries (PtrArray4 / I64Array4)
+    "octic_depth_logits": (c_int, [c_void_p] * 5 + [c_int, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                                    c_void_p]),
+    "octic_depth_expect": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p]),
 }
 
 

@@ -2509,3 +2509,85 @@ def crop_resize_u8(data, rows, coef, mean, std, dst):
                                      *[float(v) for v in mean], *[float(v) for v in std], _stream(data)))
     KERNEL_TIMER.stop(t, "crop_resize_kernel", data.numel() + dst.numel() * dst.element_size())
     return dst
+
+
+# ---------------------------------------------------------------------------- linear depth head of the hub (csrc/depth.hip)
+DEPTH_BINS = 256
+
+
+def depth_head_ok(D, layers, n_bins=DEPTH_BINS, upsample=4):
+    """The depth kernels take this head (octic_depth_ok, the only place the limits live): D % 64 == 0, 64 <= D <= 4096,
+    1 <= layers <= 4, 256 bins, upsample 1 | 2 | 4."""
+    return bool(lib().octic_depth_ok(int(D), int(layers), int(n_bins), int(upsample)))
+
+
+def depth_plan(B, h, w, D, layers, n_bins=DEPTH_BINS, upsample=4):
+    """octic_depth_plan: (patch rows per workgroup of the logits launch, its workgroups, chains per logit, workgroups of the
+    expectation launch), or None where the launchers refuse the shape."""
+    return _lib.plan("octic_depth_plan", int(B), int(h), int(w), int(D), int(layers), int(n_bins), int(upsample))
+
+
+def _depth_rows(t, what):
+    """t ([B, n, D] patch rows or [B, D] class tokens) as the f32 view the kernel reads in place."""
+    _require_cuda(t)
+    if t.dtype != torch.float32 or t.stride(-1) != 1:
+        raise ValueError(f"depth_logits: {what} must be f32 with contiguous channels")
+    if t.data_ptr() % 16 or any(s % 4 for s in t.stride()[:-1]):
+        raise ValueError(f"depth_logits: {what} needs 16-byte aligned rows (strides that are multiples of 4 floats)")
+    return t
+
+
+def depth_logits(pairs, weight, bias, grid, out=None):
+    """Lo [B, h w, 256] f32 = the bin logits of BNHead's 1x1 convolution at patch resolution.  pairs: per layer (patch rows
+    [B, h w, D], class token [B, D]) - any views with contiguous channels, read in place (out[:, 1 + R:] and out[:, 0] of a block
+    output); weight: f32 [256, 2 D layers] contiguous in the reference's channel order; bias f32 [256]; grid = (h, w)."""
+    layers = len(pairs)
+    if not 1 <= layers <= 4:
+        raise ValueError("depth_logits: 1 to 4 layers")
+    h, w = int(grid[0]), int(grid[1])
+    B, _, D = pairs[0][0].shape
+    dev = pairs[0][0].device
+    P, LB, LR, C, CB = _lib.PtrArray4(), _lib.I64Array4(), _lib.I64Array4(), _lib.PtrArray4(), _lib.I64Array4()
+    for l, (p, c) in enumerate(pairs):
+        if tuple(p.shape) != (B, h * w, D) or tuple(c.shape) != (B, D):
+            raise ValueError(f"depth_logits: layer {l} must be ([B, h w, D], [B, D]) = ({(B, h * w, D)}, {(B, D)}), got "
+                             f"{tuple(p.shape)}, {tuple(c.shape)}")
+        _depth_rows(p, "patch rows")
+        _depth_rows(c, "class tokens")
+        P[l], LB[l], LR[l], C[l], CB[l] = p.data_ptr(), p.stride(0), p.stride(1), c.data_ptr(), c.stride(0)
+    if (weight.dtype != torch.float32 or not weight.is_contiguous() or tuple(weight.shape) != (DEPTH_BINS, 2 * D * layers)
+            or bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != DEPTH_BINS
+            or weight.device != dev or bias.device != dev):
+        raise ValueError(f"depth_logits: weight must be a contiguous f32 [{DEPTH_BINS}, {2 * D * layers}], bias an f32 [{DEPTH_BINS}]")
+    if out is None:
+        out = torch.empty((B, h * w, DEPTH_BINS), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (B, h * w, DEPTH_BINS) or out.device != dev:
+        raise ValueError("depth_logits: out must be a contiguous f32 [B, h w, 256] on the operands' device")
+    image_bias = torch.empty((B, DEPTH_BINS), dtype=torch.float32, device=dev)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_depth_logits(P, LB, LR, C, CB, layers, B, h, w, D, _p(weight), _p(bias), DEPTH_BINS, _p(image_bias),
+                                   _p(out), _stream(out)))
+    KERNEL_TIMER.stop(t, "depth_logits_kernel", 4 * (B * h * w * (D * layers + DEPTH_BINS) + DEPTH_BINS * 2 * D * layers),
+                      2.0 * B * h * w * D * layers * DEPTH_BINS)
+    return out
+
+
+def depth_expect(Lo, grid, upsample, bins, min_depth, max_depth, out=None):
+    """depth [B, 1, u h, u w] f32 from the patch-level logits Lo [B, h w, 256]: bilinear resize (align_corners=False),
+    relu + 0.1, the normalised expectation over bins (f32 [256]) and the clamp to [min_depth, max_depth], one launch."""
+    _require_cuda(Lo)
+    h, w, u = int(grid[0]), int(grid[1]), int(upsample)
+    if Lo.dtype != torch.float32 or not Lo.is_contiguous() or Lo.dim() != 3 or tuple(Lo.shape[1:]) != (h * w, DEPTH_BINS):
+        raise ValueError("depth_expect: Lo must be a contiguous f32 [B, h w, 256]")
+    if bins.dtype != torch.float32 or not bins.is_contiguous() or bins.numel() != DEPTH_BINS or bins.device != Lo.device:
+        raise ValueError("depth_expect: bins must be a contiguous f32 [256] on Lo's device")
+    B = Lo.shape[0]
+    if out is None:
+        out = torch.empty((B, 1, u * h, u * w), dtype=torch.float32, device=Lo.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * u * h * u * w or out.device != Lo.device:
+        raise ValueError("depth_expect: out must be a contiguous f32 [B, 1, u h, u w] on Lo's device")
+    t = KERNEL_TIMER.start()
+    check(lib().octic_depth_expect(_p(Lo), B, h, w, DEPTH_BINS, u, _p(bins), float(min_depth), float(max_depth), _p(out),
+                                   _stream(Lo)))
+    KERNEL_TIMER.stop(t, "depth_expect_kernel", 4 * (Lo.numel() + out.numel()))
+    return out
