@@ -306,6 +306,23 @@ int octic_linear_d8_wgrad_splits(int64_t M, int cin, int cout);
 int octic_linear_d8_wgrad_tile(int64_t M, int cin, int cout);   /* tile width 32*TT of wgrad_kernel<TIN, TT> */
 int octic_linear_d8_wgrad(const octic_view* x, const octic_view* dy, int64_t M, int cin, int cout, int dtype,
                           float* workspace, int splits, void* stream);
+/* octic_linear_d8_wgrad under the stochastic-depth mask of the branch: sample_scale = one f32 factor per sample of
+ * rows_per_sample token rows (M % rows_per_sample == 0, else OCTIC_ESHAPE; a pointer off 4 bytes: OCTIC_EALIGN), or NULL.
+ * sample_scale[b] == 0 PROMISES that every dy row of sample b is zero.  A bf16 launch on the ring kernel whose groups have at
+ * most 4096 steps of 32 rows then reads only the LIVE steps - those with a token row of a kept sample - and deals them evenly:
+ * of a group's L live steps, split s of S sums those of rank [L s / S, L (s + 1) / S) in ascending order; a split left
+ * without steps stores zeros.  Plan, workspace, `splits` and grid are those of the plain entry; the f32 slab sums are grouped
+ * differently, so the gradients agree with the plain entry's as two summation orders of the same f32 terms do (bit for bit
+ * where those sums are exact).  Without the promise the dropped rows are simply left out.  NULL, f32 operands, the tiled
+ * kernel and longer groups launch exactly what octic_linear_d8_wgrad launches, which forwards NULL.                    */
+int octic_linear_d8_wgrad_skip(const octic_view* x, const octic_view* dy, int64_t M, int cin, int cout, int dtype,
+                               float* workspace, int splits, const float* sample_scale, int rows_per_sample, void* stream);
+/* Host-only query: the steps a masked launch walks, through the kernel's own liveness and share rules.  sample_scale is a HOST
+ * array here.  Writes (group in launch order: E first, then A1 A2 B1 B2; split; step) for every step walked, groups and
+ * splits ascending and the steps of a split in the order it takes them, `cap` entries at most.  Returns their number, or
+ * OCTIC_ESHAPE for a launch that would run unmasked (f32, the tiled kernel, more than 4096 steps) or a cap too small. */
+int octic_linear_d8_wgrad_order_dropped(int64_t M, int cin, int cout, int dtype, int splits, const float* sample_scale,
+                                        int rows_per_sample, int cap, int* out_group, int* out_split, int* out_step);
 int octic_linear_d8_wgrad_finish(const float* workspace, int splits, int cin, int cout,
                                  const float* const w32[5], const float* const cs[5], const float* bias,
                                  const float* dysum, float* const dw[5], float* const dcs[5], float* dbias,

@@ -81,6 +81,9 @@ _PROTOS = {
     "octic_linear_d8_wgrad_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
     "octic_linear_d8_wgrad_splits": (c_int, [c_i64, c_int, c_int]),
     "octic_linear_d8_wgrad": (c_int, [VP, VP, c_i64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "octic_linear_d8_wgrad_skip": (c_int, [VP, VP, c_i64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "octic_linear_d8_wgrad_order_dropped": (c_int, [c_i64, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                                                    c_void_p, c_void_p]),
     "octic_linear_d8_wgrad_finish": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p]),
     "octic_linear_d8_wgrad_finish_batch": (c_int, [c_void_p, c_int, c_void_p]),

@@ -35,6 +35,10 @@ struct WgArgs {
   int wgs;         // workgroups in all
   int64_t slab_elems;
   float* slabs;
+  // Stochastic depth (octic_linear_d8_wgrad_skip; wgrad_ring_kernel<true> only): the branch's per-sample factor,
+  // [M / rows_per_sample] f32.  sample_scale[b] == 0 PROMISES that every dY row of sample b is zero.
+  const float* sample_scale;
+  int rows_per_sample;
 };
 
 template <typename T> struct WElem;
@@ -215,6 +219,30 @@ __device__ inline void wg_wait_tiles(int ahead) {
   else asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
 }
 
+// ---- stochastic depth (wgrad_ring_kernel<true>).  A STEP is 32 LDS rows of a group counted from the group's row 0 (the fixed
+// splits of the unmasked kernel begin at multiples of 32 rows, so these are its steps too); LDS row mm of the pair group is
+// token mm >> 1.  A step is LIVE if one of the token rows it covers belongs to a sample whose factor is non-zero.  The L live
+// steps of a group are dealt evenly: split s of S walks those of rank [L s / S, L (s + 1) / S), ascending.  The three rules
+// below are what the kernel runs and what octic_linear_d8_wgrad_order_dropped reports.
+constexpr int kWgLiveWords = 64;                         // bitmap words of 64 steps: 4096 steps; a longer group runs unmasked
+__host__ __device__ inline int wg_group_steps(int64_t rows) { return (int)((rows + kWgR - 1) / kWgR); }
+// first and last sample that step t of a group (t < wg_group_steps(rows)) touches
+__host__ __device__ inline void wg_step_samples(int t, int64_t rows, int pair, int rows_per_sample, int& b0, int& b1) {
+  const int64_t m0 = (int64_t)t * kWgR;
+  const int64_t m1 = m0 + kWgR < rows ? m0 + kWgR : rows;
+  b0 = (int)((m0 >> pair) / rows_per_sample);
+  b1 = (int)(((m1 - 1) >> pair) / rows_per_sample);
+}
+__host__ __device__ inline bool wg_step_live(const float* sample_scale, int t, int64_t rows, int pair, int rows_per_sample) {
+  int b0, b1;
+  wg_step_samples(t, rows, pair, rows_per_sample, b0, b1);
+  bool live = false;
+  for (int b = b0; b <= b1; ++b) live |= sample_scale[b] != 0.f;
+  return live;
+}
+__host__ __device__ inline int wg_share_begin(int L, int s, int S) { return (int)((int64_t)L * s / S); }
+
+template <bool SKIP>
 __global__ __launch_bounds__(256, 2) void wgrad_ring_kernel(WgArgs args) {
   constexpr int TT = 5, BW = 160;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -234,13 +262,51 @@ __global__ __launch_bounds__(256, 2) void wgrad_ring_kernel(WgArgs args) {
   const int K = G.K, N = G.N;
   int64_t chunk = (G.rows + G.splits - 1) / G.splits;
   chunk = (chunk + kWgR - 1) / kWgR * kWgR;
-  const int64_t r0 = (int64_t)split * chunk;
-  const int64_t r1 = r0 + chunk < G.rows ? r0 + chunk : G.rows;
-  const int nsteps = r0 < r1 ? (int)((r1 - r0 + kWgR - 1) / kWgR) : 0;
+  // SKIP: the descriptors below are those of the group's step 0 and a split ends where the group does
+  const int64_t r0 = SKIP ? 0 : (int64_t)split * chunk;
+  const int64_t r1 = (!SKIP && r0 + chunk < G.rows) ? r0 + chunk : G.rows;
+  int nsteps = r0 < r1 ? (int)((r1 - r0 + kWgR - 1) / kWgR) : 0;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wk = wid & 1, wn = wid >> 1;
   const int fr = lane & 15, kg = lane >> 4;
+
+  // ---- SKIP: the live-step bitmap of this workgroup's GROUP, lane = step: wave w builds words w, w + 4, .. with one ballot
+  // each.  The factors of the first five words of a wave (1280 steps) are requested here, ahead of the descriptor set-up that
+  // overlaps them; a lane reads the first and the last sample its step touches at once and loops over those in between (none
+  // from 32 token rows per sample up).
+  constexpr int PRE = 5;
+  [[maybe_unused]] const int gsteps = nsteps;   // SKIP: wg_group_steps(G.rows)
+  [[maybe_unused]] unsigned long long* live_words = nullptr;
+  [[maybe_unused]] float pre_a[PRE], pre_b[PRE];
+  [[maybe_unused]] int nwords = 0;
+  [[maybe_unused]] auto live_request = [&](int w, float& fa, float& fb) {
+    const int t = w * 64 + lane;
+    int b0, b1;
+    wg_step_samples(t < gsteps ? t : gsteps - 1, G.rows, G.pair, args.rows_per_sample, b0, b1);
+    fa = args.sample_scale[b0];
+    fb = args.sample_scale[b1];
+  };
+  [[maybe_unused]] auto live_store = [&](int w, float fa, float fb) {
+    const int t = w * 64 + lane;
+    bool live = false;
+    if (t < gsteps) {
+      int b0, b1;
+      wg_step_samples(t, G.rows, G.pair, args.rows_per_sample, b0, b1);
+      live = fa != 0.f || fb != 0.f;
+      for (int b = b0 + 1; b < b1; ++b) live |= args.sample_scale[b] != 0.f;
+    }
+    const unsigned long long m = __ballot(live);
+    if (lane == 0) live_words[w] = m;
+  };
+  if constexpr (SKIP) {
+    __shared__ unsigned long long wg_live[kWgLiveWords];
+    live_words = wg_live;
+    nwords = (gsteps + 63) >> 6;          // >= 1; the launcher keeps it within kWgLiveWords
+#pragma unroll
+    for (int i = 0; i < PRE; ++i)
+      if (wid + 4 * i < nwords) live_request(wid + 4 * i, pre_a[i], pre_b[i]);
+  }
 
   // ---- DMA descriptors: instruction j of this wave is tile chunk q = wid + 4j (0-9: X, 10-19: dY)
   const char* src[5];
@@ -266,15 +332,43 @@ __global__ __launch_bounds__(256, 2) void wgrad_ring_kernel(WgArgs args) {
     ldst[j] = (isY ? kWgTile : 0) + qq * 1024;
   }
   int l_step = 0, l_stage = 0;
+  // SKIP: the scalar walk over the bitmap that finds the step a tile comes from - the current word in SGPRs, find-first-set,
+  // one LDS read per 64 steps (as dense_tn_kernel<KW, true>).  Called once per issued tile: nsteps times, which is what the
+  // words from (live_wi, live_w) on still hold.
+  [[maybe_unused]] int live_wi = 0;
+  [[maybe_unused]] unsigned long long live_w = 0;
+  [[maybe_unused]] auto next_live = [&]() {
+    while (live_w == 0) {
+      ++live_wi;
+      const unsigned long long v = live_words[live_wi];
+      live_w = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+               (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+    }
+    const int j = __builtin_ctzll(live_w);
+    live_w &= live_w - 1;
+    return (live_wi << 6) + j;
+  };
   auto issue = [&]() {
     const unsigned st = lds_offset(lds) + l_stage * kWgStage;
-    const bool tail = (int64_t)(l_step + 1) * kWgR > r1 - r0;
+    if constexpr (SKIP) {
+      // the source of step t from t itself; the zero-page tail belongs to the group's last step
+      const int t = next_live();
+      const bool tail = (int64_t)(t + 1) * kWgR > G.rows;
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const char* p = src[j];
-      if (tail && r0 + (int64_t)l_step * kWgR + row_in_tile[j] >= r1) p = (const char*)g_wg_zero + cbyte[j];
-      dma16_to_lds(st + ldst[j], p);
-      src[j] += inc[j];
+      for (int j = 0; j < 5; ++j) {
+        const char* p = src[j] + (int64_t)t * inc[j];
+        if (tail && (int64_t)t * kWgR + row_in_tile[j] >= G.rows) p = (const char*)g_wg_zero + cbyte[j];
+        dma16_to_lds(st + ldst[j], p);
+      }
+    } else {
+      const bool tail = (int64_t)(l_step + 1) * kWgR > r1 - r0;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        const char* p = src[j];
+        if (tail && r0 + (int64_t)l_step * kWgR + row_in_tile[j] >= r1) p = (const char*)g_wg_zero + cbyte[j];
+        dma16_to_lds(st + ldst[j], p);
+        src[j] += inc[j];
+      }
     }
     l_stage = l_stage == kWgS - 1 ? 0 : l_stage + 1;
     ++l_step;
@@ -306,6 +400,38 @@ __global__ __launch_bounds__(256, 2) void wgrad_ring_kernel(WgArgs args) {
     offb[i] = kWgTile + frow * 320 + ((cb + rot) % 20) * 16 + (fr & 1) * 8;
   }
 
+  if constexpr (SKIP) {
+    // ---- the bitmap, one barrier, then this split's share: lane w holds word w, an inclusive scan of the popcounts gives the
+    // count L and the word in which rank L s / S lies.  An empty share (L < S, or nobody kept) issues nothing, passes no
+    // further barrier - nsteps is the same in all four waves - and stores its zero accumulators below.
+#pragma unroll
+    for (int i = 0; i < PRE; ++i)
+      if (wid + 4 * i < nwords) live_store(wid + 4 * i, pre_a[i], pre_b[i]);
+    for (int w = wid + 4 * PRE; w < nwords; w += 4) {
+      float fa, fb;
+      live_request(w, fa, fb);
+      live_store(w, fa, fb);
+    }
+    __syncthreads();
+    const unsigned long long mine = lane < nwords ? live_words[lane] : 0ull;
+    const int pc = __popcll(mine);
+    int incl = pc;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int v = __shfl_up(incl, d);
+      if (lane >= d) incl += v;
+    }
+    const int L = __builtin_amdgcn_readfirstlane(__shfl(incl, 63));
+    const int lo = wg_share_begin(L, split, G.splits), hi = wg_share_begin(L, split + 1, G.splits);
+    nsteps = hi - lo;
+    const int wi = __builtin_amdgcn_readfirstlane(__popcll(__ballot(incl <= lo)));   // words wholly below rank lo (< nwords if nsteps)
+    const int below = __builtin_amdgcn_readfirstlane(__shfl(incl - pc, wi & 63));
+    unsigned long long w0 = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(__shfl((int)(mine >> 32), wi & 63)) << 32) |
+                            (unsigned)__builtin_amdgcn_readfirstlane(__shfl((int)mine, wi & 63));
+    for (int i = below; i < lo && nsteps > 0; ++i) w0 &= w0 - 1;
+    live_wi = wi;
+    live_w = nsteps > 0 ? w0 : 0ull;
+  }
 #pragma unroll
   for (int pz = 0; pz < kWgS - 1; ++pz)
     if (pz < nsteps) issue();
@@ -484,6 +610,14 @@ int launch_wgrad_tt(WgArgs& a, hipStream_t s) {
   return launch_status();
 }
 
+// a ring launch runs wgrad_ring_kernel<true> when it has a mask and every group's steps fit the bitmap
+inline bool wgrad_ring_masked(const WgArgs& a) {
+  if (!a.sample_scale) return false;
+  for (int i = 0; i < a.ngroups; ++i)
+    if (wg_group_steps(a.g[i].rows) > kWgLiveWords * 64) return false;
+  return true;
+}
+
 inline int launch_wgrad_ring(WgArgs& a, hipStream_t s) {
   int t = 0;
   for (int i = 0; i < a.ngroups; ++i) {
@@ -495,10 +629,12 @@ inline int launch_wgrad_ring(WgArgs& a, hipStream_t s) {
   a.wgs = t;
   static DeviceOnce once;
   if (kWgS * kWgStage > 64 * 1024 && once.first()) {
-    (void)hipFuncSetAttribute((const void*)wgrad_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kWgS * kWgStage);
+    (void)hipFuncSetAttribute((const void*)wgrad_ring_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kWgS * kWgStage);
+    (void)hipFuncSetAttribute((const void*)wgrad_ring_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kWgS * kWgStage);
     (void)hipGetLastError();
   }
-  wgrad_ring_kernel<<<t, 256, kWgS * kWgStage, s>>>(a);
+  if (wgrad_ring_masked(a)) wgrad_ring_kernel<true><<<t, 256, kWgS * kWgStage, s>>>(a);
+  else wgrad_ring_kernel<false><<<t, 256, kWgS * kWgStage, s>>>(a);
   return launch_status();
 }
 
@@ -592,16 +728,64 @@ int octic_linear_d8_wgrad_splits(int64_t M, int cin, int cout) {
   return octic_linear_d8_wgrad_plan(M, cin, cout, OCTIC_F32, out) == OCTIC_OK ? out[2] : 1;
 }
 
+// the mask of the _skip entry point: NULL, or one f32 factor per sample of rows_per_sample token rows (as dw_mask_status of
+// csrc/dense_wgrad.hip)
+static int wg_mask_status(const float* sample_scale, int rows_per_sample, int64_t M) {
+  if (!sample_scale) return OCTIC_OK;
+  if (rows_per_sample <= 0 || M % rows_per_sample) return OCTIC_ESHAPE;
+  return ((uintptr_t)sample_scale & 3) ? OCTIC_EALIGN : OCTIC_OK;
+}
+
 int octic_linear_d8_wgrad(const octic_view* x, const octic_view* dy, int64_t M, int cin, int cout, int dtype,
                           float* workspace, int splits, void* stream) {
+  return octic_linear_d8_wgrad_skip(x, dy, M, cin, cout, dtype, workspace, splits, nullptr, 0, stream);
+}
+
+int octic_linear_d8_wgrad_order_dropped(int64_t M, int cin, int cout, int dtype, int splits, const float* sample_scale,
+                                        int rows_per_sample, int cap, int* out_group, int* out_split, int* out_step) {
+  int e;
+  if ((e = check_c_dt(cin, dtype)) || (e = check_c_dt(cout, dtype))) return e;
+  if (M <= 0 || splits <= 0 || cap < 0) return OCTIC_ESHAPE;
+  if (!sample_scale || !out_group || !out_split || !out_step) return OCTIC_ENULL;
+  if ((e = wg_mask_status(sample_scale, rows_per_sample, M))) return e;
+  WgArgs a = {};
+  d8_group_table(a, M, cin, cout);
+  a.sample_scale = sample_scale;
+  if (wgrad_plan(a, dtype).kernel != OCTIC_WGRAD_RING || !wgrad_ring_masked(a)) return OCTIC_ESHAPE;
+  int n = 0;
+  for (int gidx = 0; gidx < 5; ++gidx) {
+    const WgGroup& g = a.g[gidx];
+    const int S = group_splits(splits, gidx == 0), T = wg_group_steps(g.rows);
+    int L = 0;
+    for (int t = 0; t < T; ++t) L += wg_step_live(sample_scale, t, g.rows, g.pair, rows_per_sample);
+    int rank = 0, s = 0;
+    for (int t = 0; t < T; ++t) {
+      if (!wg_step_live(sample_scale, t, g.rows, g.pair, rows_per_sample)) continue;
+      while (rank >= wg_share_begin(L, s + 1, S)) ++s;
+      if (n >= cap) return OCTIC_ESHAPE;
+      out_group[n] = gidx;
+      out_split[n] = s;
+      out_step[n] = t;
+      ++n;
+      ++rank;
+    }
+  }
+  return n;
+}
+
+int octic_linear_d8_wgrad_skip(const octic_view* x, const octic_view* dy, int64_t M, int cin, int cout, int dtype,
+                               float* workspace, int splits, const float* sample_scale, int rows_per_sample, void* stream) {
   int e;
   if ((e = check_c_dt(cin, dtype)) || (e = check_c_dt(cout, dtype))) return e;
   if ((e = check_view(x, cin, dtype)) || (e = check_view(dy, cout, dtype))) return e;
   if (!workspace) return OCTIC_ENULL;
   if (M <= 0 || splits <= 0) return OCTIC_ESHAPE;
+  if ((e = wg_mask_status(sample_scale, rows_per_sample, M))) return e;
   WgArgs a = {};
   a.slab_elems = linear_slab_elems(cin, cout);
   a.slabs = workspace;
+  a.sample_scale = sample_scale;
+  a.rows_per_sample = rows_per_sample;
   d8_group_table(a, M, cin, cout);
   // slab layout: [W_A1 | W_A2 | W_B1 | W_B2 | W_E]; launch order E first
   for (int gidx = 0; gidx < 5; ++gidx) {

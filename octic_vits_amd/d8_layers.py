@@ -298,13 +298,17 @@ class LinearD8(nn.Module):
     def weights(self):
         return tuple(getattr(self, "lin_" + n).weight for n in _IRREPS)
 
-    def forward(self, x_batched, resid=None, rs=None, cs=None, next_norm=None, skip_out=None, skip_dx=None, zero_dx=None):
+    def forward(self, x_batched, resid=None, rs=None, cs=None, next_norm=None, skip_out=None, skip_dx=None, zero_dx=None,
+                zero_dy=None):
         """next_norm (a LayerNormD8, only with resid): also return next_norm(result) -> (Octic, Octic or None); on the
         bf16 GPU path the two are ONE autograd node whose backward skips the cast pass (OF.LinearD8NormFn).
         skip_out / skip_dx: the branch's stochastic-depth factor as the sample mask of the forward / the input-gradient
         launch (OF.LinearD8Fn) - the caller's promise that every reader of that output honours the same mask.
         zero_dx (plain layers): the same factor as the `dropped` mask of the input-gradient launch - the caller's promise that
-        the cotangent rows of a dropped sample arrive as exact zeros (OF.LinearD8Fn)."""
+        the cotangent rows of a dropped sample arrive as exact zeros (OF.LinearD8Fn).
+        zero_dy (plain layers): the factor of the branch where the cotangent rows of this layer's OUTPUT are exact zeros for a
+        dropped sample - the mask of the weight gradient (OF.linear_wgrad_skip_scale).  A layer with rs uses its own: its
+        backward multiplies the cotangent by rs.  Not in the compacted batch, whose rows are all kept."""
         assert len(x_batched) == 5, "Input should be a 5-tuple"
         xp, cin = as_packed(x_batched)
         if 8 * cin != self.input_channels:
@@ -315,6 +319,7 @@ class LinearD8(nn.Module):
         if rs is not None and rs.numel() == xp.numel() // xp.shape[-1] and rs.numel() != xp.shape[0]:
             rps = 1                                   # one factor per ROW (several crop sets in one row tensor: ragged.py)
         cs5 = (None,) * 5 if cs is None else tuple(cs)
+        zero_dy = None if COMPACT_DROP_PATH else (rs if rs is not None else zero_dy)
         if torch.compiler.is_compiling():
             # being traced: the same kernels through the dispatcher (dispatch.py), no Python-side weight cache
             from . import dispatch as _D   # noqa: F401
@@ -328,10 +333,10 @@ class LinearD8(nn.Module):
                 and resid.dtype == torch.float32 and type(next_norm) is LayerNormD8):
             a, beta = next_norm.affine()
             y, yn = OF.LinearD8NormFn.apply(xp, *self.weights(), self.lin_A1.bias, resid, rs, *cs5, cin, cout, rps, dtype,
-                                            self._prep, *a, beta, next_norm.eps, skip_dx)
+                                            self._prep, *a, beta, next_norm.eps, skip_dx, zero_dy)
             return Octic(y, cout), Octic(yn, cout)
         y = OF.LinearD8Fn.apply(xp, *self.weights(), self.lin_A1.bias, resid, rs, *cs5, cin, cout, rps, dtype, self._prep,
-                                skip_out, skip_dx, zero_dx)
+                                skip_out, skip_dx, zero_dx, zero_dy)
         return Octic(y, cout) if next_norm is None else (Octic(y, cout), None)
 
     def extra_repr(self) -> str:
@@ -439,22 +444,30 @@ class MlpD8(nn.Module):
         feeds fc1's gradients (zeros again).  Only for exactly that chain: this class's own layers with nothing in between,
         the fused tail, whole samples of a plain batch (OF.linear_skip_scale: not the compacted batch, whose rows are all
         kept; not ragged rows; not a traced call, which stays on the dispatcher ops)."""
-        if not (OF.LINEAR_SKIP_DROPPED and rs is not None and resid is not None and not COMPACT_DROP_PATH
-                and type(self.fc1) is LinearD8 and type(self.fc2) is LinearD8 and type(self.act) is TritonGeluD8
-                and type(self.norm) is nn.Identity and not self.drop1.active and not self.drop2.active
-                and isinstance(xs, Octic) and xs.packed.dim() == 3 and xs.packed.is_cuda):
+        if not (OF.LINEAR_SKIP_DROPPED and self._plain_chain(xs, resid, rs)):
             return None
         xp = xs.packed
         return OF.linear_skip_scale(rs, xp.shape[1], xp.shape[0] * xp.shape[1])
 
+    def _plain_chain(self, xs, resid, rs):
+        """The structural half of _sample_mask, whatever the skip switches say: fc1, the D8-GELU and fc2 with its fused tail and
+        nothing in between.  fc1's output cotangent is then the GELU backward of (rs * dy) W2 - exact zeros in every row of a
+        sample with rs = 0, computed or stored."""
+        return (rs is not None and resid is not None and not COMPACT_DROP_PATH
+                and type(self.fc1) is LinearD8 and type(self.fc2) is LinearD8 and type(self.act) is TritonGeluD8
+                and type(self.norm) is nn.Identity and not self.drop1.active and not self.drop2.active
+                and isinstance(xs, Octic) and xs.packed.dim() == 3 and xs.packed.is_cuda)
+
     def forward(self, xs, resid=None, rs=None, cs=None, next_norm=None):
         mask = self._sample_mask(xs, resid, rs)
+        # fc1's weight gradient reads the GELU backward's output too: its mask goes out in both branches below
+        zero_dy = rs if (self._plain_chain(xs, resid, rs) and not torch.compiler.is_compiling()) else None
         if mask is not None:
             # (fc1's input gradient reads the GELU backward's output: +0 in every row of a dropped sample)
-            h = self.fc1(xs, skip_out=mask, zero_dx=mask)
+            h = self.fc1(xs, skip_out=mask, zero_dx=mask, zero_dy=zero_dy)
             a = Octic(OF.GeluD8PackedFn.apply(h.packed, h.c, mask, h.packed.shape[1]), h.c)
             return self.fc2(a, resid=resid, rs=rs, cs=cs, next_norm=next_norm, skip_dx=mask)
-        xs = self.norm(self.drop1(self.act(self.fc1(xs))))
+        xs = self.norm(self.drop1(self.act(self.fc1(xs, zero_dy=zero_dy) if zero_dy is not None else self.fc1(xs))))
         if self.drop2.active or resid is None:
             out = _tail(self.drop2(self.fc2(xs)), resid, rs, cs)
             return out if next_norm is None else (out, None)
@@ -751,7 +764,8 @@ class AttentionD8(nn.Module):
         # qkv's input gradient reads dqkv, the attention backward of dO = 0 for a dropped sample (proj's tail multiplies the branch
         # by rs): exact zeros wherever the packed attention node below gets rs, whether its kernels skip the sample or compute it
         zero_dx = rs if self._plain_packed(xp, c, resid, rs, drop, rag) else None
-        qkv = self.qkv(xs if isinstance(xs, Octic) else Octic(xp, c), skip_out=gemm_mask, zero_dx=zero_dx)
+        # (the same zeros are the dY rows of qkv's weight gradient)
+        qkv = self.qkv(xs if isinstance(xs, Octic) else Octic(xp, c), skip_out=gemm_mask, zero_dx=zero_dx, zero_dy=zero_dx)
         if rag is not None and rag.matches(xp):
             # several crop sets in one row tensor: the softmax core walks the sets, everything around it ran once on all rows
             from . import ragged as _R

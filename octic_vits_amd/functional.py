@@ -275,9 +275,10 @@ def _linear_d8_fwd_prep(ctx, x, w5, cs5, bias, rs, cin, cout, rps, dtype, out_dt
     return x, wb, M, y, b32, cs32, rs32
 
 
-def _linear_d8_grads(ctx, x, g, w5, cs32, b32, ss_dx, z_dx=None):
+def _linear_d8_grads(ctx, x, g, w5, cs32, b32, ss_dx, z_dx=None, ss_dw=None):
     """The gradient half of both LinearD8 nodes' backward, from g = the cotangent of the branch in the compute dtype: the
-    input-gradient launch under its masks (ss_dx / z_dx: LinearD8Fn.forward), the bias column sums and the weight gradients.
+    input-gradient launch under its masks (ss_dx / z_dx: LinearD8Fn.forward), the bias column sums and the weight gradients
+    (ss_dw: linear_wgrad_skip_scale - the rows of g are zero for the samples it drops; f32 masters only).
     Returns (dx or None, dw5, dbias, dcs5)."""
     cin, cout, rps, dtype, has_cs, has_bias, x_in_dtype, wt = ctx.lin
     M = x.numel() // (8 * cin)
@@ -295,7 +296,8 @@ def _linear_d8_grads(ctx, x, g, w5, cs32, b32, ss_dx, z_dx=None):
     w32 = [_c(w.detach().float()) for w in w5] if has_cs else None
     f32_masters = all(w.dtype == torch.float32 for w in w5)      # else the casts below read dw at once: no deferral
     dw, dcs, dbias = ops.linear_wgrad(xv, gv, M, cin, cout, dtype, x, w32=w32, cs5=cs32, bias=b32, dysum=dysum,
-                                      want_bias=has_bias, may_defer=f32_masters, wparams=w5 if f32_masters else None)
+                                      want_bias=has_bias, may_defer=f32_masters, wparams=w5 if f32_masters else None,
+                                      sample_scale=ss_dw if f32_masters else None, rows_per_sample=rps)
     if not f32_masters:
         dw = [d.to(w.dtype) for d, w in zip(dw, w5)]
     return dx, dw, dbias, (dcs if has_cs else [None] * 5)
@@ -306,13 +308,16 @@ class LinearD8Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wA1, wA2, wB1, wB2, wE, bias, resid, rs, sA1, sA2, sB1, sB2, sE, cin, cout, rps, dtype, prep,
-                skip_out=None, skip_dx=None, zero_dx=None):
+                skip_out=None, skip_dx=None, zero_dx=None, zero_dy=None):
         """skip_out / skip_dx: the stochastic-depth factor of the branch this layer sits in, as the sample mask of the forward
         launch / of the input-gradient launch - given by the caller only where EVERY reader of that launch's output honours the
         same mask (linear_skip_scale; DESIGN.md 'Routing rules').  The rows of a dropped sample may then stay unwritten.
         zero_dx: the same factor as the `dropped` mask of a plain layer's input-gradient launch (ring_skip_scale) - given only
         where the cotangent rows of a dropped sample are exactly zero; every row of dx is written (zeros there).  A fused
-        forward hands its own rs to the launch as `dropped`: the tail multiplies those samples' rows by 0."""
+        forward hands its own rs to the launch as `dropped`: the tail multiplies those samples' rows by 0.
+        zero_dy: the factor of the branch where the cotangent rows of THIS layer's output are exactly zero for a dropped
+        sample, as the mask of the weight gradient (linear_wgrad_skip_scale) - the layer's own rs, or the caller's promise
+        for a plain layer; it asks no skip switch, so both arms of a bitwise comparison sum alike."""
         w5 = (wA1, wA2, wB1, wB2, wE)
         cs5 = None if sA1 is None else (sA1, sA2, sB1, sB2, sE)
         fused = resid is not None
@@ -329,22 +334,23 @@ class LinearD8Fn(torch.autograd.Function):
         z_dx = ring_skip_scale(zero_dx, rps, M) if (plain and ss_dx is None) else None
         # zero cotangent rows in, zero dx rows out (computed or stored, every row written): the norm in front may skip them
         row_skip_fill(handed, row_skip_scale(zero_dx, rps, M) if (plain and ss_dx is None) else None, rps, M)
-        ctx.save_for_backward(x, rs32, b32, ss_dx, z_dx, *w5, *(cs32 or []))
+        ss_dw = linear_wgrad_skip_scale(rs32 if (rs is not None and zero_dy is rs) else zero_dy, rps, M)
+        ctx.save_for_backward(x, rs32, b32, ss_dx, z_dx, ss_dw, *w5, *(cs32 or []))
         ctx.fused = fused
         return y
 
     @staticmethod
     def backward(ctx, dy):
         cin, cout, rps, dtype, has_cs = ctx.lin[:5]
-        x, rs32, b32, ss_dx, z_dx, *rest = ctx.saved_tensors
+        x, rs32, b32, ss_dx, z_dx, ss_dw, *rest = ctx.saved_tensors
         w5, cs32 = rest[:5], (rest[5:] if has_cs else None)
         dy = _c(dy)
         if ctx.fused or rs32 is not None or dy.dtype != dtype:
             g = ops.cast_rowscale(_c(dy.float()), rs32, rps, dtype, cout)  # cotangent of the branch
         else:
             g = dy
-        dx, dw, dbias, dcs = _linear_d8_grads(ctx, x, g, w5, cs32, b32, ss_dx, z_dx)
-        return (dx, *dw, dbias, dy if ctx.fused else None, None, *dcs, None, None, None, None, None, None, None, None)
+        dx, dw, dbias, dcs = _linear_d8_grads(ctx, x, g, w5, cs32, b32, ss_dx, z_dx, ss_dw)
+        return (dx, *dw, dbias, dy if ctx.fused else None, None, *dcs, None, None, None, None, None, None, None, None, None)
 
 
 class LinearD8NormFn(torch.autograd.Function):
@@ -356,9 +362,9 @@ class LinearD8NormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wA1, wA2, wB1, wB2, wE, bias, resid, rs, sA1, sA2, sB1, sB2, sE, cin, cout, rps, dtype, prep,
-                a1, a2, b1, b2, ae, beta, eps, skip_dx=None):
+                a1, a2, b1, b2, ae, beta, eps, skip_dx=None, zero_dy=None):
         """skip_dx: as in LinearD8Fn (the sample mask of the input-gradient launch).  The fused forward hands rs to the launch as
-        its `dropped` mask (ring_skip_scale)."""
+        its `dropped` mask (ring_skip_scale).  zero_dy: as in LinearD8Fn (the layer's own rs as the weight gradient's mask)."""
         w5 = (wA1, wA2, wB1, wB2, wE)
         cs5 = None if sA1 is None else (sA1, sA2, sB1, sB2, sE)
         x, wb, M, y, b32, cs32, rs32 = _linear_d8_fwd_prep(ctx, x, w5, cs5, bias, rs, cin, cout, rps, dtype, resid.dtype, prep)
@@ -367,7 +373,9 @@ class LinearD8NormFn(torch.autograd.Function):
                        dropped_rps=rps)
         alpha = None if a1 is None else [_c(t.float()) for t in (a1, a2, b1, b2, ae)]
         yn, stats = ops.layernorm_fwd(y, alpha, None if beta is None else _c(beta.float()), eps, dtype, cout)
-        ctx.save_for_backward(x, rs32, b32, y, stats, linear_skip_scale(skip_dx, rps, M), *w5, *(cs32 or []), *(alpha or []))
+        ss_dw = linear_wgrad_skip_scale(rs32 if (rs is not None and zero_dy is rs) else zero_dy, rps, M)
+        ctx.save_for_backward(x, rs32, b32, y, stats, linear_skip_scale(skip_dx, rps, M), ss_dw, *w5, *(cs32 or []),
+                              *(alpha or []))
         ctx.has_affine, ctx.has_beta = alpha is not None, beta is not None
         ctx.set_materialize_grads(False)
         row_skip_attach(ctx, yn)
@@ -377,7 +385,7 @@ class LinearD8NormFn(torch.autograd.Function):
     def backward(ctx, dy, dyn):
         cin, cout, rps, dtype, has_cs = ctx.lin[:5]
         has_affine = ctx.has_affine
-        x, rs32, b32, y, stats, ss_dx, *rest = ctx.saved_tensors
+        x, rs32, b32, y, stats, ss_dx, ss_dw, *rest = ctx.saved_tensors
         w5 = rest[:5]
         cs32 = rest[5:10] if has_cs else None
         alpha = rest[(10 if has_cs else 5):] if has_affine else None
@@ -400,8 +408,9 @@ class LinearD8NormFn(torch.autograd.Function):
         dy = _c(dy)
         if g is None:
             g = ops.cast_rowscale(_c(dy.float()), rs32, rps, dtype, cout)  # cotangent of the branch
-        dx, dw, dbias, dcs = _linear_d8_grads(ctx, x, g, w5, cs32, b32, ss_dx)
-        return (dx, *dw, dbias, dy, None, *dcs, None, None, None, None, None, *dal, dbeta if ctx.has_beta else None, None, None)
+        dx, dw, dbias, dcs = _linear_d8_grads(ctx, x, g, w5, cs32, b32, ss_dx, ss_dw=ss_dw)
+        return (dx, *dw, dbias, dy, None, *dcs, None, None, None, None, None, *dal, dbeta if ctx.has_beta else None, None, None,
+                None)
 
 
 # --------------------------------------------------------------------------------- head packing
@@ -576,6 +585,21 @@ def linear_skip_scale(rs, rps, M, rows_to=None):
 # first, dealt evenly over the XCDs, and writes zeros / the residual for the dead ones without loading them.  A switch of its
 # own, effective only while LINEAR_SKIP_DROPPED is on: OCTIC_RING_SKIP (0 = off), read once at import.
 RING_SKIP_DROPPED = _skip_from_env("OCTIC_RING_SKIP")
+
+
+# The four weight gradients of an octic block (wgrad_ring_kernel, csrc/wgrad.hip) reduce over every token row, and every dY row
+# of a dropped sample is an exact zero (proj and fc2: g = rs * dy; fc1: the D8-GELU backward of a zero cotangent; qkv: the
+# attention backward of dO = 0).  With LINEAR_WGRAD_SKIP_DROPPED the factor travels to the kernel, which reads only the 32-row
+# steps that touch a kept sample and deals them evenly over its row splits (include/octic_hip.h: octic_linear_d8_wgrad_skip) -
+# same launch shapes, the f32 partial sums regrouped: same terms, last-bit differences.  The mask asks NO other switch (the
+# layers hand it on by structure alone, d8_layers.py), so every bitwise on / off comparison of another switch sums alike in both
+# arms.  Read once at import from OCTIC_LINEAR_WGRAD_SKIP (0 = off: the launches are exactly the former ones).
+LINEAR_WGRAD_SKIP_DROPPED = _skip_from_env("OCTIC_LINEAR_WGRAD_SKIP")
+
+
+def linear_wgrad_skip_scale(rs, rps, M):
+    """rs as the sample_scale of a LinearD8 weight gradient over M token rows: whole_sample_mask while the switch is on."""
+    return whole_sample_mask(rs, rps, M) if LINEAR_WGRAD_SKIP_DROPPED else None
 
 
 def ring_skip_scale(rs, rps, M):

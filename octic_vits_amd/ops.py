@@ -476,16 +476,23 @@ def linear_kernel_name(cin, cout, dtype, out_dtype, fused, M):
 
 
 def linear_wgrad(xv, dyv, M, cin, cout, dtype, ref, w32=None, cs5=None, bias=None, dysum=None, want_bias=False,
-                 may_defer=True, wparams=None):
+                 may_defer=True, wparams=None, sample_scale=None, rows_per_sample=0):
     """Returns (dw5 [f32], dcs5 or None, dbias or None).  may_defer=False: the caller reads the results at once (e.g. casts
-    them for non-f32 master weights), so the slab reduction must not be postponed to the end of the backward pass."""
+    them for non-f32 master weights), so the slab reduction must not be postponed to the end of the backward pass.
+    sample_scale / rows_per_sample (functional.linear_wgrad_skip_scale): the stochastic-depth factor of the branch, zero for
+    the samples whose dy rows are all zero; the ring kernel then walks the live steps only (octic_linear_d8_wgrad_skip).  The
+    booked name, bytes and FLOP stay those of the full batch."""
     L = lib()
     dev = ref.device
     kernel, tile, splits, _ = _lib.plan("octic_linear_d8_wgrad_plan", M, cin, cout, dt_code(dtype))
     ws = torch.empty(L.octic_linear_d8_wgrad_workspace_bytes(cin, cout, splits) // 4, dtype=torch.float32, device=dev)
     t = KERNEL_TIMER.start()
-    check(L.octic_linear_d8_wgrad(ctypes.byref(xv), ctypes.byref(dyv), M, cin, cout, dt_code(dtype), _p(ws), splits,
-                                  _stream(ref)))
+    if sample_scale is None:
+        check(L.octic_linear_d8_wgrad(ctypes.byref(xv), ctypes.byref(dyv), M, cin, cout, dt_code(dtype), _p(ws), splits,
+                                      _stream(ref)))
+    else:
+        check(L.octic_linear_d8_wgrad_skip(ctypes.byref(xv), ctypes.byref(dyv), M, cin, cout, dt_code(dtype), _p(ws), splits,
+                                           _p(sample_scale), int(rows_per_sample), _stream(ref)))
     if t is not None:
         es = 2 if dtype == torch.bfloat16 else 4
         name = "wgrad_ring_kernel<bf16>" if kernel == _lib.WGRAD_RING else f"wgrad_kernel<{_DTN[dtype]},{tile // 32}>"
