@@ -1032,6 +1032,35 @@ typedef struct octic_head_segment {
 int octic_head_rows(const octic_head_segment* segments_dev, int n_segments, int64_t rows_out, int64_t D, int dtype, void* out,
                     int64_t ldo, int scatter, void* stream);
 
+/* ---- the normalisations of the DINO / iBOT head (dinov2/layers/dino_head.py:36-41) -----------------------------------------
+ * F.normalize(x, dim=-1, p=2, eps) over the rows of x [rows, D] (OCTIC_F32 / OCTIC_BF16, element stride 1, row stride ldx >=
+ * D, 16-byte aligned rows).  octic_l2norm_rows_fwd: the sum of squares in f32 after one widening, n = sqrt(sum),
+ * d = n < eps ? eps : n (clamp_min: a NaN norm stays NaN), y = x / d rounded once to y_dtype, inv[row] = 1 / d (f32 [rows]).
+ * octic_l2norm_rows_bwd: from the cotangent g of y, x and the saved inv: with yh = x inv (f32) and the norm summed again in
+ * the forward's order, dx = inv (g - yh (yh . g)) where n >= eps (or NaN) and dx = g inv where n < eps - clamp_min passes no
+ * gradient there, as autograd has it; dx has x's dtype, rounded once.  One wave per row; a lane adds the elements of its 16-byte
+ * chunks (chunk c: lane c % 64) in ascending order and the 64 lane sums meet in a fixed butterfly: the order depends on D
+ * alone, a row's bytes do not depend on the row count, its position or its neighbours (a NaN row stays alone), no atomics, two
+ * calls are bitwise equal.  octic_l2norm_ok: 1 where the kernels take the shape - 1 <= rows < 2^31, 8 <= D <= 4096,
+ * D % 8 == 0 - else 0.  OCTIC_ENULL, OCTIC_ESHAPE (also a row stride < D), OCTIC_EDTYPE and OCTIC_EALIGN come before any launch.
+ *
+ * nn.utils.weight_norm(nn.Linear(K, N, bias=False)) (dim 0) without the f32 weight.  octic_weight_norm_prep: from v [N, K] and
+ * g [N] (f32, dense, 16-byte aligned) in one pass: norms[n] = ||v[n]|| (f32 sum in a fixed order that depends on K alone),
+ * W[n, k] = bf16(g[n] v[n, k] (1 / norms[n])) dense [N, K] - torch._weight_norm's arithmetic, rounded once - and, where Wt is
+ * not NULL, the same values as Wt [K, N] (N % 8 == 0 then), staged through LDS so that its stores run along N; Wt == NULL
+ * writes nothing but W and norms.  octic_weight_norm_bwd: from the f32 gradient dW [N, K] of that weight, v, g and norms: with
+ * r = 1 / norms[n] and s = dW[n] . v[n]:  dg[n] = s r,  dv[n, k] = g[n] (r dW[n, k] - r^3 s v[n, k])  (autograd of
+ * torch._weight_norm), f32 throughout, one wave per row.  1 <= N < 2^29, 8 <= K <= 2048, K % 8 == 0.  OCTIC_ENULL,
+ * OCTIC_ESHAPE and OCTIC_EALIGN come before any launch. */
+int octic_l2norm_ok(int64_t rows, int64_t D);
+int octic_l2norm_rows_fwd(const void* x, int x_dtype, int64_t ldx, int64_t rows, int64_t D, float eps, void* y, int y_dtype,
+                          int64_t ldy, float* inv, void* stream);
+int octic_l2norm_rows_bwd(const void* g, int g_dtype, int64_t ldg, const void* x, int x_dtype, int64_t ldx, const float* inv,
+                          int64_t rows, int64_t D, float eps, void* dx, int64_t lddx, void* stream);
+int octic_weight_norm_prep(const float* v, const float* g, int64_t N, int64_t K, void* W, void* Wt, float* norms, void* stream);
+int octic_weight_norm_bwd(const float* dW, const float* v, const float* g, const float* norms, int64_t N, int64_t K, float* dv,
+                          float* dg, void* stream);
+
 /* ---- linear-probe evaluation of a frozen backbone (dinov2/eval/linear.py) ----------------------------------------------
  * The grid of nn.Linear(K_h, C) classifiers of setup_linear_classifiers (linear.py:237-258) as one launch per stage over
  * all classifiers.  Every classifier reads a column range [col0, col0 + K) of one f32 feature row

@@ -143,6 +143,12 @@ _PROTOS = {
     "octic_koleo_bwd": (c_int, [c_void_p, c_int, c_i64, c_i64, c_i64, c_i64, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_i64, c_void_p]),
     "octic_head_rows": (c_int, [c_void_p, c_int, c_i64, c_i64, c_int, c_void_p, c_i64, c_int, c_void_p]),
+    "octic_l2norm_ok": (c_int, [c_i64, c_i64]),
+    "octic_l2norm_rows_fwd": (c_int, [c_void_p, c_int, c_i64, c_i64, c_i64, c_float, c_void_p, c_int, c_i64, c_void_p, c_void_p]),
+    "octic_l2norm_rows_bwd": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_int, c_i64, c_void_p, c_i64, c_i64, c_float, c_void_p,
+                                      c_i64, c_void_p]),
+    "octic_weight_norm_prep": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "octic_weight_norm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "octic_scale_residual_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int,
                                          c_void_p]),
     "octic_scale_residual_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_void_p,

@@ -1675,6 +1675,172 @@ def head_rows_ok(rows_out, specs, sources):
     return True
 
 
+# ------------------------------------------------------------------ the DINO / iBOT head itself (ssl.DINO_HEAD_HIP)
+# dinov2/layers/dino_head.py:36-41 under bf16 autocast: the MLP on csrc/dense_gemm.hip (bias / GELU epilogues, GELU' and the bias
+# column sums in the input-gradient GEMMs), F.normalize as one row kernel each way and the weight-normed prototype layer straight
+# from weight_g / weight_v (csrc/dino_norm.hip).  The bf16 operands are made per call - in a training step every head runs once
+# per parameter version, so a cache could not hit - and nothing here keeps state between calls: a raw-pointer write of the fused
+# optimizer or of update_teacher is seen by the next call.  Gradients leave as ordinary autograd outputs (f32, the parameters'
+# shapes).  NEVER capture a backward pass through a DINOHead in a hipGraph or run it on a side stream: the stock module's
+# last_layer.weight keeps the AccumulateGrad nodes of weight_g / weight_v alive from its constructor on (NOTES 'DINO head').
+class L2NormRowsFn(torch.autograd.Function):
+    """F.normalize(x, dim=-1, p=2, eps) of x [rows, D] (f32 / bf16) in x's dtype: one row kernel each way (ops.l2norm_rows)."""
+
+    @staticmethod
+    def forward(ctx, x, eps=1e-12):
+        x2 = ops._aligned_rows2d(x.detach(), "L2NormRowsFn")
+        y, inv = ops.l2norm_rows(x2, eps)
+        ctx.save_for_backward(x2, inv)
+        ctx.eps = eps
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x2, inv = ctx.saved_tensors
+        return ops.l2norm_rows_bwd(ops._aligned_rows2d(g, "L2NormRowsFn"), x2, inv, ctx.eps), None
+
+
+def _bf16_rows(t):
+    return _c(t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16))
+
+
+class WeightNormLinearFn(torch.autograd.Function):
+    """x [rows, K] @ (weight_g weight_v / ||weight_v||_row)^T of nn.utils.weight_norm(nn.Linear(K, N, bias=False)) in bf16: one
+    ops.weight_norm_prep launch makes both GEMM operands from the f32 parameters (the transposed one only where x wants a
+    gradient), the NT GEMM of csrc/dense_gemm.hip; backward: the input-gradient GEMM on the transposed operand, the TN weight
+    gradient in f32 (_wgrad_lib), then ops.weight_norm_bwd -> (dv, dg)."""
+
+    @staticmethod
+    def forward(ctx, x, weight_g, weight_v):
+        xb = _bf16_rows(x.detach())
+        g32, v32 = _c(weight_g.detach()), _c(weight_v.detach())
+        w, wt, norms = ops.weight_norm_prep(v32, g32, want_wt=ctx.needs_input_grad[0])
+        y = ops.dense_gemm_nt(xb, w, 0, name="dense_nt_kernel<prototypes>")
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(xb, wt, norms, g32, v32)
+        ctx.x_dtype = x.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xb, wt, norms, g32, v32 = ctx.saved_tensors
+        g2 = _bf16_rows(gy)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.dense_gemm_nt(g2, wt, 0, name="dense_nt_kernel<dprototypes>").to(ctx.x_dtype)
+        dg = dv = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dv, dg = ops.weight_norm_bwd(_c(_wgrad_lib(g2, xb)), v32, g32, norms)
+        return dx, dg, dv
+
+
+class DinoMlpFn(torch.autograd.Function):
+    """The head's MLP - nl Linear layers with exact GELU between them - on x [rows, K0] in bf16: params = (w0, b0, w1, b1, ...),
+    a missing bias None.  Forward: bias + GELU in the GEMM epilogue with the pre-activation kept (mode 1; mode 6 where no backward
+    will come: the teacher), the last layer plain.  Backward, last layer first: the bias gradient of the last layer as a column
+    sum, every other one out of the GELU' epilogue of the input-gradient GEMM behind it (mode 3), weight gradients in f32
+    (_wgrad_lib)."""
+
+    @staticmethod
+    def forward(ctx, x, nl, *params):
+        a = _bf16_rows(x.detach())
+        need = any(ctx.needs_input_grad)
+        acts, pre, wbs = [], [], []
+        for i in range(nl):
+            w, b = params[2 * i], params[2 * i + 1]
+            wb = _c(w.detach().to(torch.bfloat16))                 # one cast per weight and call
+            acts.append(a)
+            wbs.append(wb)
+            if i == nl - 1:
+                a = ops.dense_gemm_nt(a, wb, 0, bias=_f32(b), name="dense_nt_kernel<head-plain>")
+            elif need:
+                h, a = ops.dense_gemm_nt(a, wb, 1, bias=_f32(b), name="dense_nt_kernel<head-gelu>")
+                pre.append(h)
+            else:
+                a = ops.dense_gemm_nt(a, wb, 6, bias=_f32(b), name="dense_nt_kernel<head-gelu-only>")
+        if need:
+            ctx.save_for_backward(*acts, *pre, *wbs)
+        ctx.nl, ctx.x_dtype = nl, x.dtype
+        ctx.has_b = [params[2 * i + 1] is not None for i in range(nl)]
+        return a
+
+    @staticmethod
+    def backward(ctx, gy):
+        nl = ctx.nl
+        saved = ctx.saved_tensors
+        acts, pre, wbs = saved[:nl], saved[nl:2 * nl - 1], saved[2 * nl - 1:]
+        g = _bf16_rows(gy)
+        grads = [None] * (2 * nl)
+        db = ops.dense_colsum(g) if ctx.has_b[nl - 1] else None
+        dx = None
+        for i in reversed(range(nl)):
+            grads[2 * i] = _wgrad_lib(g, acts[i])
+            grads[2 * i + 1] = db
+            if i > 0:
+                wt = wbs[i].t().contiguous()
+                if ctx.has_b[i - 1]:
+                    g, db = ops.dense_gemm_nt(g, wt, 3, h=pre[i - 1], name="dense_nt_kernel<head-dgelu>", want_colsum=True)
+                else:
+                    g, db = ops.dense_gemm_nt(g, wt, 3, h=pre[i - 1], name="dense_nt_kernel<head-dgelu>"), None
+            elif ctx.needs_input_grad[0]:
+                dx = ops.dense_gemm_nt(g, wbs[0].t().contiguous(), 0, name="dense_nt_kernel<head-dgrad>").to(ctx.x_dtype)
+        return (dx, None, *grads)
+
+
+def _dino_head_linears(head):
+    """The nn.Linear layers of head.mlp where it is Linear (GELU Linear)* with exact GELUs, else None."""
+    mlp = head.mlp
+    mods = [mlp] if isinstance(mlp, torch.nn.Linear) else list(mlp) if isinstance(mlp, torch.nn.Sequential) else None
+    if not mods or len(mods) % 2 == 0:
+        return None
+    for i, m in enumerate(mods):
+        if i % 2 == 0 and type(m) is not torch.nn.Linear:
+            return None
+        if i % 2 == 1 and not (type(m) is torch.nn.GELU and m.approximate == "none"):
+            return None
+    return mods[0::2]
+
+
+def dino_head_ok(head, x):
+    """The one routing predicate of the head's engine path (dino_head_forward): x [rows >= 1, in_dim] f32 / bf16 on the GPU under
+    bf16 autocast, not under torch.compile tracing; a head without BatchNorm whose parameters are f32 on x's device; and EVERY
+    GEMM of the head - MLP layers and prototypes, forward (K = in_features) and input gradient (K = out_features) - a shape
+    ops.dense_gemm_ok takes, the bottleneck a width the row kernels take.  One refusal and the whole head keeps the stock path."""
+    if torch.compiler.is_compiling() or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 2 or x.shape[0] < 1:
+        return False
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        return False
+    if not torch.is_autocast_enabled() or torch.get_autocast_gpu_dtype() != torch.bfloat16:
+        return False
+    lins = _dino_head_linears(head)
+    last = getattr(head, "last_layer", None)
+    wg, wv = getattr(last, "weight_g", None), getattr(last, "weight_v", None)
+    if lins is None or wg is None or wv is None or getattr(last, "bias", None) is not None:
+        return False
+    rows = x.shape[0]
+    tensors = [t for m in lins for t in (m.weight, m.bias) if t is not None] + [wg, wv]
+    if any(t.device != x.device or t.dtype != torch.float32 for t in tensors):
+        return False
+    if lins[0].in_features != x.shape[1] or wv.dim() != 2 or tuple(wg.shape) != (wv.shape[0], 1):
+        return False
+    shapes = [(m.out_features, m.in_features) for m in lins] + [tuple(wv.shape)]
+    if any(a[0] != b[1] for a, b in zip(shapes, shapes[1:])):
+        return False
+    if not all(ops.dense_gemm_ok(rows, N, K) and ops.dense_gemm_ok(rows, K, N) for N, K in shapes):
+        return False
+    P, D = shapes[-1]
+    return bool(ops.l2norm_ok(rows, D) and ops.weight_norm_ok(P, D))
+
+
+def dino_head_forward(head, x):
+    """ssl.DINOHead.forward on the engine (check dino_head_ok first): reads last_layer.weight_g / weight_v directly and never
+    touches last_layer.weight."""
+    lins = _dino_head_linears(head)
+    y = DinoMlpFn.apply(x, len(lins), *[t for m in lins for t in (m.weight, m.bias)])
+    y = L2NormRowsFn.apply(y, 1e-12)
+    return WeightNormLinearFn.apply(y, head.last_layer.weight_g, head.last_layer.weight_v)
+
+
 class HandoffCatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, c, out_dtype):

@@ -1302,6 +1302,120 @@ def head_rows(segments, out, scatter=False):
     return out
 
 
+# ------------------------------------------------------------ the normalisations of the DINO / iBOT heads (csrc/dino_norm.hip)
+def l2norm_ok(rows, D):
+    """Shapes the L2-normalisation row kernels take (octic_l2norm_ok: the only place the range lives)."""
+    return bool(lib().octic_l2norm_ok(int(rows), int(D)))
+
+
+def _l2_rows(t, what, dtype=None):
+    """t as [rows, D] f32 / bf16 with unit column stride and 16-byte aligned rows, or a ValueError."""
+    _require_cuda(t)
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{what}: expected [rows, D] with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
+    dt_code(t.dtype)
+    if dtype is not None and t.dtype != dtype:
+        raise ValueError(f"{what}: expected {dtype}, got {t.dtype}")
+    if t.data_ptr() % 16 or (t.shape[0] > 1 and (t.stride(0) * t.element_size()) % 16):
+        raise ValueError(f"{what}: rows must be 16-byte aligned")
+    return t
+
+
+def l2norm_rows(x, eps=1e-12, out_dtype=None):
+    """F.normalize(x, dim=-1, p=2, eps) of x [rows, D] (f32 / bf16) -> (y [rows, D] in out_dtype (default: x's), inv [rows] f32 =
+    1 / max(||x||, eps)) - octic_l2norm_rows_fwd: f32 sum of squares, one rounding."""
+    x = _l2_rows(x, "l2norm_rows")
+    rows, D = x.shape
+    out_dtype = out_dtype or x.dtype
+    dt_code(out_dtype)
+    if not l2norm_ok(rows, D):
+        raise ValueError(f"l2norm_rows: [rows, D] = {tuple(x.shape)} is outside the kernel's range (octic_l2norm_ok)")
+    y = torch.empty((rows, D), dtype=out_dtype, device=x.device)
+    inv = torch.empty(rows, dtype=torch.float32, device=x.device)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_l2norm_rows_fwd(_p(x), dt_code(x.dtype), _ldrow(x), rows, D, float(eps), _p(y), dt_code(out_dtype), D, _p(inv),
+                                      _stream(x)))
+    KERNEL_TIMER.stop(t, f"l2norm_fwd_kernel<{_DTN[x.dtype]},{_DTN[out_dtype]}>", rows * D * (x.element_size() + y.element_size()))
+    return y, inv
+
+
+def l2norm_rows_bwd(g, x, inv, eps=1e-12):
+    """dx (x's dtype) of l2norm_rows from the cotangent g [rows, D] (f32 / bf16) of y, x and the saved inv
+    (octic_l2norm_rows_bwd): inv (g - yh (yh . g)) with yh = x inv, and g inv on the rows whose norm is below eps."""
+    x = _l2_rows(x, "l2norm_rows_bwd: x")
+    g = _l2_rows(g, "l2norm_rows_bwd: g")
+    rows, D = x.shape
+    if tuple(g.shape) != (rows, D) or not l2norm_ok(rows, D):
+        raise ValueError(f"l2norm_rows_bwd: g {tuple(g.shape)} must match x {tuple(x.shape)} inside the kernel's range")
+    if not inv.is_cuda or inv.dtype != torch.float32 or tuple(inv.shape) != (rows,) or not inv.is_contiguous():
+        raise ValueError("l2norm_rows_bwd: inv must be the contiguous f32 [rows] vector of l2norm_rows")
+    dx = torch.empty((rows, D), dtype=x.dtype, device=x.device)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_l2norm_rows_bwd(_p(g), dt_code(g.dtype), _ldrow(g), _p(x), dt_code(x.dtype), _ldrow(x), _p(inv), rows, D,
+                                      float(eps), _p(dx), D, _stream(x)))
+    KERNEL_TIMER.stop(t, f"l2norm_bwd_kernel<{_DTN[g.dtype]},{_DTN[x.dtype]}>", rows * D * (g.element_size() + 2 * x.element_size()))
+    return dx
+
+
+WEIGHT_NORM_MAX_K = 2048       # csrc/dino_norm.hip: a row of v lives in one wave's registers
+
+
+def weight_norm_ok(N, K):
+    """Shapes octic_weight_norm_prep (with the transposed operand) and octic_weight_norm_bwd take."""
+    return N >= 8 and N % 8 == 0 and N < 2 ** 29 and 8 <= K <= WEIGHT_NORM_MAX_K and K % 8 == 0
+
+
+def _wn_operands(v, g, what):
+    _require_cuda(v)
+    if v.dim() != 2 or v.dtype != torch.float32 or not v.is_contiguous() or v.data_ptr() % 16:
+        raise ValueError(f"{what}: weight_v must be a contiguous, 16-byte aligned f32 [N, K] tensor on the device")
+    N, K = v.shape
+    if not g.is_cuda or g.dtype != torch.float32 or g.numel() != N or not g.is_contiguous():
+        raise ValueError(f"{what}: weight_g must be a contiguous f32 [N, 1] tensor on the device")
+    if N < 1 or N >= 2 ** 29 or K < 8 or K > WEIGHT_NORM_MAX_K or K % 8:
+        raise ValueError(f"{what}: [N, K] = {(N, K)} is outside the kernel's range (K % 8 == 0, 8 <= K <= {WEIGHT_NORM_MAX_K})")
+    return N, K
+
+
+def weight_norm_prep(v, g, want_wt=True, wt_out=None):
+    """The bf16 operands of a weight-normed linear layer (nn.utils.weight_norm, dim 0) from weight_v [N, K] and weight_g [N, 1],
+    f32, in one pass: (W [N, K] = bf16(g v / ||v||_row), W^T [K, N] or None, norms [N] f32) - octic_weight_norm_prep.  The f32
+    weight is never written.  want_wt False: the transposed operand (the input-gradient GEMM's) is not produced and wt_out, if
+    given, is left alone."""
+    N, K = _wn_operands(v, g, "weight_norm_prep")
+    w = torch.empty((N, K), dtype=torch.bfloat16, device=v.device)
+    wt = None
+    if want_wt:
+        if N % 8:
+            raise ValueError("weight_norm_prep: the transposed operand needs N % 8 == 0")
+        wt = wt_out if wt_out is not None else torch.empty((K, N), dtype=torch.bfloat16, device=v.device)
+        if (not wt.is_cuda or wt.dtype != torch.bfloat16 or tuple(wt.shape) != (K, N) or not wt.is_contiguous()
+                or wt.data_ptr() % 16):
+            raise ValueError("weight_norm_prep: wt_out must be a contiguous, 16-byte aligned bf16 [K, N] tensor on the device")
+    norms = torch.empty(N, dtype=torch.float32, device=v.device)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_weight_norm_prep(_p(v), _p(g), N, K, _p(w), _p(wt), _p(norms), _stream(v)))
+    KERNEL_TIMER.stop(t, f"weight_norm_prep_kernel<{'nt' if want_wt else 'n'}>", N * K * (4 + (4 if want_wt else 2)) + 8 * N)
+    return w, wt, norms
+
+
+def weight_norm_bwd(dw, v, g, norms):
+    """(dv [N, K], dg [N, 1]) of the weight-normed weight from its f32 gradient dw [N, K], weight_v, weight_g and the norms
+    weight_norm_prep saved (octic_weight_norm_bwd; autograd of torch._weight_norm, f32)."""
+    N, K = _wn_operands(v, g, "weight_norm_bwd")
+    if (not dw.is_cuda or dw.dtype != torch.float32 or tuple(dw.shape) != (N, K) or not dw.is_contiguous()
+            or dw.data_ptr() % 16):
+        raise ValueError("weight_norm_bwd: dw must be a contiguous, 16-byte aligned f32 [N, K] tensor on the device")
+    if not norms.is_cuda or norms.dtype != torch.float32 or tuple(norms.shape) != (N,) or not norms.is_contiguous():
+        raise ValueError("weight_norm_bwd: norms must be the contiguous f32 [N] vector of weight_norm_prep")
+    dv = torch.empty((N, K), dtype=torch.float32, device=v.device)
+    dg = torch.empty(g.shape, dtype=torch.float32, device=v.device)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_weight_norm_bwd(_p(dw), _p(v), _p(g), _p(norms), N, K, _p(dv), _p(dg), _stream(v)))
+    KERNEL_TIMER.stop(t, "weight_norm_bwd_kernel", 12 * N * K + 12 * N)
+    return dv, dg
+
+
 def scale_residual_fwd(x, y, gamma, rs, rps):
     """out = x + rs[row // rps] * gamma * y   (x f32, y f32/bf16, same shape [..., d])."""
     _require_cuda(x)

@@ -6,7 +6,8 @@ Same classes, constructor arguments, ``state_dict`` keys and arithmetic as the r
 FSDP (parameters and optimizer state of a ViT-H student + teacher are ~13 GB: nothing to shard on a 288 GB device; the
 student is wrapped in DistributedDataParallel by ``SSLTrainer`` when a process group exists, the centre statistics are
 all-reduced as in the reference).  The backbones run on the HIP engine (octic blocks, attention, standard half); the
-heads are a few small dense ops per step and stay on torch, their input rows are assembled by csrc/dino_head.hip under
+heads run on the engine too under bf16 autocast (``DINO_HEAD_HIP``: the MLP on csrc/dense_gemm.hip, F.normalize and the
+weight-normed prototype layer on csrc/dino_norm.hip), their input rows are assembled by csrc/dino_head.hip under
 ``HEAD_HIP``; the losses' row passes run on csrc/ssl_loss.hip (the prototype axis of the DINO / iBOT terms, both centerings) and
 csrc/koleo.hip (the KoLeo regularizer) under ``FUSED_LOSS_ROWS``.
 
@@ -15,6 +16,7 @@ reference as shipped (tuple patch size); ``OcticDinoVisionTransforme
 (bicubic resize of the unfolded grids, ``d8_utils.py:453-499`` with an integer patch side).
 """
 import math
+import os
 import random
 
 import numpy as np
@@ -28,6 +30,11 @@ from . import functional as _OF
 FUSED_LOSS_ROWS = True      # GPU: the prototype-axis passes of the DINO / iBOT terms, both centerings, on csrc/ssl_loss.hip and the KoLeo term on csrc/koleo.hip (False: the eager composition)
 
 HEAD_HIP = True             # GPU: the input rows of the DINO / iBOT head calls (class tokens | masked patch tokens | zero padding) as one gather launch of csrc/dino_head.hip, one scatter launch backward (False: new_zeros + index_select + copy_ + cat)
+
+# GPU, bf16 autocast: DINOHead itself on the engine - MLP on csrc/dense_gemm.hip, F.normalize and the weight-normed prototype layer
+# on csrc/dino_norm.hip (functional.dino_head_forward; False or OCTIC_DINO_HEAD_HIP=0: the stock composition).  Eager only: a
+# backward pass through a DINOHead must never be captured in a hipGraph or run on a side stream (NOTES 'DINO head').
+DINO_HEAD_HIP = os.environ.get("OCTIC_DINO_HEAD_HIP", "1").strip() != "0"
 
 
 def _world():
@@ -70,6 +77,8 @@ class DINOHead(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     def forward(self, x):
+        if DINO_HEAD_HIP and _OF.dino_head_ok(self, x):
+            return _OF.dino_head_forward(self, x)
         x = self.mlp(x)
         eps = 1e-6 if x.dtype == torch.float16 else 1e-12
         x = F.normalize(x, dim=-1, p=2, eps=eps)
