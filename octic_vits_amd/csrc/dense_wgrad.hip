@@ -669,7 +669,12 @@ static int dwn_launch(const bf16* Y, const bf16* X, int64_t ldy, int64_t ldx, in
 // routing overrides (octic_route_override): OCTIC_ROUTE_WGRAD_SLABS forces the number of row slabs, OCTIC_ROUTE_WGRAD_TILE
 // (256 | 320) the tile width where the shape allows it; 0 = automatic
 static int dw_slabs(int tiles, int steps) {
-  if (route(OCTIC_ROUTE_WGRAD_SLABS) > 0) return route(OCTIC_ROUTE_WGRAD_SLABS) <= steps / 2 ? route(OCTIC_ROUTE_WGRAD_SLABS) : (steps / 2 > 0 ? steps / 2 : 1);
+  if (route(OCTIC_ROUTE_WGRAD_SLABS) > 0) {                       // forced: the automatic path's limits still hold
+    int S = route(OCTIC_ROUTE_WGRAD_SLABS);
+    S = S > 16 ? 16 : S;                                           // (what the workspace query sizes a forced launch for)
+    S = S > steps / 2 ? steps / 2 : S;
+    return S < 1 ? 1 : S;
+  }
   const int cus = device_cus();
   const int tiles8 = (tiles + 7) / 8 * 8;
   const int per_slab = DW_MAP == 1 ? tiles : tiles8;
@@ -800,7 +805,8 @@ int octic_dense_wgrad_tn_skip(const void* dY, const void* X, int M, int N, int K
   const DwRoute r = dw_route(M, N, 0, K, ldy > ldx ? ldy : ldx);
   if (r.err) return r.err;
   if (const int e = dw_mask_status(sample_scale, rows_per_sample, M)) return e;
-  if ((ldy % 8) || (ldx % 8) || (r.plan.kw == 1 && (ldy < N || ldx < K))) return OCTIC_ESHAPE;
+  // (a row stride shorter than the row: the wide kernel's descriptors span M * ld elements and would read the last rows as zero)
+  if ((ldy % 8) || (ldx % 8) || ldy < N || ldx < K) return OCTIC_ESHAPE;
   if ((((uintptr_t)dY) | ((uintptr_t)X) | ((uintptr_t)dW)) & 15) return OCTIC_EALIGN;
   if (r.plan.kw == 1)
     return dwn_launch((const bf16*)dY, (const bf16*)X, ldy, ldx, M, N, K, r.plan.tiles, r.plan.S, dW, workspace, (hipStream_t)stream);
@@ -828,7 +834,7 @@ int octic_dense_wgrad_tn_pair_skip(const void* dY0, const void* X0, int N0, int6
   const DwRoute r = dw_route(M, N0, N1, K, ld0 > ld1 ? ld0 : ld1);
   if (r.err) return r.err;
   if (const int e = dw_mask_status(sample_scale, rows_per_sample, M)) return e;
-  if ((ldy0 % 8) || (ldx0 % 8) || (ldy1 % 8) || (ldx1 % 8)) return OCTIC_ESHAPE;
+  if ((ldy0 % 8) || (ldx0 % 8) || (ldy1 % 8) || (ldx1 % 8) || ldy0 < N0 || ldx0 < K || ldy1 < N1 || ldx1 < K) return OCTIC_ESHAPE;
   if ((((uintptr_t)dY0) | ((uintptr_t)X0) | ((uintptr_t)dW0) | ((uintptr_t)dY1) | ((uintptr_t)X1) | ((uintptr_t)dW1)) & 15) return OCTIC_EALIGN;
   DwArgs a = {};
   a.Y = (const bf16*)dY0; a.X = (const bf16*)X0; a.ldy = ldy0; a.ldx = ldx0; a.M = M; a.N = N0; a.K = K; a.W = dW0;
