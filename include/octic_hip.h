@@ -1551,6 +1551,36 @@ int octic_depth_logits(const float* const* patch, const int64_t* patch_ldb, cons
 int octic_depth_expect(const float* Lo, int64_t B, int h, int w, int n_bins, int upsample, const float* bins, float min_depth,
                        float max_depth, float* depth, void* stream);
 
+/* ---- orbit invariants: MaxFilteringInvariant / CanonizationInvariant (d8_invariantization.py:142-280) -----------------------
+ * The eight action matrices of D8 on the 8-tuple are signed permutations that touch 12 (i, j) pairs, so the eight products
+ * of a (row, reference) pair are signed sums of 12 dot products of length c (the 8 E dots pair up into 4 of length 2c).
+ * dtype is the operand dtype of x / dx / planes / g (OCTIC_BF16: bf16 MFMA; OCTIC_F32: exact-f32 MFMA); partials, signed
+ * sums and comparisons are f32.  Group order e, r, rr, rrr, m, mr, mrr, mrrr; the winner is the lowest index among equal
+ * products and the first NaN product.  No address behind row M - 1, reference R - 1 or column c - 1 is read.
+ * Nothing of M x 8 x R or M x 8 x 8c elements is written anywhere.                                                          */
+/* references [R, c, 8] f32 (component innermost) -> planes [8][R][c] in dtype (R c 8 elements, 16-byte aligned). */
+int octic_max_filter_prep(const float* references, void* planes, int64_t R, int c, int dtype, void* stream);
+/* out [M, R] dense (out_dtype) = max_g, idx [M, R] uint8 = argmax_g of x[t] . (A_g references[d]). */
+int octic_max_filter_fwd(const octic_view* x, const void* planes, void* out, uint8_t* idx, int64_t M, int64_t R, int c, int dtype,
+                         int out_dtype, void* stream);
+/* dx_i[t, :] = sum_j sum_d (g[t, d] A_idx[t, d][i, j]) ref_j[d, :]; g [M, R] dense in dtype (16-byte aligned), idx 8-byte aligned. */
+int octic_max_filter_bwd_x(const void* g, const uint8_t* idx, const void* planes, const octic_view* dx, int64_t M, int64_t R, int c,
+                           int dtype, void* stream);
+/* The row slabs of octic_max_filter_bwd_ref, a function of (M, R, c) alone: out = {slabs, rows per slab, tile edge, workgroups per slab}. */
+int octic_max_filter_bwd_ref_plan(int64_t M, int64_t R, int c, int out[4]);
+int64_t octic_max_filter_bwd_ref_workspace_bytes(int64_t M, int64_t R, int c);
+/* dref [R, c, 8] f32: dref_j[d, :] = sum_i sum_t (g[t, d] A_idx[t, d][i, j]) x_i[t, :].  f32 partials per row slab in the
+ * workspace, then summed in slab order; no atomics. */
+int octic_max_filter_bwd_ref(const void* g, const uint8_t* idx, const octic_view* x, float* dref, void* workspace,
+                             int64_t workspace_bytes, int64_t M, int64_t R, int c, int dtype, void* stream);
+/* reference [8c] f32, i-major.  idx [M] uint8 = argmax_g of reference . (A_g x[t]); out [M, 8c] dense (out_dtype), i-major
+ * [x'0 | ... | x'7] = A_idx x[t]: a signed copy of the row's values.  One wave per row. */
+int octic_canonize_fwd(const octic_view* x, const float* reference, void* out, uint8_t* idx, int64_t M, int c, int dtype,
+                       int out_dtype, void* stream);
+/* dx = the inverse signed permutation of g [M, 8c] dense (g_dtype). */
+int octic_canonize_bwd(const void* g, int g_dtype, const uint8_t* idx, const octic_view* dx, int64_t M, int c, int dtype,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

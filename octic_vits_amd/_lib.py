@@ -316,6 +316,14 @@ _PROTOS = {
     "octic_depth_logits": (c_int, [c_void_p] * 5 + [c_int, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                                     c_void_p]),
     "octic_depth_expect": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p]),
+    "octic_max_filter_prep": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p]),
+    "octic_max_filter_fwd": (c_int, [VP, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p]),
+    "octic_max_filter_bwd_x": (c_int, [c_void_p, c_void_p, c_void_p, VP, c_i64, c_i64, c_int, c_int, c_void_p]),
+    "octic_max_filter_bwd_ref_plan": (c_int, [c_i64, c_i64, c_int, ctypes.POINTER(c_int)]),
+    "octic_max_filter_bwd_ref_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
+    "octic_max_filter_bwd_ref": (c_int, [c_void_p, c_void_p, VP, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_void_p]),
+    "octic_canonize_fwd": (c_int, [VP, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p]),
+    "octic_canonize_bwd": (c_int, [c_void_p, c_int, c_void_p, VP, c_i64, c_int, c_int, c_void_p]),
 }
 
 

@@ -1,10 +1,13 @@
 """Invariant maps (reference: octic_vits/d8_invariantization.py).
 
-PowerSpectrumInvariant — the one the models use (model.py:89-91) — is a HIP kernel (fwd + bwd).
-The other maps are only exercised by the equivariance tests; they are table-driven composites:
-polynomial invariants are evaluated from a compact monomial table ("356+347" = x3*x5*x6 + x3*x4*x7),
-orbit-based ones from the group-action tables of d8_utils.
+PowerSpectrumInvariant — the models' default (model.py:89-91) — is a HIP kernel (fwd + bwd), and so are the two orbit-based
+maps with learned parameters, MaxFilteringInvariant and CanonizationInvariant (csrc/orbit_invariant.hip: all eight products
+of an orbit from 12 partial dots, nothing eightfold in memory); `orbit_hip_ok` is their routing rule, and what it refuses
+runs the reference's composition from the group-action tables of d8_utils.  The polynomial maps are table-driven
+composites evaluated from a compact monomial table ("356+347" = x3*x5*x6 + x3*x4*x7).
 """
+import inspect
+import os
 import re
 
 import torch
@@ -14,6 +17,28 @@ import torch.nn.functional as F
 from . import functional as OF
 from .d8_utils import _ISO, convert_5tuple_to_8tuple, group_elements
 from .functional import as_packed
+
+
+ORBIT_HIP = os.environ.get("OCTIC_ORBIT_HIP", "1") != "0"     # MaxFiltering / Canonization on the HIP kernels where they can run
+
+
+def orbit_hip_ok(xtuple, *params) -> bool:
+    """The one routing rule of the orbit kernels: GPU tensors, a float32 / bfloat16 input whose compute dtype is one of the
+    two, c a multiple of 8, not under torch.compile tracing, and the switch ORBIT_HIP on."""
+    if not ORBIT_HIP or torch.compiler.is_compiling():
+        return False
+    ts = [xtuple.packed] if isinstance(xtuple, OF.Octic) else list(xtuple)
+    if len(ts) not in (1, 5) or not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts + list(params)):
+        return False
+    if any(t.dtype not in (torch.float32, torch.bfloat16) for t in ts) or any(p.dtype != torch.float32 for p in params):
+        return False
+    if torch.is_autocast_enabled("cuda"):
+        adt = torch.get_autocast_dtype("cuda")
+        # fp16 autocast computes the octic half in float32 and takes float32 inputs only (functional.compute_dtype)
+        if adt not in (torch.bfloat16, torch.float16) or (adt == torch.float16 and any(t.dtype != torch.float32 for t in ts)):
+            return False
+    c = xtuple.c if isinstance(xtuple, OF.Octic) else ts[0].shape[-1]
+    return c > 0 and c % 8 == 0 and ts[0].numel() > 0
 
 
 class Invariant(nn.Module):
@@ -44,7 +69,7 @@ class LinearInvariant(Invariant):  # :43-48
     def __init__(self, C: int):
         super().__init__(C // 8)
 
-    def forward(self, xtuple):
+    def forward(self, xtuple, _out_dtype=None):
         return torch.abs(xtuple[0])
 
 
@@ -79,7 +104,7 @@ class PolynomialInvariant(Invariant):  # :66-112
     def __init__(self, C: int):
         super().__init__(32 * C // 8)
 
-    def forward(self, xtuple):
+    def forward(self, xtuple, _out_dtype=None):
         x = convert_5tuple_to_8tuple(xtuple)
         return torch.cat([x[0]] + [_poly(s, x) for s in _DEG2 + _DEG3 + _DEG4], dim=-1)
 
@@ -88,7 +113,7 @@ class ThirdOrderInvariant(Invariant):  # :114-141
     def __init__(self, C: int):
         super().__init__(15 * C // 8)
 
-    def forward(self, xtuple):
+    def forward(self, xtuple, _out_dtype=None):
         x = convert_5tuple_to_8tuple(xtuple)
         return torch.cat([x[0] ** 3] + [_poly(s, x, prefix="0") for s in _DEG2] + [_poly(s, x) for s in _DEG3], dim=-1)
 
@@ -121,7 +146,12 @@ class MaxFilteringInvariant(Invariant):  # :142-210
         mats = torch.stack(_orbit_matrices()).to(self.references)          # [8 g, 8, 8]
         return torch.einsum("gij,dcj->gdic", mats, self.references).flatten(start_dim=-2)
 
-    def forward(self, xtuple):
+    def forward(self, xtuple, _out_dtype=None):
+        if orbit_hip_ok(xtuple, self.references):
+            xp, c = as_packed(xtuple)
+            if c != self.references.shape[1]:
+                raise ValueError(f"MaxFilteringInvariant: input has c = {c}, the references have {self.references.shape[1]}")
+            return OF.MaxFilterFn.apply(xp, self.references, c, _out_dtype or OF.compute_dtype(xp))
         x = torch.cat(convert_5tuple_to_8tuple(xtuple), dim=-1)
         refs = self.expand_references_d8()
         prod = torch.einsum("kdc,bc->bkd", refs, x) if self.global_avg else torch.einsum("kdc,bnc->bnkd", refs, x)
@@ -140,7 +170,12 @@ class CanonizationInvariant(Invariant):  # :212-280
         mats = torch.stack(_orbit_matrices()).to(x)
         return torch.einsum("gij,...cj->...gic", mats, x).flatten(start_dim=-2)
 
-    def forward(self, xtuple):
+    def forward(self, xtuple, _out_dtype=None):
+        if orbit_hip_ok(xtuple, self.reference):
+            xp, c = as_packed(xtuple)
+            if 8 * c != self.reference.numel():
+                raise ValueError(f"CanonizationInvariant: input has {8 * c} channels, the reference has {self.reference.numel()}")
+            return OF.CanonizeFn.apply(xp, self.reference, c, _out_dtype or OF.compute_dtype(xp))
         x = torch.stack(convert_5tuple_to_8tuple(xtuple), dim=-1)
         if self.global_avg:
             x = x.unsqueeze(1)
@@ -148,3 +183,24 @@ class CanonizationInvariant(Invariant):  # :212-280
         best = torch.einsum("c,bnkc->bnk", self.reference, orbit).argmax(dim=-1, keepdim=True)
         out = torch.gather(orbit, 2, best.unsqueeze(-1).expand(-1, -1, -1, orbit.shape[-1])).squeeze(-2)
         return out.squeeze(1) if self.global_avg else out
+
+
+INVARIANTIZATIONS = {"linear": LinearInvariant, "power_spectrum": PowerSpectrumInvariant, "polynomial": PolynomialInvariant,
+                     "third_order": ThirdOrderInvariant, "max_filtering": MaxFilteringInvariant,
+                     "canonization": CanonizationInvariant}
+
+
+def make_invariantization(spec, embed_dim: int) -> Invariant:
+    """The invariant map of a model built with invariant=True: one of the names above, or a callable embed_dim -> Invariant
+    whose forward takes the keyword `_out_dtype` (the models pass it; the stock maps take and ignore it)."""
+    if callable(spec):
+        inv = spec(embed_dim)
+        if not isinstance(inv, Invariant):
+            raise TypeError(f"invariantization callable must return an Invariant, got {type(inv).__name__}")
+        params = inspect.signature(inv.forward).parameters
+        if "_out_dtype" not in params and not any(p.kind == p.VAR_KEYWORD for p in params.values()):
+            raise TypeError(f"{type(inv).__name__}.forward must take the keyword _out_dtype (the models pass it)")
+        return inv
+    if spec not in INVARIANTIZATIONS:
+        raise ValueError(f"invariantization must be one of {sorted(INVARIANTIZATIONS)} or a callable, got {spec!r}")
+    return INVARIANTIZATIONS[spec](embed_dim)

@@ -46,12 +46,12 @@ class OcticDinoVisionTransformer(OcticVisionTransformer):
                  num_heads: int = 12, mlp_ratio: float = 4.0, num_register_tokens: int = 0,
                  drop_path_rate: float = 0.0, octic_block_layers: Callable = BlockD8,
                  standard_block_layers: Callable = partial(Block, attn_class=MemEffAttention),
-                 invariant: bool = False, **kwargs):
+                 invariant: bool = False, invariantization="power_spectrum", **kwargs):
         super().__init__(img_size=img_size, patch_size=patch_size, embed_dim=embed_dim, depth=depth,
                          num_heads=num_heads, mlp_ratio=mlp_ratio, num_register_tokens=0,
                          octic_block_layers=octic_block_layers, standard_block_layers=standard_block_layers,
                          drop_path_rate=drop_path_rate, invariant=invariant, qkv_bias=True, ffn_bias=True,
-                         proj_bias=True)
+                         proj_bias=True, invariantization=invariantization)
         self.depth = depth
         self.num_register_tokens = num_register_tokens
         c = embed_dim // 8

@@ -1900,3 +1900,57 @@ class LiftFn(torch.autograd.Function):
         dbias = dpos.sum(0) if has_bias else None
         dcls = dout[:, 0].sum(0) if tok0 else None
         return None, dw, dbias, dpos if has_pos else None, dcls, None, None
+
+
+# ------------------------------------------------------------------------------------------ orbit invariants
+class MaxFilterFn(torch.autograd.Function):
+    """MaxFilteringInvariant on packed rows: out[t, d] = max_g x[t] . (A_g references[d]).  Saves x in the compute dtype, the
+    winners (uint8) and the component planes of this call (R c 8 elements of the compute dtype)."""
+
+    @staticmethod
+    def forward(ctx, x, references, c, out_dtype):
+        dt = compute_dtype(x)
+        lead = x.shape[:-1]
+        xc = _c(x.detach().reshape(-1, 8 * c).to(dt))
+        refs = _c(references.detach().float())
+        planes = ops.max_filter_prep(refs, dt)
+        out, idx = ops.max_filter_fwd(xc, planes, c, out_dtype)
+        ctx.save_for_backward(xc, idx, planes)
+        ctx.meta = (c, x.dtype, references.dtype, lead)
+        return out.view(*lead, refs.shape[0])
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, idx, planes = ctx.saved_tensors
+        c, x_dtype, ref_dtype, lead = ctx.meta
+        g = _c(g.reshape(idx.shape).to(xc.dtype))
+        dx = dref = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.max_filter_bwd_x(g, idx, planes, c).view(*lead, 8 * c).to(x_dtype)
+        if ctx.needs_input_grad[1]:
+            dref = ops.max_filter_bwd_ref(g, idx, xc, c).to(ref_dtype)
+        return dx, dref, None, None
+
+
+class CanonizeFn(torch.autograd.Function):
+    """CanonizationInvariant on packed rows: out[t] = A_g x[t] for the g that maximises reference . (A_g x[t]), as the dense
+    i-major row.  The reference only feeds the argmax: it gets no gradient.  Saves the winners alone."""
+
+    @staticmethod
+    def forward(ctx, x, reference, c, out_dtype):
+        dt = compute_dtype(x)
+        lead = x.shape[:-1]
+        xc = _c(x.detach().reshape(-1, 8 * c).to(dt))
+        out, idx = ops.canonize_fwd(xc, _c(reference.detach().float()), c, out_dtype)
+        ctx.save_for_backward(idx)
+        ctx.meta = (c, x.dtype, dt, lead)
+        return out.view(*lead, 8 * c)
+
+    @staticmethod
+    def backward(ctx, g):
+        (idx,) = ctx.saved_tensors
+        c, x_dtype, dt, lead = ctx.meta
+        if g.dtype not in (torch.float32, torch.bfloat16):
+            g = g.float()
+        dx = ops.canonize_bwd(_c(g.reshape(-1, 8 * c)), idx, c, dt)
+        return dx.view(*lead, 8 * c).to(x_dtype), None, None, None

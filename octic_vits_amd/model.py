@@ -12,7 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import functional as OF
-from .d8_invariantization import PowerSpectrumInvariant
+from .d8_invariantization import make_invariantization
 from .d8_layers import BlockD8, LayerNormD8, PatchEmbedD8, TritonGeluD8
 from .d8_utils import SQRT2_OVER_2, packed_pos_embed
 from .functional import Octic, compute_dtype
@@ -29,7 +29,8 @@ class OcticVisionTransformer(nn.Module):
                  qkv_bias: bool = False, drop_rate: float = 0., attn_drop_rate: float = 0., drop_path_rate: float = 0.,
                  octic_block_layers: Callable = BlockD8, standard_block_layers: Callable = Block,
                  Patch_layer: Callable = PatchEmbedD8, init_scale: float = 1e-4, num_register_tokens: int = 0,
-                 global_pool: bool = False, invariant: bool = False, octic_equi_break_layer=None, **kwargs):
+                 global_pool: bool = False, invariant: bool = False, octic_equi_break_layer=None,
+                 invariantization="power_spectrum", **kwargs):
         super().__init__()
         assert embed_dim % 8 == 0, "embed_dim must be divisible by 8"
         self.dropout_rate = drop_rate
@@ -46,7 +47,7 @@ class OcticVisionTransformer(nn.Module):
         self.invariant = invariant
         self.num_register_tokens = num_register_tokens
         if self.invariant:
-            self.invariantization = PowerSpectrumInvariant(embed_dim)
+            self.invariantization = make_invariantization(invariantization, embed_dim)
             self.invariant_proj = torch.nn.Linear(self.invariantization.output_dim, embed_dim)
         self.patch_embed = Patch_layer(img_size=img_size, patch_size=patch_size, in_chans=in_chans, embed_dim=embed_dim)
         norm_layer = partial(nn.LayerNorm, eps=1e-6)

@@ -2712,3 +2712,97 @@ def depth_expect(Lo, grid, upsample, bins, min_depth, max_depth, out=None):
                                    _stream(Lo)))
     KERNEL_TIMER.stop(t, "depth_expect_kernel", 4 * (Lo.numel() + out.numel()))
     return out
+
+
+# ------------------------------------------------------------------------------------------ orbit invariants
+def _orbit_view(x, c):
+    """octic_view of packed rows [..., 8c]: contiguous, or a 2-d row-strided view [M, 8c] (stride(1) == 1)."""
+    if x.is_contiguous():
+        return pview(x, c)
+    _require_cuda(x)
+    if x.dim() != 2 or x.shape[1] != 8 * c or x.stride(1) != 1:
+        raise ValueError(f"expected packed rows [M, {8 * c}] with unit column stride, got {tuple(x.shape)} / {x.stride()}")
+    es, base = x.element_size(), x.data_ptr()
+    v = OcticView()
+    for i in range(5):
+        v.ptr[i] = base + min(i, 4) * c * es
+        v.ld[i] = x.stride(0)
+    return v
+
+
+def max_filter_prep(references, dtype):
+    """references [R, c, 8] f32 -> the eight component planes [8, R, c] in `dtype` (one launch, nothing cached)."""
+    R, c, _ = references.shape
+    planes = torch.empty((8, R, c), dtype=dtype, device=references.device)
+    check(lib().octic_max_filter_prep(_p(references), _p(planes), R, c, dt_code(dtype), _stream(references)))
+    return planes
+
+
+def max_filter_fwd(x, planes, c, out_dtype):
+    """x: packed rows [M, 8c] in the planes' dtype.  Returns (out [M, R] out_dtype, idx [M, R] uint8)."""
+    M, R = x.shape[0], planes.shape[1]
+    out = torch.empty((M, R), dtype=out_dtype, device=x.device)
+    idx = torch.empty((M, R), dtype=torch.uint8, device=x.device)
+    xv = _orbit_view(x, c)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_max_filter_fwd(ctypes.byref(xv), _p(planes), _p(out), _p(idx), M, R, c, dt_code(x.dtype),
+                                     dt_code(out_dtype), _stream(x)))
+    KERNEL_TIMER.stop(t, "max_filter_fwd_kernel", x.element_size() * 8 * c * (M + R) + M * R * (out.element_size() + 1),
+                      24.0 * M * R * c)
+    return out, idx
+
+
+def max_filter_bwd_x(g, idx, planes, c):
+    """g [M, R] in the planes' dtype -> dx packed [M, 8c] in that dtype."""
+    M, R = g.shape
+    dx = torch.empty((M, 8 * c), dtype=planes.dtype, device=g.device)
+    dv = pview(dx, c)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_max_filter_bwd_x(_p(g), _p(idx), _p(planes), ctypes.byref(dv), M, R, c, dt_code(planes.dtype), _stream(g)))
+    KERNEL_TIMER.stop(t, "max_filter_bwd_x_kernel", g.element_size() * (M * R + 8 * c * (M + R)) + M * R, 24.0 * M * R * c)
+    return dx
+
+
+def max_filter_bwd_ref_plan(M, R, c):
+    """(row slabs, rows per slab, tile edge, workgroups per slab) of max_filter_bwd_ref."""
+    answer = _lib.plan("octic_max_filter_bwd_ref_plan", M, R, c)
+    if answer is None:
+        check(-1)
+    return answer
+
+
+def max_filter_bwd_ref(g, idx, x, c):
+    """dref [R, c, 8] f32 from g [M, R] and the packed rows x [M, 8c] (both in the compute dtype)."""
+    M, R = g.shape
+    need = int(lib().octic_max_filter_bwd_ref_workspace_bytes(M, R, c))
+    if need < 0:
+        check(need)
+    ws = torch.empty(need, dtype=torch.uint8, device=g.device)
+    dref = torch.empty((R, c, 8), dtype=torch.float32, device=g.device)
+    xv = _orbit_view(x, c)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_max_filter_bwd_ref(_p(g), _p(idx), ctypes.byref(xv), _p(dref), _p(ws), need, M, R, c, dt_code(g.dtype),
+                                         _stream(g)))
+    KERNEL_TIMER.stop(t, "max_filter_bwd_ref_kernel", g.element_size() * (M * R + 8 * c * M) + M * R + 2 * need,
+                      24.0 * M * R * c)
+    return dref
+
+
+def canonize_fwd(x, reference, c, out_dtype):
+    """x packed rows [M, 8c]; reference [8c] f32.  Returns (out [M, 8c] i-major in out_dtype, idx [M] uint8)."""
+    M = x.shape[0]
+    out = torch.empty((M, 8 * c), dtype=out_dtype, device=x.device)
+    idx = torch.empty((M,), dtype=torch.uint8, device=x.device)
+    xv = _orbit_view(x, c)
+    check(lib().octic_canonize_fwd(ctypes.byref(xv), _p(reference), _p(out), _p(idx), M, c, dt_code(x.dtype), dt_code(out_dtype),
+                                   _stream(x)))
+    return out, idx
+
+
+def canonize_bwd(g, idx, c, dtype):
+    """g [M, 8c] dense i-major (f32 or bf16) -> dx packed [M, 8c] in `dtype`."""
+    M = g.shape[0]
+    dx = torch.empty((M, 8 * c), dtype=dtype, device=g.device)
+    dv = pview(dx, c)
+    check(lib().octic_canonize_bwd(_p(g), dt_code(g.dtype), _p(idx), ctypes.byref(dv), M, c, dt_code(dtype), _stream(g)))
+    return dx
