@@ -1581,6 +1581,21 @@ int octic_canonize_fwd(const octic_view* x, const float* reference, void* out, u
 int octic_canonize_bwd(const void* g, int g_dtype, const uint8_t* idx, const octic_view* dx, int64_t M, int c, int dtype,
                        void* stream);
 
+/* ---- polynomial invariants: PolynomialInvariant / ThirdOrderInvariant (d8_invariantization.py:66-141) ----------------------
+ * Element-wise over (row, column).  x, dx: float32 views.  out / g: dense [M, P c], generator k at columns [k c, (k + 1) c),
+ * P = 32 (OCTIC_POLY_POLYNOMIAL) or 15 (OCTIC_POLY_THIRD_ORDER), in the plane order of the Python modules; 16-byte aligned.
+ * Forward: every generator in f32 with the expression tree of the Python composition (monomials as left-to-right products of
+ * their digits, terms in table order, every multiply and add rounded on its own: no fma), so the f32 output equals the
+ * composition bit for bit and the bf16 output is its round-to-nearest-even.
+ * Backward: dx_i = sum_k g_k dp_k/dx_i recomputed from x; f32 sums in a fixed order (generators in plane order, terms in table
+ * order, the distinct digits of a term in order of first appearance); no atomics, no workspace.
+ * One thread per group of 4 (forward) / 2 (backward) adjacent columns of a row in an uncapped grid: M c / 2 must stay below
+ * 2^31 (else -1).                                                                                                          */
+enum { OCTIC_POLY_POLYNOMIAL = 0, OCTIC_POLY_THIRD_ORDER = 1 };
+int octic_poly_invariant_fwd(const octic_view* x, void* out, int64_t M, int c, int map, int out_dtype, void* stream);
+int octic_poly_invariant_bwd(const void* g, int g_dtype, const octic_view* x, const octic_view* dx, int64_t M, int c, int map,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

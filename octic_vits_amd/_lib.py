@@ -324,6 +324,8 @@ _PROTOS = {
     "octic_max_filter_bwd_ref": (c_int, [c_void_p, c_void_p, VP, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_void_p]),
     "octic_canonize_fwd": (c_int, [VP, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p]),
     "octic_canonize_bwd": (c_int, [c_void_p, c_int, c_void_p, VP, c_i64, c_int, c_int, c_void_p]),
+    "octic_poly_invariant_fwd": (c_int, [VP, c_void_p, c_i64, c_int, c_int, c_int, c_void_p]),
+    "octic_poly_invariant_bwd": (c_int, [c_void_p, c_int, VP, VP, c_i64, c_int, c_int, c_void_p]),
 }
 
 

@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "liboctic_hip.so")
-SOURCES = ["elementwise.hip", "layernorm.hip", "gemm.hip", "gemm_wreg.hip", "wgrad.hip", "lamb.hip", "attention.hip", "attn80.hip", "attn80_bwd.hip", "attn_stream.hip", "attn_f32.hip", "dense.hip", "swiglu.hip", "dense_gemm.hip", "dense_wgrad.hip", "dense_f32.hip", "ssl_loss.hip", "koleo.hip", "dino_head.hip", "dino_norm.hip", "probe.hip", "attnpool.hip", "segeval.hip", "segknn.hip", "knn_cls.hip", "topk_metric.hip", "mixup.hip", "augment.hip", "dino_augment.hip", "crop.hip", "depth.hip", "orbit_invariant.hip"]
+SOURCES = ["elementwise.hip", "layernorm.hip", "gemm.hip", "gemm_wreg.hip", "wgrad.hip", "lamb.hip", "attention.hip", "attn80.hip", "attn80_bwd.hip", "attn_stream.hip", "attn_f32.hip", "dense.hip", "swiglu.hip", "dense_gemm.hip", "dense_wgrad.hip", "dense_f32.hip", "ssl_loss.hip", "koleo.hip", "dino_head.hip", "dino_norm.hip", "probe.hip", "attnpool.hip", "segeval.hip", "segknn.hip", "knn_cls.hip", "topk_metric.hip", "mixup.hip", "augment.hip", "dino_augment.hip", "crop.hip", "depth.hip", "orbit_invariant.hip", "poly_invariant.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 

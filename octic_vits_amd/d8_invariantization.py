@@ -3,8 +3,12 @@
 PowerSpectrumInvariant — the models' default (model.py:89-91) — is a HIP kernel (fwd + bwd), and so are the two orbit-based
 maps with learned parameters, MaxFilteringInvariant and CanonizationInvariant (csrc/orbit_invariant.hip: all eight products
 of an orbit from 12 partial dots, nothing eightfold in memory); `orbit_hip_ok` is their routing rule, and what it refuses
-runs the reference's composition from the group-action tables of d8_utils.  The polynomial maps are table-driven
-composites evaluated from a compact monomial table ("356+347" = x3*x5*x6 + x3*x4*x7).
+runs the reference's composition from the group-action tables of d8_utils.  The polynomial maps (PolynomialInvariant,
+ThirdOrderInvariant) are defined by a compact monomial table ("356+347" = x3*x5*x6 + x3*x4*x7); on float32 GPU tensors they
+are one fused kernel forward and one backward (csrc/poly_invariant.hip, `poly_hip_ok` is the routing rule) that evaluate the
+same expression trees in float32 without fma, so the result equals the table-driven torch composition bit for bit; what the
+rule refuses - CPU tensors, bf16 / fp16 tensors, torch.compile tracing - runs that composition.  The digits of the tables are
+ordered so that both arms are invariant under the eight group elements bit for bit.  LinearInvariant is one `abs`.
 """
 import inspect
 import os
@@ -39,6 +43,22 @@ def orbit_hip_ok(xtuple, *params) -> bool:
             return False
     c = xtuple.c if isinstance(xtuple, OF.Octic) else ts[0].shape[-1]
     return c > 0 and c % 8 == 0 and ts[0].numel() > 0
+
+
+POLY_HIP = os.environ.get("OCTIC_POLY_HIP", "1") != "0"       # Polynomial / ThirdOrder on the HIP kernels where they can run
+
+
+def poly_hip_ok(xtuple) -> bool:
+    """The one routing rule of the polynomial kernels: the switch POLY_HIP on, not under torch.compile tracing (Inductor fuses
+    the composition itself), non-empty float32 GPU tensors and c a positive multiple of 8.  Any autocast state passes: the
+    arithmetic is float32 either way.  bf16 / fp16 tensors stay on the composition, which rounds per operation."""
+    if not POLY_HIP or torch.compiler.is_compiling():
+        return False
+    ts = [xtuple.packed] if isinstance(xtuple, OF.Octic) else list(xtuple)
+    if len(ts) not in (1, 5) or not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return False
+    c = xtuple.c if isinstance(xtuple, OF.Octic) else ts[0].shape[-1]
+    return c > 0 and c % 8 == 0 and all(t.numel() > 0 for t in ts)
 
 
 class Invariant(nn.Module):
@@ -82,12 +102,16 @@ class PowerSpectrumInvariant(Invariant):  # :49-64 -> octic_power_spectrum_fwd/b
         return OF.PowerSpectrumFn.apply(xp, c, _out_dtype or xp.dtype)
 
 
-# monomial tables: digits are 8-tuple indices, repeated digits are powers
+# monomial tables: digits are 8-tuple indices, repeated digits are powers.  A monomial is evaluated as the left-to-right product
+# of its digits, so the ORDER of the digits is part of the float32 result.  It is chosen so that every generator is invariant
+# bit for bit, not only up to rounding: the four group elements that exchange x4 <-> x5 and x6 <-> x7 map a two-term generator's
+# first string onto its second digit by digit ("14456" -> "15547"), and a one-term generator that holds such a pair multiplies
+# the pair first ("673": x6 * x7 == x7 * x6).  The other four elements only flip signs.
 _DEG2 = ["66+77", "46+57", "44+55", "33", "22", "11"]
-_DEG3 = ["367", "356+347", "345", "266-277", "246-257", "244-255", "156-147", "123"]
+_DEG3 = ["673", "356+347", "453", "266-277", "246-257", "244-255", "156-147", "123"]
 _DEG4 = ["6666+7777", "4666+5777", "4466+5577", "4446+5557", "4444+5555", "2356-2347", "1366-1377", "1346-1357",
-         "1344-1355", "1267", "1256+1247", "1245", "16667-16777", "15666-14777", "14566-14577", "14456-14557",
-         "14445-14555"]
+         "1344-1355", "6712", "1256+1247", "4512", "16667-17776", "15666-14777", "14566-15477", "14456-15547",
+         "14445-15554"]
 
 
 def _poly(spec, x, prefix=""):
@@ -100,20 +124,26 @@ def _poly(spec, x, prefix=""):
     return out
 
 
-class PolynomialInvariant(Invariant):  # :66-112
+class PolynomialInvariant(Invariant):  # :66-112 -> octic_poly_invariant_fwd/bwd
     def __init__(self, C: int):
         super().__init__(32 * C // 8)
 
     def forward(self, xtuple, _out_dtype=None):
+        if poly_hip_ok(xtuple):
+            xp, c = as_packed(xtuple)
+            return OF.PolyInvariantFn.apply(xp, c, "polynomial", _out_dtype or xp.dtype)
         x = convert_5tuple_to_8tuple(xtuple)
         return torch.cat([x[0]] + [_poly(s, x) for s in _DEG2 + _DEG3 + _DEG4], dim=-1)
 
 
-class ThirdOrderInvariant(Invariant):  # :114-141
+class ThirdOrderInvariant(Invariant):  # :114-141 -> octic_poly_invariant_fwd/bwd
     def __init__(self, C: int):
         super().__init__(15 * C // 8)
 
     def forward(self, xtuple, _out_dtype=None):
+        if poly_hip_ok(xtuple):
+            xp, c = as_packed(xtuple)
+            return OF.PolyInvariantFn.apply(xp, c, "third_order", _out_dtype or xp.dtype)
         x = convert_5tuple_to_8tuple(xtuple)
         return torch.cat([x[0] ** 3] + [_poly(s, x, prefix="0") for s in _DEG2] + [_poly(s, x) for s in _DEG3], dim=-1)
 

@@ -1954,3 +1954,25 @@ class CanonizeFn(torch.autograd.Function):
             g = g.float()
         dx = ops.canonize_bwd(_c(g.reshape(-1, 8 * c)), idx, c, dt)
         return dx.view(*lead, 8 * c).to(x_dtype), None, None, None
+
+
+# ------------------------------------------------------------------------------------------ polynomial invariants
+class PolyInvariantFn(torch.autograd.Function):
+    """PolynomialInvariant / ThirdOrderInvariant on packed float32 rows (map: "polynomial" | "third_order").  Saves x alone -
+    for a contiguous float32 input that is the input itself, not a copy - and takes the cotangent in the dtype it arrives in
+    (float32 or bfloat16)."""
+
+    @staticmethod
+    def forward(ctx, x, c, map, out_dtype):
+        x = _c(x.float())
+        ctx.save_for_backward(x)
+        ctx.meta = (c, map)
+        return ops.poly_invariant_fwd(x, c, map, out_dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        c, map = ctx.meta
+        if g.dtype not in (torch.float32, torch.bfloat16):
+            g = g.float()
+        return ops.poly_invariant_bwd(_c(g), x, c, map), None, None, None

@@ -2806,3 +2806,46 @@ def canonize_bwd(g, idx, c, dtype):
     dv = pview(dx, c)
     check(lib().octic_canonize_bwd(_p(g), dt_code(g.dtype), _p(idx), ctypes.byref(dv), M, c, dt_code(dtype), _stream(g)))
     return dx
+
+
+# ------------------------------------------------------------------------------------------ polynomial invariants
+POLY_MAPS = {"polynomial": (0, 32), "third_order": (1, 15)}       # name -> (OCTIC_POLY_* code, generators)
+
+
+def _poly_map(map):
+    try:
+        return POLY_MAPS[map]
+    except KeyError:
+        raise ValueError(f"poly_invariant: map must be one of {sorted(POLY_MAPS)}, got {map!r}") from None
+
+
+def poly_invariant_fwd(x, c, map, out_dtype):
+    """x: float32 packed rows [..., 8c] (contiguous, or a 2-d row-strided view) -> [..., P c] in out_dtype, generator k of the
+    map ("polynomial": P = 32, "third_order": P = 15) at columns [k c, (k + 1) c)."""
+    code, P = _poly_map(map)
+    if x.dtype != torch.float32:
+        raise TypeError(f"poly_invariant_fwd: x must be float32, got {x.dtype}")
+    xv = _orbit_view(x, c)
+    M = x.numel() // (8 * c)
+    out = torch.empty(x.shape[:-1] + (P * c,), dtype=out_dtype, device=x.device)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_poly_invariant_fwd(ctypes.byref(xv), _p(out), M, c, code, dt_code(out_dtype), _stream(x)))
+    KERNEL_TIMER.stop(t, "poly_invariant_fwd_kernel", M * c * (32 + P * out.element_size()))
+    return out
+
+
+def poly_invariant_bwd(g, x, c, map):
+    """g: contiguous [..., P c] float32 or bfloat16 cotangent, x as in poly_invariant_fwd -> dx float32, packed like x."""
+    code, P = _poly_map(map)
+    if x.dtype != torch.float32:
+        raise TypeError(f"poly_invariant_bwd: x must be float32, got {x.dtype}")
+    M = x.numel() // (8 * c)
+    if not g.is_contiguous() or g.numel() != M * P * c or g.device != x.device:
+        raise ValueError(f"poly_invariant_bwd: g must be contiguous with {M * P * c} elements on x's device, got {tuple(g.shape)}")
+    xv = _orbit_view(x, c)
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    dv = pview(dx, c)
+    t = KERNEL_TIMER.start()
+    check(lib().octic_poly_invariant_bwd(_p(g), dt_code(g.dtype), ctypes.byref(xv), ctypes.byref(dv), M, c, code, _stream(x)))
+    KERNEL_TIMER.stop(t, "poly_invariant_bwd_kernel", M * c * (64 + P * g.element_size()))
+    return dx
